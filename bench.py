@@ -18,10 +18,27 @@ N > 1 (launched by torch.distributed.run, one rank per GPU), weak scaling -- eve
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (K2 zl_k2_render): algorithmic bytes per launch / its
 average duration measured with HIP events on the launch stream, for the timed workload (Infinity-Cache assisted: 2 s sources
-are re-read inside a plan window) AND for the same kernel on sources that are never re-read (frac_hbm_no_reuse: HBM only).
-After the timed region one more step is rendered and 3 random (bus, block) rows of it are compared with the CPU oracle, bit
-for bit; a mismatch fails the run.  `cpu_baseline` times the CPU oracle (a port: the reference is not compilable here) on a
-bounded sample of the same workload on all of this box's host cores.
+are re-read inside a plan window).
+
+A plain run sets up, warms up, times --steps steps and prints the line.  Everything else runs only with --full:
+  - two more timed regions of the same steps (value_per_gpu_repeats),
+  - the output check: one more step is rendered and 3 random (bus, block) rows of it are compared with the CPU oracle, bit for
+    bit; a mismatch fails the run,
+  - the device-to-device copy rate and the same kernel on sources that are never re-read (frac_hbm_no_reuse: HBM only),
+  - `cpu_baseline`: the CPU oracle (a port: the reference is not compilable here) on a bounded sample of the same workload on
+    all of this box's host cores,
+  - N > 1: the `span_buses` sub-record.
+The --no-* switches below leave out single parts of a --full run.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's engine) as .npy files, right after the timed region:
+  bus_sample.npy         float32 [buses, 2, S, frames]  the bus audio of S blocks drawn with a fixed seed (bus_sample_blocks.npy)
+  bus_sample_blocks.npy  float64 [S]                    which blocks of the step (ascending)
+  block_peaks.npy        float64 [blocks, buses, 2]     the engine's integer bus peaks of every block (of the S sampled blocks when
+                                                        every block's would take more than 16 MB; block_peaks_blocks.npy then says which)
+  voice_reports.npy      float64 [voices, 4]            playing, gain, progress, source_sample_position of every voice after the step
+  fanout_sample.npy      float32 [buses, 6, S, frames]  the JackPassthrough fan-out of the same blocks (--fanout only)
+S is chosen so that the audio samples stay within 32 MB.  The scene, the sources and the clocks depend on the arguments only, so
+two runs with the same arguments render the same inputs.
 """
 from __future__ import annotations
 
@@ -412,7 +429,46 @@ def parse_args(argv=None):
     ap.add_argument("--launch-check", action="store_true",
                     help="no GPU, no engine: start the ranks, form the process group, push a small bus through the exchange's collectives and "
                          "print a line with n_gpus (CPU-tier check that `bench.py --gpus N` becomes N ranks by itself)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: repeats, output check against the oracle, device copy rate, "
+                         "HBM-only leg, CPU baseline, and at N > 1 the span_buses sub-record (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (see the module docstring)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_AUDIO_BYTES = 32 << 20          # --dump-outputs: bus (+ fan-out) audio of the sampled blocks
+DUMP_PEAKS_BYTES = 16 << 20          # --dump-outputs: every block's peaks up to this size, else the sampled blocks'
+
+
+def dump_outputs(out_dir, syn, torch, bus_dev, fan_dev, B, KB, N):
+    """--dump-outputs: the arrays a caller of zlhip_render_batch receives after the last timed step -- the bus audio (and the fan-out)
+    of a fixed, seeded sample of the step's blocks, the per-block integer bus peaks, the voice reports -- as float32 / float64 .npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    per_block = B * 2 * N * 4 * (4 if fan_dev is not None else 1)
+    S = max(1, min(KB, DUMP_AUDIO_BYTES // per_block))
+    blocks = np.sort(np.random.default_rng(0xD0A7).choice(KB, size=S, replace=False)) if S < KB else np.arange(KB)
+    idx = torch.as_tensor(blocks, device=bus_dev.device, dtype=torch.long)
+    torch.cuda.synchronize()
+    np.save(os.path.join(out_dir, "bus_sample.npy"),
+            bus_dev.view(B, 2, KB, N).index_select(2, idx).cpu().numpy().astype(np.float32, copy=False))
+    np.save(os.path.join(out_dir, "bus_sample_blocks.npy"), blocks.astype(np.float64))
+    if fan_dev is not None:
+        np.save(os.path.join(out_dir, "fanout_sample.npy"),
+                fan_dev.view(B, 6, KB, N).index_select(2, idx).cpu().numpy().astype(np.float32, copy=False))
+    peaks = syn.block_peaks()                                        # [KB, B, 2] int32 (waits for the engine)
+    if peaks.nbytes * 2 > DUMP_PEAKS_BYTES:
+        peaks = peaks[blocks]
+        np.save(os.path.join(out_dir, "block_peaks_blocks.npy"), blocks.astype(np.float64))
+    np.save(os.path.join(out_dir, "block_peaks.npy"), peaks.astype(np.float64))
+    reps = syn.voice_reports()
+    np.save(os.path.join(out_dir, "voice_reports.npy"),
+            np.array([(r.playing, r.gain, r.progress, r.source_sample_position) for r in reps], dtype=np.float64).reshape(-1, 4))
 
 
 def _free_port():
@@ -531,7 +587,7 @@ def main():
     # the rows checked against the oracle after the timed region: 3 random (bus, block) of one step, drawn up front so that the
     # sources of those buses can be kept on the host while the scene is built
     pick_rng = np.random.default_rng(seed ^ 0xC0FFEE)
-    picks = [] if (args.no_spot_check or args.beat_locked) else sorted((int(pick_rng.integers(0, B)), int(pick_rng.integers(0, KB))) for _ in range(3))
+    picks = [] if (not args.full or args.no_spot_check or args.beat_locked) else sorted((int(pick_rng.integers(0, B)), int(pick_rng.integers(0, KB))) for _ in range(3))
     P, kept = build_scene(syn, torch, dev, vpb, B, args.fs, loop_frames, seed, notes=notes, source_rate=source_rate, mono=args.mono,
                           beat_locked=args.beat_locked, keep_buses={b for b, _ in picks})
     syn.set_profiling(not os.environ.get('ZL_BENCH_NOPROF'))      # diagnostic switch: cost of the per-launch HIP events
@@ -620,10 +676,15 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
 
-    # ---- spread: the same K steps timed twice more (each region bracketed by a synchronisation like the first; `value` stays the
+    # ---- what the last timed step computed (before anything below renders into the same buffers)
+    if args.dump_outputs and rank == 0:
+        last_bus = overlapped.bus[(overlapped.i - 1) & 1] if overlapped is not None else bus
+        dump_outputs(args.dump_outputs, syn, torch, last_bus, fan, B, KB, N)
+
+    # ---- --full: spread: the same K steps timed twice more (each region bracketed by a synchronisation like the first; `value` stays the
     #      first region's).  Not for --span-buses (the exchange pipeline would have to be flushed per region).
     repeats = []
-    if not exchange and not args.no_repeats:
+    if args.full and not exchange and not args.no_repeats:
         for rep in range(2):
             torch.cuda.synchronize()
             tr0 = time.perf_counter()
@@ -632,7 +693,7 @@ def main():
             torch.cuda.synchronize()
             repeats.append(float(V) * KB * N * args.steps / (time.perf_counter() - tr0))
 
-    # ---- output check (every rank, its own voices): one more step, untimed, rendered like the timed ones; 3 random
+    # ---- --full: output check (every rank, its own voices): one more step, untimed, rendered like the timed ones; 3 random
     #      (bus, block) rows of it against the CPU oracle, bit for bit.  A mismatch fails the run.
     check = None
     if picks:
@@ -648,9 +709,9 @@ def main():
             os.dup2(real_stdout, 1)
             raise SystemExit(3)
 
-    # practical ceiling of this box: a device-to-device copy (read + write bytes / time), measured after the timed region
+    # --full: practical ceiling of this box: a device-to-device copy (read + write bytes / time), measured after the timed region
     copy_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         a = torch.empty(1 << 28, device=dev, dtype=torch.float32); b = torch.empty_like(a)      # 1 GiB each
         b.copy_(a); torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -660,7 +721,7 @@ def main():
         copy_gbs = 5 * 2 * a.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
         del a, b
 
-    # ---- the HBM-only figure: the same kernel, same launch shape, on sources long enough that no byte is re-read inside a launch
+    # ---- --full: the HBM-only figure: the same kernel, same launch shape, on sources long enough that no byte is re-read inside a launch
     #      (a plan window), so neither L2 nor the 256 MiB Infinity Cache can serve a source read.  N = 1 only, --no-reuse-calls
     #      calls after the timed region.
     no_reuse = None
@@ -678,7 +739,7 @@ def main():
         nr_window = args.plan_window or min(std_window, max(1, int(nr_seconds * args.fs * 0.97) // N))
     else:
         nr_seconds, nr_window = float(int(KB * N / args.fs * 1.03) + 1), args.plan_window
-    if rank == 0 and not distributed and not args.no_reuse_check and args.loop_seconds < 10.0:
+    if rank == 0 and args.full and not distributed and not args.no_reuse_check and args.loop_seconds < 10.0:
         lf2 = int(nr_seconds * source_rate)
         syn2 = SamplerSynth(B, vpb, max_frames=N, max_batch_blocks=KB, max_sounds=V, mode=mode,
                             playback_sample_rate=args.fs, sound_arena_bytes=(lf2 + 16) * (4 if args.mono else 8) * V + (1 << 20),
@@ -752,7 +813,7 @@ def main():
                 "bound": "hbm", "kernel": "zl_k2_render", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                 # the timed workload re-reads its 2 s sources inside a plan window: most of those re-reads are Infinity-Cache hits.
-                # The HBM-only figures of the same kernel (no_reuse_variant, measured in this run) are first-class:
+                # The HBM-only figures of the same kernel (no_reuse_variant, measured in a --full run) are first-class:
                 "cache_assisted": bool(args.loop_seconds * args.fs < KB * N),
                 "achieved_hbm_no_reuse": no_reuse["achieved"] if no_reuse else None,
                 "frac_hbm_no_reuse": no_reuse["frac"] if no_reuse else None,
@@ -774,7 +835,7 @@ def main():
             },
             "output_check": {"rows_vs_oracle": check, "what": "3 random (bus, block) rows of one extra step rendered after the timed region, bit-exact against oracle/zl_oracle.c"} if check is not None else None,
         }
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # the CPU leg is timed on rank 0 at N = 1 only (a reported baseline of the same workload, not part of the scaling curve)
             out["cpu_baseline"] = cpu_baseline(args, seed) if world == 1 else None
 
@@ -784,9 +845,9 @@ def main():
         print(json.dumps(out), flush=True)
         os.dup2(2, 1)
 
-    # ---- N > 1: the spanning-bus exchange next to the collective-free headline (same engine, same voices).  A watchdog bounds
+    # ---- --full, N > 1: the spanning-bus exchange next to the collective-free headline (same engine, same voices).  A watchdog bounds
     #      it: should a collective never complete on this node, rank 0 prints the line with what is there and every rank leaves.
-    if distributed and not exchange and not args.no_span_leg and args.fanout == "none":
+    if args.full and distributed and not exchange and not args.no_span_leg and args.fanout == "none":
         import threading
 
         def give_up():

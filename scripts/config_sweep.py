@@ -45,7 +45,7 @@ def bench_line(args, extra=()):
     # (the timed region starts behind a synchronisation: its first call plans with nothing to hide behind.  Small engines' calls are a
     # quarter of a millisecond, so they get more of them per region -- 48 instead of 6 -- or the start-up reads as 15 % of every step)
     small = any(a in args for a in ("--voices 64", "--voices 96"))
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-reuse-check", "--no-repeats", "--steps", "48" if small else "6", "--warmup", "2"] + args.split() + list(extra)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-reuse-check", "--no-repeats", "--steps", "48" if small else "6", "--warmup", "2"] + args.split() + list(extra)
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=400)
     if p.returncode != 0:
         return None, p.stderr.decode(errors="replace")[-600:]

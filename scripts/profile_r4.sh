@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/$tag; mkdir -p $O
 if [ $part = a ]; then
 B="--no-cpu-baseline --no-reuse-check --no-spot-check --no-repeats --steps 4 --warmup 1"
-python3 bench.py > $O/bench_line.json 2> $O/bench.err || { echo "bench failed"; tail -5 $O/bench.err; exit 1; }
+python3 bench.py --full > $O/bench_line.json 2> $O/bench.err || { echo "bench failed"; tail -5 $O/bench.err; exit 1; }
 for wl in "reuse:" "noreuse:--loop-seconds 12 --plan-window 2048"; do      # (noreuse = the shape of bench.py's own HBM-only leg: 12 s sources, plan windows of 2048 blocks = 10.9 s)
   name=${wl%%:*}; args=${wl#*:}
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/${name}_trace -- python3 bench.py $B $args > $O/${name}_trace.log 2>&1 || echo "trace $name failed"

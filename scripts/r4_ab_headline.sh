@@ -4,7 +4,7 @@
 O=gpurun_out/${1:-r4_abhead}; mkdir -p $O
 PREV=$PWD/libzl_amd/lib/libzlhip_prev.so
 run() { # label, env
-  ( export $2; timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-repeats --steps 12 --warmup 3 2>$O/err.log ) | python3 -c "
+  ( export $2; timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-repeats --steps 12 --warmup 3 2>$O/err.log ) | python3 -c "
 import json,sys
 l=[x for x in sys.stdin if x.startswith('{')]
 d=json.loads(l[-1]); r=d['roofline']; nr=r.get('no_reuse_variant') or {}

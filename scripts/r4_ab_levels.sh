@@ -5,7 +5,7 @@
 O=gpurun_out/${1:-r4_ablv}; mkdir -p $O
 PREV=$PWD/libzl_amd/lib/libzlhip_prev.so
 run() { # label, env, args, steps
-  ( export $2; timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-repeats --no-reuse-check --steps $4 --warmup 2 $3 2>$O/err.log ) | python3 -c "
+  ( export $2; timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-repeats --no-reuse-check --steps $4 --warmup 2 $3 2>$O/err.log ) | python3 -c "
 import json,sys
 l=[x for x in sys.stdin if x.startswith('{')]
 d=json.loads(l[-1]); r=d['roofline']

@@ -2,7 +2,7 @@
 # A/B on ONE box: K2's split tail (ZL_K2_TAIL=0 / 1): the last blocks of a narrow-bus launch rendered by four short workgroups each.
 O=gpurun_out/${1:-r4_abtail}; mkdir -p $O
 run() { # label, env, args, steps
-  ( export $2; timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-repeats --no-reuse-check --steps $4 --warmup 2 $3 2>$O/err.log ) | python3 -c "
+  ( export $2; timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-repeats --no-reuse-check --steps $4 --warmup 2 $3 2>$O/err.log ) | python3 -c "
 import json,sys
 l=[x for x in sys.stdin if x.startswith('{')]
 d=json.loads(l[-1]); r=d['roofline']

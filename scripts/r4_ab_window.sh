@@ -3,7 +3,7 @@
 # when every playing voice is cheap to plan).  Alternating runs; prints value, K2 fractions (timed and HBM-only).
 O=gpurun_out/${1:-r4_abw}; mkdir -p $O
 run() { # label, env, args
-  ( export $2; timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-repeats --steps 8 --warmup 2 $3 2>$O/err.log ) | python3 -c "
+  ( export $2; timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-repeats --steps 8 --warmup 2 $3 2>$O/err.log ) | python3 -c "
 import json,sys
 l=[x for x in sys.stdin if x.startswith('{')]
 d=json.loads(l[-1]); r=d['roofline']; nr=r.get('no_reuse_variant') or {}

@@ -34,7 +34,8 @@ def test_pcm16_known_answers_and_restatements_agree(built):
     rng = np.random.default_rng(16)
     x = np.concatenate([rng.uniform(-1.2, 1.2, 100000), rng.normal(0, 1e-4, 20000), (np.arange(-40000, 40000) + 0.5) / 32768.0]).astype(f32)
     out = np.empty((len(x), 2), dtype=np.int16)
-    lib.zlo_pcm16_stereo(x.ctypes.data, x[::-1].copy().ctypes.data, len(x), out.ctypes.data)
+    xr = x[::-1].copy()                              # (held: the call receives only its address)
+    lib.zlo_pcm16_stereo(x.ctypes.data, xr.ctypes.data, len(x), out.ctypes.data)
     assert np.array_equal(out[:, 0], npr.pcm16(x)) and np.array_equal(out[:, 1], npr.pcm16(x[::-1]))
 
 
