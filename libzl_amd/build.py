@@ -18,7 +18,7 @@ LIBDIR = os.path.join(ROOT, "libzl_amd", "lib")
 LIB = os.path.join(LIBDIR, "libzlhip.so")
 
 HIP_SOURCES = ["zl_kernels.hip", "zl_engine.cpp", "zl_libzl.cpp"]
-HEADERS = ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_kernels.h", "zl_host.h", "zl_sched.h", "zl_handoff.h",
+HEADERS = ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_render.h", "zl_kernels.h", "zl_host.h", "zl_sched.h", "zl_handoff.h",
            os.path.join("..", "..", "include", "zlhip.h"), os.path.join("..", "..", "include", "libzl_hotpath.h")]
 
 
@@ -64,8 +64,8 @@ def build_engine(force: bool = False, verbose: bool = False, stamps: bool = Fals
 # per source: the headers it includes (a change of one of them recompiles only the sources that see it)
 _INC = os.path.join("..", "..", "include")
 SOURCE_DEPS = {
-    "zl_kernels.hip": ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_kernels.h"],
-    "zl_engine.cpp": ["zl_types.h", "zl_plan.h", "zl_host.h", "zl_kernels.h", os.path.join(_INC, "zlhip.h")],
+    "zl_kernels.hip": ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_kernels.h"],
+    "zl_engine.cpp": ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_host.h", "zl_kernels.h", os.path.join(_INC, "zlhip.h")],
     "zl_libzl.cpp": ["zl_render.h", "zl_types.h", "zl_sched.h", "zl_handoff.h", os.path.join(_INC, "zlhip.h"), os.path.join(_INC, "libzl_hotpath.h")],
 }
 
@@ -182,6 +182,23 @@ def build_cpu_harness(force: bool = False) -> str:
         if res.returncode != 0:
             sys.stderr.write(res.stdout + res.stderr)
             raise RuntimeError("building the CPU scheduler harness failed")
+    return target
+
+
+def build_order_harness(force: bool = False) -> str:
+    """Host build of K2's phase order (zl_order.h, tests/cpu_harness/order_host.cpp) for the CPU tier."""
+    hdir = os.path.join(ROOT, "tests", "cpu_harness")
+    target = os.path.join(hdir, "_build", "libzl_order_host.so")
+    src = os.path.join(hdir, "order_host.cpp")
+    deps = [src] + [os.path.join(CSRC, h) for h in ("zl_types.h", "zl_plan.h", "zl_order.h", "zl_host.h")] + [os.path.join(ROOT, "include", "zlhip.h")]
+    if force or _stale(target, deps):
+        os.makedirs(os.path.dirname(target), exist_ok=True)
+        cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
+               "-Wl,-Bsymbolic", "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-o", target, src]
+        res = subprocess.run(cmd, capture_output=True, text=True)
+        if res.returncode != 0:
+            sys.stderr.write(res.stdout + res.stderr)
+            raise RuntimeError("building the CPU phase-order harness failed")
     return target
 
 

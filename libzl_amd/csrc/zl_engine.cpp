@@ -23,6 +23,7 @@
 #include "../../include/zlhip.h"
 #include "zl_host.h"
 #include "zl_kernels.h"
+#include "zl_order.h"
 #include "zl_plan.h"
 #include "zl_types.h"
 
@@ -85,6 +86,7 @@ struct zlhip_engine {
         unsigned long long ctlBase = 0;                   // host side: past every value the counter can have reached
         ZlSimConst *simConst = nullptr;
         float *partials = nullptr;
+        int32_t *order = nullptr; size_t orderInts = 0;  // K2's phase order of the window's blocks (K1o): [z-slots][K], allocated on first use
         hipEvent_t planned = nullptr, rendered = nullptr, k1done = nullptr;
         hipEvent_t renderedEv = nullptr; // the event that marks the end of the last rendering from this set (rendered, or a profiling event)
         bool used = false;               // `rendered` has been recorded at least once
@@ -381,7 +383,7 @@ void zlhip_engine_destroy(zlhip_engine *e)
     void *dev[] = { e->arena, e->dSounds, e->dClips, e->dVoices, e->dGain, e->dBus, e->dLevels, e->dLevelState, e->dTrace, e->dPass, e->dPassCache };
     for (void *p : dev) if (p) (void)hipFree(p);
     for (auto &q : e->ps) {
-        void *pd[] = { q.vconst, q.runs, q.tsegs, q.hdr, q.seg0, q.seg1, q.ctlP, q.ctlEnv, q.partials, q.ctlNext, q.simConst };
+        void *pd[] = { q.vconst, q.runs, q.tsegs, q.hdr, q.seg0, q.seg1, q.ctlP, q.ctlEnv, q.partials, q.ctlNext, q.simConst, q.order };
         for (void *p : pd) if (p) (void)hipFree(p);
         if (q.planned) (void)hipEventDestroy(q.planned);
         if (q.rendered) (void)hipEventDestroy(q.rendered);
@@ -1106,12 +1108,10 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
     // resampled or beat-locked voices keep the pipeline of shorter windows, whose planning hides behind rendering.  ZL_WINDOW_MUL=<n> forces n.
     // (measured on one box, alternating runs, profiles/round4_window_ab.txt: headline +2 %, 4096 voices at 96 kHz +5.5 %, Hermite at ratio 1 +5.5 %,
     // narrow buses +0.5..1 %; two 128-frame blocks per workgroup -3 % -- short blocks keep the fixed size)
+    bool cheap = nframes >= 256;
+    for (const ZlHostVoice &hv : e->hc.voices) if (hv.isPlaying && !hv.cheapPlan) { cheap = false; break; }
     int windowMul = windowMulEnv;
-    if (windowMul == 0) {
-        bool cheap = nframes >= 256;
-        for (const ZlHostVoice &hv : e->hc.voices) if (hv.isPlaying && !hv.cheapPlan) { cheap = false; break; }
-        windowMul = cheap ? 4 : 1;
-    }
+    if (windowMul == 0) windowMul = cheap ? 4 : 1;
     // (engines that split buses into mix groups keep the fixed size: their partial rows are sized for it)
     const size_t mul = e->maxGroups > 1 ? 1 : (size_t)windowMul;
     int W = e->windowBlocks > 0 ? e->windowBlocks : (int)std::max<size_t>(1, std::min<size_t>(mul * e->windowFrames / (size_t)nframes, (size_t)1 << 30));
@@ -1140,6 +1140,31 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
         }
     }
     const int nwin = (int)wins.size();
+    // ---- K2's phase order (K1o, zl_order.h): a window whose voices re-read their loops is rendered in the loop-phase order
+    //      of a key voice, so that the re-reads of a source line run together on one XCD and hit its L2.  Results do not depend on it (K2's
+    //      blocks are independent).  ZL_K2_PHASE_ORDER: 0 = off, 1 = auto (default), 2 = wherever the launch shape allows (tests, A/B); read
+    //      per call.  Auto: every playing voice cheap to plan (unit ratio, sample-space loop), blocks of 256 frames or more, no mix groups,
+    //      not staged, no bounce, and the window longer than a playing loop (zl_order_window; K1o itself keeps time order in a z-slot whose
+    //      key voice's pass is longer than the window).  Elsewhere the launch is the one without the order.
+    const int phaseMode = [] { const char *v = std::getenv("ZL_K2_PHASE_ORDER"); return v ? std::atoi(v) : 1; }();
+    const int orderSlots = A.NB > 1 ? (A.B + A.NB - 1) / A.NB : A.B;
+    const bool orderShape = zl_order_shape(A.groups, A.staged, nblocks, nframes);
+    const double loopFrames = phaseMode == 1 ? e->hc.phase_order_loop_frames() : INFINITY;
+    auto orderWindow = [&](int K) { return zl_order_window(phaseMode, orderShape, e->bnc.sink.on, nframes, K, loopFrames); };
+    {
+        size_t need = 0;
+        for (const auto &wk : wins) if (orderWindow(wk.second)) need = std::max(need, (size_t)orderSlots * (size_t)wk.second);
+        if (need > e->ps[0].orderInts || (e->ps[1].hdr != nullptr && need > e->ps[1].orderInts)) {
+            ZlQuiesce quiet(e);                                    // (as for the trace buffer: hipFree waits for the whole device)
+            for (auto &q : e->ps) {
+                if (need <= q.orderInts || q.hdr == nullptr) continue;
+                if (q.order) ZL_HIP(e, hipFree(q.order));
+                q.order = nullptr; q.orderInts = 0;
+                ZL_HIP(e, dalloc(&q.order, need));
+                q.orderInts = need;
+            }
+        }
+    }
     // (a bounce queues its sub-batches back to back: planning on the planning stream from the first one on orders the second
     // sub-batch's planning behind the first one's PLANNING, not behind its rendering)
     const bool overlap = e->ps[1].hdr != nullptr && (nwin > 1 || behindPrev || e->bnc.active);
@@ -1191,6 +1216,7 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
         // every (block, voice) of a window asks for at most one slot: the next window of this set counts from past that
         Aw.ctl_base = q.ctlBase;
         q.ctlBase += (unsigned long long)Aw.K * (unsigned long long)e->V + 1ull;
+        Aw.order = orderWindow(Aw.K) && q.order ? q.order : nullptr;
         if (w > 0) { Aw.n_op_ranges = 0; Aw.ops = nullptr; Aw.op_ranges = nullptr; Aw.n_clip_edits = 0; Aw.clip_edits = nullptr; }   // commands and parameter edits apply before the first block only
         // planning may not overwrite a record set while an earlier window (of this or the previous call) still renders from it
         if (ps != s && q.used) ZL_HIP(e, hipStreamWaitEvent(ps, q.renderedEv, 0));
@@ -1201,10 +1227,12 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
             ZL_HIP(e, hipEventRecord(q.k1done, ps));
             ZL_HIP(e, hipStreamWaitEvent(e->asmStream, q.k1done, 0));
             ZL_KERNEL(e, zl_launch_assemble(Aw, e->asmStream));
+            if (Aw.order) ZL_KERNEL(e, zl_launch_order(Aw, q.order, orderSlots, e->asmStream));
             ZL_HIP(e, hipEventRecord(q.planned, e->asmStream));
             ZL_HIP(e, hipStreamWaitEvent(s, q.planned, 0));
         } else {
             if (!Aw.fuse_assemble) ZL_KERNEL(e, zl_launch_assemble(Aw, ps));
+            if (Aw.order) ZL_KERNEL(e, zl_launch_order(Aw, q.order, orderSlots, ps));
             if (ps != s) {
                 ZL_HIP(e, hipEventRecord(q.planned, ps));
                 ZL_HIP(e, hipStreamWaitEvent(s, q.planned, 0));

@@ -303,4 +303,16 @@ struct ZlHostControl {
         const double inc = (1.0f - 0.0) / 16;
         for (int i = 0; i < 16; ++i) { p->slice_positions[i] = pos; pos += inc; }
     }
+    // K2's phase order, auto mode (zl_order.h): when every playing voice is cheap to plan, the shortest playing loop in playback frames
+    // (an estimate from the clip's length -- a gate, never a result); INFINITY when a voice is not cheap or nothing loops
+    double phase_order_loop_frames() const
+    {
+        double m = INFINITY;
+        for (const ZlHostVoice &hv : voices) {
+            if (!hv.isPlaying) continue;
+            if (!hv.cheapPlan) return INFINITY;
+            if (hv.cmd.looping && hv.sound >= 0) m = std::min(m, (double)clipParams[(size_t)hv.sound].length_seconds * playback_sample_rate);
+        }
+        return m;
+    }
 };

@@ -4,6 +4,7 @@
 //   K1 zl_k1_plan        per-voice control plan of SamplerSynthVoice::process (:174-270), zl_plan.h
 //   K1c zl_k1c_assemble  segment streams -> per-block plan records, multi-segment blocks -> per-frame control
 //                        (lane-parallel)
+//   K1o zl_k1o_order     K2's block order sorted by loop phase (zl_order.h)
 //   K2 zl_k2_render      gather + interpolate + gain/ADSR/pan + voice->bus sum (:198-221,
 //                        SamplerSynth.cpp:134-140); HBM-bound, no MFMA (about 22 flop per 8 bytes)
 //   K3 zl_k3_finalize    ordered sum of mix-group partials + AudioLevels block scan
@@ -21,6 +22,7 @@
 #include "zl_types.h"
 #include "zl_plan.h"
 #include "zl_render.h"
+#include "zl_order.h"
 #include "zl_kernels.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -157,6 +159,52 @@ __global__ void __launch_bounds__(64) zl_k1c_assemble(const ZlBatch A, int block
     ZlAssembler as;
     as.begin(A, mine ? v : 0, kbeg, mine ? kend : kbeg);
     for (int k = kbeg; k < kend; ++k) zl_k1c_block(A, as, v, lane, k);
+}
+
+// K1o: K2's launch order of the window's blocks, sorted by the loop phase of each z-slot's key voice (zl_order.h).  One
+// workgroup per z-slot: a counting sort over at most ZL_ORDER_MAXBKT buckets in LDS.  It runs beside a rendering K2 (the
+// planner's free wave slot, 9 KB of LDS), so it is small: 4 waves, a few us.  Without a key voice, or when the window is no
+// longer than the key voice's pass, the slot's order is the identity.
+__global__ void __launch_bounds__(256) zl_k1o_order(const ZlBatch A, int32_t *order)
+{
+    __shared__ int s_hist[ZL_ORDER_MAXBKT];
+    __shared__ int s_part[256];
+    __shared__ int s_key;
+    const int tid = threadIdx.x, K = A.K;
+    int vb, ve;
+    zl_order_slot_voices((int)blockIdx.x, A.NB, A.VPB, A.V, vb, ve);
+    int32_t *out = order + (size_t)blockIdx.x * K;
+    if (tid == 0) s_key = INT_MAX;
+    __syncthreads();
+    for (int v = vb + tid; v < ve; v += 256)
+        if (zl_order_is_key(A.runs[v], K)) atomicMin(&s_key, v);
+    __syncthreads();
+    ZlOrderKey key;
+    if (s_key == INT_MAX || !zl_order_setup(A.runs[s_key], K, A.N, key)) {
+        for (int k = tid; k < K; k += 256) out[k] = k;
+        return;
+    }
+    for (int b = tid; b < key.nbkt; b += 256) s_hist[b] = 0;
+    __syncthreads();
+    for (int k = tid; k < K; k += 256) atomicAdd(&s_hist[zl_order_bucket(key, k)], 1);
+    __syncthreads();
+    // exclusive scan of the histogram: a run of buckets per thread, the runs' sums scanned across the workgroup
+    const int per = (key.nbkt + 255) / 256, b0 = tid * per, b1 = b0 + per < key.nbkt ? b0 + per : key.nbkt;
+    int sum = 0;
+    for (int b = b0; b < b1; ++b) sum += s_hist[b];
+    s_part[tid] = sum;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int t = tid >= off ? s_part[tid - off] : 0;
+        __syncthreads();
+        s_part[tid] += t;
+        __syncthreads();
+    }
+    int run = s_part[tid] - sum;
+    for (int b = b0; b < b1; ++b) { const int c = s_hist[b]; s_hist[b] = run; run += c; }
+    __syncthreads();
+    // (the blocks of one bucket land in any order: every bijection renders the same bits)
+    for (int k = tid; k < K; k += 256) out[atomicAdd(&s_hist[zl_order_bucket(key, k)], 1)] = k;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -846,7 +894,8 @@ static __device__ __forceinline__ void zl_k2_chunk(const ZlBatch &A, const ZlBlo
 // (the body is a device function so that the persistent real-time kernel below can run it too: bx / by / bz / gdx / gdy stand for
 // blockIdx.x / .y / .z and gridDim.x / .y of the batch launch)
 // REPORTS: the workgroups of a call's last block also publish its per-voice reports (batch launches; the resident kernel has its own)
-template <uint32_t MODE, int BPW, bool ST, bool REPORTS = true>
+// ORD: launch slots are mapped through A.order (phase order, zl_k2_phase_render; one block per workgroup, register gathers)
+template <uint32_t MODE, int BPW, bool ST, bool REPORTS = true, bool ORD = false>
 static __device__ __forceinline__ void zl_k2_body(const ZlBatch &A, const unsigned bx, const unsigned by, const unsigned bz, const unsigned gdx, const unsigned gdy)
 {
     constexpr int U = (MODE & ZL_MODE_HERMITE) ? ZL_K2_U_HERMITE : ZL_K2_U;
@@ -876,8 +925,13 @@ static __device__ __forceinline__ void zl_k2_body(const ZlBatch &A, const unsign
     const bool inTail = tailed && (int)by >= A.tail_from;
     const int tj = inTail ? (int)by - A.tail_from : 0;
     const int ky = tailed ? A.tail_from : (int)gdy, xq = ky >> 3, xr = ky & 7, xx = (int)(by & 7u);
-    const int yb = inTail ? A.tail_from + tj / A.tail_split
+    const int ys = inTail ? A.tail_from + tj / A.tail_split
                           : xx * xq + (xx < xr ? xx : xr) + (int)(by >> 3);      // a bijection of [0, ky) for every ky
+    // Phase order (A.order, K1o, zl_order.h): slot ys of z-slot bz renders block order[bz][ys] -- the blocks sorted by the loop phase
+    // of the slot's key voice, so XCD x holds an eighth of the loop's phases and the repeats of one phase, which read the same
+    // source lines, run together in its L2.  (The split tail exists only with one z-slot: bz == 0 there too.)
+    static_assert(!ORD || (BPW == 1 && !ST && REPORTS), "the phase order is a batch launch of one block per workgroup");
+    const int yb = ORD ? A.order[(size_t)bz * A.K + ys] : ys;
     const int k = yb * BPW + blk;
     const bool live = k < A.K;                                     // the last workgroup may hold fewer than BPW blocks
     const ZlBlockPlan *s_plan = s_plan_[blk];
@@ -1328,6 +1382,15 @@ template <uint32_t MODE, int BPW, bool ST>
 __global__ void __launch_bounds__(256, ST ? 3 : (MODE & (ZL_MODE_HERMITE | ZL_MODE_FIX_DELAY)) == 0 ? (BPW == 1 ? ZL_K2_WAVES_LINEAR : 5) : ZL_K2_MINWAVES) zl_k2_render(const ZlBatch A)
 {
     zl_k2_body<MODE, BPW, ST>(A, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y);
+}
+
+// the same render with the window's blocks in phase order (A.order, K1o).  A kernel of its own: the table's block number is one more
+// scalar held through the whole body (SGPR spills 111 -> 115, all of them to VGPR lanes: the compiler reserves 36 bytes of private
+// segment that no instruction touches), and launches without the order stay the kernel they were.
+template <uint32_t MODE>
+__global__ void __launch_bounds__(256, (MODE & (ZL_MODE_HERMITE | ZL_MODE_FIX_DELAY)) == 0 ? ZL_K2_WAVES_LINEAR : ZL_K2_MINWAVES) zl_k2_phase_render(const ZlBatch A)
+{
+    zl_k2_body<MODE, 1, false, true, true>(A, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1867,6 +1930,13 @@ int zl_launch_assemble(const ZlBatch &A, hipStream_t s)
     return 0;
 }
 
+int zl_launch_order(const ZlBatch &A, int32_t *order, int nslots, hipStream_t s)
+{
+    hipLaunchKernelGGL(zl_k1o_order, dim3(nslots), dim3(256), 0, s, A, order);
+    ZL_LAUNCH_CHECK();
+    return 0;
+}
+
 int zl_launch_render(const ZlBatch &A, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop)
 {
     // blocks of 64 / 128 frames: 4 / 2 blocks per workgroup (batches only; a single block keeps its small workgroup; other lengths
@@ -1903,6 +1973,7 @@ int zl_launch_render(const ZlBatch &A, hipStream_t s, hipEvent_t ev_start, hipEv
     // event packets around the launch for the command processor to handle
     // LDS-staged source windows (A.staged): batches only, whole 256-thread workgroups; the ring is dynamic LDS
     const bool st = A.staged && A.K > 1 && tpb == 256;
+    if (st || bpw > 1) At.order = nullptr;                         // (the phase order exists for one block per workgroup, register gathers)
     const int ring = 4 * ZL_ST_D * ZL_ST_SLOT;
     switch (A.mode & 7u) {
 #define ZL_CASE(M) case M: \
@@ -1911,6 +1982,7 @@ int zl_launch_render(const ZlBatch &A, hipStream_t s, hipEvent_t ev_start, hipEv
         else if (st)             hipExtLaunchKernelGGL((zl_k2_render<M, 1, true>), grid, block, ring, s, ev_start, ev_stop, 0, At); \
         else if (bpw == 4)       hipExtLaunchKernelGGL((zl_k2_render<M, 4, false>), grid, block, 0, s, ev_start, ev_stop, 0, At); \
         else if (bpw == 2)       hipExtLaunchKernelGGL((zl_k2_render<M, 2, false>), grid, block, 0, s, ev_start, ev_stop, 0, At); \
+        else if (At.order)       hipExtLaunchKernelGGL((zl_k2_phase_render<M>), grid, block, pad, s, ev_start, ev_stop, 0, At); \
         else                     hipExtLaunchKernelGGL((zl_k2_render<M, 1, false>), grid, block, pad, s, ev_start, ev_stop, 0, At); \
         break;
         ZL_CASE(0) ZL_CASE(1) ZL_CASE(2) ZL_CASE(3) ZL_CASE(4) ZL_CASE(5) ZL_CASE(6) ZL_CASE(7)

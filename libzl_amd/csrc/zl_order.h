@@ -1,0 +1,76 @@
+// zl_order.h -- K2's launch order of a window's blocks, sorted by loop phase (K1o, zl_kernels.hip).
+//
+// A looping voice re-reads its loop once per pass: block k and block k + M / N read the same source lines.  In time order
+// two such reads on one XCD are a whole pass apart -- a pass of every voice of the z-slot streams through the XCD's 4 MiB L2
+// in between -- so every read misses L2.  Sorted by the loop phase of one key voice, the blocks that read the same lines
+// are neighbours in launch order: they run at the same time on the same XCD (zl_k2_body gives XCD x one contiguous
+// eighth of the launch slots) and the repeats hit L2.  K2's blocks are independent, so any permutation renders the same bits.
+//
+// Everything here is __host__ __device__: the CPU tier tests the keys, the key voice and the host reference of the sort
+// (tests/cpu_harness/order_host.cpp); the product runs them in K1o only.
+#pragma once
+#include "zl_types.h"
+
+#define ZL_ORDER_MAXBKT 2048      // phase buckets per z-slot (K1o's LDS histogram: 8 KB); longer loops get buckets of several blocks
+
+// voices of z-slot z of the K2 grid: one bus (NB == 1, no mix groups) or NB consecutive narrow buses
+ZL_HD inline void zl_order_slot_voices(int z, int NB, int VPB, int V, int &vb, int &ve)
+{
+    vb = z * NB * VPB;
+    ve = vb + NB * VPB < V ? vb + NB * VPB : V;
+}
+
+// a voice can key the order: it plays through the whole window and has a periodic part (a sample-space loop in sustain)
+ZL_HD inline bool zl_order_is_key(const ZlRunList &rl, int K)
+{
+    return rl.per_n > 0 && rl.per_M > 0 && rl.dead_from >= K;
+}
+
+struct ZlOrderKey { int t0, M, N, width, nbkt; };
+
+// the key voice's phase buckets; false: no order (the window is no longer than one pass -- the sort would be time order
+// rotated -- or nothing loops)
+ZL_HD inline bool zl_order_setup(const ZlRunList &rl, int K, int N, ZlOrderKey &key)
+{
+    if (rl.per_n <= 0 || rl.per_M <= 0 || N <= 0 || (long long)K * N <= (long long)rl.per_M) return false;
+    const int blocks = (rl.per_M + N - 1) / N;                     // buckets of one block's frames ...
+    const int per = (blocks + ZL_ORDER_MAXBKT - 1) / ZL_ORDER_MAXBKT;   // ... or of `per` blocks' when the pass is long
+    key.t0 = rl.per_t0; key.M = rl.per_M; key.N = N; key.width = per * N;
+    key.nbkt = (rl.per_M + key.width - 1) / key.width;
+    return true;
+}
+
+// bucket of block k: its first frame's offset into the key voice's pass, in buckets (0 .. nbkt - 1)
+ZL_HD inline int zl_order_bucket(const ZlOrderKey &key, int k)
+{
+    long long p = ((long long)k * key.N - key.t0) % key.M;
+    if (p < 0) p += key.M;
+    return (int)(p / key.width);
+}
+
+// the launch shapes K2 can take an order in: one block per workgroup (not the 64- / 128-frame batch forms), no mix groups, not staged
+inline bool zl_order_shape(int groups, int staged, int nblocks, int nframes)
+{
+    return groups == 1 && !staged && nblocks > 1 && nframes != 64 && nframes != 128;
+}
+
+// does a window of K blocks get the order?  mode = ZL_K2_PHASE_ORDER: 0 off, 1 auto, 2 wherever the shape allows.  Auto: blocks of
+// 256 frames or more, no bounce, and the window longer than the shortest playing loop (ZlHostControl::phase_order_loop_frames:
+// INFINITY unless every playing voice is cheap to plan)
+inline bool zl_order_window(int mode, bool shape, bool bounce, int nframes, int K, double loopFrames)
+{
+    if (mode == 2) return shape;
+    return mode == 1 && shape && !bounce && nframes >= 256 && (double)K * nframes > loopFrames;
+}
+
+// host reference of K1o for one z-slot: a stable counting sort of blocks [0, K) by bucket (K1o places the blocks of one
+// bucket in any order: every bijection renders the same bits).  key == nullptr: the identity.  hist holds nbkt ints.
+inline void zl_order_sort_host(const ZlOrderKey *key, int K, int *hist, int *order)
+{
+    if (!key) { for (int k = 0; k < K; ++k) order[k] = k; return; }
+    for (int b = 0; b < key->nbkt; ++b) hist[b] = 0;
+    for (int k = 0; k < K; ++k) ++hist[zl_order_bucket(*key, k)];
+    int run = 0;
+    for (int b = 0; b < key->nbkt; ++b) { const int c = hist[b]; hist[b] = run; run += c; }
+    for (int k = 0; k < K; ++k) order[hist[zl_order_bucket(*key, k)]++] = k;
+}

@@ -322,5 +322,6 @@ struct ZlBatch {
     int32_t             pad_reports;
     ZlBlockLevels      *levels;   // [K][B]
     int32_t            *pos_trace;// [K][V][N] or null
+    const int32_t      *order;    // [z-slots][K] K2's block of each launch slot (K1o, zl_order.h), or null: time order
     ZlBatchStats       *stats;
 };
