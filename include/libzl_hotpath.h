@@ -50,9 +50,9 @@ const char *ClipAudioSource_getFileName(ClipAudioSource *c);                    
 void ClipAudioSource_setStartPosition(ClipAudioSource *c, float startPositionInSeconds);/* libzl.h:34 */
 void ClipAudioSource_setLength(ClipAudioSource *c, float beat, int bpm);                /* libzl.h:36 */
 void ClipAudioSource_setPan(ClipAudioSource *c, float pan);                             /* libzl.h:37 */
-void ClipAudioSource_setSpeedRatio(ClipAudioSource *c, float speedRatio);               /* libzl.h:38 (stored, unused by the voice: Q11) */
-void ClipAudioSource_setPitch(ClipAudioSource *c, float pitchChange);                   /* libzl.h:39 (stored, unused by the voice: Q11) */
-void ClipAudioSource_setGain(ClipAudioSource *c, float db);                             /* libzl.h:40 (stored, unused by the voice: Q11) */
+void ClipAudioSource_setSpeedRatio(ClipAudioSource *c, float speedRatio);               /* libzl.h:38 (re-renders the clip on the device, clamped to [0.25, 4]; zlhip_sound_rerender) */
+void ClipAudioSource_setPitch(ClipAudioSource *c, float pitchChange);                   /* libzl.h:39 (re-renders the clip on the device, clamped to [-24, 24] semitones) */
+void ClipAudioSource_setGain(ClipAudioSource *c, float db);                             /* libzl.h:40 (re-renders the clip on the device; a NaN gain is ignored) */
 void ClipAudioSource_setVolume(ClipAudioSource *c, float vol);                          /* libzl.h:41 */
 void ClipAudioSource_setAudioLevelChangedCallback(ClipAudioSource *c, void (*functionPtr)(float)); /* libzl.h:42 */
 void ClipAudioSource_setSlices(ClipAudioSource *c, int slices);                         /* libzl.h:44 */

@@ -190,6 +190,36 @@ void zlhip_clip_params_default(zlhip_clip_params *p, float duration_seconds);   
  * real-time kernel keeps running. */
 int zlhip_clip_set(zlhip_engine *e, int32_t id, const zlhip_clip_params *p);
 
+/* Clip re-render: ClipAudioSource::setGain / setPitch / setSpeedRatio re-render the clip's playback file from its source
+ * (ClipAudioSource.cpp:279-311,404-413) and the sound reloads it (SamplerSynthSound.cpp:28-68).  The render is build-defined
+ * (a SoundTouch-shaped WSOLA stretch by speed / 2^(pitch/12), a linear resampler by 2^(pitch/12), a gain)
+ * and runs on the device: one seek launch and one synthesis launch per call, for every clip of the call.
+ *   Ranges: speed_ratio in [0.25, 4], pitch_semitones in [-24, 24], finite gain_db; anything else is ZLHIP_ERR_INVALID.
+ *   Every render starts from the ORIGINAL upload; gain 0, pitch 0, speed 1 goes back to it (no render, no copy).
+ *   The playback data has max(1, floor(length / speed_ratio)) frames at the source's sample rate.  Clip parameters keep their
+ *   meaning: start / length / slices are seconds of the playback data; duration_seconds stays the source's.
+ *   The sound table switches at a block boundary (the resident real-time kernel leaves, queued batches finish first); the clip id
+ *   keeps its slot, and a voice playing the clip reads the new data from its next block at its unchanged position.
+ *   An arena that cannot hold the call returns ZLHIP_ERR_CAPACITY and leaves every clip as it was.
+ * zlhip_sound_rerender_batch: ids must be distinct; all or nothing. */
+typedef struct zlhip_rerender_params {
+    float   gain_db;
+    float   pitch_semitones;
+    float   speed_ratio;
+    int32_t reserved;                /* 0 */
+} zlhip_rerender_params;
+int zlhip_sound_rerender(zlhip_engine *e, int32_t id, const zlhip_rerender_params *params);
+int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_rerender_params *params, int32_t count);
+/* The sound's current playback data as planar fp32 (left / right: host [capacity]; right may be NULL, and is left alone for a mono
+ * sound).  *length receives its frames; left == NULL asks for the length only.  Returns the number of channels (1 or 2), < 0 on
+ * error (ZLHIP_ERR_CAPACITY: capacity < length). */
+int zlhip_sound_read(zlhip_engine *e, int32_t id, float *left, float *right, int32_t capacity, int32_t *length);
+/* debug: the seek offsets off_k of the sound's last render, one per stretch segment (*count = 0: the stretch did not run) */
+int zlhip_debug_rerender_offsets(zlhip_engine *e, int32_t id, int32_t *out, int32_t capacity, int32_t *count);
+/* measurement: device time of the seek launch and of the synthesis launch of the last re-render call made with profiling on
+ * (zlhip_set_profiling; HIP events on the engine's stream) */
+int zlhip_debug_rerender_timings(zlhip_engine *e, float *seek_ms, float *synth_ms);
+
 /* ---- commands ------------------------------------------------------------------------------ */
 void zlhip_clip_command_clear(zlhip_clip_command *c);           /* ClipCommand.h:74-91 */
 /* SamplerChannel::handleCommand for the bus whose midi channel matches (bus b has midi channel

@@ -95,6 +95,10 @@ class Timings(C.Structure):
     ]
 
 
+class RerenderParams(C.Structure):
+    _fields_ = [("gain_db", C.c_float), ("pitch_semitones", C.c_float), ("speed_ratio", C.c_float), ("reserved", C.c_int32)]
+
+
 class RtCycleTrace(C.Structure):
     _fields_ = [
         ("cycle", C.c_uint64), ("resident", C.c_int32), ("reserved", C.c_int32),
@@ -119,6 +123,11 @@ SIGNATURES = {
     "zlhip_sound_release": (C.c_int, [_E, C.c_int32]),
     "zlhip_clip_params_default": (None, [C.POINTER(ClipParams), C.c_float]),
     "zlhip_clip_set": (C.c_int, [_E, C.c_int32, C.POINTER(ClipParams)]),
+    "zlhip_sound_rerender": (C.c_int, [_E, C.c_int32, C.POINTER(RerenderParams)]),
+    "zlhip_sound_rerender_batch": (C.c_int, [_E, C.POINTER(C.c_int32), C.POINTER(RerenderParams), C.c_int32]),
+    "zlhip_sound_read": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zlhip_debug_rerender_offsets": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zlhip_debug_rerender_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "zlhip_clip_command_clear": (None, [C.POINTER(ClipCommand)]),
     "zlhip_handle_command": (C.c_int, [_E, C.POINTER(ClipCommand), C.c_uint64]),
     "zlhip_handle_commands": (C.c_int, [_E, C.POINTER(ClipCommand), C.c_int32, C.c_uint64, C.POINTER(C.c_int32)]),

@@ -17,8 +17,8 @@ CSRC = os.path.join(ROOT, "libzl_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "libzl_amd", "lib")
 LIB = os.path.join(LIBDIR, "libzlhip.so")
 
-HIP_SOURCES = ["zl_kernels.hip", "zl_engine.cpp", "zl_libzl.cpp"]
-HEADERS = ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_render.h", "zl_kernels.h", "zl_host.h", "zl_sched.h", "zl_handoff.h",
+HIP_SOURCES = ["zl_kernels.hip", "zl_stretch.hip", "zl_engine.cpp", "zl_libzl.cpp"]
+HEADERS = ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_render.h", "zl_kernels.h", "zl_host.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h",
            os.path.join("..", "..", "include", "zlhip.h"), os.path.join("..", "..", "include", "libzl_hotpath.h")]
 
 
@@ -65,8 +65,9 @@ def build_engine(force: bool = False, verbose: bool = False, stamps: bool = Fals
 _INC = os.path.join("..", "..", "include")
 SOURCE_DEPS = {
     "zl_kernels.hip": ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_kernels.h"],
-    "zl_engine.cpp": ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_host.h", "zl_kernels.h", os.path.join(_INC, "zlhip.h")],
-    "zl_libzl.cpp": ["zl_render.h", "zl_types.h", "zl_sched.h", "zl_handoff.h", os.path.join(_INC, "zlhip.h"), os.path.join(_INC, "libzl_hotpath.h")],
+    "zl_stretch.hip": ["zl_types.h", "zl_stretch.h"],
+    "zl_engine.cpp": ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_host.h", "zl_kernels.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h")],
+    "zl_libzl.cpp": ["zl_render.h", "zl_types.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h"), os.path.join(_INC, "libzl_hotpath.h")],
 }
 
 
@@ -127,7 +128,9 @@ def _build_engine(force: bool, verbose: bool, extra: list) -> str:
                 sys.stderr.write(res.stdout + res.stderr)
                 raise RuntimeError(f"hipcc failed compiling {name}")
             if kernels:
-                _write_kernel_resources(res.stderr, os.path.join(os.path.dirname(LIB), os.path.splitext(os.path.basename(LIB))[0] + "_kernel_resources.txt"))
+                # zl_kernels.hip -> <library>_kernel_resources.txt; every other kernel source -> <library>_<source>_kernel_resources.txt
+                stem = os.path.splitext(os.path.basename(LIB))[0] + ("" if name == "zl_kernels.hip" else "_" + os.path.splitext(name)[0])
+                _write_kernel_resources(res.stderr, os.path.join(os.path.dirname(LIB), stem + "_kernel_resources.txt"))
             elif verbose and res.stderr:
                 sys.stderr.write(res.stderr)
             rebuilt = True
@@ -182,6 +185,16 @@ def build_cpu_harness(force: bool = False) -> str:
         if res.returncode != 0:
             sys.stderr.write(res.stdout + res.stderr)
             raise RuntimeError("building the CPU scheduler harness failed")
+    # the clip re-render (zl_stretch.h), host build: the CPU tier's bit-exact check and the host side of scripts/rerender_bench.py
+    t3 = os.path.join(hdir, "_build", "libzl_stretch_host.so")
+    src3 = os.path.join(hdir, "stretch_host.cpp")
+    if force or _stale(t3, [src3, os.path.join(CSRC, "zl_stretch.h"), os.path.join(CSRC, "zl_types.h")]):
+        cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wall", "-Wl,-Bsymbolic", "-pthread",
+               "-I", CSRC, "-o", t3, src3]
+        res = subprocess.run(cmd, capture_output=True, text=True)
+        if res.returncode != 0:
+            sys.stderr.write(res.stdout + res.stderr)
+            raise RuntimeError("building the CPU re-render harness failed")
     return target
 
 

@@ -25,6 +25,7 @@
 #include "zl_kernels.h"
 #include "zl_order.h"
 #include "zl_plan.h"
+#include "zl_stretch.h"
 #include "zl_types.h"
 
 // buses at least this wide are split into one voice per workgroup for single real-time blocks (pick_group)
@@ -74,7 +75,17 @@ struct zlhip_engine {
     struct ArenaSegment { float *p; size_t off, floats; };   // off: the segment's float offset from `arena`, modulo 2^64
     std::vector<ArenaSegment> arenaSegments;
     size_t arenaSegmentFloats = 0;       // floats in those segments (zlhip_memory_bytes)
-    std::vector<size_t> soundFloats;     // per sound slot: floats it holds in the arena
+    std::vector<size_t> soundFloats;     // per sound slot: floats its original upload holds in the arena
+    // clip re-render (zlhip_sound_rerender): per sound slot, the original upload -- every render starts from it, as tracktion renders
+    // from the clip's source file -- and the rendered extent the slot plays instead while it has one (hc.sounds holds what it plays)
+    std::vector<ZlSound> origSounds;
+    std::vector<size_t> renderFloats;    // floats of the slot's rendered extent, 0 = it plays its original
+    std::vector<std::vector<int32_t>> renderOffsets;   // the seek offsets of the slot's last render (zlhip_debug_rerender_offsets)
+    ZlStretchJob *dStJobs = nullptr; size_t stJobsCap = 0;      // a call's jobs, the jobs whose stretch runs, their seek offsets
+    int32_t *dStList = nullptr; size_t stListCap = 0;
+    int32_t *dStOffs = nullptr; size_t stOffsCap = 0;
+    hipEvent_t stEv[3] = {nullptr, nullptr, nullptr};     // profiling (zlhip_set_profiling): before the seek, between the launches, after
+    float stSeekMs = 0.0f, stSynthMs = 0.0f;             // ... of the last call (zlhip_debug_rerender_timings)
     ZlSound *dSounds = nullptr; ZlClip *dClips = nullptr;
     ZlVoiceState *dVoices = nullptr;
     // K1 -> K2 records, double buffered so that planning window i+1 overlaps rendering window i
@@ -380,7 +391,8 @@ void zlhip_engine_destroy(zlhip_engine *e)
     if (e->planStream) (void)hipStreamSynchronize(e->planStream);
     if (e->asmStream) (void)hipStreamSynchronize(e->asmStream);
     for (auto &seg : e->arenaSegments) if (seg.p) (void)hipFree(seg.p);
-    void *dev[] = { e->arena, e->dSounds, e->dClips, e->dVoices, e->dGain, e->dBus, e->dLevels, e->dLevelState, e->dTrace, e->dPass, e->dPassCache };
+    void *dev[] = { e->arena, e->dSounds, e->dClips, e->dVoices, e->dGain, e->dBus, e->dLevels, e->dLevelState, e->dTrace, e->dPass, e->dPassCache,
+                    e->dStJobs, e->dStList, e->dStOffs };
     for (void *p : dev) if (p) (void)hipFree(p);
     for (auto &q : e->ps) {
         void *pd[] = { q.vconst, q.runs, q.tsegs, q.hdr, q.seg0, q.seg1, q.ctlP, q.ctlEnv, q.partials, q.ctlNext, q.simConst, q.order };
@@ -409,6 +421,7 @@ void zlhip_engine_destroy(zlhip_engine *e)
     if (e->asmStream) (void)hipStreamDestroy(e->asmStream);
     void *host[] = { e->hBus, e->hLevelState, e->hFan, e->hPassRt };
     for (void *p : host) if (p) (void)hipHostFree(p);
+    for (hipEvent_t ev : e->stEv) if (ev) (void)hipEventDestroy(ev);
     if (e->evJoin) (void)hipEventDestroy(e->evJoin);
     if (e->evPlanTail) (void)hipEventDestroy(e->evPlanTail);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -619,6 +632,9 @@ int zlhip_engine_create(const zlhip_config *cfg_in, zlhip_engine **out)
     }
     e->hc.init(cfg->num_buses, cfg->voices_per_bus, cfg->max_sounds, cfg->playback_sample_rate);
     e->soundFloats.assign((size_t)cfg->max_sounds, 0);
+    e->origSounds.assign((size_t)cfg->max_sounds, ZlSound{0, 0, 0, 0.0});
+    e->renderFloats.assign((size_t)cfg->max_sounds, 0);
+    e->renderOffsets.assign((size_t)cfg->max_sounds, std::vector<int32_t>());
     e->arenaFree.assign(1, { (size_t)0, e->arenaFloats & ~(size_t)3 });
     for (auto &c : e->slots) { std::memset(c.hReports, 0, V * sizeof(ZlReport)); std::memset(c.hStats, 0, sizeof(ZlBatchStats)); }
     e->latest = &e->slots[0];
@@ -640,15 +656,9 @@ void zlhip_clip_params_default(zlhip_clip_params *p, float duration_seconds)
     ZlHostControl::default_clip_params(p, duration_seconds);
 }
 
-static int alloc_sound_slot(zlhip_engine *e, int32_t length, int channels, double sample_rate, int32_t *out_id, float **dst)
+// an extent of `floats` floats (a multiple of 4) of the arena: first fit over the free extents, else a further arena segment
+static int alloc_extent(zlhip_engine *e, size_t floats, size_t *out_off)
 {
-    if (length < 1 || !(sample_rate > 0.0) || !out_id) return fail(e, ZLHIP_ERR_INVALID, "bad sound arguments");
-    int id = -1;
-    for (int i = 0; i < e->cfg.max_sounds; ++i) if (!e->hc.soundUsed[i]) { id = i; break; }
-    if (id < 0) return fail(e, ZLHIP_ERR_CAPACITY, "sound table full");
-    const size_t pad = 8;
-    size_t floats = ((size_t)length + pad) * (size_t)channels;
-    floats = (floats + 3) & ~(size_t)3;                           // keep every source 16-byte aligned
     // first fit over the free extents (offsets and sizes are multiples of 4 floats, so every source stays aligned)
     size_t off = (size_t)-1;
     for (size_t i = 0; i < e->arenaFree.size(); ++i) {
@@ -677,28 +687,57 @@ static int alloc_sound_slot(zlhip_engine *e, int32_t length, int channels, doubl
             e->arenaFree.insert(std::lower_bound(e->arenaFree.begin(), e->arenaFree.end(), rest), rest);
         }
     }
+    *out_off = off;
+    return ZLHIP_OK;
+}
+
+// floats of the arena extent of a source of `length` frames: ZL_ST_PAD zero frames behind it, 16-byte aligned
+static size_t extent_floats(int64_t length, int channels)
+{
+    const size_t floats = ((size_t)length + ZL_ST_PAD) * (size_t)channels;
+    return (floats + 3) & ~(size_t)3;                             // keep every source 16-byte aligned
+}
+
+// (integer arithmetic: a segment below the first arena in the address space has an offset that wraps -- no pointer ever leaves its allocation)
+static float *arena_ptr(const zlhip_engine *e, uint64_t off)
+{
+    return reinterpret_cast<float *>((uintptr_t)e->arena + (uintptr_t)off * sizeof(float));
+}
+
+static int alloc_sound_slot(zlhip_engine *e, int32_t length, int channels, double sample_rate, int32_t *out_id, float **dst)
+{
+    if (length < 1 || !(sample_rate > 0.0) || !out_id) return fail(e, ZLHIP_ERR_INVALID, "bad sound arguments");
+    int id = -1;
+    for (int i = 0; i < e->cfg.max_sounds; ++i) if (!e->hc.soundUsed[i]) { id = i; break; }
+    if (id < 0) return fail(e, ZLHIP_ERR_CAPACITY, "sound table full");
+    const size_t floats = extent_floats(length, channels);
+    size_t off = 0;
+    { const int rc = alloc_extent(e, floats, &off); if (rc != ZLHIP_OK) return rc; }
     ZlSound s; s.offset = off; s.length = length; s.channels = channels; s.sample_rate = sample_rate;
-    // (integer arithmetic: a segment below the first arena in the address space has an offset that wraps -- no pointer ever leaves its allocation)
-    *dst = reinterpret_cast<float *>((uintptr_t)e->arena + (uintptr_t)off * sizeof(float));
+    *dst = arena_ptr(e, off);
     e->hc.sounds[id] = s;
     e->hc.soundUsed[id] = 1;
     e->soundFloats[(size_t)id] = floats;
+    e->origSounds[(size_t)id] = s;
+    e->renderFloats[(size_t)id] = 0;
+    e->renderOffsets[(size_t)id].clear();
     *out_id = id;
     return ZLHIP_OK;
 }
 
-// the arena extent of a sound slot goes back to the free list (coalesced with its neighbours); the slot is free again
-static void free_sound_slot(zlhip_engine *e, int id)
+// an arena extent goes back to the free list (coalesced with its neighbours)
+static void free_extent(zlhip_engine *e, size_t off, size_t n)
 {
-    const size_t off = (size_t)e->hc.sounds[id].offset, n = e->soundFloats[(size_t)id];
-    e->hc.soundUsed[id] = 0;
-    e->hc.sounds[id] = ZlSound{0, 0, 0, 0.0};
-    e->soundFloats[(size_t)id] = 0;
     if (n == 0) return;
     auto it = std::lower_bound(e->arenaFree.begin(), e->arenaFree.end(), std::make_pair(off, (size_t)0));
     it = e->arenaFree.insert(it, {off, n});
     if (it + 1 != e->arenaFree.end() && it->first + it->second == (it + 1)->first) { it->second += (it + 1)->second; e->arenaFree.erase(it + 1); }
-    if (it != e->arenaFree.begin() && (it - 1)->first + (it - 1)->second == it->first) { (it - 1)->second += it->second; e->arenaFree.erase(it); --it; }
+    if (it != e->arenaFree.begin() && (it - 1)->first + (it - 1)->second == it->first) {
+        const auto prev = it - 1;                                  // (stays valid: it lies in front of the erased element)
+        prev->second += it->second;
+        e->arenaFree.erase(it);
+        it = prev;
+    }
     // a later arena segment whose every float is free again goes back to the device (the first arena stays for the engine's life).  The
     // caller has waited for the engine and stopped its resident kernel; the free waits for the device: other engines' kernels step aside.
     for (size_t si = 0; si < e->arenaSegments.size(); ++si) {
@@ -717,6 +756,21 @@ static void free_sound_slot(zlhip_engine *e, int id)
         e->arenaSegments.erase(e->arenaSegments.begin() + (long)si);
         break;                                                     // (one extent, at most one whole segment: segments are separate allocations)
     }
+}
+
+// the arena extents of a sound slot -- its original upload and the render it plays, if any -- go back to the free list; the slot is free again
+static void free_sound_slot(zlhip_engine *e, int id)
+{
+    const size_t off = (size_t)e->origSounds[(size_t)id].offset, n = e->soundFloats[(size_t)id];
+    const size_t roff = (size_t)e->hc.sounds[id].offset, rn = e->renderFloats[(size_t)id];
+    e->hc.soundUsed[id] = 0;
+    e->hc.sounds[id] = ZlSound{0, 0, 0, 0.0};
+    e->origSounds[(size_t)id] = ZlSound{0, 0, 0, 0.0};
+    e->soundFloats[(size_t)id] = 0;
+    e->renderFloats[(size_t)id] = 0;
+    e->renderOffsets[(size_t)id].clear();
+    free_extent(e, off, n);
+    free_extent(e, roff, rn);
 }
 
 static int publish_sound(zlhip_engine *e, int id)
@@ -808,6 +862,176 @@ int zlhip_sound_release(zlhip_engine *e, int32_t id)
     free_sound_slot(e, id);
     ZL_HIP(e, hipMemcpyAsync(e->dSounds + id, &e->hc.sounds[id], sizeof(ZlSound), hipMemcpyHostToDevice, e->stream));
     { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    return ZLHIP_OK;
+}
+
+// ---- clip re-render (zl_stretch.h, zl_stretch.hip) ----------------------------------------------------------------------
+// ClipAudioSource::setPitch / setSpeedRatio / setGain re-render the clip's playback file from its source and the sound reloads it
+// (ClipAudioSource.cpp:279-311,404-413, SamplerSynthSound.cpp:28-68).  Here: every clip of the call is rendered from its ORIGINAL
+// upload into a new arena extent (one seek launch, one synthesis launch for the call), then the sound table entries switch -- at a
+// block boundary: the resident kernel has left and every queued batch has finished -- and the extents the clips played before go
+// back to the arena.  The clip id keeps its slot; a voice playing it reads the new data from its next block at its unchanged position,
+// as the reference's voices read the sound's data pointer and length on every block (SamplerSynthVoice.cpp:186-191).
+// (a call's device records, grown when a call needs more: the free waits for the device, other engines' kernels step aside)
+static int st_reserve(zlhip_engine *e, void **p, size_t *cap, size_t need, size_t elem)
+{
+    if (need <= *cap) return ZLHIP_OK;
+    if (*p) {
+        { ZlQuiesce quiet(e); (void)hipFree(*p); }
+        e->deviceBytes -= *cap * elem;
+        *p = nullptr; *cap = 0;
+    }
+    const size_t n = std::max<size_t>(need, 64);
+    if (hipMalloc(p, n * elem) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return fail(e, ZLHIP_ERR_CAPACITY, "sound_rerender: no device memory for the call's records"); }
+    e->deviceBytes += n * elem;
+    *cap = n;
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_rerender_params *params, int32_t count)
+{
+    if (!e || count < 0 || (count > 0 && (!ids || !params))) return ZLHIP_ERR_INVALID;
+    if (count == 0) return ZLHIP_OK;
+    if (count > 65535) return fail(e, ZLHIP_ERR_INVALID, "sound_rerender_batch: more than 65535 clips in one call");
+    // validate everything before anything changes
+    std::vector<ZlStretchGeom> geo((size_t)count);
+    std::vector<char> ident((size_t)count, 0);
+    {
+        std::vector<char> seen((size_t)e->cfg.max_sounds, 0);
+        for (int32_t i = 0; i < count; ++i) {
+            const int32_t id = ids[i];
+            if (id < 0 || id >= e->cfg.max_sounds || !e->hc.soundUsed[id]) return fail(e, ZLHIP_ERR_INVALID, "sound_rerender: no such sound");
+            if (seen[(size_t)id]) return fail(e, ZLHIP_ERR_INVALID, "sound_rerender_batch: a clip appears twice");
+            seen[(size_t)id] = 1;
+            const zlhip_rerender_params &q = params[i];
+            const ZlSound &o = e->origSounds[(size_t)id];
+            if (zl_st_geometry(o.sample_rate, o.length, q.gain_db, q.pitch_semitones, q.speed_ratio, &geo[(size_t)i]) != 0)
+                return fail(e, ZLHIP_ERR_INVALID, "sound_rerender: speed outside [0.25, 4], pitch outside [-24, 24], non-finite gain, or a sample rate the stretch cannot take");
+            ident[(size_t)i] = zl_st_identity(q.gain_db, q.pitch_semitones, q.speed_ratio) ? 1 : 0;
+        }
+    }
+    ZL_HIP(e, hipSetDevice(e->device));
+    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }         // the sound table and the arena change under the resident kernel otherwise
+    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }     // queued batches still read the table
+
+    // the new extents (all or none: an arena that cannot hold the call leaves every clip as it was)
+    std::vector<size_t> newOff((size_t)count, 0), newFloats((size_t)count, 0);
+    auto rollback = [&]() { for (int32_t i = 0; i < count; ++i) free_extent(e, newOff[(size_t)i], newFloats[(size_t)i]); };
+    std::vector<ZlStretchJob> jobs;
+    std::vector<int32_t> seekList, jobClip;
+    int64_t maxFrames = 0, offs = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        if (ident[(size_t)i]) continue;
+        const ZlSound &o = e->origSounds[(size_t)ids[i]];
+        const ZlStretchGeom &g = geo[(size_t)i];
+        const size_t floats = extent_floats(g.N, o.channels);
+        const int rc = alloc_extent(e, floats, &newOff[(size_t)i]);
+        if (rc != ZLHIP_OK) { rollback(); return rc; }
+        newFloats[(size_t)i] = floats;
+        ZlStretchJob J; std::memset(&J, 0, sizeof J);
+        J.geom = g;
+        J.src = (uint64_t)(uintptr_t)arena_ptr(e, o.offset);
+        J.dst = (uint64_t)(uintptr_t)arena_ptr(e, newOff[(size_t)i]);
+        J.channels = o.channels;
+        J.off_base = offs;
+        if (g.stretch && g.nseg > 0) { seekList.push_back((int32_t)jobs.size()); offs += g.nseg; }
+        maxFrames = std::max(maxFrames, g.N);
+        jobs.push_back(J);
+        jobClip.push_back(i);
+    }
+    std::vector<int32_t> hOffs((size_t)offs);
+    if (!jobs.empty()) {
+        int rc = st_reserve(e, (void **)&e->dStJobs, &e->stJobsCap, jobs.size(), sizeof(ZlStretchJob));
+        if (rc == ZLHIP_OK) rc = st_reserve(e, (void **)&e->dStList, &e->stListCap, std::max<size_t>(seekList.size(), 1), sizeof(int32_t));
+        if (rc == ZLHIP_OK) rc = st_reserve(e, (void **)&e->dStOffs, &e->stOffsCap, std::max<size_t>((size_t)offs, 1), sizeof(int32_t));
+        if (rc != ZLHIP_OK) { rollback(); return rc; }
+        hipError_t st = hipMemcpyAsync(e->dStJobs, jobs.data(), jobs.size() * sizeof(ZlStretchJob), hipMemcpyHostToDevice, e->stream);
+        if (st == hipSuccess && !seekList.empty())
+            st = hipMemcpyAsync(e->dStList, seekList.data(), seekList.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+        int krc = (int)st;
+        const bool prof = e->profiling;
+        for (int x = 0; prof && krc == 0 && x < 3; ++x) if (!e->stEv[x]) krc = (int)hipEventCreate(&e->stEv[x]);
+        if (prof && krc == 0) krc = (int)hipEventRecord(e->stEv[0], e->stream);
+        if (krc == 0) krc = zl_launch_stretch_seek(e->dStJobs, e->dStList, (int)seekList.size(), e->dStOffs, e->stream);
+        if (prof && krc == 0) krc = (int)hipEventRecord(e->stEv[1], e->stream);
+        if (krc == 0) krc = zl_launch_stretch_synth(e->dStJobs, (int)jobs.size(), maxFrames, e->dStOffs, e->stream);
+        if (prof && krc == 0) krc = (int)hipEventRecord(e->stEv[2], e->stream);
+        if (krc == 0 && offs > 0) krc = (int)hipMemcpyAsync(hOffs.data(), e->dStOffs, (size_t)offs * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream);
+        if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);
+        if (prof && krc == 0) {
+            krc = (int)hipEventElapsedTime(&e->stSeekMs, e->stEv[0], e->stEv[1]);
+            if (krc == 0) krc = (int)hipEventElapsedTime(&e->stSynthMs, e->stEv[1], e->stEv[2]);
+        }
+        if (krc != 0) {
+            e->err = std::string("sound_rerender: ") + hipGetErrorString((hipError_t)krc);
+            (void)hipStreamSynchronize(e->stream);
+            rollback();
+            return ZLHIP_ERR_HIP;
+        }
+    }
+    // the swap: nothing queued can read the extents the clips played until now any more
+    for (int32_t i = 0; i < count; ++i) {
+        const int32_t id = ids[i];
+        const ZlSound cur = e->hc.sounds[id];
+        free_extent(e, (size_t)cur.offset, e->renderFloats[(size_t)id]);
+        ZlSound s = e->origSounds[(size_t)id];
+        if (!ident[(size_t)i]) { s.offset = newOff[(size_t)i]; s.length = (int32_t)geo[(size_t)i].N; }
+        e->hc.sounds[id] = s;
+        e->renderFloats[(size_t)id] = newFloats[(size_t)i];
+        e->renderOffsets[(size_t)id].clear();
+    }
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        const ZlStretchGeom &g = jobs[j].geom;
+        if (g.stretch && g.nseg > 0)
+            e->renderOffsets[(size_t)ids[jobClip[j]]].assign(hOffs.begin() + jobs[j].off_base, hOffs.begin() + jobs[j].off_base + g.nseg);
+    }
+    for (int32_t i = 0; i < count; ++i)
+        ZL_HIP(e, hipMemcpyAsync(e->dSounds + ids[i], &e->hc.sounds[ids[i]], sizeof(ZlSound), hipMemcpyHostToDevice, e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_rerender(zlhip_engine *e, int32_t id, const zlhip_rerender_params *params)
+{
+    return zlhip_sound_rerender_batch(e, &id, params, 1);
+}
+
+int zlhip_sound_read(zlhip_engine *e, int32_t id, float *left, float *right, int32_t capacity, int32_t *length)
+{
+    if (!e || id < 0 || id >= e->cfg.max_sounds || !e->hc.soundUsed[id]) return ZLHIP_ERR_INVALID;
+    const ZlSound s = e->hc.sounds[id];
+    if (length) *length = s.length;
+    if (!left) return s.channels;
+    if (capacity < s.length) return fail(e, ZLHIP_ERR_CAPACITY, "sound_read: capacity below the sound's length");
+    ZL_HIP(e, hipSetDevice(e->device));
+    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    std::vector<float> tmp((size_t)s.length * (size_t)s.channels);
+    ZL_HIP(e, hipMemcpyAsync(tmp.data(), arena_ptr(e, s.offset), tmp.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    if (s.channels == 2) {
+        for (int32_t i = 0; i < s.length; ++i) { left[i] = tmp[2 * (size_t)i]; if (right) right[i] = tmp[2 * (size_t)i + 1]; }
+    } else {
+        std::memcpy(left, tmp.data(), tmp.size() * sizeof(float));
+    }
+    return s.channels;
+}
+
+int zlhip_debug_rerender_timings(zlhip_engine *e, float *seek_ms, float *synth_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (seek_ms) *seek_ms = e->stSeekMs;
+    if (synth_ms) *synth_ms = e->stSynthMs;
+    return ZLHIP_OK;
+}
+
+int zlhip_debug_rerender_offsets(zlhip_engine *e, int32_t id, int32_t *out, int32_t capacity, int32_t *count)
+{
+    if (!e || id < 0 || id >= e->cfg.max_sounds || !e->hc.soundUsed[id]) return ZLHIP_ERR_INVALID;
+    const std::vector<int32_t> &o = e->renderOffsets[(size_t)id];
+    if (count) *count = (int32_t)o.size();
+    if (!out) return ZLHIP_OK;
+    if ((size_t)capacity < o.size()) return fail(e, ZLHIP_ERR_CAPACITY, "debug_rerender_offsets: capacity below the count");
+    if (!o.empty()) std::memcpy(out, o.data(), o.size() * sizeof(int32_t));
     return ZLHIP_OK;
 }
 

@@ -13,6 +13,7 @@
 #ifndef ZLHIP_NO_LIBZL_NAMES
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -25,6 +26,7 @@
 #include "../../include/libzl_hotpath.h"
 #include "zl_render.h"       // zl_pcm16: the recorder's 16-bit sample format
 #include "zl_sched.h"        // the ClipCommand scheduling front-end (SyncTimer.cpp:452-702,1011-1048)
+#include "zl_stretch.h"      // the re-render's parameter ranges (ClipAudioSource_setSpeedRatio / setPitch)
 #include "zl_handoff.h"      // what crosses from the callers' threads to the cycle: the request queue, the parameter snapshots
 
 namespace {
@@ -742,9 +744,45 @@ void ClipAudioSource_setLength(ClipAudioSource *c, float beat, int bpm)   // Cli
 }
 
 void ClipAudioSource_setPan(ClipAudioSource *c, float pan) { std::lock_guard<std::mutex> sl(c->setMu); if (c->pan != pan) { c->pan = pan; publish_params(c); } }          // :623-629
-void ClipAudioSource_setSpeedRatio(ClipAudioSource *c, float v) { c->speedRatio = v; }                                             // :292-303 (offline re-render, out of scope)
-void ClipAudioSource_setPitch(ClipAudioSource *c, float v) { c->pitchChange = v; }                                                 // :279-290
-void ClipAudioSource_setGain(ClipAudioSource *c, float db) { c->gainDb = db; }                                                     // :305-311
+// setSpeedRatio / setPitch / setGain change the tracktion clip, whose playback file is re-rendered and reloaded by the sound
+// (ClipAudioSource.cpp:279-311,404-413; SamplerSynthSound.cpp:28-68).  Here: the clip is re-rendered on the device from its source with
+// all three current values (zlhip_sound_rerender), under the lock its upload takes; the voices play the new data from their next block.
+// The values are clamped to the render's ranges -- speed [0.25, 4], pitch [-24, 24] semitones; a NaN speed or pitch becomes the range's
+// lower end, a NaN gain leaves the gain as it was and an infinite one becomes +-FLT_MAX dB (silence, or an infinite gain).
+static void clip_rerender(ClipAudioSource *c)                      // call with G.mu held
+{
+    if (!G.engine || c->engineClip < 0) return;
+    zlhip_rerender_params p;
+    {
+        std::lock_guard<std::mutex> sl(c->setMu);
+        p.gain_db = c->gainDb; p.pitch_semitones = c->pitchChange; p.speed_ratio = c->speedRatio; p.reserved = 0;
+    }
+    const int rc = zlhip_sound_rerender(G.engine, c->engineClip, &p);
+    if (rc != ZLHIP_OK)
+        std::fprintf(stderr, "libzl hot path: cannot re-render %s: %s (%s)\n", c->filePath.c_str(), zlhip_strerror(rc), zlhip_last_error(G.engine));
+}
+
+void ClipAudioSource_setSpeedRatio(ClipAudioSource *c, float v)    // :292-303
+{
+    std::lock_guard<std::mutex> lk(G.mu);
+    { std::lock_guard<std::mutex> sl(c->setMu); c->speedRatio = std::min(std::max(ZL_ST_SPEED_MIN, v), ZL_ST_SPEED_MAX); }
+    clip_rerender(c);
+}
+
+void ClipAudioSource_setPitch(ClipAudioSource *c, float v)         // :279-290
+{
+    std::lock_guard<std::mutex> lk(G.mu);
+    { std::lock_guard<std::mutex> sl(c->setMu); c->pitchChange = std::min(std::max(ZL_ST_PITCH_MIN, v), ZL_ST_PITCH_MAX); }
+    clip_rerender(c);
+}
+
+void ClipAudioSource_setGain(ClipAudioSource *c, float db)         // :305-311
+{
+    std::lock_guard<std::mutex> lk(G.mu);
+    if (db != db) return;
+    { std::lock_guard<std::mutex> sl(c->setMu); c->gainDb = std::min(std::max(-FLT_MAX, db), FLT_MAX); }
+    clip_rerender(c);
+}
 
 void ClipAudioSource_setVolume(ClipAudioSource *c, float vol)      // ClipAudioSource.cpp:313-326
 {

@@ -14,7 +14,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _abi
-from ._abi import (Clock, ClipCommand, ClipParams, Config, Levels, PassthroughParams, Timings, VoiceReport,
+from ._abi import (Clock, ClipCommand, ClipParams, Config, Levels, PassthroughParams, RerenderParams, Timings, VoiceReport,
                    MODE_FAITHFUL, MODE_FIX_DELAY, MODE_FIX_GAIN, MODE_HERMITE, ZlHipError)
 
 __all__ = ["SamplerSynth", "Clock", "ClipCommand", "ClipParams", "Levels", "PassthroughParams", "VoiceReport",
@@ -191,6 +191,44 @@ class SamplerSynth:
 
     def set_clip_params(self, clip: int, params: ClipParams):
         self._ck(self._lib.zlhip_clip_set(self._e, clip, C.byref(params)), "clip_set")
+
+    def rerender_clip(self, clip: int, gain_db: float = 0.0, pitch: float = 0.0, speed: float = 1.0):
+        """ClipAudioSource::setGain / setPitch / setSpeedRatio: re-render the clip's playback data on the device from its original
+        upload (zlhip_sound_rerender); gain 0, pitch 0, speed 1 plays the original again."""
+        p = RerenderParams(float(gain_db), float(pitch), float(speed), 0)
+        self._ck(self._lib.zlhip_sound_rerender(self._e, clip, C.byref(p)), "sound_rerender")
+
+    def rerender_clips(self, clips: Sequence[int], gain_db=0.0, pitch=0.0, speed=1.0):
+        """Several clips in one call (zlhip_sound_rerender_batch: one seek and one synthesis launch); each parameter is a scalar
+        for every clip or a sequence with one value per clip."""
+        n = len(clips)
+        col = lambda v: [float(x) for x in v] if isinstance(v, (list, tuple, np.ndarray)) else [float(v)] * n
+        g, p, s = col(gain_db), col(pitch), col(speed)
+        ids = (C.c_int32 * n)(*clips)
+        params = (RerenderParams * n)(*[RerenderParams(g[i], p[i], s[i], 0) for i in range(n)])
+        self._ck(self._lib.zlhip_sound_rerender_batch(self._e, ids, params, n), "sound_rerender_batch")
+
+    def read_clip(self, clip: int):
+        """The clip's current playback data: (left, right) float32, right None for a mono clip (zlhip_sound_read)."""
+        n = C.c_int32(0)
+        self._ck(self._lib.zlhip_sound_read(self._e, clip, None, None, 0, C.byref(n)), "sound_read")
+        L = np.empty(n.value, np.float32); R = np.empty(n.value, np.float32)
+        ch = self._ck(self._lib.zlhip_sound_read(self._e, clip, L.ctypes.data, R.ctypes.data, n.value, C.byref(n)), "sound_read")
+        return L, (R if ch == 2 else None)
+
+    def rerender_offsets(self, clip: int) -> np.ndarray:
+        """debug: the seek offsets of the clip's last render, one per stretch segment (empty: the stretch did not run)"""
+        n = C.c_int32(0)
+        self._ck(self._lib.zlhip_debug_rerender_offsets(self._e, clip, None, 0, C.byref(n)), "debug_rerender_offsets")
+        out = np.zeros(max(n.value, 1), np.int32)
+        self._ck(self._lib.zlhip_debug_rerender_offsets(self._e, clip, out.ctypes.data, out.size, C.byref(n)), "debug_rerender_offsets")
+        return out[:n.value]
+
+    def rerender_timings(self):
+        """(seek ms, synthesis ms) of the last re-render call made with profiling on (set_profiling)"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        self._ck(self._lib.zlhip_debug_rerender_timings(self._e, C.byref(a), C.byref(b)), "debug_rerender_timings")
+        return a.value, b.value
 
     # -- commands ---------------------------------------------------------------------------
     def handle_clip_command(self, cmd: ClipCommand, current_tick: int = 0) -> int:
