@@ -317,6 +317,71 @@ int zlhip_bus_reduce_sum_scan(zlhip_engine *e, const float *pieces_dev, int32_t 
                               int32_t nframes, float *sum_out_dev, zlhip_unit_levels *levels_out_dev, void *stream);
 int zlhip_levels_import_units(zlhip_engine *e, const zlhip_unit_levels *units_dev, int32_t nblocks, int32_t nframes, void *stream);
 
+/* ---- engine group: one synth over several GPUs in one process (ABI 3, additive) --------------------------------------------
+ * A group is n engines ("members", n in 1..ZLHIP_GROUP_MAX_MEMBERS), one per listed device, driven as ONE synth with the buses and
+ * voices of one zlhip_config.  Devices may repeat: [0, 0] is a valid group on one GPU.  zlhip_group_create enables peer access for
+ * every ordered pair of distinct devices (tolerating "already enabled"); a pair that cannot reach each other fails creation.
+ * Every argument check happens before the first HIP call; without a device the call returns ZLHIP_ERR_NO_DEVICE and *out stays NULL
+ * (zlhip_group_last_error(NULL) then tells why the last creation on this thread failed).
+ *
+ * Two partitions (the two of the Python ranks, libzl_amd/sharding.py):
+ *   ZLHIP_GROUP_BUS_ALIGNED (needs num_buses >= n): member r owns the global buses g with (g * n) / num_buses == r -- contiguous,
+ *     as its local buses 0.. with the global voices_per_bus and voices_per_task.  Buses never interact, so the output is bit-identical
+ *     to one engine with the whole config; nothing crosses devices.  bus_out_dev of zlhip_group_render_batch must be NULL.
+ *   ZLHIP_GROUP_SPAN (needs voices_per_bus % n == 0 and voices_per_task 0 or voices_per_bus / n): every member has all buses with
+ *     voices_per_bus / n voices; member r holds the global slots [r * VPB / n, (r + 1) * VPB / n) of every bus and renders them into
+ *     a partial bus.  The bus is summed per sample IN RANK ORDER, ((0 + p0) + p1) + ... -- bit-identical to one engine with
+ *     voices_per_task = VPB / n (the reference's voice order inside a member, the mix-group order across members).  The sum is one
+ *     kernel per member over 1/n of the (block, bus) pairs, which reads every member's partial (the others' over xGMI) and writes the
+ *     root's bus and the root's meters; the root's stream waits for it, and every member's next render waits for every sum of the call
+ *     before.  The group's levels and peaks are the root's.
+ *   ZLHIP_GROUP_AUTO: bus-aligned when num_buses >= n, else span.
+ * Numbers at this surface are GLOBAL: buses, slots, voices (bus * voices_per_bus + slot) and midi channels (bus g has channel g - 2).
+ * Commands of a spanning bus follow SamplerChannel::handleCommand over the bus's voices in global slot order: a stop or an update goes
+ * to every member, a start to the first member with a free voice in its slice (a stop + start: the members before it apply the stop,
+ * the one that takes it applies both, the ones after it the stop); taken / voices are what one engine would report.
+ * Sounds and clips are broadcast: every member holds every clip (any bus may play any clip), so the group's source HBM is n x one
+ * engine's; ids agree across members.
+ * zlhip_group_member: the borrowed engine of member r, for read-only and measurement calls (zlhip_last_timings, zlhip_memory_bytes,
+ * zlhip_device_name ...).  Commands, sounds and renders go through the group: a member driven directly leaves the group undefined. */
+#define ZLHIP_GROUP_MAX_MEMBERS 8
+enum { ZLHIP_GROUP_AUTO = 0, ZLHIP_GROUP_BUS_ALIGNED = 1, ZLHIP_GROUP_SPAN = 2 };
+typedef struct zlhip_group zlhip_group;
+typedef struct zlhip_group_config {
+    uint32_t struct_size;            /* sizeof(zlhip_group_config) */
+    int32_t  partition;              /* ZLHIP_GROUP_* */
+    int32_t  root;                   /* span: the member that holds the summed bus and the meters (default 0) */
+    int32_t  reserved;               /* 0 */
+} zlhip_group_config;
+void zlhip_group_config_default(zlhip_group_config *gc);
+/* cfg describes the WHOLE synth (global num_buses, voices_per_bus ...); cfg->device is ignored */
+int  zlhip_group_create(const int32_t *devices, int32_t n, const zlhip_config *cfg, const zlhip_group_config *gc, zlhip_group **out);
+void zlhip_group_destroy(zlhip_group *g);
+const char *zlhip_group_last_error(const zlhip_group *g);
+/* per member [n] each: its partition, first global bus and number of buses, first global slot and number of slots of each bus */
+int  zlhip_group_layout(zlhip_group *g, int32_t *partition, int32_t *first_bus, int32_t *num_buses, int32_t *first_slot, int32_t *slots);
+zlhip_engine *zlhip_group_member(zlhip_group *g, int32_t r);
+int  zlhip_group_sound_upload(zlhip_group *g, const float *left, const float *right, int32_t length, double sample_rate, int32_t *out_id);
+int  zlhip_group_sound_release(zlhip_group *g, int32_t id);
+int  zlhip_group_clip_set(zlhip_group *g, int32_t id, const zlhip_clip_params *p);
+int  zlhip_group_sound_rerender_batch(zlhip_group *g, const int32_t *ids, const zlhip_rerender_params *params, int32_t count);
+/* zlhip_handle_commands_voices over the whole synth (taken, voices optional) */
+int  zlhip_group_handle_commands(zlhip_group *g, const zlhip_clip_command *cmds, int32_t count, uint64_t current_tick, int32_t *taken,
+                                 int32_t *voices);
+int  zlhip_group_start_voice(zlhip_group *g, int32_t bus, int32_t slot, const zlhip_clip_command *cmd, uint64_t current_tick);
+int  zlhip_group_stop_voice(zlhip_group *g, int32_t bus, int32_t slot, int allow_tail_off);
+int  zlhip_group_update_voice(zlhip_group *g, int32_t bus, int32_t slot, const zlhip_clip_command *cmd);
+int  zlhip_group_voice_is_playing(zlhip_group *g, int32_t bus, int32_t slot);
+int  zlhip_group_bus_set_enabled(zlhip_group *g, int32_t bus, int enabled);
+/* Asynchronous, like zlhip_render_batch.  bus_out_dev: span only, optional, a DEVICE buffer on the root's device laid out
+ * [num_buses][2][nblocks*nframes] (NULL: the root's internal buffer, read with zlhip_group_read_bus); bus-aligned: must be NULL. */
+int  zlhip_group_render_batch(zlhip_group *g, int32_t nblocks, int32_t nframes, const zlhip_clock *clocks, float *bus_out_dev);
+int  zlhip_group_synchronize(zlhip_group *g);
+int  zlhip_group_read_bus(zlhip_group *g, float *out, size_t out_floats);               /* [num_buses][2][nblocks*nframes] */
+int  zlhip_group_voice_reports(zlhip_group *g, zlhip_voice_report *out, int32_t count);  /* [num_buses*voices_per_bus] */
+int  zlhip_group_levels_tick(zlhip_group *g, int32_t block_index, int32_t with_hold_bus, zlhip_levels *out);   /* [num_buses] */
+int  zlhip_group_block_peaks(zlhip_group *g, int32_t *out, size_t out_ints);           /* [nblocks][num_buses][2] */
+
 /* ---- JackPassthrough fan-out ---------------------------------------------------------------- */
 void zlhip_passthrough_params_default(zlhip_passthrough_params *p);
 /* in_dev: [num_buses][2][frames]; out_dev: [num_buses][6][frames] = dryL,dryR,fx1L,fx1R,fx2L,fx2R.

@@ -107,6 +107,14 @@ class RtCycleTrace(C.Structure):
     ]
 
 
+GROUP_MAX_MEMBERS = 8
+GROUP_AUTO, GROUP_BUS_ALIGNED, GROUP_SPAN = 0, 1, 2
+
+
+class GroupConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("partition", C.c_int32), ("root", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/zlhip.h declares: name -> (restype, argtypes)
 _F = C.POINTER(C.c_float)
 _E = C.c_void_p
@@ -165,6 +173,29 @@ SIGNATURES = {
     "zlhip_rt_stats": (C.c_int, [_E, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "zlhip_rt_residency": (C.c_int, [_E, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "zlhip_rt_last_cycle": (C.c_int, [_E, C.POINTER(RtCycleTrace)]),
+    # engine group (one synth over several engines / devices in one process)
+    "zlhip_group_config_default": (None, [C.POINTER(GroupConfig)]),
+    "zlhip_group_create": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(Config), C.POINTER(GroupConfig), C.POINTER(_E)]),
+    "zlhip_group_destroy": (None, [_E]),
+    "zlhip_group_last_error": (C.c_char_p, [_E]),
+    "zlhip_group_layout": (C.c_int, [_E, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "zlhip_group_member": (C.c_void_p, [_E, C.c_int32]),
+    "zlhip_group_sound_upload": (C.c_int, [_E, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_int32)]),
+    "zlhip_group_sound_release": (C.c_int, [_E, C.c_int32]),
+    "zlhip_group_clip_set": (C.c_int, [_E, C.c_int32, C.POINTER(ClipParams)]),
+    "zlhip_group_sound_rerender_batch": (C.c_int, [_E, C.POINTER(C.c_int32), C.POINTER(RerenderParams), C.c_int32]),
+    "zlhip_group_handle_commands": (C.c_int, [_E, C.POINTER(ClipCommand), C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "zlhip_group_start_voice": (C.c_int, [_E, C.c_int32, C.c_int32, C.POINTER(ClipCommand), C.c_uint64]),
+    "zlhip_group_stop_voice": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_int]),
+    "zlhip_group_update_voice": (C.c_int, [_E, C.c_int32, C.c_int32, C.POINTER(ClipCommand)]),
+    "zlhip_group_voice_is_playing": (C.c_int, [_E, C.c_int32, C.c_int32]),
+    "zlhip_group_bus_set_enabled": (C.c_int, [_E, C.c_int32, C.c_int]),
+    "zlhip_group_render_batch": (C.c_int, [_E, C.c_int32, C.c_int32, C.POINTER(Clock), C.c_void_p]),
+    "zlhip_group_synchronize": (C.c_int, [_E]),
+    "zlhip_group_read_bus": (C.c_int, [_E, C.c_void_p, C.c_size_t]),
+    "zlhip_group_voice_reports": (C.c_int, [_E, C.POINTER(VoiceReport), C.c_int32]),
+    "zlhip_group_levels_tick": (C.c_int, [_E, C.c_int32, C.c_int32, C.POINTER(Levels)]),
+    "zlhip_group_block_peaks": (C.c_int, [_E, C.c_void_p, C.c_size_t]),
 }
 
 # ZLHIP_LIBRARY selects another build of the same library (A/B measurements of kernel variants); never a fallback
@@ -198,6 +229,12 @@ class UnitLevels(C.Structure):
 
 class ZlHipError(RuntimeError):
     pass
+
+
+def check_group(lib, group, rc, what):
+    if rc < 0:
+        raise ZlHipError(f"{what}: {lib.zlhip_strerror(rc).decode()} ({rc}) {lib.zlhip_group_last_error(group).decode()}")
+    return rc
 
 
 def check(lib, engine, rc, what):

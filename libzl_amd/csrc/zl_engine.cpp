@@ -23,6 +23,7 @@
 #include "../../include/zlhip.h"
 #include "zl_host.h"
 #include "zl_kernels.h"
+#include "zl_member.h"
 #include "zl_order.h"
 #include "zl_plan.h"
 #include "zl_stretch.h"
@@ -2221,3 +2222,13 @@ int zlhip_memory_bytes(zlhip_engine *e, uint64_t *total_device_bytes, uint64_t *
 }
 
 }  // extern "C"
+
+// ---- engine group (zl_group.cpp): what a group does to its members beyond the C-ABI (zl_member.h) ----------------------
+ZlHostControl *zl_member_control(zlhip_engine *e, int *rc)
+{
+    *rc = refresh_host_voices(e);                                  // voices that ended on the device free their slots first
+    return *rc == ZLHIP_OK ? &e->hc : nullptr;
+}
+hipStream_t zl_member_stream(const zlhip_engine *e) { return e->stream; }
+float *zl_member_last_bus(const zlhip_engine *e) { return e->lastBus; }
+ZlBlockLevels *zl_member_levels(const zlhip_engine *e) { return e->dLevels; }

@@ -16,6 +16,17 @@ int zl_launch_passthrough(const void *params_dev, const float *in, float *out, i
 int zl_launch_deliver(const float *bus, void *out, int pcm16, int B, long long in_stride, long long off, long long frames, long long total, hipStream_t s);
 int zl_launch_interleave(const float *L, const float *R, float *dst, int length, int pad, hipStream_t s);
 int zl_launch_reduce_scan(const float *pieces, int npieces, long long stride, long long units, int N, int off, float *out, ZlUnitLevels *lv, hipStream_t s);
+// the spanning-bus sum of an engine group (zl_k_group_reduce_scan): the members' partial buses [B][2][K*N] in rank order, the
+// root's bus and level table, the pairs (k * B + b) this launch sums
+#define ZL_GROUP_MAX_MEMBERS 8
+struct ZlGroupReduceArgs {
+    const float *part[ZL_GROUP_MAX_MEMBERS];
+    float *out;
+    ZlBlockLevels *levels;
+    long long p0, p1;
+    int B, K, N, off;
+};
+int zl_launch_group_reduce(const ZlGroupReduceArgs &a, int members, hipStream_t s);
 int zl_launch_levels_import(const ZlUnitLevels *units, ZlBlockLevels *levels, int B, int K, hipStream_t s);
 int zl_launch_rt_loop(const ZlBatch &A, void *mailbox_dev, void *dev_state, unsigned long long first_seq, unsigned long long idle_ticks, float *gain_out,
                       ZlReport *host_reports, float *host_gain, ZlOpRange *dev_ranges, int vw, int threads, hipStream_t s);

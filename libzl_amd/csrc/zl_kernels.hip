@@ -1771,6 +1771,52 @@ __global__ void __launch_bounds__(256) zl_k_reduce_scan(const float *pieces, int
     if (lane == 0) { ZlUnitLevels r; r.peak = pk; r.sumsq = sq; lv[u] = r; }
 }
 
+// Spanning-bus sum of an engine group (zlhip_group_*, span partition): every member rendered all buses with its slice of each bus's
+// voices into a partial bus [B][2][K*N] on its own device.  One wave per (block, bus) pair, pair = k * B + b (the ZlBlockLevels order),
+// both channels, so the wave writes its ZlBlockLevels whole.  Per sample it sums the NM members' partials IN RANK ORDER from 0,
+// ((0 + p0) + p1) + ... -- K3's mix-group order and zl_k_reduce_scan's -- with all 2 * NM loads in flight before the ordered adds, stores
+// the sum into the root's bus and scans it exactly as zl_scan_rows does (front frame with `off`, 64-frame tiles, zl_wave_sum per tile).
+// Member r launches it on its own device for its share [p0, p1) of the pairs; the other members' partials are read over xGMI (peer
+// access).  A pair is read and written by one wave only, so the root's own partial may be the output (summed in place).
+template <int NM>
+__global__ void __launch_bounds__(256) zl_k_group_reduce_scan(const ZlGroupReduceArgs a)
+{
+    const long long pair = a.p0 + (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pair >= a.p1) return;                                      // whole waves leave
+    const int lane = threadIdx.x & 63;
+    const int N = a.N;
+    const int k = (int)(pair / a.B), b = (int)(pair - (long long)k * a.B);
+    const long long KN = (long long)a.K * N;
+    const long long rowL = (long long)b * 2 * KN + (long long)k * N, rowR = rowL + KN;
+    auto sum2 = [&](int f, float &l, float &r) {
+        float xl[NM], xr[NM];
+#pragma unroll
+        for (int j = 0; j < NM; ++j) { xl[j] = a.part[j][rowL + f]; xr[j] = a.part[j][rowR + f]; }
+        l = 0.0f; r = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NM; ++j) { l += xl[j]; r += xr[j]; }
+    };
+    int pkL = 0, pkR = 0; float sqL = 0.0f, sqR = 0.0f;
+    if (a.off) {                                                   // the frame in front of the first tile (every lane: one address)
+        float l, r;
+        sum2(0, l, r);
+        if (lane == 0) { a.out[rowL] = l; a.out[rowR] = r; }
+        pkL = zl_sample_to_peak_int(l); pkR = zl_sample_to_peak_int(r);
+        sqL = l * l; sqR = r * r;
+    }
+    for (int t0 = a.off; t0 < N; t0 += 64) {
+        const int f = t0 + lane;
+        float l = 0.0f, r = 0.0f;
+        if (f < N) { sum2(f, l, r); a.out[rowL + f] = l; a.out[rowR + f] = r; }
+        const int pa = zl_sample_to_peak_int(l), pc = zl_sample_to_peak_int(r);
+        pkL = pa > pkL ? pa : pkL; pkR = pc > pkR ? pc : pkR;
+        sqL += zl_wave_sum(l * l); sqR += zl_wave_sum(r * r);      // wave-uniform running sums, tile order
+    }
+    ZlBlockLevels o;
+    o.peak_l = zl_wave_max_nonneg(pkL); o.peak_r = zl_wave_max_nonneg(pkR); o.sumsq_l = sqL; o.sumsq_r = sqR;
+    if (lane == 0) a.levels[pair] = o;
+}
+
 // unit levels of a whole bus ([bus][channel][block], as the exchange gathers them) -> the engine's per-block levels
 __global__ void zl_k_levels_import(const ZlUnitLevels *units, ZlBlockLevels *levels, int B, int K)
 {
@@ -2061,6 +2107,26 @@ int zl_launch_levels_tick(ZlLevelsState *state, const ZlBlockLevels *levels, int
 int zl_launch_reduce_scan(const float *pieces, int npieces, long long stride, long long units, int N, int off, float *out, ZlUnitLevels *lv, hipStream_t s)
 {
     hipLaunchKernelGGL(zl_k_reduce_scan, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, pieces, npieces, stride, units, N, off, out, lv);
+    ZL_LAUNCH_CHECK();
+    return 0;
+}
+
+int zl_launch_group_reduce(const ZlGroupReduceArgs &a, int members, hipStream_t s)
+{
+    const long long pairs = a.p1 - a.p0;
+    if (pairs <= 0) return 0;
+    const dim3 grid((unsigned)((pairs + 3) / 4)), block(256);
+    switch (members) {
+    case 1: hipLaunchKernelGGL(zl_k_group_reduce_scan<1>, grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL(zl_k_group_reduce_scan<2>, grid, block, 0, s, a); break;
+    case 3: hipLaunchKernelGGL(zl_k_group_reduce_scan<3>, grid, block, 0, s, a); break;
+    case 4: hipLaunchKernelGGL(zl_k_group_reduce_scan<4>, grid, block, 0, s, a); break;
+    case 5: hipLaunchKernelGGL(zl_k_group_reduce_scan<5>, grid, block, 0, s, a); break;
+    case 6: hipLaunchKernelGGL(zl_k_group_reduce_scan<6>, grid, block, 0, s, a); break;
+    case 7: hipLaunchKernelGGL(zl_k_group_reduce_scan<7>, grid, block, 0, s, a); break;
+    case 8: hipLaunchKernelGGL(zl_k_group_reduce_scan<8>, grid, block, 0, s, a); break;
+    default: return (int)hipErrorInvalidValue;
+    }
     ZL_LAUNCH_CHECK();
     return 0;
 }

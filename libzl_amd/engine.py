@@ -17,7 +17,7 @@ from . import _abi
 from ._abi import (Clock, ClipCommand, ClipParams, Config, Levels, PassthroughParams, RerenderParams, Timings, VoiceReport,
                    MODE_FAITHFUL, MODE_FIX_DELAY, MODE_FIX_GAIN, MODE_HERMITE, ZlHipError)
 
-__all__ = ["SamplerSynth", "Clock", "ClipCommand", "ClipParams", "Levels", "PassthroughParams", "VoiceReport",
+__all__ = ["SamplerSynth", "SamplerSynthGroup", "Clock", "ClipCommand", "ClipParams", "Levels", "PassthroughParams", "VoiceReport",
            "MODE_FAITHFUL", "MODE_FIX_GAIN", "MODE_FIX_DELAY", "MODE_HERMITE", "ZlHipError", "clip_command", "synthetic_clocks", "running_playhead"]
 
 
@@ -422,3 +422,184 @@ class SamplerSynth:
 
     def bus_device_ptr(self) -> int:
         return self._lib.zlhip_bus_device_ptr(self._e)
+
+
+class SamplerSynthGroup:
+    """One synth over several engines in one process (zlhip_group_*, include/zlhip.h): one member engine per entry of `devices`
+    (a device may repeat: [0, 0] is two members on one GPU).  `num_buses` / `voices_per_bus` and the keyword arguments describe the
+    WHOLE synth, as for SamplerSynth.  partition: "auto" (bus-aligned when num_buses >= members, else span), "bus" or "span"; root:
+    the member that holds the summed bus and the meters in span mode.  Buses, slots, voices and midi channels are global."""
+
+    _PARTITIONS = {"auto": _abi.GROUP_AUTO, "bus": _abi.GROUP_BUS_ALIGNED, "bus_aligned": _abi.GROUP_BUS_ALIGNED, "span": _abi.GROUP_SPAN}
+
+    def __init__(self, devices: Sequence[int], num_buses: int = 12, voices_per_bus: int = 8, *, partition: str = "auto", root: int = 0,
+                 max_frames: int = 1024, max_batch_blocks: int = 64, max_sounds: int = 1024, mode: int = MODE_FAITHFUL,
+                 playback_sample_rate: float = 48000.0, sound_arena_bytes: int = 256 << 20, voices_per_task: int = 0,
+                 plan_window_blocks: int = 0, rt_idle_timeout_us: int = 0, sound_arena_max_bytes: int = 0):
+        self._lib = _abi.load()
+        cfg = Config()
+        self._lib.zlhip_config_default(C.byref(cfg))
+        cfg.num_buses = num_buses
+        cfg.voices_per_bus = voices_per_bus
+        cfg.max_frames = max_frames
+        cfg.max_batch_blocks = max_batch_blocks
+        cfg.max_sounds = max_sounds
+        cfg.mode = mode
+        cfg.playback_sample_rate = playback_sample_rate
+        cfg.sound_arena_bytes = sound_arena_bytes
+        cfg.voices_per_task = voices_per_task
+        cfg.plan_window_blocks = plan_window_blocks
+        cfg.rt_idle_timeout_us = rt_idle_timeout_us
+        cfg.sound_arena_max_bytes = sound_arena_max_bytes
+        gc = _abi.GroupConfig()
+        self._lib.zlhip_group_config_default(C.byref(gc))
+        gc.partition = self._PARTITIONS[partition]
+        gc.root = root
+        self.cfg, self.gcfg = cfg, gc
+        self.devices = list(devices)
+        self.n = len(self.devices)
+        devs = (C.c_int32 * max(1, self.n))(*self.devices)
+        self._g = C.c_void_p()
+        rc = self._lib.zlhip_group_create(devs, self.n, C.byref(cfg), C.byref(gc), C.byref(self._g))
+        if rc != 0:
+            raise ZlHipError(f"zlhip_group_create: {self._lib.zlhip_strerror(rc).decode()} ({rc}) {self._lib.zlhip_group_last_error(None).decode()}")
+        self.num_buses = num_buses
+        self.voices_per_bus = voices_per_bus
+        self.num_voices = num_buses * voices_per_bus
+        self._last = (0, 0)
+
+    # -- lifecycle --------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_g", None) and self._g.value:
+            self._lib.zlhip_group_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _ck(self, rc, what):
+        return _abi.check_group(self._lib, self._g, rc, what)
+
+    @property
+    def handle(self):
+        return self._g
+
+    def layout(self):
+        """per member: dict(partition, first_bus, num_buses, first_slot, slots) -- partition "bus" or "span"."""
+        arrs = [(C.c_int32 * self.n)() for _ in range(5)]
+        self._ck(self._lib.zlhip_group_layout(self._g, *arrs), "group_layout")
+        names = {_abi.GROUP_BUS_ALIGNED: "bus", _abi.GROUP_SPAN: "span"}
+        return [dict(partition=names[arrs[0][r]], first_bus=arrs[1][r], num_buses=arrs[2][r], first_slot=arrs[3][r], slots=arrs[4][r])
+                for r in range(self.n)]
+
+    def member(self, r: int) -> int:
+        """the borrowed zlhip_engine * of member r (read-only and measurement calls: zlhip_last_timings, zlhip_memory_bytes ...)"""
+        return self._lib.zlhip_group_member(self._g, r)
+
+    def device_name(self) -> str:
+        buf = C.create_string_buffer(256)
+        _abi.check(self._lib, C.c_void_p(self.member(0)), self._lib.zlhip_device_name(self.member(0), buf, 256), "device_name")
+        return buf.value.decode()
+
+    # -- clips (broadcast to every member) ----------------------------------------------------
+    def register_clip(self, left: np.ndarray, right: Optional[np.ndarray], sample_rate: float) -> int:
+        left = np.ascontiguousarray(left, dtype=np.float32)
+        rp = None
+        if right is not None:
+            right = np.ascontiguousarray(right, dtype=np.float32)
+            assert right.shape == left.shape
+            rp = right.ctypes.data
+        out = C.c_int32(-1)
+        self._ck(self._lib.zlhip_group_sound_upload(self._g, left.ctypes.data, rp, left.shape[0], float(sample_rate), C.byref(out)), "group_sound_upload")
+        return out.value
+
+    def unregister_clip(self, clip: int):
+        self._ck(self._lib.zlhip_group_sound_release(self._g, clip), "group_sound_release")
+
+    def default_clip_params(self, duration_seconds: float) -> ClipParams:
+        p = ClipParams()
+        self._lib.zlhip_clip_params_default(C.byref(p), float(duration_seconds))
+        return p
+
+    def set_clip_params(self, clip: int, params: ClipParams):
+        self._ck(self._lib.zlhip_group_clip_set(self._g, clip, C.byref(params)), "group_clip_set")
+
+    def rerender_clips(self, clips: Sequence[int], gain_db=0.0, pitch=0.0, speed=1.0):
+        """SamplerSynth.rerender_clips on every member (zlhip_group_sound_rerender_batch)"""
+        n = len(clips)
+        col = lambda v: [float(x) for x in v] if isinstance(v, (list, tuple, np.ndarray)) else [float(v)] * n
+        g, p, s = col(gain_db), col(pitch), col(speed)
+        ids = (C.c_int32 * n)(*clips)
+        params = (RerenderParams * n)(*[RerenderParams(g[i], p[i], s[i], 0) for i in range(n)])
+        self._ck(self._lib.zlhip_group_sound_rerender_batch(self._g, ids, params, n), "group_sound_rerender_batch")
+
+    def rerender_clip(self, clip: int, gain_db: float = 0.0, pitch: float = 0.0, speed: float = 1.0):
+        self.rerender_clips([clip], gain_db, pitch, speed)
+
+    # -- commands (global buses, slots and midi channels) --------------------------------------
+    def handle_clip_commands(self, cmds: Sequence[ClipCommand], current_tick: int = 0, want_voices: bool = False):
+        n = len(cmds)
+        arr = (ClipCommand * max(1, n))(*cmds)
+        taken = (C.c_int32 * max(1, n))()
+        voices = (C.c_int32 * max(1, n))()
+        self._ck(self._lib.zlhip_group_handle_commands(self._g, arr, n, current_tick, taken, voices), "group_handle_commands")
+        return (list(taken)[:n], list(voices)[:n]) if want_voices else list(taken)[:n]
+
+    def handle_clip_command(self, cmd: ClipCommand, current_tick: int = 0) -> int:
+        return self.handle_clip_commands([cmd], current_tick)[0]
+
+    def set_bus_enabled(self, bus: int, enabled: bool) -> None:
+        self._ck(self._lib.zlhip_group_bus_set_enabled(self._g, bus, 1 if enabled else 0), "group_bus_set_enabled")
+
+    def start_voice(self, bus: int, slot: int, cmd: ClipCommand, current_tick: int = 0) -> int:
+        return self._ck(self._lib.zlhip_group_start_voice(self._g, bus, slot, C.byref(cmd), current_tick), "group_start_voice")
+
+    def stop_voice(self, bus: int, slot: int, allow_tail_off: bool = True) -> int:
+        return self._ck(self._lib.zlhip_group_stop_voice(self._g, bus, slot, 1 if allow_tail_off else 0), "group_stop_voice")
+
+    def update_voice(self, bus: int, slot: int, cmd: ClipCommand) -> int:
+        return self._ck(self._lib.zlhip_group_update_voice(self._g, bus, slot, C.byref(cmd)), "group_update_voice")
+
+    def voice_is_playing(self, bus: int, slot: int) -> bool:
+        return self._ck(self._lib.zlhip_group_voice_is_playing(self._g, bus, slot), "group_voice_is_playing") == 1
+
+    # -- render -----------------------------------------------------------------------------
+    def render_batch(self, nblocks: int, nframes: int, clocks, bus_out_dev: Optional[int] = None):
+        """Asynchronous.  bus_out_dev (span only): a device buffer [num_buses][2][nblocks*nframes] on the root's device."""
+        self._ck(self._lib.zlhip_group_render_batch(self._g, nblocks, nframes, clocks, bus_out_dev), "group_render_batch")
+        self._last = (nblocks, nframes)
+
+    def synchronize(self):
+        self._ck(self._lib.zlhip_group_synchronize(self._g), "group_synchronize")
+
+    def read_bus(self) -> np.ndarray:
+        K, N = self._last
+        out = np.empty((self.num_buses, 2, K * N), dtype=np.float32)
+        self._ck(self._lib.zlhip_group_read_bus(self._g, out.ctypes.data, out.size), "group_read_bus")
+        return out
+
+    def voice_reports(self):
+        arr = (VoiceReport * self.num_voices)()
+        self._ck(self._lib.zlhip_group_voice_reports(self._g, arr, self.num_voices), "group_voice_reports")
+        return arr
+
+    # -- levels -----------------------------------------------------------------------------
+    def levels_tick(self, block_index: int = -1, with_hold_bus: int = -1):
+        arr = (Levels * self.num_buses)()
+        self._ck(self._lib.zlhip_group_levels_tick(self._g, block_index, with_hold_bus, arr), "group_levels_tick")
+        return arr
+
+    def block_peaks(self) -> np.ndarray:
+        K, _ = self._last
+        out = np.empty((K, self.num_buses, 2), dtype=np.int32)
+        self._ck(self._lib.zlhip_group_block_peaks(self._g, out.ctypes.data, out.size), "group_block_peaks")
+        return out
