@@ -66,7 +66,7 @@ _INC = os.path.join("..", "..", "include")
 SOURCE_DEPS = {
     "zl_kernels.hip": ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_kernels.h"],
     "zl_stretch.hip": ["zl_types.h", "zl_stretch.h"],
-    "zl_engine.cpp": ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h")],
+    "zl_engine.cpp": ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h")],
     "zl_group.cpp": ["zl_types.h", "zl_plan.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_group.h", os.path.join(_INC, "zlhip.h")],
     "zl_libzl.cpp": ["zl_render.h", "zl_types.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h"), os.path.join(_INC, "libzl_hotpath.h")],
 }
@@ -213,6 +213,23 @@ def build_order_harness(force: bool = False) -> str:
         if res.returncode != 0:
             sys.stderr.write(res.stdout + res.stderr)
             raise RuntimeError("building the CPU phase-order harness failed")
+    return target
+
+
+def build_ongrid_harness(force: bool = False) -> str:
+    """Host build of K2's on-grid form (zl_render.h, tests/cpu_harness/ongrid_host.cpp) for the CPU tier."""
+    hdir = os.path.join(ROOT, "tests", "cpu_harness")
+    target = os.path.join(hdir, "_build", "libzl_ongrid_host.so")
+    src = os.path.join(hdir, "ongrid_host.cpp")
+    deps = [src] + [os.path.join(CSRC, h) for h in ("zl_types.h", "zl_render.h")]
+    if force or _stale(target, deps):
+        os.makedirs(os.path.dirname(target), exist_ok=True)
+        cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
+               "-Wl,-Bsymbolic", "-I", CSRC, "-o", target, src]
+        res = subprocess.run(cmd, capture_output=True, text=True)
+        if res.returncode != 0:
+            sys.stderr.write(res.stdout + res.stderr)
+            raise RuntimeError("building the CPU on-grid harness failed")
     return target
 
 

@@ -26,6 +26,7 @@
 #include "zl_member.h"
 #include "zl_order.h"
 #include "zl_plan.h"
+#include "zl_render.h"
 #include "zl_stretch.h"
 #include "zl_types.h"
 
@@ -155,6 +156,7 @@ struct zlhip_engine {
     // parameter table the resident kernel reads ([B], mapped host memory) and its version (never 0; moved when an entry changes)
     float *hFan = nullptr, *hFanDev = nullptr;
     ZlPassParams *hPassRt = nullptr, *hPassRtDev = nullptr;
+    uint32_t *hNonFinite = nullptr, *hNonFiniteDev = nullptr;   // mapped host word: zl_k_interleave sets it when an uploaded sample is NaN or infinite
     uint32_t passSeq = 1;
     // zero-copy delivery of a real-time cycle: when the caller's out_left / out_right (/ fan_out) are page-locked and mapped (zlhip_host_alloc,
     // hipHostMalloc, hipHostRegister) the kernels write them directly -- no copy on the host behind the cycle (24 KB + 72 KB for 12 buses:
@@ -420,7 +422,7 @@ void zlhip_engine_destroy(zlhip_engine *e)
     for (hipEvent_t ev : e->bnc.winEv) if (ev) (void)hipEventDestroy(ev);
     if (e->planStream) (void)hipStreamDestroy(e->planStream);
     if (e->asmStream) (void)hipStreamDestroy(e->asmStream);
-    void *host[] = { e->hBus, e->hLevelState, e->hFan, e->hPassRt };
+    void *host[] = { e->hBus, e->hLevelState, e->hFan, e->hPassRt, e->hNonFinite };
     for (void *p : host) if (p) (void)hipHostFree(p);
     for (hipEvent_t ev : e->stEv) if (ev) (void)hipEventDestroy(ev);
     if (e->evJoin) (void)hipEventDestroy(e->evJoin);
@@ -585,6 +587,8 @@ int zlhip_engine_create(const zlhip_config *cfg_in, zlhip_engine **out)
     chk(hipHostMalloc((void **)&e->hPassRt, B * sizeof(ZlPassParams)), "hPassRt");
     if (rc == ZLHIP_OK) { chk(hipHostGetDevicePointer((void **)&e->hPassRtDev, e->hPassRt, 0), "map hPassRt"); std::memset(e->hPassRt, 0xff, B * sizeof(ZlPassParams)); }
     chk(hipHostMalloc((void **)&e->hLevelState, B * sizeof(ZlLevelsState)), "hLevelState");
+    chk(hipHostMalloc((void **)&e->hNonFinite, sizeof(uint32_t)), "hNonFinite");
+    if (rc == ZLHIP_OK) { chk(hipHostGetDevicePointer((void **)&e->hNonFiniteDev, e->hNonFinite, 0), "map hNonFinite"); *e->hNonFinite = 1u; }
     chk(hipEventCreateWithFlags(&e->evJoin, hipEventDisableTiming), "hipEventCreate");
     chk(hipEventCreateWithFlags(&e->evPlanTail, hipEventDisableTiming), "hipEventCreate");
     if (rc == ZLHIP_OK) {
@@ -714,7 +718,7 @@ static int alloc_sound_slot(zlhip_engine *e, int32_t length, int channels, doubl
     const size_t floats = extent_floats(length, channels);
     size_t off = 0;
     { const int rc = alloc_extent(e, floats, &off); if (rc != ZLHIP_OK) return rc; }
-    ZlSound s; s.offset = off; s.length = length; s.channels = channels; s.sample_rate = sample_rate;
+    ZlSound s; s.offset = off; s.length = length; s.channels = channels; s.sample_rate = sample_rate; s.flags = 0; s.pad = 0;
     *dst = arena_ptr(e, off);
     e->hc.sounds[id] = s;
     e->hc.soundUsed[id] = 1;
@@ -774,12 +778,23 @@ static void free_sound_slot(zlhip_engine *e, int id)
     free_extent(e, roff, rn);
 }
 
-static int publish_sound(zlhip_engine *e, int id)
+// dev_checked: the extent was written by zl_k_interleave, which leaves its verdict on the samples in *hNonFinite -- read after the wait
+// that is here anyway; a finite source then gets ZL_SOUND_FINITE (the table entry goes to the device once more, in stream order)
+// ZL_K2_ONGRID: 0 = K2 never takes the one-tap form of on-grid unit-step chunks, 1 = wherever its condition holds (default); read per call
+// (A/B runs of one build, tests that compare both forms).  Results do not depend on it.
+static int zl_ongrid_switch() { const char *v = std::getenv("ZL_K2_ONGRID"); return (v ? std::atoi(v) : 1) != 0 ? 1 : 0; }
+
+static int publish_sound(zlhip_engine *e, int id, bool dev_checked = false)
 {
     ZL_HIP(e, hipMemcpyAsync(e->dSounds + id, &e->hc.sounds[id], sizeof(ZlSound), hipMemcpyHostToDevice, e->stream));
     zlhip_clip_params p;
     zlhip_clip_params_default(&p, (float)(e->hc.sounds[id].length / e->hc.sounds[id].sample_rate));
     { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    if (dev_checked && __atomic_load_n(e->hNonFinite, __ATOMIC_ACQUIRE) == 0u) {
+        e->hc.sounds[id].flags |= ZL_SOUND_FINITE;
+        e->origSounds[(size_t)id].flags |= ZL_SOUND_FINITE;
+        ZL_HIP(e, hipMemcpyAsync(e->dSounds + id, &e->hc.sounds[id], sizeof(ZlSound), hipMemcpyHostToDevice, e->stream));
+    }
     e->hc.forget_clip_params(id);                                  // (the first edit of a slot carries the whole record)
     return zlhip_clip_set(e, id, &p);
 }
@@ -822,13 +837,14 @@ static int sound_upload_device(zlhip_engine *e, const float *left_dev, const flo
         ZlQuiesce quiet(e);
         st = hipDeviceSynchronize();
     }
-    int krc = st == hipSuccess ? zl_launch_interleave(left_dev, right_dev, dst, length, 8, e->stream) : (int)st;
+    __atomic_store_n(e->hNonFinite, 0u, __ATOMIC_RELEASE);         // (nothing of this engine's is in flight that writes it: see the waits above)
+    int krc = st == hipSuccess ? zl_launch_interleave(left_dev, right_dev, dst, length, 8, e->hNonFiniteDev, e->stream) : (int)st;
     if (krc != 0) {
         free_sound_slot(e, *out_id); *out_id = -1;
         e->err = std::string("sound_upload_device: ") + hipGetErrorString((hipError_t)krc);
         return ZLHIP_ERR_HIP;
     }
-    rc = publish_sound(e, *out_id);
+    rc = publish_sound(e, *out_id, true);
     if (rc != ZLHIP_OK) { free_sound_slot(e, *out_id); *out_id = -1; }
     return rc;
 }
@@ -846,6 +862,10 @@ int zlhip_sound_upload(zlhip_engine *e, const float *left, const float *right, i
     std::vector<float> tmp(((size_t)length + 8) * ch, 0.0f);
     if (right) for (int32_t i = 0; i < length; ++i) { tmp[2 * (size_t)i] = left[i]; tmp[2 * (size_t)i + 1] = right[i]; }
     else std::memcpy(tmp.data(), left, (size_t)length * sizeof(float));
+    if (zl_all_finite(tmp.data(), tmp.size())) {                   // every sample looked at: K2's on-grid form may drop the second tap (zl_render.h)
+        e->hc.sounds[*out_id].flags |= ZL_SOUND_FINITE;
+        e->origSounds[(size_t)*out_id].flags |= ZL_SOUND_FINITE;
+    }
     hipError_t st = hipMemcpyAsync(dst, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice, e->stream);
     rc = st == hipSuccess ? engine_wait(e) : ZLHIP_ERR_HIP;
     if (st != hipSuccess) e->err = std::string("sound_upload: ") + hipGetErrorString(st);
@@ -976,7 +996,8 @@ int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_
         const ZlSound cur = e->hc.sounds[id];
         free_extent(e, (size_t)cur.offset, e->renderFloats[(size_t)id]);
         ZlSound s = e->origSounds[(size_t)id];
-        if (!ident[(size_t)i]) { s.offset = newOff[(size_t)i]; s.length = (int32_t)geo[(size_t)i].N; }
+        // (a rendered extent has not been looked at: it plays without ZL_SOUND_FINITE; identity parameters play the original, with its own flag)
+        if (!ident[(size_t)i]) { s.offset = newOff[(size_t)i]; s.length = (int32_t)geo[(size_t)i].N; s.flags &= ~(int32_t)ZL_SOUND_FINITE; }
         e->hc.sounds[id] = s;
         e->renderFloats[(size_t)id] = newFloats[(size_t)i];
         e->renderOffsets[(size_t)id].clear();
@@ -1295,6 +1316,7 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
         A.NB = std::max(1, std::min(128 / A.VPB, A.B));
     A.clocks_regular = regular ? 1 : 0;
     A.mode = e->cfg.mode;
+    A.ongrid = zl_ongrid_switch();
     A.staged = (e->staged && !e->trace && nframes % 64 == 0) ? 1 : 0;   // (the position trace lives in the gather paths; a staged wave is a whole 64-frame tile)
     A.sounds = e->dSounds; A.clips = e->dClips; A.arena = e->arena;
     A.voices = e->dVoices; A.reports = c.dReports; A.pass_cache = e->dPassCache;
@@ -1710,6 +1732,7 @@ static int rt_start(zlhip_engine *e, int nframes)
     A.clocks_regular = 1; A.inline_clock = 1; A.fuse_assemble = 1;
     A.rt_stamps = e->rt.stampsOn ? 1 : 0;
     A.mode = e->cfg.mode;
+    A.ongrid = zl_ongrid_switch();                                 // (the resident kernel keeps the value it was started with)
     A.sounds = e->dSounds; A.clips = e->dClips; A.arena = e->arena; A.voices = e->dVoices; A.reports = c.dReports; A.pass_cache = e->dPassCache;
     A.bus = e->hBusDev; A.stats = nullptr; A.levels = e->dLevels;
     A.fan = e->hFanDev; A.pass = e->hPassRtDev;                     // a cycle says whether it wants the fan-out (ZlRtShared::fan_seq)

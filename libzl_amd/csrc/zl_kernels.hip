@@ -289,6 +289,12 @@ typedef float zl_f2a4 __attribute__((ext_vector_type(2), aligned(4)));
 #ifndef ZL_K2_U
 #define ZL_K2_U     8        // gathers in flight per wavefront
 #endif
+#ifndef ZL_K2_U_ONGRID
+// loads in flight per wavefront in the on-grid chunk (2 registers a voice): ZL_K2_U, or twice that (two such chunks in a row go as one).
+// 16 measured and NOT shipped: + 2 % on the headline, but the time-order headline kernel gains scratch memory, the 64- / 128-frame kernels go
+// to 100 bytes of it and the FIX_DELAY kernels from 5 to 4 waves per SIMD (profiles/round6_ongrid_bench.txt)
+#define ZL_K2_U_ONGRID 8
+#endif
 #ifndef ZL_K2_U_HERMITE
 #define ZL_K2_U_HERMITE 4    // voices per chunk with 4-tap interpolation (two 16-byte gathers per voice)
 #endif
@@ -509,6 +515,44 @@ static __device__ __forceinline__ void zl_k2_chunk_simple(const ZlBatch &A, cons
     ZlSimpleTaps<(MODE & ZL_MODE_HERMITE) != 0, U> T;
     zl_k2_simple_issue<MODE, SEG2, UNIT, INT, U>(A, s_plan, s_vc, s_unit, c0, f, fd, T);
     zl_k2_simple_mix<MODE, INT, U>(A, s_plan, s_vc, s_unit, c0, vfirst, wantPeak, T, accL, accR);
+}
+
+// ON-GRID chunks (zl_render.h, zl_voice_ongrid): every voice of the chunk plays at its own rate from an integer position inside a
+// source known to be finite.  alpha = 0 in every frame, so the lane loads its OWN frame only -- one 8-byte load per voice (4 bytes
+// mono), 512 contiguous bytes per wave instead of a 1 KiB overlapping gather -- and mixes it with zl_mix_frame_ongrid: no second tap,
+// no gain chain, no read of the gains from LDS.  U loads in flight, the voices accumulated in voice order, the report as in
+// zl_k2_simple_mix.  Same bus and reports as the two-tap form, bit for bit.
+typedef float zl_f2a8 __attribute__((ext_vector_type(2), aligned(8)));
+template <bool MONO, int U>
+static __device__ __forceinline__ void zl_k2_chunk_ongrid(const ZlBatch &A, const ZlVoiceConst *s_vc, const ZlUnit *s_unit,
+                                                           int c0, int vfirst, int f, bool wantPeak, float &accL, float &accR)
+{
+    zl_f2a8 d2[MONO ? 1 : U];
+    float   d1[MONO ? U : 1];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int i = c0 + u;
+        const int pos = s_unit[i].ipos + f;                       // interior: 0 <= pos < duration for every frame of the block
+        const uint64_t so = s_vc[i].src_offset;
+        const char *src = reinterpret_cast<const char *>(A.arena + (((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(so >> 32)) << 32)
+                                                                    | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)so)));
+        // (sources start on 16-byte boundaries: a stereo frame is 8-byte aligned)
+        if (MONO) d1[u] = *reinterpret_cast<const float *>(src + ((uint32_t)pos << 2));
+        else      d2[u] = *reinterpret_cast<const zl_f2a8 *>(src + ((uint32_t)pos << 3));
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int i = c0 + u;
+        float l, r;
+        zl_mix_frame_ongrid(MONO ? d1[u] : d2[u].x, MONO ? d1[u] : d2[u].y, s_vc[i].lpan, s_vc[i].rpan, l, r);
+        accL += l; accR += r;                                     // :218-221 (index shift applied at the store)
+        if (wantPeak) {                                           // :213-216, signed peak from 0 (Q6)
+            const float ng = l + r;
+            float pk = ng > 0.0f ? ng : 0.0f;
+            pk = zl_wave_max(pk);
+            if ((threadIdx.x & 63) == 0 && pk > 0.0f) atomicMax(&A.reports[vfirst + i].peak_bits, __float_as_uint(pk));
+        }
+    }
 }
 
 // UNIT + INT chunks with SHARED taps (ZL_K2_UNIT_SHARE=1): at the playback rate inside an exact run, lane f + 1's first tap IS lane
@@ -1149,6 +1193,9 @@ static __device__ __forceinline__ void zl_k2_body(const ZlBatch &A, const unsign
                 const bool interior = pl.nseg == 1 && pl.P0 >= (HM ? 1.0 : 0.0) && Pmax < (double)(vc.sample_duration - (HM ? 1 : 0));
                 cls |= 4 | (pl.nseg == 2 ? 8 : 0) | (vc.channels == 1 ? 16 : 0) | ((pl.nseg == 1 && pl.step == 1.0 && pl.P0 < 1073741824.0) ? 32 : 0)
                      | (interior ? 64 : 0);
+                // 128 = "on-grid": a unit-step interior block from an integer position of a source known to be finite -- alpha = 0 in
+                // every frame, the second tap only adds a signed zero (zl_render.h): zl_k2_chunk_ongrid mixes it from one tap
+                cls |= zl_voice_ongrid(MODE, A.ongrid, true, (cls & 32) != 0, interior, pl.P0, pl.step, vc.pad[0]) ? 128 : 0;
             }
             if (ST) {
                 // windows of the block's waves (BPW == 1: the workgroup's four frame tiles; else the N / 64 waves of block b).
@@ -1179,7 +1226,7 @@ static __device__ __forceinline__ void zl_k2_body(const ZlBatch &A, const unsign
             // class of each chunk of U voices: OR of bits 1, 2, 8; 4 = every voice simple and of one source layout, 16 = all
             // mono (ballots over the wave's 64 voices)
             const unsigned long long m1 = __ballot(cls & 1), m2 = __ballot(cls & 2), m4 = __ballot(cls & 4), m8 = __ballot(cls & 8),
-                                     m16 = __ballot(cls & 16), m32 = __ballot(cls & 32), m64 = __ballot(cls & 64);
+                                     m16 = __ballot(cls & 16), m32 = __ballot(cls & 32), m64 = __ballot(cls & 64), m128 = __ballot(cls & 128);
             const int lane = i & 63;
             if (lane < 64 / U) {
                 const unsigned long long full = (1ull << U) - 1ull;
@@ -1187,7 +1234,7 @@ static __device__ __forceinline__ void zl_k2_body(const ZlBatch &A, const unsign
                 const unsigned long long mono = (m16 >> sh) & full;
                 const int cc = (((m1 >> sh) & full) ? 1 : 0) | (((m2 >> sh) & full) ? 2 : 0) | (((m8 >> sh) & full) ? 8 : 0)
                              | (((((m4 >> sh) & full) == full) && (mono == 0 || mono == full)) ? 4 : 0) | (mono == full ? 16 : 0)
-                             | ((((m32 >> sh) & full) == full) ? 32 : 0) | ((((m64 >> sh) & full) == full) ? 64 : 0);
+                             | ((((m32 >> sh) & full) == full) ? 32 : 0) | ((((m64 >> sh) & full) == full) ? 64 : 0) | ((((m128 >> sh) & full) == full) ? 128 : 0);
                 s_chunk_[b][(i >> 6) * (64 / U) + lane] = cc;
             }
         }
@@ -1296,6 +1343,18 @@ static __device__ __forceinline__ void zl_k2_body(const ZlBatch &A, const unsign
         for (int c0 = 0; c0 < nv; ) {
             const int cc = __builtin_amdgcn_readfirstlane(s_chunk[c0 / U]);
             if (cc == 0) {                                        // nobody in this chunk plays (SamplerSynth.cpp:137)
+            } else if ((cc & 132) == 132) {
+                // every voice of the chunk on-grid (which implies simple, unit, interior) and of one source layout
+                // (ZL_K2_U_ONGRID = 2 U: two such chunks in a row, inside one bus, go as one -- twice the loads in flight)
+                const int cn = (ZL_K2_U_ONGRID > U && c0 + 2 * U <= nv && !(NB > 1 && vbase + c0 + U == busEnd))
+                                   ? __builtin_amdgcn_readfirstlane(s_chunk[c0 / U + 1]) : 0;
+                if (ZL_K2_U_ONGRID > U && (cn & 132) == 132 && ((cn ^ cc) & 16) == 0) {
+                    if (cc & 16) zl_k2_chunk_ongrid<true, 2 * U>(A, s_vc, s_unit, c0, vb, fc, wantPeak, accL, accR);
+                    else         zl_k2_chunk_ongrid<false, 2 * U>(A, s_vc, s_unit, c0, vb, fc, wantPeak, accL, accR);
+                    c0 += U;
+                }
+                else if (cc & 16) zl_k2_chunk_ongrid<true, U>(A, s_vc, s_unit, c0, vb, fc, wantPeak, accL, accR);
+                else              zl_k2_chunk_ongrid<false, U>(A, s_vc, s_unit, c0, vb, fc, wantPeak, accL, accR);
             } else if ((cc & 124) == 100) {
                 // (the shared-tap form needs a wave's lanes to be consecutive frames of one block: true for every launch shape --
                 // a wave is a 64-frame tile of its block)
@@ -1940,13 +1999,23 @@ __global__ void __launch_bounds__(256) zl_k_deliver(const float *bus, void *out,
 }
 
 // planar (L, R) -> interleaved arena layout; R == nullptr copies mono
-__global__ void zl_k_interleave(const float *L, const float *R, float *dst, int length, int pad)
+// nonfinite: set to 1 when a sample is NaN or infinite -- the kernel holds every value anyway; one OR over the workgroup, and a store
+// (every writer writes the same word: no atomic) only from a workgroup that saw one.  The host turns "still 0" into ZL_SOUND_FINITE.
+__global__ void zl_k_interleave(const float *L, const float *R, float *dst, int length, int pad, uint32_t *nonfinite)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= length + pad) return;
     const bool in = i < length;
-    if (R) { dst[2 * i] = in ? L[i] : 0.0f; dst[2 * i + 1] = in ? R[i] : 0.0f; }
-    else   { dst[i] = in ? L[i] : 0.0f; }
+    bool bad = false;
+    if (i < length + pad) {
+        const float l = in ? L[i] : 0.0f, r = (in && R) ? R[i] : 0.0f;
+        bad = !zl_f32_bits_finite(__float_as_uint(l)) || !zl_f32_bits_finite(__float_as_uint(r));
+        if (R) { dst[2 * i] = l; dst[2 * i + 1] = r; }
+        else   { dst[i] = l; }
+    }
+    if (nonfinite) {
+        const int any = __syncthreads_or(bad ? 1 : 0);
+        if (any && threadIdx.x == 0) __hip_atomic_store(nonfinite, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2165,9 +2234,9 @@ int zl_launch_deliver(const float *bus, void *out, int pcm16, int B, long long i
     return 0;
 }
 
-int zl_launch_interleave(const float *L, const float *R, float *dst, int length, int pad, hipStream_t s)
+int zl_launch_interleave(const float *L, const float *R, float *dst, int length, int pad, uint32_t *nonfinite, hipStream_t s)
 {
-    hipLaunchKernelGGL(zl_k_interleave, dim3((length + pad + 255) / 256), dim3(256), 0, s, L, R, dst, length, pad);
+    hipLaunchKernelGGL(zl_k_interleave, dim3((length + pad + 255) / 256), dim3(256), 0, s, L, R, dst, length, pad, nonfinite);
     ZL_LAUNCH_CHECK();
     return 0;
 }

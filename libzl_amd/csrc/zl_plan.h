@@ -505,7 +505,7 @@ struct ZlPlanner {
         vc.lpan = (float)(0.5 * (1.0 + (double)cl.pan));          // :193
         vc.rpan = (float)(0.5 * (1.0 - (double)cl.pan));          // :194
         vc.env = st.sustain;
-        vc.pad[0] = 0; vc.pad[1] = 0;
+        vc.pad[0] = sd.flags; vc.pad[1] = 0;
         A.vconst[v] = vc;
 
         // algorithmic source bytes of one block of this voice

@@ -8,6 +8,8 @@
 #pragma once
 #include "zl_types.h"
 #include <math.h>
+#include <stddef.h>
+#include <string.h>
 
 // Position and envelope of frame f of a planned FAST block (at most two inline segments; blocks with per-frame control: zl_plan.h,
 // zl_slow_control).
@@ -85,6 +87,39 @@ ZL_HD inline void zl_mix_frame(const ZlTaps &t, float alpha, bool inb, bool wide
     const float sSignal = l - r;                                 // :209
     lout = lpan * mSignal + sSignal;                             // :210
     rout = rpan * mSignal - sSignal;                             // :211
+}
+
+// ---- on-grid unit-step voices: one tap ---------------------------------------------------------------------------------------------
+// A voice that plays at its own rate from an integer position has alpha = 0 in every frame, and the plain linear expression above is
+//   l = x0l * 1.0f + (((x1l * 0.0f) * lgain) * env) * vol = x0l + (a signed zero)          whenever x1l and the gains are finite.
+// The zero's sign reaches no output: l + r and l - r depend on it only when l and r are both zero; then lout and rout are zeros, the
+// bus accumulator starts at +0 and never becomes -0 (+0 + -0 = +0, x + -x = +0), and the report peak is ng > 0 ? ng : 0.  So the
+// second tap, its gain chain and 1 - alpha can go -- where the source is KNOWN to be finite (inf * 0 = NaN): ZL_SOUND_FINITE.
+//
+// Does K2 take the short form for this voice-block?  simple / unit / interior: the staging classes of zl_k2_body (whole block in
+// sustain with finite gains; one segment of step exactly 1; every tap inside the source).
+ZL_HD inline bool zl_voice_ongrid(uint32_t mode, int enabled, bool simple, bool unit, bool interior, double P0, double step, int sound_flags)
+{
+    return enabled != 0 && simple && unit && interior && step == 1.0 && P0 == (double)(int)P0 && (sound_flags & ZL_SOUND_FINITE) != 0
+        && (mode & (ZL_MODE_HERMITE | ZL_MODE_FIX_GAIN)) == 0;
+}
+
+// :208-211 on the one tap (x0l, x0r) of an on-grid frame; a mono source passes x0r = x0l (r = l, :205)
+ZL_HD inline void zl_mix_frame_ongrid(float x0l, float x0r, float lpan, float rpan, float &lout, float &rout)
+{
+    const float mSignal = 0.5f * (x0l + x0r);                    // :208
+    const float sSignal = x0l - x0r;                             // :209
+    lout = lpan * mSignal + sSignal;                             // :210
+    rout = rpan * mSignal - sSignal;                             // :211
+}
+
+// is every sample of a host buffer finite?  (the exponent field of a NaN or an infinity is all ones)
+ZL_HD inline bool zl_f32_bits_finite(uint32_t bits) { return (bits & 0x7f800000u) != 0x7f800000u; }
+inline bool zl_all_finite(const float *x, size_t n)
+{
+    uint32_t worst = 0;
+    for (size_t i = 0; i < n; ++i) { uint32_t b; memcpy(&b, x + i, sizeof b); worst |= zl_f32_bits_finite(b) ? 0u : 1u; }
+    return worst == 0;
 }
 
 // JackPassthrough fan-out of one bus frame (JackPassthrough.cpp:55-109): output pair c (0 dry, 1 wetFx1, 2 wetFx2) of

@@ -32,7 +32,10 @@ struct ZlSound {
     int32_t  length;              // frames
     int32_t  channels;            // 1 or 2; 0 = slot free / invalid
     double   sample_rate;
+    int32_t  flags;               // ZL_SOUND_FINITE: every sample of the extent has been looked at and is finite (0 only costs speed)
+    int32_t  pad;
 };
+enum { ZL_SOUND_FINITE = 1 };
 
 // ClipAudioSource fields the voice reads (ClipAudioSource.cpp:63-82), device copy.
 struct ZlClip {
@@ -97,7 +100,7 @@ struct ZlVoiceConst {             // per voice, constant over a batch; 48 bytes 
     float    lgain, rgain, clip_volume, lpan;
     float    rpan;
     float    env;                 // envelope of the implied (run) blocks: the sustain level
-    int32_t  pad[2];
+    int32_t  pad[2];              // pad[0]: the source's ZlSound::flags (K2's on-grid class reads ZL_SOUND_FINITE)
 };
 
 enum { ZL_PLAN_ACTIVE = 1, ZL_PLAN_SLOW = 2, ZL_PLAN_ENV = 4,      // ENV: the envelope ramps inside the block (ZlPlanSeg1 holds the slopes)
@@ -307,7 +310,7 @@ struct ZlBatch {
     float              *fan;      // [B][6][Ktot*N] dry L,R / wetFx1 L,R / wetFx2 L,R of every bus, or nullptr
     ZlPassParams        pass0;    // pass_inline = 1 (resident kernel): the parameters of the workgroup's bus travel here instead of in pass[]
     int32_t             pass_inline;
-    int32_t             pad_batch;
+    int32_t             ongrid;     // ZL_K2_ONGRID: 1 = K2 may mix on-grid unit-step chunks from one tap (zl_render.h, zl_voice_ongrid), 0 = never
     int32_t             tile_accum; // 1 (resident kernel, blocks longer than 256 frames): ONE workgroup walks the frame tiles of its block in
                                     // order (bx = 0, 1, ...), and the fused level scan carries on from tile to tile (same defined order)
     // the call's per-voice reports, published by the K2 workgroups that render its LAST block (fused_reports = 1: every bus of that
