@@ -2,6 +2,8 @@
 
     libzl_amd/lib/libzlhip.so      HIP engine + C-ABI (include/zlhip.h), gfx950 only
     oracle/_build/libzl_oracle.so  CPU oracle (test infrastructure; never loaded by the product)
+    oracle/_ref/libzl_refvoice.so  the reference's own SamplerSynthVoice.cpp, compiled unmodified (test infrastructure; only where
+                                   the reference tree is present, never committed)
 
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the CPU-only build container.
 """
@@ -158,6 +160,53 @@ def build_oracle(force: bool = False) -> str:
         if res.returncode != 0:
             sys.stderr.write(res.stdout + res.stderr)
             raise RuntimeError("building the CPU oracle failed")
+    return target
+
+
+def reference_dir():
+    """The reference tree (zynthbox/libzl): $ZL_REFERENCE_DIR, else /root/reference; None where there is none."""
+    for cand in (os.environ.get("ZL_REFERENCE_DIR"), "/root/reference"):
+        if cand and os.path.exists(os.path.join(cand, "lib", "SamplerSynthVoice.cpp")):
+            return cand
+    return None
+
+
+REF_LIB = os.path.join(ROOT, "oracle", "_ref", "libzl_refvoice.so")
+REF_LIB_CONTRACTED = os.path.join(ROOT, "oracle", "_ref", "libzl_refvoice_fma.so")
+
+
+def build_reference(force: bool = False, contracted: bool = False):
+    """oracle/_ref/libzl_refvoice.so: the reference's lib/SamplerSynthVoice.cpp as it stands, compiled against the stand-in
+    headers of oracle/ref_shim/ with the oracle's floating-point flags (x86-64 baseline, no contraction), linked with
+    oracle/ref_driver.cpp (the neighbours' getters + a C interface) and oracle/zl_oracle.c (juce::ADSR stand-in, positions rows).
+    Returns None, leaving an existing oracle/_ref/ alone, where there is no reference tree (the built library travels).
+    contracted=True builds libzl_refvoice_fma.so with -mfma -ffp-contract=fast: a measurement of how far a contracting build
+    of the reference may sit from the definition, which no test depends on."""
+    ref = reference_dir()
+    if ref is None:
+        return None
+    odir = os.path.join(ROOT, "oracle")
+    target = REF_LIB_CONTRACTED if contracted else REF_LIB
+    voice = os.path.join(ref, "lib", "SamplerSynthVoice.cpp")
+    driver = os.path.join(odir, "ref_driver.cpp")
+    shim = os.path.join(odir, "ref_shim")
+    deps = [voice, driver, os.path.join(odir, "zl_oracle.c"), os.path.join(odir, "zl_oracle.h"), os.path.abspath(__file__)]
+    deps += [os.path.join(d, f) for d, _, fs in os.walk(shim) for f in fs]
+    deps += [os.path.join(ref, "lib", f) for f in os.listdir(os.path.join(ref, "lib")) if f.endswith(".h")]
+    if not force and not _stale(target, deps):
+        return target
+    os.makedirs(os.path.dirname(target), exist_ok=True)
+    fp = ["-O2", "-mfma", "-ffp-contract=fast"] if contracted else ["-O2", "-ffp-contract=off", "-fno-fast-math"]
+    cobj = os.path.join(os.path.dirname(target), "zl_oracle_fma.o" if contracted else "zl_oracle.o")
+    # (the envelope keeps the oracle's flags in both builds: only the reference's own text is contracted)
+    cmds = [["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-c", os.path.join(odir, "zl_oracle.c"), "-o", cobj],
+            ["g++", "-std=c++17"] + fp + ["-fPIC", "-shared", "-Wall", "-Wl,-Bsymbolic", "-I", shim, "-I", odir, "-I", os.path.join(ref, "lib"),
+                                          "-o", target, voice, driver, cobj, "-lm", "-lpthread"]]
+    for cmd in cmds:
+        res = subprocess.run(cmd, capture_output=True, text=True)
+        if res.returncode != 0:
+            sys.stderr.write(res.stdout + res.stderr)
+            raise RuntimeError("building the reference voice failed")
     return target
 
 

@@ -5,14 +5,15 @@
  * and bench.py's cpu_baseline leg may build, load or call it.  The product path
  * (libzl_amd/, include/) never links or falls back to anything in oracle/.
  *
- * PARITY STATUS: "parity unpinned".  The reference (zynthbox/libzl @ v1) cannot be compiled in
- * this image (needs JUCE, tracktion_engine [empty submodule], JACK, Qt >= 5.11, rtmidi) and its
- * test/ directory holds no golden vectors, known-answer tests or audio fixtures for this path.
- * The oracle is therefore a line-by-line behavioural restatement of the reference source text,
- * cross-checked against an independently written numpy restatement (oracle/np_restatement.py)
- * and hand-derived known answers (tests/test_oracle_kat.py).  juce::ADSR is third-party code
- * absent from /root/reference (un-vendored submodule tracktion_engine/modules/juce, version
- * unpinned); its published JUCE 6 algorithm is restated in zlo_adsr_*.
+ * PARITY STATUS: the voice (zlo_voice_set_current_command / _start_note / _stop_note / _process, mode 0) is PINNED to the
+ * reference's own lib/SamplerSynthVoice.cpp, compiled unmodified against the stand-in headers of oracle/ref_shim/ and driven by
+ * oracle/ref_driver.cpp (libzl_amd/build.py build_reference -> oracle/_ref/, never committed): tests/test_reference_anchor.py
+ * compares the two bit for bit.  Everything else here stays a line-by-line behavioural restatement of the reference source text
+ * (the reference, zynthbox/libzl @ v1, needs JUCE, tracktion_engine [empty submodule], JACK, Qt >= 5.11 and rtmidi to build as a
+ * whole, and its test/ directory holds no golden vectors), cross-checked against an independently written numpy restatement
+ * (oracle/np_restatement.py) and hand-derived known answers (tests/test_oracle_kat.py).  juce::ADSR is third-party code absent
+ * from the reference tree (un-vendored submodule tracktion_engine/modules/juce, version unpinned); its published JUCE 6 algorithm
+ * is restated in zlo_adsr_* -- the anchor's juce::ADSR is a wrapper over these same functions and does not pin them.
  *
  * Every function cites the reference file:line it follows (paths relative to /root/reference/lib).
  * Compile with -ffp-contract=off: the oracle DEFINES the fp32 rounding sequence (one IEEE

@@ -1,7 +1,8 @@
 """ctypes binding of the CPU oracle (oracle/zl_oracle.c).  TEST INFRASTRUCTURE ONLY.
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this module; the
-product package libzl_amd never does.  Parity status: "parity unpinned" (see zl_oracle.h).
+product package libzl_amd never does.  Parity status: the voice is pinned to the reference's compiled source, the rest is
+restated (see zl_oracle.h).
 """
 from __future__ import annotations
 

@@ -19,9 +19,27 @@ def golden_names():
     return sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(GOLDEN_DIR, "g[0-9]*.npz")))
 
 
+def reference_fixture_names():
+    """tests/golden/ref_*.npz: scenes recorded from the reference's own compiled voice (tests/golden/make_reference_golden.py)"""
+    return sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(GOLDEN_DIR, "ref_[0-9]*.npz")))
+
+
+def load_reference_fixture(name):
+    """-> the Scene and what the reference voice gave: bus [B][2][K*N], tail [K][B][2] (the frame it stores to [nframes]), reports
+    [K][V][3] (valid, gain, progress per block), playing [K][V] (isPlaying after each block)"""
+    z = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
+    sc = _scene_of(z, json.loads(bytes(z["meta"]).decode()))
+    return sc, dict(bus=np.stack([z["busL"], z["busR"]], axis=1), tail=z["tail"], reports=z["reports"], playing=z["playing"])
+
+
 def load_golden(name):
     z = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
-    meta = json.loads(bytes(z["meta"]).decode())
+    sc = _scene_of(z, json.loads(bytes(z["meta"]).decode()))
+    expect = dict(bus=np.stack([z["busL"], z["busR"]], axis=1), trace=z["trace"], reports=z["reports"], state=z["state"])
+    return sc, expect
+
+
+def _scene_of(z, meta):
     sc = Scene(num_buses=meta["B"], voices_per_bus=meta["VPB"], fs=meta["fs"], mode=meta["mode"], nframes=meta["nframes"],
                nblocks=meta["nblocks"], bpm=meta["bpm"])
     for i, sr in enumerate(meta["sample_rates"]):
@@ -75,8 +93,7 @@ def load_golden(name):
             arr[j].jack_playhead, arr[j].jack_playhead_usecs, arr[j].jack_subbeat_length_usecs = int(row[2]), int(row[3]), int(row[4])
         return arr
     sc.clocks = make_clocks
-    expect = dict(bus=np.stack([z["busL"], z["busR"]], axis=1), trace=z["trace"], reports=z["reports"], state=z["state"])
-    return sc, expect
+    return sc
 
 
 def load_config1():
