@@ -20,7 +20,7 @@ LIBDIR = os.path.join(ROOT, "libzl_amd", "lib")
 LIB = os.path.join(LIBDIR, "libzlhip.so")
 
 HIP_SOURCES = ["zl_kernels.hip", "zl_stretch.hip", "zl_engine.cpp", "zl_libzl.cpp", "zl_group.cpp"]
-HEADERS = ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_render.h", "zl_kernels.h", "zl_host.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", "zl_group.h", "zl_member.h",
+HEADERS = ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_pair.h", "zl_render.h", "zl_kernels.h", "zl_host.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", "zl_group.h", "zl_member.h",
            os.path.join("..", "..", "include", "zlhip.h"), os.path.join("..", "..", "include", "libzl_hotpath.h")]
 
 
@@ -66,9 +66,9 @@ def build_engine(force: bool = False, verbose: bool = False, stamps: bool = Fals
 # per source: the headers it includes (a change of one of them recompiles only the sources that see it)
 _INC = os.path.join("..", "..", "include")
 SOURCE_DEPS = {
-    "zl_kernels.hip": ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_kernels.h"],
+    "zl_kernels.hip": ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_pair.h", "zl_kernels.h"],
     "zl_stretch.hip": ["zl_types.h", "zl_stretch.h"],
-    "zl_engine.cpp": ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h")],
+    "zl_engine.cpp": ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_pair.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h")],
     "zl_group.cpp": ["zl_types.h", "zl_plan.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_group.h", os.path.join(_INC, "zlhip.h")],
     "zl_libzl.cpp": ["zl_render.h", "zl_types.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h"), os.path.join(_INC, "libzl_hotpath.h")],
 }
@@ -279,6 +279,21 @@ def build_ongrid_harness(force: bool = False) -> str:
         if res.returncode != 0:
             sys.stderr.write(res.stdout + res.stderr)
             raise RuntimeError("building the CPU on-grid harness failed")
+    return target
+
+
+def build_pair_harness(force: bool = False) -> str:
+    """Host build of the gate of K2's two-frames-per-lane kernels (zl_pair.h, tests/cpu_harness/pair_host.cpp) for the CPU tier."""
+    hdir = os.path.join(ROOT, "tests", "cpu_harness")
+    target = os.path.join(hdir, "_build", "libzl_pair_host.so")
+    src = os.path.join(hdir, "pair_host.cpp")
+    if force or _stale(target, [src, os.path.join(CSRC, "zl_pair.h")]):
+        os.makedirs(os.path.dirname(target), exist_ok=True)
+        cmd = ["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-Wl,-Bsymbolic", "-I", CSRC, "-o", target, src]
+        res = subprocess.run(cmd, capture_output=True, text=True)
+        if res.returncode != 0:
+            sys.stderr.write(res.stdout + res.stderr)
+            raise RuntimeError("building the CPU pair-gate harness failed")
     return target
 
 

@@ -25,6 +25,7 @@
 #include "zl_kernels.h"
 #include "zl_member.h"
 #include "zl_order.h"
+#include "zl_pair.h"
 #include "zl_plan.h"
 #include "zl_render.h"
 #include "zl_stretch.h"
@@ -1398,6 +1399,9 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
     const bool orderShape = zl_order_shape(A.groups, A.staged, nblocks, nframes);
     const double loopFrames = phaseMode == 1 ? e->hc.phase_order_loop_frames() : INFINITY;
     auto orderWindow = [&](int K) { return zl_order_window(phaseMode, orderShape, e->bnc.sink.on, nframes, K, loopFrames); };
+    // ---- K2 with two frames per lane (zl_pair.h): ZL_K2_PAIR 0 = never, 1 = auto (default: every playing voice cheap to plan, the
+    //      voices whose interior blocks are on-grid), 2 = wherever the launch shape allows (tests, A/B); read per call
+    const int pairMode = [] { const char *v = std::getenv("ZL_K2_PAIR"); return v ? std::atoi(v) : 1; }();
     {
         size_t need = 0;
         for (const auto &wk : wins) if (orderWindow(wk.second)) need = std::max(need, (size_t)orderSlots * (size_t)wk.second);
@@ -1493,6 +1497,7 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
         // profiling: the K2 dispatch carries its own start / stop events (hipExtLaunchKernel); the call's last launch carries `done`
         const bool closes = fusedReports && w == nwin - 1;
         if (fusedReports) { Aw.fused_reports = 1; Aw.rep_gain = e->dGain; Aw.rep_host = c.hReportsDev; Aw.rep_host_gain = c.hGainDev; Aw.rep_host_stats = c.hStatsDev; }
+        Aw.pair = zl_pair_window(pairMode, zl_pair_shape(Aw.mode, Aw.N, Aw.K, Aw.NB, Aw.groups, Aw.staged, Aw.trace, Aw.fan != nullptr, Aw.host_out != nullptr, Aw.ongrid), cheap) ? 1 : 0;
         hipEvent_t k2stop = closes ? c.done : (e->profiling ? c.evK2[2 * (size_t)w + 1] : nullptr);
         ZL_KERNEL(e, zl_launch_render(Aw, s, e->profiling ? c.evK2[2 * (size_t)w] : nullptr, k2stop));
         if (k3) ZL_KERNEL(e, zl_launch_finalize(Aw, nullptr, s));

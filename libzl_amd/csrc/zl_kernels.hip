@@ -23,6 +23,7 @@
 #include "zl_plan.h"
 #include "zl_render.h"
 #include "zl_order.h"
+#include "zl_pair.h"
 #include "zl_kernels.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -274,6 +275,27 @@ static __device__ __forceinline__ void zl_wave_levels4(int &pkL, int &pkR, float
         "v_readlane_b32 %4, %0, 63\n\tv_readlane_b32 %5, %1, 63\n\tv_readlane_b32 %6, %2, 63\n\tv_readlane_b32 %7, %3, 63"
         : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "=s"(ra), "=s"(rb), "=s"(rc), "=s"(rd));
     pkL = ra; pkR = rb; sqL = rc; sqR = rd;
+}
+// The twin for two frames per lane (zl_k2_pair_body): a 64-frame tile sits in HALF a wave, lane j' of the half holding the tile's elements
+// 2 j' and 2 j' + 1.  Level 1 of the tile's balanced tree is the caller's in-lane add / max; levels 2 to 6 are the same five DPP steps without
+// the last one (row_bcast:31 would join the wave's two tiles), each with the operands the 64-lane tree gives that level.  The results of the
+// wave's tiles 0 / 1 are in lanes 31 / 63.
+static __device__ __forceinline__ void zl_wave_levels4_pair(int pkL, int pkR, float sqL, float sqR, int (&opkL)[2], int (&opkR)[2], float (&osqL)[2], float (&osqR)[2])
+{
+    int a = pkL, b = pkR, ra0, rb0, ra1, rb1;
+    float c = sqL, d = sqR, rc0, rd0, rc1, rd1;
+    asm("s_nop 4\n\t"
+        ZL_DPP4("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1")
+        ZL_DPP4("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1")
+        ZL_DPP4("row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1")
+        ZL_DPP4("row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1")
+        ZL_DPP4("row_bcast:15 row_mask:0xa bank_mask:0xf")
+        "s_nop 0\n\t"
+        "v_readlane_b32 %4, %0, 31\n\tv_readlane_b32 %5, %1, 31\n\tv_readlane_b32 %6, %2, 31\n\tv_readlane_b32 %7, %3, 31\n\t"
+        "v_readlane_b32 %8, %0, 63\n\tv_readlane_b32 %9, %1, 63\n\tv_readlane_b32 %10, %2, 63\n\tv_readlane_b32 %11, %3, 63"
+        : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "=s"(ra0), "=s"(rb0), "=s"(rc0), "=s"(rd0), "=s"(ra1), "=s"(rb1), "=s"(rc1), "=s"(rd1));
+    opkL[0] = ra0; opkR[0] = rb0; osqL[0] = rc0; osqR[0] = rd0;
+    opkL[1] = ra1; opkR[1] = rb1; osqL[1] = rc1; osqR[1] = rd1;
 }
 #undef ZL_DPP4
 
@@ -550,6 +572,49 @@ static __device__ __forceinline__ void zl_k2_chunk_ongrid(const ZlBatch &A, cons
             const float ng = l + r;
             float pk = ng > 0.0f ? ng : 0.0f;
             pk = zl_wave_max(pk);
+            if ((threadIdx.x & 63) == 0 && pk > 0.0f) atomicMax(&A.reports[vfirst + i].peak_bits, __float_as_uint(pk));
+        }
+    }
+}
+
+// The on-grid chunk with TWO frames per lane (zl_k2_pair_body): the lane renders frames f0 (even) and f0 + 1.  The two frames of an on-grid
+// voice are 16 contiguous bytes, 8-byte aligned -- the alignment of the two-tap gather -- so ONE 16-byte load [L0 R0 L1 R1] per voice serves
+// two voice-samples (mono: 8 bytes [x0 x1]) and a wave's load is 1 KiB contiguous: half the load instructions per voice-sample, and the
+// address, the two v_readfirstlane and the pan read are paid once per pair.  Interior means frame N - 1 is inside the source, so f0 + 1 is.
+// Each frame keeps its own accumulator pair and is added to in voice order: per frame nothing about the summation changes.  The report peak
+// is the larger of the two frames' before the wave maximum (a maximum does not depend on order).
+#ifndef ZL_K2_U_PAIR
+#define ZL_K2_U_PAIR 8       // loads in flight per wavefront in the pair chunk (4 registers a voice); 8 or 4
+#endif
+template <bool MONO, int U>
+static __device__ __forceinline__ void zl_k2_chunk_ongrid_pair(const ZlBatch &A, const ZlVoiceConst *s_vc, const ZlUnit *s_unit, int c0, int vfirst, int f0,
+                                                                bool wantPeak, float &accL0, float &accR0, float &accL1, float &accR1)
+{
+    zl_f4a8  d4[MONO ? 1 : U];
+    zl_f2a4b d2[MONO ? U : 1];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int i = c0 + u;
+        const int pos = s_unit[i].ipos + f0;                      // interior: 0 <= pos and pos + 1 < duration
+        const uint64_t so = s_vc[i].src_offset;
+        const char *src = reinterpret_cast<const char *>(A.arena + (((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(so >> 32)) << 32)
+                                                                    | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)so)));
+        if (MONO) d2[u] = *reinterpret_cast<const zl_f2a4b *>(src + ((uint32_t)pos << 2));
+        else      d4[u] = *reinterpret_cast<const zl_f4a8 *>(src + ((uint32_t)pos << 3));
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int i = c0 + u;
+        const float lpan = s_vc[i].lpan, rpan = s_vc[i].rpan;
+        float l0, r0, l1, r1;
+        zl_mix_frame_ongrid(MONO ? d2[u].x : d4[u].x, MONO ? d2[u].x : d4[u].y, lpan, rpan, l0, r0);
+        zl_mix_frame_ongrid(MONO ? d2[u].y : d4[u].z, MONO ? d2[u].y : d4[u].w, lpan, rpan, l1, r1);
+        accL0 += l0; accR0 += r0;                                 // :218-221 (index shift applied at the store)
+        accL1 += l1; accR1 += r1;
+        if (wantPeak) {                                           // :213-216, signed peak from 0 (Q6)
+            const float ng0 = l0 + r0, ng1 = l1 + r1;
+            const float pk0 = ng0 > 0.0f ? ng0 : 0.0f, pk1 = ng1 > 0.0f ? ng1 : 0.0f;
+            const float pk = zl_wave_max(pk1 > pk0 ? pk1 : pk0);
             if ((threadIdx.x & 63) == 0 && pk > 0.0f) atomicMax(&A.reports[vfirst + i].peak_bits, __float_as_uint(pk));
         }
     }
@@ -927,6 +992,96 @@ static __device__ __forceinline__ void zl_k2_chunk(const ZlBatch &A, const ZlBlo
             pk = zl_wave_max(pk);
             if ((threadIdx.x & 63) == 0 && pk > 0.0f) atomicMax(&A.reports[vfirst + i].peak_bits, __float_as_uint(pk));
         }
+    }
+}
+
+// The staging pass of zl_k2_body below, as functions, for zl_k2_pair_body.  (zl_k2_body keeps its own text: calling these from it moved the
+// register allocation of two existing kernels -- zl_k2_phase_render<2> gained a private segment -- and those kernels are to stay as they are.)
+// The record of voice vb + i in block kk (i >= nv: a slot behind the pass's last voice, which gets the neutral record); every load the record
+// may need is issued at once.
+static __device__ __forceinline__ void zl_k2_stage_load(const ZlBatch &A, int kk, int vb, int i, int nv, ZlVoiceConst &vc, ZlBlockPlan &pl)
+{
+    const int N = A.N, V = A.V;
+    zl_plan_clear(pl);
+    vc.src_offset = 0; vc.sample_duration = 0; vc.channels = 2;
+    vc.lgain = vc.rgain = vc.clip_volume = vc.lpan = vc.rpan = vc.env = 0.0f; vc.pad[0] = vc.pad[1] = 0;
+    if (i < nv) {
+        vc = A.vconst[vb + i];                             // K1 leaves a neutral record for voices that do not play
+        if (kk < A.K) {
+            // zl_plan_lookup (implied by a run, explicit, or idle) with the run list AND the explicit record's header and first segment
+            // fetched together: ONE memory round trip per prologue where "look at the runs, then fetch the record" is two in a row (most
+            // blocks of a long window are explicit: a voice has ZL_MAXRUNS inline runs, a 2 s loop in a 43 s window restarts twenty times).
+            // The record of a block that a run covers is never written: its bits lose every select below.
+            const ZlRunList *rl = &A.runs[vb + i];
+            const size_t pidx = (size_t)kk * V + (size_t)(vb + i);
+            const ZlPlanHdr ph = A.plan_hdr[pidx];
+            const ZlPlanSeg0 ps = A.plan_seg0[pidx];
+            const int rn = rl->n, dead = rl->dead_from;
+            bool cov = false; double rP = 0.0, rstep = 0.0; int rk0 = 0;
+#pragma unroll
+            for (int j = 0; j < ZL_MAXRUNS; ++j) {
+                const ZlRun r = rl->r[j];
+                const bool hit = !cov && j < rn && kk >= r.k0 && kk < r.k1;
+                rP = hit ? r.P : rP; rstep = hit ? r.step : rstep; rk0 = hit ? r.k0 : rk0;
+                cov = cov || hit;
+            }
+            if (kk < dead) {
+                pl.flags = cov ? (int32_t)ZL_PLAN_ACTIVE : ph.flags; pl.n_active = cov ? N : ph.n_active; pl.nseg = cov ? 1 : ph.nseg;
+                pl.env = cov ? vc.env : ph.env;
+                pl.P0 = cov ? fma((double)((kk - rk0) * N), rstep, rP) : ps.P0;   // exact: inside the linear run
+                pl.step = cov ? rstep : ps.step;
+                if (!cov && ((((ph.nseg >= 2 || (ph.flags & ZL_PLAN_ENV)) && !(ph.flags & ZL_PLAN_SLOW)) || (ph.flags & (ZL_PLAN_NOSLOT_SIM | ZL_PLAN_NOSLOT_EXPAND))))) {
+                    const ZlPlanSeg1 s1 = A.plan_seg1[pidx];
+                    pl.P1 = s1.P1; pl.step1 = s1.step1; pl.n1 = s1.n1; pl.estep0 = s1.estep0; pl.E1 = s1.E1; pl.estep1 = s1.estep1;
+                }
+            }
+        }
+    }
+}
+
+// ... and its class bits: 1 = plays this block, 2 = per-frame control, and the bits of the simple forms described inside
+template <uint32_t MODE>
+static __device__ __forceinline__ int zl_k2_stage_class(const ZlBatch &A, const ZlVoiceConst &vc, const ZlBlockPlan &pl)
+{
+    const int N = A.N;
+    int cls = (pl.flags & ZL_PLAN_ACTIVE) ? (1 | ((pl.flags & ZL_PLAN_SLOW) ? 2 : 0)) : 0;
+    // 4 = "simple": whole block, sustain (and no debug trace); 8 = it has a second position segment; 16 = mono source
+    const float gprod = vc.lgain * vc.rgain * vc.clip_volume * pl.env;     // finite iff every factor is (or one is 0 * inf = NaN)
+    // (sources of 4 GiB and more take the general path: the simple paths address a source with 32-bit byte offsets)
+    if (cls == 1 && pl.nseg <= 2 && !(pl.flags & ZL_PLAN_ENV) && pl.n_active == N && (vc.channels == 1 || vc.channels == 2) && !A.trace
+        && (gprod - gprod) == 0.0f && (uint32_t)vc.sample_duration < 0x1ffffff0u)
+    {
+        // 64 = "interior": first and last position of the block (P0 and P0 + (N-1) step, step > 0) leave room for
+        // every tap: pos + 1 <= duration (pos >= 1 and pos + 2 <= duration with 4 taps)
+        constexpr bool HM = (MODE & ZL_MODE_HERMITE) != 0;
+        const double Pmax = fma((double)(N - 1), pl.step, pl.P0);
+        const bool interior = pl.nseg == 1 && pl.P0 >= (HM ? 1.0 : 0.0) && Pmax < (double)(vc.sample_duration - (HM ? 1 : 0));
+        cls |= 4 | (pl.nseg == 2 ? 8 : 0) | (vc.channels == 1 ? 16 : 0) | ((pl.nseg == 1 && pl.step == 1.0 && pl.P0 < 1073741824.0) ? 32 : 0)
+             | (interior ? 64 : 0);
+        // 128 = "on-grid": a unit-step interior block from an integer position of a source known to be finite -- alpha = 0 in
+        // every frame, the second tap only adds a signed zero (zl_render.h): zl_k2_chunk_ongrid mixes it from one tap
+        cls |= zl_voice_ongrid(MODE, A.ongrid, true, (cls & 32) != 0, interior, pl.P0, pl.step, vc.pad[0]) ? 128 : 0;
+    }
+    return cls;
+}
+
+// ... and the class of each chunk of U voices of the pass, from the classes of the wave's 64 voices (voice i of the pass = this lane's)
+template <int U>
+static __device__ __forceinline__ void zl_k2_stage_chunks(int cls, int i, int *s_chunk)
+{
+    // class of each chunk of U voices: OR of bits 1, 2, 8; 4 = every voice simple and of one source layout, 16 = all
+    // mono (ballots over the wave's 64 voices)
+    const unsigned long long m1 = __ballot(cls & 1), m2 = __ballot(cls & 2), m4 = __ballot(cls & 4), m8 = __ballot(cls & 8),
+                             m16 = __ballot(cls & 16), m32 = __ballot(cls & 32), m64 = __ballot(cls & 64), m128 = __ballot(cls & 128);
+    const int lane = i & 63;
+    if (lane < 64 / U) {
+        const unsigned long long full = (1ull << U) - 1ull;
+        const int sh = lane * U;
+        const unsigned long long mono = (m16 >> sh) & full;
+        const int cc = (((m1 >> sh) & full) ? 1 : 0) | (((m2 >> sh) & full) ? 2 : 0) | (((m8 >> sh) & full) ? 8 : 0)
+                     | (((((m4 >> sh) & full) == full) && (mono == 0 || mono == full)) ? 4 : 0) | (mono == full ? 16 : 0)
+                     | ((((m32 >> sh) & full) == full) ? 32 : 0) | ((((m64 >> sh) & full) == full) ? 64 : 0) | ((((m128 >> sh) & full) == full) ? 128 : 0);
+        s_chunk[(i >> 6) * (64 / U) + lane] = cc;
     }
 }
 
@@ -1451,6 +1606,162 @@ __global__ void __launch_bounds__(256, (MODE & (ZL_MODE_HERMITE | ZL_MODE_FIX_DE
 {
     zl_k2_body<MODE, 1, false, true, true>(A, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y);
 }
+
+// ------------------------------------------------------------------------------------------------
+// K2 with TWO frames per lane (zl_k2_pair_render / zl_k2_pair_phase_render): the launches zl_pair_shape (zl_pair.h) lets through -- faithful
+// linear mode, blocks of 256 frames, one bus per workgroup, no mix groups, no fan-out, no bounce, no trace, batches.  A workgroup is 128
+// lanes; lane j renders frames 2 j and 2 j + 1 of its block.  What it buys is the on-grid chunk (zl_k2_chunk_ongrid_pair): the texture
+// addresser's cost is per load instruction and lane whatever the width (profiles/round6_ongrid_pmc.txt), and this form issues half of
+// them.  Every other chunk class runs through the one-frame chunk functions, once per frame of the lane -- the same operands in the same
+// order, each frame into its own accumulator pair -- in a loop that is not unrolled: those chunks are rare (blocks at a loop's ends,
+// envelopes, pitched voices) and cost what they cost in zl_k2_body.  Staging, store (Q2), level scan and reports are zl_k2_body's:
+// the scan's defined order is kept by zl_wave_levels4_pair, a wave leaving the partial results of two 64-frame tiles.
+#ifndef ZL_K2_PAIR_WAVES
+// waves per SIMD the launch reaches: 8 two-wave workgroups per CU (the LDS cap of zl_launch_render), each wave with twice the
+// bytes in flight of a zl_k2_body wave
+#define ZL_K2_PAIR_WAVES 4
+#endif
+#define ZL_K2_PAIR_LDS 18432   // LDS per workgroup the launch pads to: 8 workgroups and the planner's 12 KB fit a CU's 160 KB, a ninth does not
+template <bool ORD>
+static __device__ __forceinline__ void zl_k2_pair_body(const ZlBatch &A)
+{
+    constexpr uint32_t MODE = 0;
+    constexpr int U = ZL_K2_U, UP = ZL_K2_U_PAIR, CH = ZL_K2_CHUNK;
+    static_assert(UP == U || 2 * UP == U, "the pair chunk walks a chunk class of U voices whole or in halves");
+    __shared__ ZlBlockPlan  s_plan[CH];
+    __shared__ ZlVoiceConst s_vc[CH];
+    __shared__ int s_cls[CH];                         // per voice: 1 = plays this block, 2 = per-frame control
+    __shared__ int s_chunk[CH / U];                   // class of each chunk of U voices
+    __shared__ ZlUnit s_unit[CH];
+    __shared__ int   s_pk[2][4];                      // fused level scan: the block's four 64-frame tiles (two per wave)
+    __shared__ float s_sq[2][4];
+
+    const int N = A.N, V = A.V;                                    // N == 256
+    const int f0 = 2 * (int)threadIdx.x;
+    // XCD-aware block order and phase order: as in zl_k2_body
+    const unsigned by = blockIdx.y, bz = blockIdx.z;
+    const int ky = (int)gridDim.y, xq = ky >> 3, xr = ky & 7, xx = (int)(by & 7u);
+    const int ys = xx * xq + (xx < xr ? xx : xr) + (int)(by >> 3);
+    const int k = ORD ? A.order[(size_t)bz * A.K + ys] : ys;
+    __builtin_assume(k >= 0 && k < 65536);                         // (a launch slot's block: what the compiler knows of ys it may know of the table's entry)
+    const int bus = (int)bz;
+    const int v0 = bus * A.VPB, vlim = (bus + 1) * A.VPB;
+    const int v1 = (v0 + A.G < vlim) ? v0 + A.G : vlim;
+    const bool wantPeak = __builtin_amdgcn_readfirstlane((int)(A.k0 + k == A.Ktot - 1)) != 0;
+
+    float accL0 = 0.0f, accR0 = 0.0f, accL1 = 0.0f, accR1 = 0.0f;
+    for (int vb = v0; vb < v1; vb += CH) {
+        const int nv = (v1 - vb < CH) ? v1 - vb : CH;
+        if (vb != v0) __syncthreads();                            // (nothing to wait for before the first pass)
+        for (int i = threadIdx.x; i < CH; i += blockDim.x) {
+            ZlVoiceConst vc;
+            ZlBlockPlan pl;
+            zl_k2_stage_load(A, k, vb, i, nv, vc, pl);
+            const int cls = zl_k2_stage_class<MODE>(A, vc, pl);
+            { ZlUnit un; un.ipos = (int)pl.P0; un.alpha = (float)(pl.P0 - (double)un.ipos);
+              un.gpl = (vc.lgain * pl.env) * vc.clip_volume; un.gpr = (vc.rgain * pl.env) * vc.clip_volume; s_unit[i] = un; }
+            s_vc[i] = vc;
+            s_plan[i] = pl;
+            s_cls[i] = cls;
+            zl_k2_stage_chunks<U>(cls, i, s_chunk);
+        }
+        __syncthreads();
+        for (int c0 = 0; c0 < nv; c0 += U) {
+            const int cc = __builtin_amdgcn_readfirstlane(s_chunk[c0 / U]);
+            if (cc == 0) {                                        // nobody in this chunk plays (SamplerSynth.cpp:137)
+            } else if ((cc & 132) == 132) {
+                // every voice of the chunk on-grid and of one source layout
+#pragma unroll
+                for (int h = 0; h < U; h += UP) {
+                    if (cc & 16) zl_k2_chunk_ongrid_pair<true, UP>(A, s_vc, s_unit, c0 + h, vb, f0, wantPeak, accL0, accR0, accL1, accR1);
+                    else         zl_k2_chunk_ongrid_pair<false, UP>(A, s_vc, s_unit, c0 + h, vb, f0, wantPeak, accL0, accR0, accL1, accR1);
+                }
+            } else {
+                // the other classes: zl_k2_body's dispatch, one frame of the lane after the other
+#pragma nounroll
+                for (int h = 0; h < 2; ++h) {
+                    const int fc = f0 + h;
+                    const double fd = (double)fc;
+                    float accL = h ? accL1 : accL0, accR = h ? accR1 : accR0;
+                    if ((cc & 124) == 100)      zl_k2_chunk_simple<MODE, false, true, true, U>(A, s_plan, s_vc, s_unit, c0, vb, fc, fd, wantPeak, accL, accR);
+                    else if ((cc & 92) == 68)   zl_k2_chunk_simple<MODE, false, false, true, U>(A, s_plan, s_vc, s_unit, c0, vb, fc, fd, wantPeak, accL, accR);
+                    else if ((cc & 28) == 4)    zl_k2_chunk_simple<MODE, false, false, false, U>(A, s_plan, s_vc, s_unit, c0, vb, fc, fd, wantPeak, accL, accR);
+                    else if ((cc & 20) == 4)    zl_k2_chunk_simple<MODE, true, false, false, U>(A, s_plan, s_vc, s_unit, c0, vb, fc, fd, wantPeak, accL, accR);
+                    else if ((cc & 124) == 116) zl_k2_chunk_simple_mono<MODE, false, true, true, U>(A, s_plan, s_vc, s_unit, c0, vb, fc, fd, wantPeak, accL, accR);
+                    else if ((cc & 92) == 84)   zl_k2_chunk_simple_mono<MODE, false, false, true, U>(A, s_plan, s_vc, s_unit, c0, vb, fc, fd, wantPeak, accL, accR);
+                    else if ((cc & 28) == 20)   zl_k2_chunk_simple_mono<MODE, false, false, false, U>(A, s_plan, s_vc, s_unit, c0, vb, fc, fd, wantPeak, accL, accR);
+                    else if ((cc & 20) == 20)   zl_k2_chunk_simple_mono<MODE, true, false, false, U>(A, s_plan, s_vc, s_unit, c0, vb, fc, fd, wantPeak, accL, accR);
+                    else {
+                        constexpr int H = U / 2;                  // (general chunks as two half-chunks, as in zl_k2_body)
+                        const size_t pbase = (size_t)k * V + vb;
+                        for (int q = 0; q < U; q += H) {
+                            if (cc & 2) zl_k2_chunk<MODE, true, H>(A, s_plan, s_vc, s_cls, c0 + q, pbase, vb, fc, wantPeak, accL, accR);
+                            else        zl_k2_chunk<MODE, false, H>(A, s_plan, s_vc, s_cls, c0 + q, pbase, vb, fc, wantPeak, accL, accR);
+                        }
+                    }
+                    if (h) { accL1 = accL; accR1 = accR; } else { accL0 = accL; accR0 = accR; }
+                }
+            }
+        }
+    }
+
+    // ---- the finished bus.  Quirk Q2: frame f lands in out[f + 1], out[0] stays 0 and the sample of frame N - 1 is dropped
+    {
+        const long long KN = (long long)A.Ktot * N;
+        float *outL = A.bus + (long long)bus * (A.bus_stride ? A.bus_stride : 2 * KN) + (long long)(A.k0 + k) * N;
+        float *outR = outL + (A.ch_stride ? A.ch_stride : KN);
+        const bool written1 = f0 + 2 < N;
+        outL[f0 + 1] = accL0; outR[f0 + 1] = accR0;
+        if (written1) { outL[f0 + 2] = accL1; outR[f0 + 2] = accR1; }
+        if (f0 == 0)  { outL[0] = 0.0f; outR[0] = 0.0f; }
+        // ---- fused AudioLevels block scan (AudioLevels.cpp:361-383) in its defined order: tiles of 64 frames from out[1], a balanced
+        //      pairwise tree inside a tile, tiles added in order.  This lane holds elements 2 j', 2 j' + 1 (j' = lane mod 32) of tile
+        //      2 * wave + (lane >= 32): level 1 of the tree is the in-lane add, the rest zl_wave_levels4_pair.  The dropped frame scans as 0.
+        if (A.levels) {
+            const float bL = written1 ? accL1 : 0.0f, bR = written1 ? accR1 : 0.0f;
+            const int pa = zl_sample_to_peak_int(accL0), pb = zl_sample_to_peak_int(bL), pc = zl_sample_to_peak_int(accR0), pd = zl_sample_to_peak_int(bR);
+            int pkL[2], pkR[2]; float sqL[2], sqR[2];
+            zl_wave_levels4_pair(pb > pa ? pb : pa, pd > pc ? pd : pc, accL0 * accL0 + bL * bL, accR0 * accR0 + bR * bR, pkL, pkR, sqL, sqR);
+            const int w = (int)(threadIdx.x >> 6) * 2;
+            if ((threadIdx.x & 63) == 0) {
+                s_pk[0][w] = pkL[0]; s_pk[1][w] = pkR[0]; s_sq[0][w] = sqL[0]; s_sq[1][w] = sqR[0];
+                s_pk[0][w + 1] = pkL[1]; s_pk[1][w + 1] = pkR[1]; s_sq[0][w + 1] = sqL[1]; s_sq[1][w + 1] = sqR[1];
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                ZlBlockLevels lv; lv.peak_l = 0; lv.peak_r = 0; lv.sumsq_l = 0.0f; lv.sumsq_r = 0.0f;
+                for (int t = 0; t < 4; ++t) {
+                    lv.peak_l = s_pk[0][t] > lv.peak_l ? s_pk[0][t] : lv.peak_l;
+                    lv.peak_r = s_pk[1][t] > lv.peak_r ? s_pk[1][t] : lv.peak_r;
+                    lv.sumsq_l += s_sq[0][t]; lv.sumsq_r += s_sq[1][t];
+                }
+                A.levels[(size_t)k * A.B + bus] = lv;
+            }
+        }
+    }
+
+    // ---- the call's reports, by the workgroups that hold the call's last block (as in zl_k2_body)
+    if (A.fused_reports && A.k0 + k == A.Ktot - 1) {
+        __syncthreads();
+        for (int v = v0 + (int)threadIdx.x; v < v1; v += (int)blockDim.x) {
+            const uint4 *src = reinterpret_cast<const uint4 *>(&A.reports[v]);
+            uint4 a = src[0];
+            const uint4 b = src[1];
+            a.z = __hip_atomic_load(&A.reports[v].peak_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const float gn = __uint_as_float(a.z) * 0.5f;
+            A.rep_gain[v] = gn;
+            if (A.rep_host) { uint4 *dst = reinterpret_cast<uint4 *>(&A.rep_host[v]); dst[0] = a; dst[1] = b; A.rep_host_gain[v] = gn; }
+        }
+        if (bus == 0 && threadIdx.x == 0 && A.rep_host_stats) {
+            const unsigned long long sb = A.stats->source_bytes, sl = A.stats->slow_blocks, af = A.stats->active_frames;
+            A.rep_host_stats->source_bytes = sb; A.rep_host_stats->slow_blocks = sl; A.rep_host_stats->active_frames = af;
+            A.stats->source_bytes = 0; A.stats->slow_blocks = 0; A.stats->active_frames = 0;   // cleared for the call that reuses this slot
+        }
+    }
+}
+
+__global__ void __launch_bounds__(128, ZL_K2_PAIR_WAVES) zl_k2_pair_render(const ZlBatch A) { zl_k2_pair_body<false>(A); }
+__global__ void __launch_bounds__(128, ZL_K2_PAIR_WAVES) zl_k2_pair_phase_render(const ZlBatch A) { zl_k2_pair_body<true>(A); }
 
 // ------------------------------------------------------------------------------------------------
 // Resident real-time kernel: one workgroup PER BUS that stays on the GPU and renders a JACK cycle whenever the host
@@ -2088,6 +2399,19 @@ int zl_launch_render(const ZlBatch &A, hipStream_t s, hipEvent_t ev_start, hipEv
     // event packets around the launch for the command processor to handle
     // LDS-staged source windows (A.staged): batches only, whole 256-thread workgroups; the ring is dynamic LDS
     const bool st = A.staged && A.K > 1 && tpb == 256;
+    // two frames per lane (zl_k2_pair_body): the caller asked for it (A.pair, zl_pair_window) and the launch has the shape the kernels are built
+    // for.  128 lanes per block; dynamic LDS pads a workgroup to ZL_K2_PAIR_LDS, which holds the launch at 8 workgroups per CU = 4 waves
+    // per SIMD and leaves the planner its wave slot and its LDS, as the 5-workgroup cap above does for the 256-lane kernels.
+    if (A.pair && zl_pair_shape(A.mode, A.N, A.K, A.NB, A.groups, A.staged, A.trace, A.fan != nullptr, A.host_out != nullptr, A.ongrid)) {
+        static const int pair_pad_env = [] { const char *e = getenv("ZL_K2_PAIR_LDS_PAD"); return e ? atoi(e) : -1; }();
+        static const int pair_static = [] { hipFuncAttributes fa; return hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(zl_k2_pair_render)) == hipSuccess ? (int)fa.sharedSizeBytes : ZL_K2_PAIR_LDS; }();
+        const int ppad = pair_pad_env >= 0 ? pair_pad_env : std::max(0, ZL_K2_PAIR_LDS - pair_static);
+        const dim3 pgrid(1, A.K, A.B), pblock(128);
+        if (At.order) hipExtLaunchKernelGGL(zl_k2_pair_phase_render, pgrid, pblock, ppad, s, ev_start, ev_stop, 0, At);
+        else          hipExtLaunchKernelGGL(zl_k2_pair_render, pgrid, pblock, ppad, s, ev_start, ev_stop, 0, At);
+        ZL_LAUNCH_CHECK();
+        return 0;
+    }
     if (st || bpw > 1) At.order = nullptr;                         // (the phase order exists for one block per workgroup, register gathers)
     const int ring = 4 * ZL_ST_D * ZL_ST_SLOT;
     switch (A.mode & 7u) {

@@ -1,0 +1,25 @@
+// zl_pair.h -- which K2 launches take the two-frames-per-lane kernels (zl_k2_pair_render / zl_k2_pair_phase_render, zl_kernels.hip).
+//
+// The pair form halves the load instructions of ON-GRID chunks only (a voice playing a clip at its own pitch and rate: lane j loads
+// frames 2 j and 2 j + 1 of the source with one 16-byte load); every other chunk costs what it costs in zl_k2_body.  The kernels are
+// built for one shape -- faithful linear mode, 256-frame blocks, one whole bus per workgroup -- and every other launch keeps the kernel
+// it has.  HIP-free: the CPU tier tests the truth table (tests/cpu_harness/pair_host.cpp).
+#pragma once
+#include <stdint.h>
+
+// the launch shapes the pair kernels exist for: mode exactly 0, blocks of 256 frames, a batch (K > 1: the resident kernel and single
+// real-time blocks never), one bus per workgroup (no narrow-bus packing, no mix groups), register gathers (not LDS-staged), no position
+// trace, no fused fan-out, no bounce sink, and the on-grid form switched on
+inline bool zl_pair_shape(uint32_t mode, int N, int K, int NB, int groups, int staged, int trace, bool fan, bool host_out, int ongrid)
+{
+    return mode == 0u && N == 256 && K > 1 && NB == 1 && groups == 1 && !staged && !trace && !fan && !host_out && ongrid != 0;
+}
+
+// does a launch of that shape take them?  sw = ZL_K2_PAIR: 0 never, 1 auto, 2 wherever the shape allows (tests, A/B runs).  Auto: every
+// playing voice is cheap to plan (unit ratio on a sample-space loop -- the voices whose interior blocks are on-grid; the flag that also
+// decides the one-window call and the phase order).  A window of pitched voices gains nothing from the form.
+inline bool zl_pair_window(int sw, bool shape, bool cheap)
+{
+    if (sw == 2) return shape;
+    return sw == 1 && shape && cheap;
+}
