@@ -20,7 +20,7 @@ LIBDIR = os.path.join(ROOT, "libzl_amd", "lib")
 LIB = os.path.join(LIBDIR, "libzlhip.so")
 
 HIP_SOURCES = ["zl_kernels.hip", "zl_stretch.hip", "zl_engine.cpp", "zl_libzl.cpp", "zl_group.cpp"]
-HEADERS = ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_pair.h", "zl_render.h", "zl_kernels.h", "zl_host.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", "zl_group.h", "zl_member.h",
+HEADERS = ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_render.h", "zl_kernels.h", "zl_host.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", "zl_group.h", "zl_member.h",
            os.path.join("..", "..", "include", "zlhip.h"), os.path.join("..", "..", "include", "libzl_hotpath.h")]
 
 
@@ -66,10 +66,10 @@ def build_engine(force: bool = False, verbose: bool = False, stamps: bool = Fals
 # per source: the headers it includes (a change of one of them recompiles only the sources that see it)
 _INC = os.path.join("..", "..", "include")
 SOURCE_DEPS = {
-    "zl_kernels.hip": ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_pair.h", "zl_kernels.h"],
+    "zl_kernels.hip": ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_kernels.h"],
     "zl_stretch.hip": ["zl_types.h", "zl_stretch.h"],
-    "zl_engine.cpp": ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_pair.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h")],
-    "zl_group.cpp": ["zl_types.h", "zl_plan.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_group.h", os.path.join(_INC, "zlhip.h")],
+    "zl_engine.cpp": ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h")],
+    "zl_group.cpp": ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_group.h", os.path.join(_INC, "zlhip.h")],
     "zl_libzl.cpp": ["zl_render.h", "zl_types.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h"), os.path.join(_INC, "libzl_hotpath.h")],
 }
 
@@ -210,109 +210,58 @@ def build_reference(force: bool = False, contracted: bool = False):
     return target
 
 
-def build_cpu_harness(force: bool = False) -> str:
-    """Host build of the __host__ __device__ planning / per-frame code for CPU-only unit tests."""
+_ZLHIP_H = os.path.join(_INC, "zlhip.h")
+_NO_CONTRACT = ["-ffp-contract=off", "-fno-fast-math"]
+
+
+def _build_harness(name: str, source: str, headers: list, flags: list, force: bool = False) -> str:
+    """tests/cpu_harness/<source> -> tests/cpu_harness/_build/lib<name>.so with g++: the host build of HIP-free product headers (paths relative
+    to csrc/) for the CPU tier.  (-Bsymbolic: the header-inline code of the library binds to ITS copies, not to libzlhip.so's when both are loaded)"""
     hdir = os.path.join(ROOT, "tests", "cpu_harness")
-    target = os.path.join(hdir, "_build", "libzl_plan_host.so")
-    src = os.path.join(hdir, "plan_host.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("zl_types.h", "zl_plan.h", "zl_render.h", "zl_host.h")] + [os.path.join(ROOT, "include", "zlhip.h")]
-    if force or _stale(target, deps):
+    target = os.path.join(hdir, "_build", f"lib{name}.so")
+    src = os.path.join(hdir, source)
+    if force or _stale(target, [src] + [os.path.join(CSRC, h) for h in headers]):
         os.makedirs(os.path.dirname(target), exist_ok=True)
-        # (-Bsymbolic: the header-inline code of this library binds to ITS copies, not to libzlhip.so's when both are loaded)
-        cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wl,-Bsymbolic",
-               "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-o", target, src]
+        cmd = ["g++", "-std=c++17", "-O2"] + flags + ["-fPIC", "-shared", "-Wl,-Bsymbolic", "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-o", target, src]
         res = subprocess.run(cmd, capture_output=True, text=True)
         if res.returncode != 0:
             sys.stderr.write(res.stdout + res.stderr)
-            raise RuntimeError("building the CPU test harness failed")
-    # the product's ClipCommand scheduler (zl_sched.h), host build
-    t2 = os.path.join(hdir, "_build", "libzl_sched_host.so")
-    src2 = os.path.join(hdir, "sched_host.cpp")
-    if force or _stale(t2, [src2, os.path.join(CSRC, "zl_sched.h"), os.path.join(ROOT, "include", "zlhip.h")]):
-        cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wall", "-Wl,-Bsymbolic",
-               "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-o", t2, src2]
-        res = subprocess.run(cmd, capture_output=True, text=True)
-        if res.returncode != 0:
-            sys.stderr.write(res.stdout + res.stderr)
-            raise RuntimeError("building the CPU scheduler harness failed")
-    # the clip re-render (zl_stretch.h), host build: the CPU tier's bit-exact check and the host side of scripts/rerender_bench.py
-    t3 = os.path.join(hdir, "_build", "libzl_stretch_host.so")
-    src3 = os.path.join(hdir, "stretch_host.cpp")
-    if force or _stale(t3, [src3, os.path.join(CSRC, "zl_stretch.h"), os.path.join(CSRC, "zl_types.h")]):
-        cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wall", "-Wl,-Bsymbolic", "-pthread",
-               "-I", CSRC, "-o", t3, src3]
-        res = subprocess.run(cmd, capture_output=True, text=True)
-        if res.returncode != 0:
-            sys.stderr.write(res.stdout + res.stderr)
-            raise RuntimeError("building the CPU re-render harness failed")
+            raise RuntimeError(f"building the CPU test harness {source} failed")
+    return target
+
+
+def build_cpu_harness(force: bool = False) -> str:
+    """Host builds of the __host__ __device__ planning / per-frame code, the product's ClipCommand scheduler (zl_sched.h) and the clip re-render
+    (zl_stretch.h: the CPU tier's bit-exact check and the host side of scripts/rerender_bench.py).  Returns the first."""
+    target = _build_harness("zl_plan_host", "plan_host.cpp", ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_host.h", _ZLHIP_H], _NO_CONTRACT, force)
+    _build_harness("zl_sched_host", "sched_host.cpp", ["zl_sched.h", _ZLHIP_H], _NO_CONTRACT + ["-Wall"], force)
+    _build_harness("zl_stretch_host", "stretch_host.cpp", ["zl_stretch.h", "zl_types.h"], _NO_CONTRACT + ["-Wall", "-pthread"], force)
     return target
 
 
 def build_order_harness(force: bool = False) -> str:
-    """Host build of K2's phase order (zl_order.h, tests/cpu_harness/order_host.cpp) for the CPU tier."""
-    hdir = os.path.join(ROOT, "tests", "cpu_harness")
-    target = os.path.join(hdir, "_build", "libzl_order_host.so")
-    src = os.path.join(hdir, "order_host.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("zl_types.h", "zl_plan.h", "zl_order.h", "zl_host.h")] + [os.path.join(ROOT, "include", "zlhip.h")]
-    if force or _stale(target, deps):
-        os.makedirs(os.path.dirname(target), exist_ok=True)
-        cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
-               "-Wl,-Bsymbolic", "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-o", target, src]
-        res = subprocess.run(cmd, capture_output=True, text=True)
-        if res.returncode != 0:
-            sys.stderr.write(res.stdout + res.stderr)
-            raise RuntimeError("building the CPU phase-order harness failed")
-    return target
+    """K2's phase order (zl_order.h)."""
+    return _build_harness("zl_order_host", "order_host.cpp", ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_host.h", _ZLHIP_H], _NO_CONTRACT + ["-Wall", "-Wno-unused-function"], force)
 
 
 def build_ongrid_harness(force: bool = False) -> str:
-    """Host build of K2's on-grid form (zl_render.h, tests/cpu_harness/ongrid_host.cpp) for the CPU tier."""
-    hdir = os.path.join(ROOT, "tests", "cpu_harness")
-    target = os.path.join(hdir, "_build", "libzl_ongrid_host.so")
-    src = os.path.join(hdir, "ongrid_host.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("zl_types.h", "zl_render.h")]
-    if force or _stale(target, deps):
-        os.makedirs(os.path.dirname(target), exist_ok=True)
-        cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
-               "-Wl,-Bsymbolic", "-I", CSRC, "-o", target, src]
-        res = subprocess.run(cmd, capture_output=True, text=True)
-        if res.returncode != 0:
-            sys.stderr.write(res.stdout + res.stderr)
-            raise RuntimeError("building the CPU on-grid harness failed")
-    return target
+    """K2's on-grid form (zl_render.h)."""
+    return _build_harness("zl_ongrid_host", "ongrid_host.cpp", ["zl_types.h", "zl_render.h"], _NO_CONTRACT + ["-Wall", "-Wno-unused-function"], force)
 
 
 def build_pair_harness(force: bool = False) -> str:
-    """Host build of the gate of K2's two-frames-per-lane kernels (zl_pair.h, tests/cpu_harness/pair_host.cpp) for the CPU tier."""
-    hdir = os.path.join(ROOT, "tests", "cpu_harness")
-    target = os.path.join(hdir, "_build", "libzl_pair_host.so")
-    src = os.path.join(hdir, "pair_host.cpp")
-    if force or _stale(target, [src, os.path.join(CSRC, "zl_pair.h")]):
-        os.makedirs(os.path.dirname(target), exist_ok=True)
-        cmd = ["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-Wl,-Bsymbolic", "-I", CSRC, "-o", target, src]
-        res = subprocess.run(cmd, capture_output=True, text=True)
-        if res.returncode != 0:
-            sys.stderr.write(res.stdout + res.stderr)
-            raise RuntimeError("building the CPU pair-gate harness failed")
-    return target
+    """The gate of K2's two-frames-per-lane kernels (zl_pair.h)."""
+    return _build_harness("zl_pair_host", "pair_host.cpp", ["zl_pair.h"], ["-Wall"], force)
 
 
 def build_group_harness(force: bool = False) -> str:
-    """Host build of the engine group's partition arithmetic and command routing (zl_group.h, tests/cpu_harness/group_host.cpp) for
-    the CPU tier."""
-    hdir = os.path.join(ROOT, "tests", "cpu_harness")
-    target = os.path.join(hdir, "_build", "libzl_group_host.so")
-    src = os.path.join(hdir, "group_host.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("zl_types.h", "zl_plan.h", "zl_host.h", "zl_group.h")] + [os.path.join(ROOT, "include", "zlhip.h")]
-    if force or _stale(target, deps):
-        os.makedirs(os.path.dirname(target), exist_ok=True)
-        cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
-               "-Wl,-Bsymbolic", "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-o", target, src]
-        res = subprocess.run(cmd, capture_output=True, text=True)
-        if res.returncode != 0:
-            sys.stderr.write(res.stdout + res.stderr)
-            raise RuntimeError("building the CPU group harness failed")
-    return target
+    """The engine group's partition arithmetic and command routing (zl_group.h)."""
+    return _build_harness("zl_group_host", "group_host.cpp", ["zl_types.h", "zl_plan.h", "zl_host.h", "zl_group.h", _ZLHIP_H], _NO_CONTRACT + ["-Wall", "-Wno-unused-function"], force)
+
+
+def build_launch_harness(force: bool = False) -> str:
+    """Which K2 kernel a window gets, its grid, and the call's windows (zl_launch.h)."""
+    return _build_harness("zl_launch_host", "launch_host.cpp", ["zl_types.h", "zl_order.h", "zl_pair.h", "zl_launch.h"], ["-Wall", "-Wno-unused-function"], force)
 
 
 if __name__ == "__main__":

@@ -1310,11 +1310,7 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
     A.V = e->V; A.B = e->cfg.num_buses; A.VPB = e->cfg.voices_per_bus; A.N = nframes; A.Ktot = nblocks;
     A.G = pick_group(e, nblocks, nframes);
     A.groups = (A.VPB + A.G - 1) / A.G;
-    // narrow buses in batches: several whole buses per K2 workgroup (voices of consecutive buses are contiguous); needs the
-    // bus width to be a multiple of K2's chunk of 8 voices, no mix groups, one frame tile per block
-    A.NB = 1;
-    if (nblocks > 1 && A.groups == 1 && A.VPB <= 64 && (A.VPB % 8) == 0 && nframes <= 256)
-        A.NB = std::max(1, std::min(128 / A.VPB, A.B));
+    A.NB = zl_k2_narrow_buses(nblocks, A.groups, A.VPB, A.B, nframes);
     A.clocks_regular = regular ? 1 : 0;
     A.mode = e->cfg.mode;
     A.ongrid = zl_ongrid_switch();
@@ -1340,10 +1336,7 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
 #endif
     }
 
-    // ---- plan windows: K0/K1/K1c of window i+1 run on the planning stream while K2/K3 of window i render ----
-    // Window layout: large windows keep K2 launches long (their ramp-up and drain are a fixed cost per launch), but
-    // planning window i+1 must fit behind rendering window i, and the planning of the first window is hidden by
-    // nothing but the previous call: windows start at 256 blocks and double up to the configured size.
+    // ---- plan windows: K0/K1/K1c of window i+1 run on the planning stream while K2/K3 of window i render (layout: zl_plan_windows) ----
     // (ZL_WINDOW_MUL=4: blocks longer than 64 frames may fill the record arrays -- up to four windows' worth of frames in one K2
     // launch.  Measured: K2 gains 4..9 % (fewer launch ramps; a bus's sources are re-read inside ONE launch, from the Infinity Cache),
     // the headline call 2..3.5 %, but a call is then a single window whose planning is hidden by nothing but the previous call's
@@ -1362,31 +1355,12 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
     if (windowMul == 0) windowMul = cheap ? 4 : 1;
     // (engines that split buses into mix groups keep the fixed size: their partial rows are sized for it)
     const size_t mul = e->maxGroups > 1 ? 1 : (size_t)windowMul;
-    int W = e->windowBlocks > 0 ? e->windowBlocks : (int)std::max<size_t>(1, std::min<size_t>(mul * e->windowFrames / (size_t)nframes, (size_t)1 << 30));
-    W = std::min(W, e->windowCap);
-    W = std::min(W, (1 << 30) / nframes);                          // window time is a 32-bit frame index in K1 / K1c
-    W = std::min(W, 60000);                                        // a K2 launch has one y slot per block (+ 1920 for a split tail): gridDim.y stays below 65536
     std::vector<std::pair<int, int>> &wins = e->wins;              // (first block, blocks); member: no allocation per call
-    wins.clear();
-    // when the previous call is still in flight its rendering hides the planning of this call's first window: no
-    // need to start small (fewer, longer K2 launches)
     zlhip_engine::CallSlot &prev = e->slots[(e->callIndex + 1u) & 1u];
     const bool behindPrev = prev.inflight && hipEventQuery(prev.done) == hipErrorNotReady;
-    if (nblocks <= W || e->ps[1].hdr == nullptr || behindPrev) {
-        for (int k0 = 0; k0 < nblocks; k0 += W) wins.push_back({k0, std::min(W, nblocks - k0)});
-    } else {
-        // nothing hides the planning of this call's first window: a quarter-size window first (its planning is short,
-        // and its rendering is long enough to hide the planning of a full window), then full windows.  (Doubling from
-        // 64 Ki frames cost three small, inefficient K2 launches: +280 us per such call against +110 us.)
-        const char *fw = std::getenv("ZL_FIRST_WINDOW_FRAMES");
-        int size = std::min(W, std::max(1, (fw ? std::atoi(fw) : (int)std::min<size_t>(e->windowFrames / 4, (size_t)1 << 28)) / nframes));
-        for (int k0 = 0; k0 < nblocks;) {
-            const int n = std::min(size, nblocks - k0);
-            wins.push_back({k0, n});
-            k0 += n;
-            size = W;
-        }
-    }
+    const char *fw = std::getenv("ZL_FIRST_WINDOW_FRAMES");
+    const int fwFrames = fw ? std::atoi(fw) : 0;
+    zl_plan_windows(nblocks, nframes, e->windowBlocks, e->windowFrames, e->windowCap, mul, e->ps[1].hdr != nullptr, behindPrev, fw ? &fwFrames : nullptr, wins);
     const int nwin = (int)wins.size();
     // ---- K2's phase order (K1o, zl_order.h): a window whose voices re-read their loops is rendered in the loop-phase order
     //      of a key voice, so that the re-reads of a source line run together on one XCD and hit its L2.  Results do not depend on it (K2's
@@ -1395,16 +1369,25 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
     //      not staged, no bounce, and the window longer than a playing loop (zl_order_window; K1o itself keeps time order in a z-slot whose
     //      key voice's pass is longer than the window).  Elsewhere the launch is the one without the order.
     const int phaseMode = [] { const char *v = std::getenv("ZL_K2_PHASE_ORDER"); return v ? std::atoi(v) : 1; }();
-    const int orderSlots = A.NB > 1 ? (A.B + A.NB - 1) / A.NB : A.B;
-    const bool orderShape = zl_order_shape(A.groups, A.staged, nblocks, nframes);
     const double loopFrames = phaseMode == 1 ? e->hc.phase_order_loop_frames() : INFINITY;
-    auto orderWindow = [&](int K) { return zl_order_window(phaseMode, orderShape, e->bnc.sink.on, nframes, K, loopFrames); };
     // ---- K2 with two frames per lane (zl_pair.h): ZL_K2_PAIR 0 = never, 1 = auto (default: every playing voice cheap to plan, the
     //      voices whose interior blocks are on-grid), 2 = wherever the launch shape allows (tests, A/B); read per call
     const int pairMode = [] { const char *v = std::getenv("ZL_K2_PAIR"); return v ? std::atoi(v) : 1; }();
+    // offline bounce, direct delivery: K2 itself also stores the finished bus into the caller's page-locked host buffer
+    const bool direct = e->bnc.sink.on && e->bnc.sink.hostDev && A.groups == 1;
+    // ---- which kernel a window of K blocks gets, its grid, and what follows from it (zl_launch.h) ----
+    const ZlK2Switches &k2sw = zl_k2_switches();
+    auto k2Launch = [&](int K, bool orderTable) {
+        ZlK2In in;
+        in.mode = A.mode; in.N = nframes; in.K = K; in.B = A.B; in.groups = A.groups; in.NB = A.NB;
+        in.staged = A.staged; in.trace = A.trace; in.ongrid = A.ongrid; in.fan = fan_out_dev != nullptr; in.host_out = direct;
+        in.order_mode = phaseMode; in.call_blocks = nblocks; in.bounce = e->bnc.sink.on; in.order_table = orderTable; in.loop_frames = loopFrames;
+        in.pair_mode = pairMode; in.cheap = cheap;
+        return zl_k2_launch(in, k2sw);
+    };
     {
         size_t need = 0;
-        for (const auto &wk : wins) if (orderWindow(wk.second)) need = std::max(need, (size_t)orderSlots * (size_t)wk.second);
+        for (const auto &wk : wins) { const ZlK2Launch L = k2Launch(wk.second, true); if (L.order) need = std::max(need, (size_t)L.gz * (size_t)wk.second); }
         if (need > e->ps[0].orderInts || (e->ps[1].hdr != nullptr && need > e->ps[1].orderInts)) {
             ZlQuiesce quiet(e);                                    // (as for the trace buffer: hipFree waits for the whole device)
             for (auto &q : e->ps) {
@@ -1450,7 +1433,8 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
     // the workgroups of that block publish gains, reports and statistics, and the launch carries the call's completion event -- between
     // the last render kernel of this call and the first of the next sits no report kernel any more (12 % of a 64-voice step were packets).
     // (Not while a bounce hands windows to the copy engine: its conversion kernels and copies follow the last render kernel.)
-    const bool fusedReports = A.groups == 1 && nframes <= 256 && !(e->bnc.sink.on && !(e->bnc.sink.hostDev && A.groups == 1));
+    // (scans_levels: that workgroup exists -- the same for every window of a call)
+    const bool fusedReports = k2Launch(wins[0].second, false).scans_levels && !(e->bnc.sink.on && !direct);
     c.fusedDone = fusedReports;
     for (int w = 0; w < nwin; ++w) {
         zlhip_engine::PlanSet &q = e->ps[(phase + (unsigned)w) & 1u];
@@ -1467,7 +1451,8 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
         // every (block, voice) of a window asks for at most one slot: the next window of this set counts from past that
         Aw.ctl_base = q.ctlBase;
         q.ctlBase += (unsigned long long)Aw.K * (unsigned long long)e->V + 1ull;
-        Aw.order = orderWindow(Aw.K) && q.order ? q.order : nullptr;
+        const ZlK2Launch L = k2Launch(Aw.K, q.order != nullptr);
+        Aw.order = L.order ? q.order : nullptr;
         if (w > 0) { Aw.n_op_ranges = 0; Aw.ops = nullptr; Aw.op_ranges = nullptr; Aw.n_clip_edits = 0; Aw.clip_edits = nullptr; }   // commands and parameter edits apply before the first block only
         // planning may not overwrite a record set while an earlier window (of this or the previous call) still renders from it
         if (ps != s && q.used) ZL_HIP(e, hipStreamWaitEvent(ps, q.renderedEv, 0));
@@ -1478,28 +1463,25 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
             ZL_HIP(e, hipEventRecord(q.k1done, ps));
             ZL_HIP(e, hipStreamWaitEvent(e->asmStream, q.k1done, 0));
             ZL_KERNEL(e, zl_launch_assemble(Aw, e->asmStream));
-            if (Aw.order) ZL_KERNEL(e, zl_launch_order(Aw, q.order, orderSlots, e->asmStream));
+            if (L.order) ZL_KERNEL(e, zl_launch_order(Aw, q.order, (int)L.gz, e->asmStream));
             ZL_HIP(e, hipEventRecord(q.planned, e->asmStream));
             ZL_HIP(e, hipStreamWaitEvent(s, q.planned, 0));
         } else {
             if (!Aw.fuse_assemble) ZL_KERNEL(e, zl_launch_assemble(Aw, ps));
-            if (Aw.order) ZL_KERNEL(e, zl_launch_order(Aw, q.order, orderSlots, ps));
+            if (L.order) ZL_KERNEL(e, zl_launch_order(Aw, q.order, (int)L.gz, ps));
             if (ps != s) {
                 ZL_HIP(e, hipEventRecord(q.planned, ps));
                 ZL_HIP(e, hipStreamWaitEvent(s, q.planned, 0));
             }
         }
-        // K2 scans the block for AudioLevels itself when one workgroup holds the whole block of the final mix
-        const bool k3 = !(Aw.groups == 1 && nframes <= 256);
-        // offline bounce, direct delivery: K2 itself also stores the finished bus into the caller's page-locked host buffer
-        const bool direct = e->bnc.sink.on && e->bnc.sink.hostDev && Aw.groups == 1;
+        const bool k3 = !L.scans_levels;
         if (direct) { Aw.host_out = e->bnc.sink.hostDev; Aw.host_fmt = e->bnc.sink.pcm ? 1 : 0; Aw.host_total = (long long)e->bnc.sink.totalFrames; Aw.host_k0 = 0; }
         // profiling: the K2 dispatch carries its own start / stop events (hipExtLaunchKernel); the call's last launch carries `done`
         const bool closes = fusedReports && w == nwin - 1;
         if (fusedReports) { Aw.fused_reports = 1; Aw.rep_gain = e->dGain; Aw.rep_host = c.hReportsDev; Aw.rep_host_gain = c.hGainDev; Aw.rep_host_stats = c.hStatsDev; }
-        Aw.pair = zl_pair_window(pairMode, zl_pair_shape(Aw.mode, Aw.N, Aw.K, Aw.NB, Aw.groups, Aw.staged, Aw.trace, Aw.fan != nullptr, Aw.host_out != nullptr, Aw.ongrid), cheap) ? 1 : 0;
+        Aw.pair = (L.kernel == ZL_K2_PAIR_RENDER || L.kernel == ZL_K2_PAIR_PHASE_RENDER) ? 1 : 0;
         hipEvent_t k2stop = closes ? c.done : (e->profiling ? c.evK2[2 * (size_t)w + 1] : nullptr);
-        ZL_KERNEL(e, zl_launch_render(Aw, s, e->profiling ? c.evK2[2 * (size_t)w] : nullptr, k2stop));
+        ZL_KERNEL(e, zl_launch_render(Aw, L, s, e->profiling ? c.evK2[2 * (size_t)w] : nullptr, k2stop));
         if (k3) ZL_KERNEL(e, zl_launch_finalize(Aw, nullptr, s));
         // ... or through the copy engine, window by window: the window's columns of the bus are final now
         if (e->bnc.sink.on && !direct) { int d_ = bounce_deliver_window(e, A.bus, 0, Aw.B, Aw.k0, Aw.K, nblocks, nframes, s); if (d_ != ZLHIP_OK) return d_; }
@@ -1753,7 +1735,7 @@ static int rt_start(zlhip_engine *e, int nframes)
     __atomic_store_n(&e->rt.h->state, 0u, __ATOMIC_RELEASE);
     __atomic_store_n(&e->rt.h->yield, 0u, __ATOMIC_RELEASE);
     for (uint32_t &d : e->rt.h->wg_done) __atomic_store_n(&d, (uint32_t)e->rt.seq, __ATOMIC_RELAXED);   // (no workgroup has finished the cycle to come)
-    ZL_KERNEL(e, zl_launch_rt_loop(A, e->rt.d, e->rt.dev, e->rt.seq, e->rt.idleTicks, e->dGain, c.hReportsDev, c.hGainDev, e->rt.devRanges, std::max(e->rt.vw, 1), std::min(256, (nframes + 63) & ~63), e->rt.stream));
+    ZL_KERNEL(e, zl_launch_rt_loop(A, e->rt.d, e->rt.dev, e->rt.seq, e->rt.idleTicks, e->dGain, c.hReportsDev, c.hGainDev, e->rt.devRanges, std::max(e->rt.vw, 1), zl_whole_waves(nframes), e->rt.stream));
     e->rt.running = true; e->rt.nframes = nframes; e->rt.starts += 1;
     if (std::find(g_rt.engines.begin(), g_rt.engines.end(), e) == g_rt.engines.end()) g_rt.engines.push_back(e);
     return ZLHIP_OK;

@@ -2,12 +2,14 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include "zl_types.h"
+#include "zl_launch.h"
 
 int zl_launch_apply_ops(const ZlBatch &A, hipStream_t s);
 int zl_launch_plan(const ZlBatch &A, int force_slow, hipStream_t s);
 int zl_launch_assemble(const ZlBatch &A, hipStream_t s);
 int zl_launch_order(const ZlBatch &A, int32_t *order, int nslots, hipStream_t s);   // K1o: order[nslots][A.K]
-int zl_launch_render(const ZlBatch &A, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+const ZlK2Switches &zl_k2_switches();
+int zl_launch_render(const ZlBatch &A, const ZlK2Launch &L, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);   // L = zl_k2_launch(...)
 int zl_launch_finalize(const ZlBatch &A, const float *bus_in, hipStream_t s);
 int zl_launch_reports(const ZlReport *reports, int V, float *gain_out, ZlReport *host_reports, float *host_gain,
                       const ZlBatchStats *stats, ZlBatchStats *host_stats, hipStream_t s, hipEvent_t ev_done = nullptr);

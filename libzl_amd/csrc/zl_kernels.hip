@@ -996,7 +996,10 @@ static __device__ __forceinline__ void zl_k2_chunk(const ZlBatch &A, const ZlBlo
 }
 
 // The staging pass of zl_k2_body below, as functions, for zl_k2_pair_body.  (zl_k2_body keeps its own text: calling these from it moved the
-// register allocation of two existing kernels -- zl_k2_phase_render<2> gained a private segment -- and those kernels are to stay as they are.)
+// register allocation of two existing kernels -- zl_k2_phase_render<2> gained a private segment -- and those kernels are to stay as they are.
+// Compiled again since, so that nobody need repeat it: with zl_k2_body calling zl_k2_stage_load / _class / _chunks, 72 of the 99 kernels of
+// this file change; zl_k2_phase_render<2> goes from 0 to 36 bytes of scratch; the headline kernel's SGPR spills go from 122 to 117, and
+// zl_k_rt_loop<0, wide>'s from 402 to 338 with 20 -> 12 bytes of scratch.  K2 sits at the SGPR limit: any change to its text moves the allocation.)
 // The record of voice vb + i in block kk (i >= nv: a slot behind the pass's last voice, which gets the neutral record); every load the record
 // may need is issued at once.
 static __device__ __forceinline__ void zl_k2_stage_load(const ZlBatch &A, int kk, int vb, int i, int nv, ZlVoiceConst &vc, ZlBlockPlan &pl)
@@ -2363,70 +2366,48 @@ int zl_launch_order(const ZlBatch &A, int32_t *order, int nslots, hipStream_t s)
     return 0;
 }
 
-int zl_launch_render(const ZlBatch &A, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop)
+// what zl_k2_launch (zl_launch.h) takes from the environment and the code object: read once per process
+const ZlK2Switches &zl_k2_switches()
 {
-    // blocks of 64 / 128 frames: 4 / 2 blocks per workgroup (batches only; a single block keeps its small workgroup; other lengths
-    // below 256 -- 16, 32, 48, 100 ... -- are real-time periods: one block per workgroup of whole waves)
-    const int bpw = ((A.N == 64 || A.N == 128) && A.K > 1) ? 256 / A.N : 1;
-    // (whole waves: a block of 100 frames runs on 128 lanes, one of 300 on two workgroups of 256)
-    const int tpb = bpw > 1 ? 256 : (A.N < 256 ? ((A.N + 63) & ~63) : 256);
-    dim3 grid(bpw > 1 ? 1 : (A.N + tpb - 1) / tpb, (A.K + bpw - 1) / bpw, A.NB > 1 ? (A.B + A.NB - 1) / A.NB : A.B * A.groups);
-    const dim3 block(tpb);
-    // split tail (see zl_k2_body): one workgroup per block holding ALL the buses, a window long enough to have a tail worth splitting
-    static const int tail_env = [] { const char *e = getenv("ZL_K2_TAIL"); return e ? atoi(e) : 1; }();
-    static const int tail_min = [] { const char *e = getenv("ZL_K2_TAIL_MIN_BLOCKS"); return e ? std::max(8, atoi(e)) : 2048; }();   // (the test tier lowers it)
+    static const ZlK2Switches sw = [] {
+        ZlK2Switches w = zl_k2_env_switches();
+        w.pair_lds = ZL_K2_PAIR_LDS;
+        hipFuncAttributes fa;
+        w.pair_static_lds = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(zl_k2_pair_render)) == hipSuccess ? (int)fa.sharedSizeBytes : ZL_K2_PAIR_LDS;
+        w.st_ring = 4 * ZL_ST_D * ZL_ST_SLOT;
+        return w;
+    }();
+    return sw;
+}
+
+// K2 as zl_k2_launch describes it: nothing is decided here.  The switch's key spells the kernel's template arguments.
+static constexpr int zl_k2_key(int kernel, int bpw, bool st, int mode) { return ((kernel * 8 + bpw) * 2 + (st ? 1 : 0)) * 8 + mode; }
+
+int zl_launch_render(const ZlBatch &A, const ZlK2Launch &L, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop)
+{
+    const dim3 grid(L.gx, L.gy, L.gz), block(L.threads);
     ZlBatch At = A;
-    At.tail_from = 0; At.tail_split = 1; At.tail_nb = A.NB;
-    if (tail_env && bpw == 1 && A.NB > 1 && A.NB == A.B && grid.z == 1 && grid.x == 1 && !(A.staged && A.K > 1 && tpb == 256) && A.K >= tail_min) {
-        const int split = (A.NB % 4 == 0) ? 4 : (A.NB % 2 == 0) ? 2 : 1;
-        if (split > 1) {
-            const int T = std::min(A.K / 4, 640);                  // half a generation of workgroups (5 per CU x 256 CUs)
-            At.tail_from = A.K - T; At.tail_split = split; At.tail_nb = A.NB / split;
-            grid.y = (unsigned)(At.tail_from + T * split);
-        }
-    }
-    // One-block-per-workgroup kernels fill every SIMD's register file (6 waves x 80 VGPRs; 5 x 96 with 4 taps) and
-    // leave no room for a planning wave (88 VGPRs): a K1 launch that arrives after K2 has filled the machine then
-    // crawls (measured 550 instead of 130 us).  Unused dynamic LDS caps K2 at 5 workgroups per CU (27 KB each of
-    // 160 KB) -- one wave slot per SIMD stays free for the planner, and K2 itself is 0.5 % faster that way.
-    static const int pad_env = [] { const char *e = getenv("ZL_K2_LDS_PAD"); return e ? atoi(e) : -1; }();
-    static const int pad_env_h = [] { const char *e = getenv("ZL_K2_LDS_PAD_HERMITE"); return e ? atoi(e) : -1; }();
-    // (ZL_K2_LDS_PAD=0 -- the sixth workgroup per CU -- was measured again after the planner became a single sweep: K2 itself gains
-    // 1..3 %, but a planner launch that arrives just after K2 has filled the machine then waits for the whole K2 launch every now
-    // and then (2.5 ms instead of 35 us), and across boxes the calls gain nothing: the cap stays.)
-    const int pad = (A.mode & ZL_MODE_HERMITE) ? (pad_env_h >= 0 ? pad_env_h : 0) : (pad_env >= 0 ? pad_env : 10240);
+    At.tail_from = L.tail_from; At.tail_split = L.tail_split; At.tail_nb = L.tail_nb;
+    At.order = L.order ? A.order : nullptr;
     // ev_start / ev_stop (profiling): the kernel's own begin / end timestamps, taken by the dispatch packet itself -- no
     // event packets around the launch for the command processor to handle
-    // LDS-staged source windows (A.staged): batches only, whole 256-thread workgroups; the ring is dynamic LDS
-    const bool st = A.staged && A.K > 1 && tpb == 256;
-    // two frames per lane (zl_k2_pair_body): the caller asked for it (A.pair, zl_pair_window) and the launch has the shape the kernels are built
-    // for.  128 lanes per block; dynamic LDS pads a workgroup to ZL_K2_PAIR_LDS, which holds the launch at 8 workgroups per CU = 4 waves
-    // per SIMD and leaves the planner its wave slot and its LDS, as the 5-workgroup cap above does for the 256-lane kernels.
-    if (A.pair && zl_pair_shape(A.mode, A.N, A.K, A.NB, A.groups, A.staged, A.trace, A.fan != nullptr, A.host_out != nullptr, A.ongrid)) {
-        static const int pair_pad_env = [] { const char *e = getenv("ZL_K2_PAIR_LDS_PAD"); return e ? atoi(e) : -1; }();
-        static const int pair_static = [] { hipFuncAttributes fa; return hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(zl_k2_pair_render)) == hipSuccess ? (int)fa.sharedSizeBytes : ZL_K2_PAIR_LDS; }();
-        const int ppad = pair_pad_env >= 0 ? pair_pad_env : std::max(0, ZL_K2_PAIR_LDS - pair_static);
-        const dim3 pgrid(1, A.K, A.B), pblock(128);
-        if (At.order) hipExtLaunchKernelGGL(zl_k2_pair_phase_render, pgrid, pblock, ppad, s, ev_start, ev_stop, 0, At);
-        else          hipExtLaunchKernelGGL(zl_k2_pair_render, pgrid, pblock, ppad, s, ev_start, ev_stop, 0, At);
-        ZL_LAUNCH_CHECK();
-        return 0;
-    }
-    if (st || bpw > 1) At.order = nullptr;                         // (the phase order exists for one block per workgroup, register gathers)
-    const int ring = 4 * ZL_ST_D * ZL_ST_SLOT;
-    switch (A.mode & 7u) {
-#define ZL_CASE(M) case M: \
-        if (st && bpw == 4)      hipExtLaunchKernelGGL((zl_k2_render<M, 4, true>), grid, block, ring, s, ev_start, ev_stop, 0, At); \
-        else if (st && bpw == 2) hipExtLaunchKernelGGL((zl_k2_render<M, 2, true>), grid, block, ring, s, ev_start, ev_stop, 0, At); \
-        else if (st)             hipExtLaunchKernelGGL((zl_k2_render<M, 1, true>), grid, block, ring, s, ev_start, ev_stop, 0, At); \
-        else if (bpw == 4)       hipExtLaunchKernelGGL((zl_k2_render<M, 4, false>), grid, block, 0, s, ev_start, ev_stop, 0, At); \
-        else if (bpw == 2)       hipExtLaunchKernelGGL((zl_k2_render<M, 2, false>), grid, block, 0, s, ev_start, ev_stop, 0, At); \
-        else if (At.order)       hipExtLaunchKernelGGL((zl_k2_phase_render<M>), grid, block, pad, s, ev_start, ev_stop, 0, At); \
-        else                     hipExtLaunchKernelGGL((zl_k2_render<M, 1, false>), grid, block, pad, s, ev_start, ev_stop, 0, At); \
-        break;
+#define ZL_GO(...) hipExtLaunchKernelGGL((__VA_ARGS__), grid, block, L.dyn_lds, s, ev_start, ev_stop, 0, At); break;
+    switch (zl_k2_key(L.kernel, L.bpw, L.staged, (int)(A.mode & 7u))) {
+#define ZL_CASE(M) \
+    case zl_k2_key(ZL_K2_RENDER, 4, true, M):        ZL_GO(zl_k2_render<M, 4, true>) \
+    case zl_k2_key(ZL_K2_RENDER, 2, true, M):        ZL_GO(zl_k2_render<M, 2, true>) \
+    case zl_k2_key(ZL_K2_RENDER, 1, true, M):        ZL_GO(zl_k2_render<M, 1, true>) \
+    case zl_k2_key(ZL_K2_RENDER, 4, false, M):       ZL_GO(zl_k2_render<M, 4, false>) \
+    case zl_k2_key(ZL_K2_RENDER, 2, false, M):       ZL_GO(zl_k2_render<M, 2, false>) \
+    case zl_k2_key(ZL_K2_PHASE_RENDER, 1, false, M): ZL_GO(zl_k2_phase_render<M>) \
+    case zl_k2_key(ZL_K2_RENDER, 1, false, M):       ZL_GO(zl_k2_render<M, 1, false>)
         ZL_CASE(0) ZL_CASE(1) ZL_CASE(2) ZL_CASE(3) ZL_CASE(4) ZL_CASE(5) ZL_CASE(6) ZL_CASE(7)
 #undef ZL_CASE
+    case zl_k2_key(ZL_K2_PAIR_RENDER, 1, false, 0):       ZL_GO(zl_k2_pair_render)
+    case zl_k2_key(ZL_K2_PAIR_PHASE_RENDER, 1, false, 0): ZL_GO(zl_k2_pair_phase_render)
+    default: return (int)hipErrorInvalidValue;                     // no kernel of that description: an error, never another kernel
     }
+#undef ZL_GO
     ZL_LAUNCH_CHECK();
     return 0;
 }
@@ -2475,7 +2456,7 @@ int zl_launch_finalize(const ZlBatch &A, const float *bus_in, hipStream_t s)
         const long long pairs = (long long)A.K * A.B;
         hipLaunchKernelGGL(zl_k3_scan, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, s, A, scan);
     } else {
-        hipLaunchKernelGGL(zl_k3_finalize, dim3(A.K, A.B), dim3(A.N < 256 ? ((A.N + 63) & ~63) : 256), 0, s, A, bus_in);
+        hipLaunchKernelGGL(zl_k3_finalize, dim3(A.K, A.B), dim3(zl_whole_waves(A.N)), 0, s, A, bus_in);
     }
     ZL_LAUNCH_CHECK();
     return 0;

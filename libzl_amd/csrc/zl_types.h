@@ -322,7 +322,8 @@ struct ZlBatch {
     float              *rep_host_gain;  // [V]
     ZlBatchStats       *rep_host_stats; // mapped host memory, or nullptr
     int32_t             fused_reports;
-    int32_t             pair;       // 1: zl_launch_render may take the two-frames-per-lane kernels where the launch has their shape (zl_pair.h)
+    int32_t             pair;       // 1: the launch is one of the two-frames-per-lane kernels (zl_k2_launch, zl_launch.h).  Nobody reads it any more -- the
+                                    // launcher takes the kernel from the launch description -- and it stays: the layout of the kernel argument does not move
     ZlBlockLevels      *levels;   // [K][B]
     int32_t            *pos_trace;// [K][V][N] or null
     const int32_t      *order;    // [z-slots][K] K2's block of each launch slot (K1o, zl_order.h), or null: time order

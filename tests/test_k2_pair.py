@@ -5,8 +5,9 @@ four renders are also compared with each other.  Checked against the oracle: the
 block peaks of every block of the last call and the RMS extension of several of its blocks per bus and channel (the fused level scan, whose
 defined order the pair form keeps with a tree of its own, zl_wave_levels4_pair).
 
-A test cannot see which kernel ran: with the switch at 2 every batch launch of mode 0, 256 frames, wide buses and no mix groups takes the pair
-kernels (tests/test_k2_pair_cpu.py holds the gate's truth table), and the scenes are built so that every chunk class passes through them --
+A GPU test cannot see which kernel ran; the CPU tier's table can (tests/test_k2_launch_cpu.py: the launch description zl_launch_render launches
+from).  With the switch at 2 every batch launch of mode 0, 256 frames, wide buses and no mix groups takes the pair kernels
+(tests/test_k2_pair_cpu.py holds the gate's truth table), and the scenes are built so that every chunk class passes through them --
 on-grid interior blocks, the blocks at loop restarts, pitched voices, mono sources, envelopes, voices that start and stop.
 
 NaN frames are compared as in tests/test_k2_ongrid.py: "NaN in the same frames"."""
