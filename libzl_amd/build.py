@@ -249,6 +249,11 @@ def build_ongrid_harness(force: bool = False) -> str:
     return _build_harness("zl_ongrid_host", "ongrid_host.cpp", ["zl_types.h", "zl_render.h"], _NO_CONTRACT + ["-Wall", "-Wno-unused-function"], force)
 
 
+def build_ongrid_pk_harness(force: bool = False) -> str:
+    """K2's packed on-grid mix as restated for the host (zl_render.h, zl_mix_frame_ongrid_pk)."""
+    return _build_harness("zl_ongrid_pk_host", "ongrid_pk_host.cpp", ["zl_types.h", "zl_render.h"], _NO_CONTRACT + ["-Wall", "-Wno-unused-function"], force)
+
+
 def build_pair_harness(force: bool = False) -> str:
     """The gate of K2's two-frames-per-lane kernels (zl_pair.h)."""
     return _build_harness("zl_pair_host", "pair_host.cpp", ["zl_pair.h"], ["-Wall"], force)

@@ -355,7 +355,28 @@ typedef float zl_f2 __attribute__((ext_vector_type(2)));
 
 // unit-step blocks (playback at the source rate inside an exact run): integer part of P0 and the constant fraction
 // + the gain products (gain * envelope) * volume of the Hermite mode's whole-sample gain (zl_render.h), one number per voice-block in sustain
-struct ZlUnit { int ipos; float alpha; float gpl, gpr; };
+// The gain products are read in the Hermite mode only, and no voice is on-grid there (zl_voice_ongrid): in every other mode their
+// eight bytes hold, for a voice classed on-grid, the byte address of the block's frame 0 in the arena (zl_unit_record) -- the one
+// thing the on-grid chunks read of the voice besides its pan pair.
+struct ZlUnit { int ipos; float alpha; union { struct { float gpl, gpr; }; uint64_t addr0; }; };
+static_assert(sizeof(ZlUnit) == 16, "one 16-byte LDS record per voice");
+
+// the ZlUnit of a staged voice-block (cls: zl_k2_stage_class).  addr0 = arena + 4 src_offset + 8 ipos (4 ipos mono) in 64-bit unsigned
+// arithmetic: the offset of a source in a grown arena segment is relative to the first segment and wraps modulo 2^64, as the pointer
+// arithmetic of the two-tap chunks does
+template <uint32_t MODE>
+static __device__ __forceinline__ ZlUnit zl_unit_record(const ZlBatch &A, const ZlVoiceConst &vc, const ZlBlockPlan &pl, int cls)
+{
+    ZlUnit un;
+    un.ipos = (int)pl.P0; un.alpha = (float)(pl.P0 - (double)un.ipos);
+    if (MODE & ZL_MODE_HERMITE) {
+        un.gpl = (vc.lgain * pl.env) * vc.clip_volume; un.gpr = (vc.rgain * pl.env) * vc.clip_volume;
+    } else {
+        const uint64_t frame0 = (uint64_t)(uint32_t)un.ipos << ((cls & 16) ? 2 : 3);
+        un.addr0 = (cls & 128) ? (uint64_t)reinterpret_cast<uintptr_t>(A.arena) + (vc.src_offset << 2) + frame0 : 0ull;
+    }
+    return un;
+}
 
 // zl_hermite_weights / zl_hermite4 (zl_render.h) with both channels in one register pair: the weights are scalar work shared by
 // the channels, the four multiply-adds are v_pk_fma_f32 (one rounding per fused operation, as fmaf)
@@ -544,37 +565,129 @@ static __device__ __forceinline__ void zl_k2_chunk_simple(const ZlBatch &A, cons
 // mono), 512 contiguous bytes per wave instead of a 1 KiB overlapping gather -- and mixes it with zl_mix_frame_ongrid: no second tap,
 // no gain chain, no read of the gains from LDS.  U loads in flight, the voices accumulated in voice order, the report as in
 // zl_k2_simple_mix.  Same bus and reports as the two-tap form, bit for bit.
-typedef float zl_f2a8 __attribute__((ext_vector_type(2), aligned(8)));
-template <bool MONO, int U>
-static __device__ __forceinline__ void zl_k2_chunk_ongrid(const ZlBatch &A, const ZlVoiceConst *s_vc, const ZlUnit *s_unit,
-                                                           int c0, int vfirst, int f, bool wantPeak, float &accL, float &accR)
+//
+// ONE ADDRESS PER VOICE: staging leaves the byte address of the block's frame 0 in the voice's ZlUnit (zl_unit_record), so the chunk reads one
+// 8-byte LDS word per voice, makes it the load's scalar base with two v_readfirstlane, and every load of the lane shares ONE vector offset
+// (8 f bytes, 4 f mono) formed before the loop.  PEAK = the workgroup renders the call's last block (wave-uniform, chosen once by the caller):
+// the report path is a template parameter so that the steady-state instantiation is one straight-line block.  It keeps the scalar text
+// (it runs in the workgroups of one block per call).
+//
+// ZL_K2_ONGRID_PK: the mix of an on-grid frame in packed f32 (1, zl_mix_acc_ongrid_pk) or as the scalar text of zl_mix_frame_ongrid (0).  The same
+// bits either way: each half of v_pk_add_f32 / v_pk_mul_f32 is the IEEE single operation of v_add_f32 / v_mul_f32, nothing is fused, and a - b
+// is a + (-b) by a source modifier (zl_render.h, zl_mix_frame_ongrid_pk, is the sequence restated for the CPU tier).  The compiler does not find
+// this packing (it packs across frames and pays for it in v_mov_b32), hence the inline assembly; it is five instructions a frame for nine:
+//   (l + r, l - r)            v_pk_add_f32 on the loaded pair with itself, neg_hi
+//   0.5 (l + r)               v_mul_f32 on the low half, in place
+//   (lpan m, rpan m)          v_pk_mul_f32, the low half of (m, s) in both lanes
+//   (lpan m + s, rpan m - s)  v_pk_add_f32, the high half of (m, s) in both lanes, neg_hi
+//   acc (L, R) += ...         v_pk_add_f32
+#ifndef ZL_K2_ONGRID_PK
+#define ZL_K2_ONGRID_PK 1
+#endif
+// (x.lo + x.hi, x.lo - x.hi); the _lo / _hi forms take both operands from ONE half: (x + x, x - x), the frame of a mono source
+static __device__ __forceinline__ zl_f2 zl_pk_sumdiff(zl_f2 x)
 {
-    zl_f2a8 d2[MONO ? 1 : U];
-    float   d1[MONO ? U : 1];
+    zl_f2 r; asm("v_pk_add_f32 %0, %1, %1 op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(x)); return r;
+}
+static __device__ __forceinline__ zl_f2 zl_pk_sumdiff_lo(zl_f2 x)
+{
+    zl_f2 r; asm("v_pk_add_f32 %0, %1, %1 op_sel:[0,0] op_sel_hi:[0,0] neg_hi:[0,1]" : "=v"(r) : "v"(x)); return r;
+}
+static __device__ __forceinline__ zl_f2 zl_pk_sumdiff_hi(zl_f2 x)
+{
+    zl_f2 r; asm("v_pk_add_f32 %0, %1, %1 op_sel:[1,1] op_sel_hi:[1,1] neg_hi:[0,1]" : "=v"(r) : "v"(x)); return r;
+}
+// (pan.lo * ms.lo, pan.hi * ms.lo)
+static __device__ __forceinline__ zl_f2 zl_pk_pan(zl_f2 pan, zl_f2 ms)
+{
+    zl_f2 r; asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(r) : "v"(pan), "v"(ms)); return r;
+}
+// (a.lo + ms.hi, a.hi - ms.hi)
+static __device__ __forceinline__ zl_f2 zl_pk_side(zl_f2 a, zl_f2 ms)
+{
+    zl_f2 r; asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(ms)); return r;
+}
+static __device__ __forceinline__ zl_f2 zl_pk_add(zl_f2 a, zl_f2 b)
+{
+    zl_f2 r; asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
+}
+// :208-211 and :218-221 of one on-grid frame: acc (L, R) += zl_mix_frame_ongrid(x.lo, x.hi, pan.lo, pan.hi).  SEL = 0: x is the frame (l, r);
+// 1 / 2: x holds two frames of a mono source and the frame is its low / high half (r = l, :205)
+template <int SEL>
+static __device__ __forceinline__ void zl_mix_acc_ongrid_pk(zl_f2 &acc, zl_f2 x, zl_f2 pan)
+{
+    zl_f2 ms = SEL == 0 ? zl_pk_sumdiff(x) : SEL == 1 ? zl_pk_sumdiff_lo(x) : zl_pk_sumdiff_hi(x);
+    ms.x = 0.5f * ms.x;                                           // :208
+    acc = zl_pk_add(acc, zl_pk_side(zl_pk_pan(pan, ms), ms));     // :210-211, :218-221 (index shift applied at the store)
+}
+
+// the scalar base of a voice's loads: its frame-0 address out of LDS (wave-uniform), made scalar ...
+static __device__ __forceinline__ uint64_t zl_k2_ongrid_base(const ZlUnit *s_unit, int i)
+{
+    const uint64_t a = s_unit[i].addr0;
+    return ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(a >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a);
+}
+// ... and the load from it: scalar 64-bit base + the lane's 32-bit byte offset, the scalar-base form of global_load (the address is an integer
+// here, so the pointer is given its address space by hand: a generic pointer would make it a flat load behind a 64-bit vector add)
+// The lane's byte offset is the same for every chunk of the block; left to itself the compiler widens it to 64 bits once, outside the loop over
+// the chunks, and instruction selection -- which works block by block -- no longer sees "scalar base + zero-extended 32-bit offset": each load
+// then gets a 64-bit vector add.  The empty statement makes the offset a value of the chunk's own block.
+static __device__ __forceinline__ uint32_t zl_k2_ongrid_offset(uint32_t ob) { asm volatile("" : "+v"(ob)); return ob; }
+template <typename T>
+static __device__ __forceinline__ T zl_k2_ongrid_load(uint64_t base, uint32_t ob)
+{
+    return *reinterpret_cast<const __attribute__((address_space(1))) T *>(base + (uint64_t)ob);
+}
+
+template <bool MONO, int U, bool PEAK>
+static __device__ __forceinline__ void zl_k2_chunk_ongrid(const ZlBatch &A, const ZlVoiceConst *s_vc, const ZlUnit *s_unit,
+                                                           int c0, int vfirst, int f, float &accL, float &accR)
+{
+    zl_f2 d2[MONO ? 1 : U];
+    float d1[MONO ? U : 1];
+    const uint32_t ob = zl_k2_ongrid_offset((uint32_t)f << (MONO ? 2 : 3));   // interior: frame ipos + f is inside the source for every frame of the block
+    zl_f2 pan[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        const int i = c0 + u;
-        const int pos = s_unit[i].ipos + f;                       // interior: 0 <= pos < duration for every frame of the block
-        const uint64_t so = s_vc[i].src_offset;
-        const char *src = reinterpret_cast<const char *>(A.arena + (((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(so >> 32)) << 32)
-                                                                    | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)so)));
+        const uint64_t src = zl_k2_ongrid_base(s_unit, c0 + u);
         // (sources start on 16-byte boundaries: a stereo frame is 8-byte aligned)
-        if (MONO) d1[u] = *reinterpret_cast<const float *>(src + ((uint32_t)pos << 2));
-        else      d2[u] = *reinterpret_cast<const zl_f2a8 *>(src + ((uint32_t)pos << 3));
+        if (MONO) d1[u] = zl_k2_ongrid_load<float>(src, ob);
+        else      d2[u] = zl_k2_ongrid_load<zl_f2>(src, ob);
+        pan[u] = *reinterpret_cast<const zl_f2 *>(&s_vc[c0 + u].lpan);
     }
+    // every load of the chunk is in flight before the first voice is mixed (without the per-voice branch the scheduler is free to pull each
+    // voice's arithmetic up behind its load, and then every load waits for the one before it)
+    __builtin_amdgcn_sched_barrier(0);
+    if (ZL_K2_ONGRID_PK && !PEAK && !MONO) {
+        zl_f2 acc = {accL, accR};
+#pragma unroll
+        for (int u = 0; u < U; ++u) zl_mix_acc_ongrid_pk<0>(acc, d2[u], pan[u]);
+        accL = acc.x; accR = acc.y;
+        return;
+    }
+    // (a mono frame is one register: building the pair (x, x) costs what the packing saves, so mono keeps the scalar text here)
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int i = c0 + u;
         float l, r;
-        zl_mix_frame_ongrid(MONO ? d1[u] : d2[u].x, MONO ? d1[u] : d2[u].y, s_vc[i].lpan, s_vc[i].rpan, l, r);
+        zl_mix_frame_ongrid(MONO ? d1[u] : d2[u].x, MONO ? d1[u] : d2[u].y, pan[u].x, pan[u].y, l, r);
         accL += l; accR += r;                                     // :218-221 (index shift applied at the store)
-        if (wantPeak) {                                           // :213-216, signed peak from 0 (Q6)
+        if (PEAK) {                                               // :213-216, signed peak from 0 (Q6)
             const float ng = l + r;
             float pk = ng > 0.0f ? ng : 0.0f;
             pk = zl_wave_max(pk);
             if ((threadIdx.x & 63) == 0 && pk > 0.0f) atomicMax(&A.reports[vfirst + i].peak_bits, __float_as_uint(pk));
         }
     }
+}
+
+// (the chunk's source layout, wave-uniform like PEAK)
+template <int U, bool PEAK>
+static __device__ __forceinline__ void zl_k2_ongrid_dispatch(const ZlBatch &A, const ZlVoiceConst *s_vc, const ZlUnit *s_unit,
+                                                              int c0, int vfirst, int f, bool mono, float &accL, float &accR)
+{
+    if (mono) zl_k2_chunk_ongrid<true, U, PEAK>(A, s_vc, s_unit, c0, vfirst, f, accL, accR);
+    else      zl_k2_chunk_ongrid<false, U, PEAK>(A, s_vc, s_unit, c0, vfirst, f, accL, accR);
 }
 
 // The on-grid chunk with TWO frames per lane (zl_k2_pair_body): the lane renders frames f0 (even) and f0 + 1.  The two frames of an on-grid
@@ -586,32 +699,48 @@ static __device__ __forceinline__ void zl_k2_chunk_ongrid(const ZlBatch &A, cons
 #ifndef ZL_K2_U_PAIR
 #define ZL_K2_U_PAIR 8       // loads in flight per wavefront in the pair chunk (4 registers a voice); 8 or 4
 #endif
-template <bool MONO, int U>
+template <bool MONO, int U, bool PEAK>
 static __device__ __forceinline__ void zl_k2_chunk_ongrid_pair(const ZlBatch &A, const ZlVoiceConst *s_vc, const ZlUnit *s_unit, int c0, int vfirst, int f0,
-                                                                bool wantPeak, float &accL0, float &accR0, float &accL1, float &accR1)
+                                                                float &accL0, float &accR0, float &accL1, float &accR1)
 {
-    zl_f4a8  d4[MONO ? 1 : U];
-    zl_f2a4b d2[MONO ? U : 1];
+    zl_f4a8 d4[MONO ? 1 : U];
+    zl_f2   d2[MONO ? U : 1];
+    const uint32_t ob = zl_k2_ongrid_offset((uint32_t)f0 << (MONO ? 2 : 3));   // interior: frames ipos + f0 and ipos + f0 + 1 are inside the source
+    zl_f2 pan[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        const int i = c0 + u;
-        const int pos = s_unit[i].ipos + f0;                      // interior: 0 <= pos and pos + 1 < duration
-        const uint64_t so = s_vc[i].src_offset;
-        const char *src = reinterpret_cast<const char *>(A.arena + (((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(so >> 32)) << 32)
-                                                                    | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)so)));
-        if (MONO) d2[u] = *reinterpret_cast<const zl_f2a4b *>(src + ((uint32_t)pos << 2));
-        else      d4[u] = *reinterpret_cast<const zl_f4a8 *>(src + ((uint32_t)pos << 3));
+        const uint64_t src = zl_k2_ongrid_base(s_unit, c0 + u);
+        if (MONO) d2[u] = zl_k2_ongrid_load<zl_f2a4b>(src, ob);
+        else      d4[u] = zl_k2_ongrid_load<zl_f4a8>(src, ob);
+        pan[u] = *reinterpret_cast<const zl_f2 *>(&s_vc[c0 + u].lpan);
+    }
+    __builtin_amdgcn_sched_barrier(0);                            // (all loads in flight before the first mix, as in zl_k2_chunk_ongrid)
+    if (ZL_K2_ONGRID_PK && !PEAK) {
+        // each frame's (L, R) accumulator is one register pair; a mono pair (x0, x1) feeds both frames by operand selection alone
+        zl_f2 acc0 = {accL0, accR0}, acc1 = {accL1, accR1};
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (MONO) {
+                zl_mix_acc_ongrid_pk<1>(acc0, d2[u], pan[u]);
+                zl_mix_acc_ongrid_pk<2>(acc1, d2[u], pan[u]);
+            } else {
+                zl_mix_acc_ongrid_pk<0>(acc0, __builtin_shufflevector(d4[u], d4[u], 0, 1), pan[u]);
+                zl_mix_acc_ongrid_pk<0>(acc1, __builtin_shufflevector(d4[u], d4[u], 2, 3), pan[u]);
+            }
+        }
+        accL0 = acc0.x; accR0 = acc0.y; accL1 = acc1.x; accR1 = acc1.y;
+        return;
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int i = c0 + u;
-        const float lpan = s_vc[i].lpan, rpan = s_vc[i].rpan;
+        const float lpan = pan[u].x, rpan = pan[u].y;
         float l0, r0, l1, r1;
         zl_mix_frame_ongrid(MONO ? d2[u].x : d4[u].x, MONO ? d2[u].x : d4[u].y, lpan, rpan, l0, r0);
         zl_mix_frame_ongrid(MONO ? d2[u].y : d4[u].z, MONO ? d2[u].y : d4[u].w, lpan, rpan, l1, r1);
         accL0 += l0; accR0 += r0;                                 // :218-221 (index shift applied at the store)
         accL1 += l1; accR1 += r1;
-        if (wantPeak) {                                           // :213-216, signed peak from 0 (Q6)
+        if (PEAK) {                                               // :213-216, signed peak from 0 (Q6)
             const float ng0 = l0 + r0, ng1 = l1 + r1;
             const float pk0 = ng0 > 0.0f ? ng0 : 0.0f, pk1 = ng1 > 0.0f ? ng1 : 0.0f;
             const float pk = zl_wave_max(pk1 > pk0 ? pk1 : pk0);
@@ -1376,8 +1505,7 @@ static __device__ __forceinline__ void zl_k2_body(const ZlBatch &A, const unsign
                 const unsigned long long fm = __ballot(fits);      // the wave's 64 voices are one block's voices [64 m, 64 m + 64)
                 if ((i & 63) == 0) s_stmask_[b * (CH / 64) + (i >> 6)] = fm;
             }
-            { ZlUnit un; un.ipos = (int)pl.P0; un.alpha = (float)(pl.P0 - (double)un.ipos);
-              un.gpl = (vc.lgain * pl.env) * vc.clip_volume; un.gpr = (vc.rgain * pl.env) * vc.clip_volume; s_unit_[b][i] = un; }
+            s_unit_[b][i] = zl_unit_record<MODE>(A, vc, pl, cls);
             if (b == 0) s_vc[i] = vc;
             s_plan_[b][i] = pl;                   // idle slots: a harmless record with no active frame
             s_cls_[b][i] = cls;
@@ -1499,20 +1627,22 @@ static __device__ __forceinline__ void zl_k2_body(const ZlBatch &A, const unsign
             }
         } else
         for (int c0 = 0; c0 < nv; ) {
+            // (no voice is on-grid in the Hermite and FIX_GAIN modes, zl_voice_ongrid: their kernels do not carry the chunk)
+            constexpr bool OG = (MODE & (ZL_MODE_HERMITE | ZL_MODE_FIX_GAIN)) == 0;
             const int cc = __builtin_amdgcn_readfirstlane(s_chunk[c0 / U]);
             if (cc == 0) {                                        // nobody in this chunk plays (SamplerSynth.cpp:137)
-            } else if ((cc & 132) == 132) {
+            } else if (OG && (cc & 132) == 132) {
                 // every voice of the chunk on-grid (which implies simple, unit, interior) and of one source layout
                 // (ZL_K2_U_ONGRID = 2 U: two such chunks in a row, inside one bus, go as one -- twice the loads in flight)
                 const int cn = (ZL_K2_U_ONGRID > U && c0 + 2 * U <= nv && !(NB > 1 && vbase + c0 + U == busEnd))
                                    ? __builtin_amdgcn_readfirstlane(s_chunk[c0 / U + 1]) : 0;
                 if (ZL_K2_U_ONGRID > U && (cn & 132) == 132 && ((cn ^ cc) & 16) == 0) {
-                    if (cc & 16) zl_k2_chunk_ongrid<true, 2 * U>(A, s_vc, s_unit, c0, vb, fc, wantPeak, accL, accR);
-                    else         zl_k2_chunk_ongrid<false, 2 * U>(A, s_vc, s_unit, c0, vb, fc, wantPeak, accL, accR);
+                    if (wantPeak)     zl_k2_ongrid_dispatch<2 * U, true>(A, s_vc, s_unit, c0, vb, fc, (cc & 16) != 0, accL, accR);
+                    else              zl_k2_ongrid_dispatch<2 * U, false>(A, s_vc, s_unit, c0, vb, fc, (cc & 16) != 0, accL, accR);
                     c0 += U;
                 }
-                else if (cc & 16) zl_k2_chunk_ongrid<true, U>(A, s_vc, s_unit, c0, vb, fc, wantPeak, accL, accR);
-                else              zl_k2_chunk_ongrid<false, U>(A, s_vc, s_unit, c0, vb, fc, wantPeak, accL, accR);
+                else if (wantPeak)    zl_k2_ongrid_dispatch<U, true>(A, s_vc, s_unit, c0, vb, fc, (cc & 16) != 0, accL, accR);
+                else                  zl_k2_ongrid_dispatch<U, false>(A, s_vc, s_unit, c0, vb, fc, (cc & 16) != 0, accL, accR);
             } else if ((cc & 124) == 100) {
                 // (the shared-tap form needs a wave's lanes to be consecutive frames of one block: true for every launch shape --
                 // a wave is a 64-frame tile of its block)
@@ -1595,8 +1725,11 @@ static __device__ __forceinline__ void zl_k2_body(const ZlBatch &A, const unsign
 // cap of the launch allows anyway.  Two 128-frame blocks per workgroup: 5 waves -- what its 28.8 KB of
 // LDS allow -- instead of the 4 its 104 registers give: +2..3 % with 10 spilled registers, profiles/round2_e_k2_experiments.txt;
 // four 64-frame blocks: likewise 5, with 64 voices per staging pass)
+// (linear FIX_DELAY, one block per workgroup: the same 5 -- the allocator, left alone, takes 100 registers for the straight-line on-grid chunk
+// and the kernel would fall from the 5 waves its LDS allows, and had, to 4)
 template <uint32_t MODE, int BPW, bool ST>
-__global__ void __launch_bounds__(256, ST ? 3 : (MODE & (ZL_MODE_HERMITE | ZL_MODE_FIX_DELAY)) == 0 ? (BPW == 1 ? ZL_K2_WAVES_LINEAR : 5) : ZL_K2_MINWAVES) zl_k2_render(const ZlBatch A)
+__global__ void __launch_bounds__(256, ST ? 3 : (MODE & (ZL_MODE_HERMITE | ZL_MODE_FIX_DELAY)) == 0 ? (BPW == 1 ? ZL_K2_WAVES_LINEAR : 5)
+                                              : ((MODE & ZL_MODE_HERMITE) == 0 && BPW == 1) ? ZL_K2_WAVES_LINEAR : ZL_K2_MINWAVES) zl_k2_render(const ZlBatch A)
 {
     zl_k2_body<MODE, BPW, ST>(A, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y);
 }
@@ -1605,7 +1738,7 @@ __global__ void __launch_bounds__(256, ST ? 3 : (MODE & (ZL_MODE_HERMITE | ZL_MO
 // scalar held through the whole body (SGPR spills 111 -> 115, all of them to VGPR lanes: the compiler reserves 36 bytes of private
 // segment that no instruction touches), and launches without the order stay the kernel they were.
 template <uint32_t MODE>
-__global__ void __launch_bounds__(256, (MODE & (ZL_MODE_HERMITE | ZL_MODE_FIX_DELAY)) == 0 ? ZL_K2_WAVES_LINEAR : ZL_K2_MINWAVES) zl_k2_phase_render(const ZlBatch A)
+__global__ void __launch_bounds__(256, (MODE & ZL_MODE_HERMITE) == 0 ? ZL_K2_WAVES_LINEAR : ZL_K2_MINWAVES) zl_k2_phase_render(const ZlBatch A)
 {
     zl_k2_body<MODE, 1, false, true, true>(A, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y);
 }
@@ -1661,8 +1794,7 @@ static __device__ __forceinline__ void zl_k2_pair_body(const ZlBatch &A)
             ZlBlockPlan pl;
             zl_k2_stage_load(A, k, vb, i, nv, vc, pl);
             const int cls = zl_k2_stage_class<MODE>(A, vc, pl);
-            { ZlUnit un; un.ipos = (int)pl.P0; un.alpha = (float)(pl.P0 - (double)un.ipos);
-              un.gpl = (vc.lgain * pl.env) * vc.clip_volume; un.gpr = (vc.rgain * pl.env) * vc.clip_volume; s_unit[i] = un; }
+            s_unit[i] = zl_unit_record<MODE>(A, vc, pl, cls);
             s_vc[i] = vc;
             s_plan[i] = pl;
             s_cls[i] = cls;
@@ -1676,8 +1808,12 @@ static __device__ __forceinline__ void zl_k2_pair_body(const ZlBatch &A)
                 // every voice of the chunk on-grid and of one source layout
 #pragma unroll
                 for (int h = 0; h < U; h += UP) {
-                    if (cc & 16) zl_k2_chunk_ongrid_pair<true, UP>(A, s_vc, s_unit, c0 + h, vb, f0, wantPeak, accL0, accR0, accL1, accR1);
-                    else         zl_k2_chunk_ongrid_pair<false, UP>(A, s_vc, s_unit, c0 + h, vb, f0, wantPeak, accL0, accR0, accL1, accR1);
+                    if (wantPeak) {
+                        if (cc & 16) zl_k2_chunk_ongrid_pair<true, UP, true>(A, s_vc, s_unit, c0 + h, vb, f0, accL0, accR0, accL1, accR1);
+                        else         zl_k2_chunk_ongrid_pair<false, UP, true>(A, s_vc, s_unit, c0 + h, vb, f0, accL0, accR0, accL1, accR1);
+                    }
+                    else if (cc & 16) zl_k2_chunk_ongrid_pair<true, UP, false>(A, s_vc, s_unit, c0 + h, vb, f0, accL0, accR0, accL1, accR1);
+                    else              zl_k2_chunk_ongrid_pair<false, UP, false>(A, s_vc, s_unit, c0 + h, vb, f0, accL0, accR0, accL1, accR1);
                 }
             } else {
                 // the other classes: zl_k2_body's dispatch, one frame of the lane after the other

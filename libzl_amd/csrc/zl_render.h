@@ -113,6 +113,21 @@ ZL_HD inline void zl_mix_frame_ongrid(float x0l, float x0r, float lpan, float rp
     rout = rpan * mSignal - sSignal;                             // :211
 }
 
+// The same frame as K2's packed on-grid mix evaluates it (zl_kernels.hip, zl_mix_acc_ongrid_pk: five v_pk_*_f32 over the pairs
+// (sum, difference) and (left, right)), restated operation for operation so that the CPU tier can hold it against the definition
+// above: a - b is a + (-b) (the neg_hi source modifier: a negation is exact, so this is the same IEEE operation on every input),
+// and where the 0.5 multiply is a packed one the difference rides through it in the other half of the pair, times 1.0f (x * 1.0f = x
+// for every finite or infinite x; a NaN stays a NaN) -- the kernel as built multiplies the sum's half alone, which is the same frame.
+// Nothing is fused.
+ZL_HD inline void zl_mix_frame_ongrid_pk(float x0l, float x0r, float lpan, float rpan, float &lout, float &rout)
+{
+    const float sum = x0l + x0r, dif = x0l + (-x0r);             // v_pk_add_f32, neg_hi
+    const float m = sum * 0.5f, s = dif * 1.0f;                  // v_pk_mul_f32 by (0.5, 1.0), or v_mul_f32 on the sum alone
+    const float lm = lpan * m, rm = rpan * m;                    // v_pk_mul_f32, the mid signal in both halves
+    lout = lm + s;                                               // v_pk_add_f32, neg_hi
+    rout = rm + (-s);
+}
+
 // is every sample of a host buffer finite?  (the exponent field of a NaN or an infinity is all ones)
 ZL_HD inline bool zl_f32_bits_finite(uint32_t bits) { return (bits & 0x7f800000u) != 0x7f800000u; }
 inline bool zl_all_finite(const float *x, size_t n)

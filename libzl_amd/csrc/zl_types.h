@@ -97,11 +97,13 @@ struct ZlVoiceConst {             // per voice, constant over a batch; 48 bytes 
     uint64_t src_offset;
     int32_t  sample_duration;     // length - 1 (SamplerSynthVoice.cpp:191)
     int32_t  channels;
-    float    lgain, rgain, clip_volume, lpan;
-    float    rpan;
+    float    lgain, rgain;
+    float    lpan, rpan;          // at byte 24: K2's packed on-grid mix reads the pair as one aligned 8-byte value
+    float    clip_volume;
     float    env;                 // envelope of the implied (run) blocks: the sustain level
     int32_t  pad[2];              // pad[0]: the source's ZlSound::flags (K2's on-grid class reads ZL_SOUND_FINITE)
 };
+static_assert(sizeof(ZlVoiceConst) == 48 && __builtin_offsetof(ZlVoiceConst, lpan) == 24, "the pan pair is one aligned 8-byte value");
 
 enum { ZL_PLAN_ACTIVE = 1, ZL_PLAN_SLOW = 2, ZL_PLAN_ENV = 4,      // ENV: the envelope ramps inside the block (ZlPlanSeg1 holds the slopes)
        // SLOW blocks keep their per-frame control in a slot of the window's control pool (slot index in ZlPlanSeg0::step).  When the
