@@ -169,6 +169,13 @@ double ClipAudioSource_firstProgress(ClipAudioSource *c);
 float  ClipAudioSource_volumeAbsolute(ClipAudioSource *c);                              /* ClipAudioSource.cpp:338-346 */
 void   ClipAudioSource_setVolumeAbsolute(ClipAudioSource *c, float vol);                /* ClipAudioSource.cpp:328-336 */
 int    ClipAudioSource_engineClip(ClipAudioSource *c);                                  /* zlhip clip id */
+/* The data behind WaveFormItem (lib/WaveFormItem.cpp:130-139 paints a juce::AudioThumbnail of the clip between `start` and
+ * qMin(end, total length) seconds): per pixel column (minL, maxL, minR, maxR) of the clip's current playback data -- after setPitch /
+ * setSpeedRatio / setGain the re-rendered clip -- computed on the device (zlhip_sound_overview); out: [columns][4] floats, a mono clip
+ * repeats its channel.  Seconds are seconds of the playback data; frames are floor(seconds * sample rate) in double, clamped to the
+ * data; end_seconds <= start_seconds or an end beyond the data means "to the end".  1 <= columns <= ZLHIP_OVERVIEW_MAX_COLUMNS.
+ * Returns 0 or a negative zlhip status (out is not written then).  The painting stays the host's. */
+int  libzl_hotpath_clip_waveform(ClipAudioSource *c, float start_seconds, float end_seconds, int columns, float *out);
 /* minimal RIFF/WAVE IO (decode side of SamplerSynthSound.cpp:28-59; record side of AudioLevels.cpp:35-119) */
 int  libzl_wav_read(const char *path, float **left, float **right, int *length, double *sampleRate);  /* malloc'd planes; free with libzl_wav_free */
 void libzl_wav_free(float *plane);

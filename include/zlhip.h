@@ -35,7 +35,8 @@ extern "C" {
  *    new entry points: zlhip_bounce, zlhip_host_alloc/free, zlhip_bus_reduce_sum_scan, zlhip_levels_import_units,
  *    zlhip_sound_upload_device_on; zlhip_clip_set no longer waits for the device (the edit lands at the next render call).
  * 3: new entry points only (a caller built against 2 keeps working): zlhip_render_fanout (the JackPassthrough fan-out on the
- *    real-time cycle), zlhip_rt_residency, zlhip_rt_last_cycle; the resident real-time kernel takes any period (blocks longer than 256 frames too). */
+ *    real-time cycle), zlhip_rt_residency, zlhip_rt_last_cycle; the resident real-time kernel takes any period (blocks longer than 256 frames too).
+ *    Later additions, still 3 (new entry points only): the engine group (zlhip_group_*), zlhip_sound_overview / _batch (waveform overviews). */
 #define ZLHIP_ABI_VERSION 3
 
 /* status codes */
@@ -214,6 +215,29 @@ int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_
  * sound).  *length receives its frames; left == NULL asks for the length only.  Returns the number of channels (1 or 2), < 0 on
  * error (ZLHIP_ERR_CAPACITY: capacity < length). */
 int zlhip_sound_read(zlhip_engine *e, int32_t id, float *left, float *right, int32_t capacity, int32_t *length);
+/* Waveform overviews: the data behind the reference's WaveFormItem (lib/WaveFormItem.cpp:130-139 paints a juce::AudioThumbnail of the
+ * clip between `start` and `end`) -- per pixel column the minimum and maximum of every channel, computed on the device from the
+ * sound's CURRENT playback data (what a voice reads: after zlhip_sound_rerender the rendered extent).  The painting stays the host's.
+ *   Column c of a request covers the frames [lo, hi): lo = first_frame + floor(c * num_frames / columns),
+ *   hi = first_frame + floor((c + 1) * num_frames / columns) (int64); hi == lo (more columns than frames) makes it [lo, lo + 1).
+ *   Order: samples are compared as integers -- the 32 bits of a negative value with all bits flipped, of a non-negative one with the
+ *   sign bit flipped -- so -0 < +0, denormals come back with their own bits, a NaN with the sign bit clear lies above +inf and one
+ *   with it set below -inf; the result does not depend on any order of evaluation.
+ *   out: per column four floats (minL, maxL, minR, maxR); a mono sound repeats its channel in the R pair.  The requests of a batch
+ *   are packed one behind the other, in request order, without gaps.
+ *   Limits: 1 <= columns <= ZLHIP_OVERVIEW_MAX_COLUMNS, num_frames >= 1, first_frame >= 0, first_frame + num_frames <= the sound's
+ *   length (zlhip_sound_read reports it), at most 262144 columns in one call: anything else is ZLHIP_ERR_INVALID; out_floats below
+ *   4 per column is ZLHIP_ERR_CAPACITY.  On any error out is not written.
+ *   A call is two kernel launches whatever its size, and moves 16 bytes per column to the host.  It runs on the engine's stream
+ *   behind what is queued there, like zlhip_sound_read, and the resident real-time kernel keeps running -- except in the first call
+ *   (and one that needs larger buffers than any before), which allocates the call's buffers. */
+#define ZLHIP_OVERVIEW_MAX_COLUMNS 4096
+typedef struct zlhip_overview_request { int32_t id, first_frame, num_frames, columns; } zlhip_overview_request;
+int zlhip_sound_overview(zlhip_engine *e, int32_t id, int32_t first_frame, int32_t num_frames, int32_t columns, float *out /* [columns][4] */);
+int zlhip_sound_overview_batch(zlhip_engine *e, const zlhip_overview_request *reqs, int32_t count, float *out, size_t out_floats);
+/* measurement: device time of the last overview call made with profiling on (zlhip_set_profiling; HIP events on the engine's stream
+ * around the call's launches) */
+int zlhip_debug_overview_timings(zlhip_engine *e, float *device_ms);
 /* debug: the seek offsets off_k of the sound's last render, one per stretch segment (*count = 0: the stretch did not run) */
 int zlhip_debug_rerender_offsets(zlhip_engine *e, int32_t id, int32_t *out, int32_t capacity, int32_t *count);
 /* measurement: device time of the seek launch and of the synthesis launch of the last re-render call made with profiling on
@@ -365,6 +389,9 @@ int  zlhip_group_sound_upload(zlhip_group *g, const float *left, const float *ri
 int  zlhip_group_sound_release(zlhip_group *g, int32_t id);
 int  zlhip_group_clip_set(zlhip_group *g, int32_t id, const zlhip_clip_params *p);
 int  zlhip_group_sound_rerender_batch(zlhip_group *g, const int32_t *ids, const zlhip_rerender_params *params, int32_t count);
+/* zlhip_sound_overview / _batch: every member holds every sound, member 0 answers */
+int  zlhip_group_sound_overview(zlhip_group *g, int32_t id, int32_t first_frame, int32_t num_frames, int32_t columns, float *out);
+int  zlhip_group_sound_overview_batch(zlhip_group *g, const zlhip_overview_request *reqs, int32_t count, float *out, size_t out_floats);
 /* zlhip_handle_commands_voices over the whole synth (taken, voices optional) */
 int  zlhip_group_handle_commands(zlhip_group *g, const zlhip_clip_command *cmds, int32_t count, uint64_t current_tick, int32_t *taken,
                                  int32_t *voices);

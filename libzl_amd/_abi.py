@@ -99,6 +99,13 @@ class RerenderParams(C.Structure):
     _fields_ = [("gain_db", C.c_float), ("pitch_semitones", C.c_float), ("speed_ratio", C.c_float), ("reserved", C.c_int32)]
 
 
+OVERVIEW_MAX_COLUMNS = 4096
+
+
+class OverviewRequest(C.Structure):
+    _fields_ = [("id", C.c_int32), ("first_frame", C.c_int32), ("num_frames", C.c_int32), ("columns", C.c_int32)]
+
+
 class RtCycleTrace(C.Structure):
     _fields_ = [
         ("cycle", C.c_uint64), ("resident", C.c_int32), ("reserved", C.c_int32),
@@ -134,6 +141,9 @@ SIGNATURES = {
     "zlhip_sound_rerender": (C.c_int, [_E, C.c_int32, C.POINTER(RerenderParams)]),
     "zlhip_sound_rerender_batch": (C.c_int, [_E, C.POINTER(C.c_int32), C.POINTER(RerenderParams), C.c_int32]),
     "zlhip_sound_read": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zlhip_sound_overview": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "zlhip_sound_overview_batch": (C.c_int, [_E, C.POINTER(OverviewRequest), C.c_int32, C.c_void_p, C.c_size_t]),
+    "zlhip_debug_overview_timings": (C.c_int, [_E, C.POINTER(C.c_float)]),
     "zlhip_debug_rerender_offsets": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_debug_rerender_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "zlhip_clip_command_clear": (None, [C.POINTER(ClipCommand)]),
@@ -184,6 +194,8 @@ SIGNATURES = {
     "zlhip_group_sound_release": (C.c_int, [_E, C.c_int32]),
     "zlhip_group_clip_set": (C.c_int, [_E, C.c_int32, C.POINTER(ClipParams)]),
     "zlhip_group_sound_rerender_batch": (C.c_int, [_E, C.POINTER(C.c_int32), C.POINTER(RerenderParams), C.c_int32]),
+    "zlhip_group_sound_overview": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "zlhip_group_sound_overview_batch": (C.c_int, [_E, C.POINTER(OverviewRequest), C.c_int32, C.c_void_p, C.c_size_t]),
     "zlhip_group_handle_commands": (C.c_int, [_E, C.POINTER(ClipCommand), C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "zlhip_group_start_voice": (C.c_int, [_E, C.c_int32, C.c_int32, C.POINTER(ClipCommand), C.c_uint64]),
     "zlhip_group_stop_voice": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_int]),

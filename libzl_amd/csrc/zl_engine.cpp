@@ -27,6 +27,7 @@
 #include "zl_order.h"
 #include "zl_pair.h"
 #include "zl_plan.h"
+#include "zl_overview.h"
 #include "zl_render.h"
 #include "zl_stretch.h"
 #include "zl_types.h"
@@ -89,6 +90,13 @@ struct zlhip_engine {
     int32_t *dStOffs = nullptr; size_t stOffsCap = 0;
     hipEvent_t stEv[3] = {nullptr, nullptr, nullptr};     // profiling (zlhip_set_profiling): before the seek, between the launches, after
     float stSeekMs = 0.0f, stSynthMs = 0.0f;             // ... of the last call (zlhip_debug_rerender_timings)
+    // waveform overviews (zlhip_sound_overview; zl_overview.h): a call's request records and its columns, on the device and in
+    // page-locked host memory -- allocated by the first call, grown only; an engine that never asks for an overview has none
+    struct Overview {
+        ZlOvRequest *hReq = nullptr, *dReq = nullptr; size_t reqCap = 0;
+        float *hCols = nullptr; uint32_t *dCols = nullptr; size_t colCap = 0;    // [columns][4]
+        hipEvent_t ev[2] = {nullptr, nullptr}; float ms = 0.0f;                 // profiling: around the call's launches (zlhip_debug_overview_timings)
+    } ov;
     ZlSound *dSounds = nullptr; ZlClip *dClips = nullptr;
     ZlVoiceState *dVoices = nullptr;
     // K1 -> K2 records, double buffered so that planning window i+1 overlaps rendering window i
@@ -396,7 +404,7 @@ void zlhip_engine_destroy(zlhip_engine *e)
     if (e->asmStream) (void)hipStreamSynchronize(e->asmStream);
     for (auto &seg : e->arenaSegments) if (seg.p) (void)hipFree(seg.p);
     void *dev[] = { e->arena, e->dSounds, e->dClips, e->dVoices, e->dGain, e->dBus, e->dLevels, e->dLevelState, e->dTrace, e->dPass, e->dPassCache,
-                    e->dStJobs, e->dStList, e->dStOffs };
+                    e->dStJobs, e->dStList, e->dStOffs, e->ov.dReq, e->ov.dCols };
     for (void *p : dev) if (p) (void)hipFree(p);
     for (auto &q : e->ps) {
         void *pd[] = { q.vconst, q.runs, q.tsegs, q.hdr, q.seg0, q.seg1, q.ctlP, q.ctlEnv, q.partials, q.ctlNext, q.simConst, q.order };
@@ -423,9 +431,10 @@ void zlhip_engine_destroy(zlhip_engine *e)
     for (hipEvent_t ev : e->bnc.winEv) if (ev) (void)hipEventDestroy(ev);
     if (e->planStream) (void)hipStreamDestroy(e->planStream);
     if (e->asmStream) (void)hipStreamDestroy(e->asmStream);
-    void *host[] = { e->hBus, e->hLevelState, e->hFan, e->hPassRt, e->hNonFinite };
+    void *host[] = { e->hBus, e->hLevelState, e->hFan, e->hPassRt, e->hNonFinite, e->ov.hReq, e->ov.hCols };
     for (void *p : host) if (p) (void)hipHostFree(p);
     for (hipEvent_t ev : e->stEv) if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->ov.ev) if (ev) (void)hipEventDestroy(ev);
     if (e->evJoin) (void)hipEventDestroy(e->evJoin);
     if (e->evPlanTail) (void)hipEventDestroy(e->evPlanTail);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -1037,6 +1046,114 @@ int zlhip_sound_read(zlhip_engine *e, int32_t id, float *left, float *right, int
         std::memcpy(left, tmp.data(), tmp.size() * sizeof(float));
     }
     return s.channels;
+}
+
+// ---- waveform overviews (zl_overview.h, zl_overview.hip) -----------------------------------------------------------------
+// The data behind the reference's WaveFormItem (lib/WaveFormItem.cpp:130-139): per pixel column the minimum and maximum of the
+// clip's playback data, reduced where the data lives -- after a re-render the clip that plays exists on the device only.  The
+// synchronisation is zlhip_sound_read's: the call runs on the engine's stream behind what is queued there and does NOT ask the
+// resident real-time kernel to leave (it reads the arena, which only uploads, releases and re-renders change -- and those stop the
+// kernel and wait themselves).  hipMalloc / hipFree / hipHostFree do wait for resident kernels, so the call's buffers are
+// allocated by the first call (this engine's kernel leaves once, the others' step aside) and grow only: a call that fits them makes
+// no device-synchronising HIP call.
+static int ov_reserve(zlhip_engine *e, size_t nreq, size_t ncols)
+{
+    zlhip_engine::Overview &o = e->ov;
+    if (nreq <= o.reqCap && ncols <= o.colCap) return ZLHIP_OK;
+    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }
+    ZlQuiesce quiet(e);
+    if (nreq > o.reqCap) {
+        if (o.dReq) { (void)hipFree(o.dReq); e->deviceBytes -= o.reqCap * sizeof(ZlOvRequest); }
+        if (o.hReq) (void)hipHostFree(o.hReq);
+        o.dReq = nullptr; o.hReq = nullptr; o.reqCap = 0;
+        const size_t n = std::max<size_t>(nreq * 2, 64);
+        if (hipHostMalloc((void **)&o.hReq, n * sizeof(ZlOvRequest)) != hipSuccess || hipMalloc((void **)&o.dReq, n * sizeof(ZlOvRequest)) != hipSuccess) {
+            (void)hipGetLastError();
+            if (o.hReq) (void)hipHostFree(o.hReq);
+            o.hReq = nullptr; o.dReq = nullptr;
+            return fail(e, ZLHIP_ERR_CAPACITY, "sound_overview: no memory for the call's requests");
+        }
+        e->deviceBytes += n * sizeof(ZlOvRequest);
+        o.reqCap = n;
+    }
+    if (ncols > o.colCap) {
+        if (o.dCols) { (void)hipFree(o.dCols); e->deviceBytes -= o.colCap * 4 * sizeof(float); }
+        if (o.hCols) (void)hipHostFree(o.hCols);
+        o.dCols = nullptr; o.hCols = nullptr; o.colCap = 0;
+        const size_t n = std::min<size_t>(std::max<size_t>(ncols * 2, ZL_OV_MAX_COLUMNS), ZL_OV_MAX_CALL_COLUMNS);
+        if (hipHostMalloc((void **)&o.hCols, n * 4 * sizeof(float)) != hipSuccess || hipMalloc((void **)&o.dCols, n * 4 * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            if (o.hCols) (void)hipHostFree(o.hCols);
+            o.hCols = nullptr; o.dCols = nullptr;
+            return fail(e, ZLHIP_ERR_CAPACITY, "sound_overview: no memory for the call's columns");
+        }
+        e->deviceBytes += n * 4 * sizeof(float);
+        o.colCap = n;
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_overview_batch(zlhip_engine *e, const zlhip_overview_request *reqs, int32_t count, float *out, size_t out_floats)
+{
+    if (!e || count < 0 || (count > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
+    if (count == 0) return ZLHIP_OK;
+    // validate everything before anything is written
+    int64_t columns = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        const zlhip_overview_request &q = reqs[i];
+        if (q.id < 0 || q.id >= e->cfg.max_sounds || !e->hc.soundUsed[q.id]) return fail(e, ZLHIP_ERR_INVALID, "sound_overview: no such sound");
+        if (q.columns < 1 || q.columns > ZLHIP_OVERVIEW_MAX_COLUMNS) return fail(e, ZLHIP_ERR_INVALID, "sound_overview: columns outside 1 .. 4096");
+        if (q.first_frame < 0 || q.num_frames < 1 || (int64_t)q.first_frame + q.num_frames > e->hc.sounds[q.id].length)
+            return fail(e, ZLHIP_ERR_INVALID, "sound_overview: the frames do not lie inside the sound's playback data");
+        columns += q.columns;
+        if (columns > ZL_OV_MAX_CALL_COLUMNS) return fail(e, ZLHIP_ERR_INVALID, "sound_overview_batch: more than 262144 columns in one call");
+    }
+    if (out_floats < (size_t)columns * 4) return fail(e, ZLHIP_ERR_CAPACITY, "sound_overview: out holds fewer than 4 floats per column");
+    ZL_HIP(e, hipSetDevice(e->device));
+    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    { const int rc = ov_reserve(e, (size_t)count, (size_t)columns); if (rc != ZLHIP_OK) return rc; }
+    zlhip_engine::Overview &o = e->ov;
+    // the request records: where the extent lies (64-bit, per request: a grown arena's segments are far apart), what to cut it into
+    int64_t items = 0; int32_t col = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        const zlhip_overview_request &q = reqs[i];
+        const ZlSound &s = e->hc.sounds[q.id];
+        ZlOvRequest &R = o.hReq[i];
+        R.src = (uint64_t)(uintptr_t)arena_ptr(e, s.offset);
+        R.item_base = items;
+        R.first = q.first_frame; R.frames = q.num_frames; R.columns = q.columns;
+        R.channels = s.channels;
+        R.col_base = col;
+        R.ppc = zl_ov_pieces_per_column(q.num_frames, q.columns);
+        items += zl_ov_items(q.num_frames, q.columns);
+        col += q.columns;
+    }
+    const bool prof = e->profiling;
+    for (int x = 0; prof && x < 2; ++x) if (!o.ev[x]) ZL_HIP(e, hipEventCreate(&o.ev[x]));
+    ZL_HIP(e, hipMemcpyAsync(o.dReq, o.hReq, (size_t)count * sizeof(ZlOvRequest), hipMemcpyHostToDevice, e->stream));
+    if (prof) ZL_HIP(e, hipEventRecord(o.ev[0], e->stream));
+    ZL_HIP(e, hipMemsetAsync(o.dCols, 0, (size_t)columns * 4 * sizeof(float), e->stream));
+    ZL_KERNEL(e, zl_launch_overview_reduce(o.dReq, count, items, o.dCols, e->stream));
+    ZL_KERNEL(e, zl_launch_overview_finish(o.dCols, (int32_t)columns, e->stream));
+    if (prof) ZL_HIP(e, hipEventRecord(o.ev[1], e->stream));
+    ZL_HIP(e, hipMemcpyAsync(o.hCols, o.dCols, (size_t)columns * 4 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    if (prof) ZL_HIP(e, hipEventElapsedTime(&o.ms, o.ev[0], o.ev[1]));
+    std::memcpy(out, o.hCols, (size_t)columns * 4 * sizeof(float));
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_overview(zlhip_engine *e, int32_t id, int32_t first_frame, int32_t num_frames, int32_t columns, float *out)
+{
+    const zlhip_overview_request q = { id, first_frame, num_frames, columns };
+    return zlhip_sound_overview_batch(e, &q, 1, out, columns > 0 ? (size_t)columns * 4 : 0);
+}
+
+int zlhip_debug_overview_timings(zlhip_engine *e, float *device_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (device_ms) *device_ms = e->ov.ms;
+    return ZLHIP_OK;
 }
 
 int zlhip_debug_rerender_timings(zlhip_engine *e, float *seek_ms, float *synth_ms)

@@ -255,6 +255,21 @@ int zlhip_group_sound_rerender_batch(zlhip_group *g, const int32_t *ids, const z
     return ZLHIP_OK;
 }
 
+// sounds are broadcast: every member holds the same playback data, member 0 answers
+int zlhip_group_sound_overview_batch(zlhip_group *g, const zlhip_overview_request *reqs, int32_t count, float *out, size_t out_floats)
+{
+    if (!g) return ZLHIP_ERR_INVALID;
+    const int rc = zlhip_sound_overview_batch(g->m[0], reqs, count, out, out_floats);
+    return rc != ZLHIP_OK ? member_fail(g, 0, rc) : ZLHIP_OK;
+}
+
+int zlhip_group_sound_overview(zlhip_group *g, int32_t id, int32_t first_frame, int32_t num_frames, int32_t columns, float *out)
+{
+    if (!g) return ZLHIP_ERR_INVALID;
+    const int rc = zlhip_sound_overview(g->m[0], id, first_frame, num_frames, columns, out);
+    return rc != ZLHIP_OK ? member_fail(g, 0, rc) : ZLHIP_OK;
+}
+
 // ---- commands (global buses, slots, voices and midi channels) ------------------------------------------------------------
 int zlhip_group_handle_commands(zlhip_group *g, const zlhip_clip_command *cmds, int32_t count, uint64_t current_tick, int32_t *taken,
                                 int32_t *voices)

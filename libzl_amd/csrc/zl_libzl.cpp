@@ -784,6 +784,29 @@ void ClipAudioSource_setGain(ClipAudioSource *c, float db)         // :305-311
     clip_rerender(c);
 }
 
+// WaveFormItem::paint draws the clip's thumbnail between m_start and qMin(m_end, total length) seconds (WaveFormItem.cpp:130-139).
+// Here: the columns behind that picture, reduced on the device from the data the clip plays now (zlhip_sound_overview), under the lock
+// the re-render takes -- the window cannot straddle a swap.
+int libzl_hotpath_clip_waveform(ClipAudioSource *c, float start_seconds, float end_seconds, int columns, float *out)
+{
+    if (!c || !out) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    if (!G.engine || c->engineClip < 0) return ZLHIP_ERR_STATE;
+    int32_t length = 0;
+    const int rc = zlhip_sound_read(G.engine, c->engineClip, nullptr, nullptr, 0, &length);
+    if (rc < 0) return rc;
+    if (length < 1) return ZLHIP_ERR_STATE;
+    const double sr = c->sourceSampleRate;
+    auto frame = [&](float seconds) -> int64_t {                   // floor(seconds * rate), clamped to [0, length] (a NaN: 0)
+        const double f = std::floor((double)seconds * sr);
+        return !(f > 0.0) ? 0 : (f >= (double)length ? (int64_t)length : (int64_t)f);
+    };
+    int64_t a = std::min<int64_t>(frame(start_seconds), length - 1);
+    int64_t b = end_seconds > start_seconds ? frame(end_seconds) : length;
+    if (b <= a) b = a + 1;                                         // (both ends in one frame: that frame)
+    return zlhip_sound_overview(G.engine, c->engineClip, (int32_t)a, (int32_t)(b - a), columns, out);
+}
+
 void ClipAudioSource_setVolume(ClipAudioSource *c, float vol)      // ClipAudioSource.cpp:313-326
 {
     std::lock_guard<std::mutex> sl(c->setMu);

@@ -89,6 +89,26 @@ def pinned_array(lib, shape, dtype) -> np.ndarray:
     return np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape))).reshape(shape)
 
 
+def _overview_requests(requests, length_of):
+    """(clip, columns[, first_frame[, num_frames]]) tuples -> the C request array; num_frames None / missing = to the end of the clip"""
+    reqs = (_abi.OverviewRequest * max(1, len(requests)))()
+    for i, r in enumerate(requests):
+        clip, columns = int(r[0]), int(r[1])
+        first = int(r[2]) if len(r) > 2 else 0
+        n = r[3] if len(r) > 3 else None
+        reqs[i] = _abi.OverviewRequest(clip, first, int(length_of(clip) - first if n is None else n), columns)
+    return reqs
+
+
+def _overview_split(out, reqs, count):
+    """the packed columns of a batch -> one [columns, 4] view per request"""
+    res, at = [], 0
+    for i in range(count):
+        res.append(out[at:at + reqs[i].columns])
+        at += reqs[i].columns
+    return res
+
+
 @dataclass
 class BatchResult:
     bus: np.ndarray            # [num_buses, 2, nblocks*nframes] float32
@@ -215,6 +235,33 @@ class SamplerSynth:
         L = np.empty(n.value, np.float32); R = np.empty(n.value, np.float32)
         ch = self._ck(self._lib.zlhip_sound_read(self._e, clip, L.ctypes.data, R.ctypes.data, n.value, C.byref(n)), "sound_read")
         return L, (R if ch == 2 else None)
+
+    def clip_length(self, clip: int) -> int:
+        """frames of the clip's current playback data"""
+        n = C.c_int32(0)
+        self._ck(self._lib.zlhip_sound_read(self._e, clip, None, None, 0, C.byref(n)), "sound_read")
+        return n.value
+
+    def clip_overview(self, clip: int, columns: int, first_frame: int = 0, num_frames: Optional[int] = None) -> np.ndarray:
+        """The waveform overview of the clip's current playback data (zlhip_sound_overview), computed on the device: float32
+        [columns, 4] = (minL, maxL, minR, maxR) per pixel column over the frames [first_frame, first_frame + num_frames) (None: to
+        the end); a mono clip repeats its channel.  What a WaveFormItem-shaped painter draws from."""
+        return self.clip_overviews([(clip, columns, first_frame, num_frames)])[0]
+
+    def clip_overviews(self, requests: Sequence[tuple]):
+        """Several overviews in one call (zlhip_sound_overview_batch: two launches whatever the count).  requests: tuples
+        (clip, columns[, first_frame[, num_frames]]); returns one float32 [columns, 4] array per request (views of one packed array)."""
+        reqs = _overview_requests(requests, self.clip_length)
+        total = sum(max(0, reqs[i].columns) for i in range(len(requests)))
+        out = np.empty((total, 4), np.float32)
+        self._ck(self._lib.zlhip_sound_overview_batch(self._e, reqs, len(requests), out.ctypes.data, out.size), "sound_overview_batch")
+        return _overview_split(out, reqs, len(requests))
+
+    def overview_timings(self) -> float:
+        """device ms of the last overview call made with profiling on (set_profiling)"""
+        a = C.c_float(0.0)
+        self._ck(self._lib.zlhip_debug_overview_timings(self._e, C.byref(a)), "debug_overview_timings")
+        return a.value
 
     def rerender_offsets(self, clip: int) -> np.ndarray:
         """debug: the seek offsets of the clip's last render, one per stretch segment (empty: the stretch did not run)"""
@@ -544,6 +591,23 @@ class SamplerSynthGroup:
 
     def rerender_clip(self, clip: int, gain_db: float = 0.0, pitch: float = 0.0, speed: float = 1.0):
         self.rerender_clips([clip], gain_db, pitch, speed)
+
+    def clip_length(self, clip: int) -> int:
+        n = C.c_int32(0)
+        m0 = C.c_void_p(self.member(0))
+        _abi.check(self._lib, m0, self._lib.zlhip_sound_read(m0, clip, None, None, 0, C.byref(n)), "sound_read")
+        return n.value
+
+    def clip_overview(self, clip: int, columns: int, first_frame: int = 0, num_frames: Optional[int] = None) -> np.ndarray:
+        """SamplerSynth.clip_overview: every member holds every clip, member 0 answers (zlhip_group_sound_overview_batch)"""
+        return self.clip_overviews([(clip, columns, first_frame, num_frames)])[0]
+
+    def clip_overviews(self, requests: Sequence[tuple]):
+        reqs = _overview_requests(requests, self.clip_length)
+        total = sum(max(0, reqs[i].columns) for i in range(len(requests)))
+        out = np.empty((total, 4), np.float32)
+        self._ck(self._lib.zlhip_group_sound_overview_batch(self._g, reqs, len(requests), out.ctypes.data, out.size), "group_sound_overview_batch")
+        return _overview_split(out, reqs, len(requests))
 
     # -- commands (global buses, slots and midi channels) --------------------------------------
     def handle_clip_commands(self, cmds: Sequence[ClipCommand], current_tick: int = 0, want_voices: bool = False):
