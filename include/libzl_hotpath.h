@@ -11,7 +11,8 @@
  *
  * Differences that are visible at this boundary:
  *   - ClipAudioSource_new decodes RIFF/WAVE itself (PCM 8/16/24/32, float32/64; first two channels,
- *     as SamplerSynthSound.cpp:45) instead of going through JUCE / tracktion.
+ *     as SamplerSynthSound.cpp:45) instead of going through JUCE / tracktion: the file's `data` chunk goes to the engine as raw PCM
+ *     and is decoded on the device (zlhip_sound_upload_pcm); ZL_PCM_DECODE=0, read per call, decodes on the host as before.
  *   - audio is pulled with libzl_hotpath_process() by whoever owns the JACK callback (the reference's
  *     SamplerChannel::process, SamplerSynth.cpp:116-148) instead of being pushed to JACK from inside.
  *   - ClipAudioSource_play/stop go through SyncTimer::scheduleClipCommand with delay 0 as in the reference
@@ -176,6 +177,12 @@ int    ClipAudioSource_engineClip(ClipAudioSource *c);                          
  * data; end_seconds <= start_seconds or an end beyond the data means "to the end".  1 <= columns <= ZLHIP_OVERVIEW_MAX_COLUMNS.
  * Returns 0 or a negative zlhip status (out is not written then).  The painting stays the host's. */
 int  libzl_hotpath_clip_waveform(ClipAudioSource *c, float start_seconds, float end_seconds, int columns, float *out);
+/* A bank of clips in one engine call: every file is read, their `data` chunks go to the engine as raw PCM in ONE
+ * zlhip_sound_upload_pcm_batch call (decoded on the device, one wait for the whole bank).  out[i] is the clip of paths[i], or NULL
+ * for a file that cannot be opened or decoded -- it does not fail the others.  Returns the number of clips loaded (or a negative
+ * zlhip status for bad arguments).  ZL_PCM_DECODE=0 (read per call) and files with more than ZLHIP_PCM_MAX_CHANNELS channels take
+ * ClipAudioSource_new's host decode, clip by clip; the playback data is bit-identical either way. */
+int  libzl_hotpath_clips_new(const char *const *paths, int count, ClipAudioSource **out);
 /* minimal RIFF/WAVE IO (decode side of SamplerSynthSound.cpp:28-59; record side of AudioLevels.cpp:35-119) */
 int  libzl_wav_read(const char *path, float **left, float **right, int *length, double *sampleRate);  /* malloc'd planes; free with libzl_wav_free */
 void libzl_wav_free(float *plane);

@@ -36,7 +36,8 @@ extern "C" {
  *    zlhip_sound_upload_device_on; zlhip_clip_set no longer waits for the device (the edit lands at the next render call).
  * 3: new entry points only (a caller built against 2 keeps working): zlhip_render_fanout (the JackPassthrough fan-out on the
  *    real-time cycle), zlhip_rt_residency, zlhip_rt_last_cycle; the resident real-time kernel takes any period (blocks longer than 256 frames too).
- *    Later additions, still 3 (new entry points only): the engine group (zlhip_group_*), zlhip_sound_overview / _batch (waveform overviews). */
+ *    Later additions, still 3 (new entry points only): the engine group (zlhip_group_*), zlhip_sound_overview / _batch (waveform overviews),
+ *    zlhip_sound_upload_pcm / _batch (clips from raw PCM, decoded on the device). */
 #define ZLHIP_ABI_VERSION 3
 
 /* status codes */
@@ -238,6 +239,30 @@ int zlhip_sound_overview_batch(zlhip_engine *e, const zlhip_overview_request *re
 /* measurement: device time of the last overview call made with profiling on (zlhip_set_profiling; HIP events on the engine's stream
  * around the call's launches) */
 int zlhip_debug_overview_timings(zlhip_engine *e, float *device_ms);
+/* Clips from raw PCM.  `frames` is host memory, pageable or page-locked: `length` frames of `channels`
+ *   interleaved little-endian samples, exactly the bytes of a WAV `data` chunk.  They are copied raw into a device staging buffer and
+ *   decoded there into the arena's layout; one decode launch serves each staging pass and the call waits for the device once.
+ *   The first min(2, channels) channels are kept; the sound is mono only when channels == 1.
+ *   Integer formats widen to left-justified int32 (U8: (b - 128) << 24, S16: << 16, S24: three bytes << 8), convert to float with
+ *   round-to-nearest-even and multiply by 2^-31.  F32 is moved as 32 bits (a signalling NaN, -0 and denormals keep their bits).
+ *   F64 is (float)d, round-to-nearest-even: denormal results stay denormal, overflow gives +-inf, a NaN a NaN of the same sign.
+ *   All or nothing: every argument of every source is checked before the first HIP call -- frames NULL, a format outside 1..6,
+ *   channels outside 1..ZLHIP_PCM_MAX_CHANNELS, length < 1, sample_rate <= 0, reserved != 0, count < 0 are ZLHIP_ERR_INVALID -- and
+ *   too few free sound slots or an arena that cannot hold the whole call (it may grow under sound_arena_max_bytes) are
+ *   ZLHIP_ERR_CAPACITY, decided before any copy; either way no slot is taken, no extent kept and every out_ids[i] is -1.
+ *   count == 0 is ZLHIP_OK.  On success the ids are the first free slots in request order, as `count` consecutive zlhip_sound_upload
+ *   calls would have given, every clip with its default clip parameters.  Synchronisation is zlhip_sound_upload's: the resident
+ *   kernel leaves, queued batches finish first, the call is synchronous.
+ *   The staging buffer (ZL_PCM_STAGE_BYTES, read per call; default 64 MiB, at least 4096, a multiple of 16) is allocated by the
+ *   first PCM call, only grows, and is counted in zlhip_memory_bytes. */
+enum { ZLHIP_PCM_U8 = 1, ZLHIP_PCM_S16 = 2, ZLHIP_PCM_S24 = 3, ZLHIP_PCM_S32 = 4, ZLHIP_PCM_F32 = 5, ZLHIP_PCM_F64 = 6 };
+#define ZLHIP_PCM_MAX_CHANNELS 64
+typedef struct zlhip_pcm_source { const void *frames; int32_t length, channels, format, reserved; double sample_rate; } zlhip_pcm_source;
+int zlhip_sound_upload_pcm(zlhip_engine *e, const void *frames, int32_t format, int32_t channels, int32_t length, double sample_rate, int32_t *out_id);
+int zlhip_sound_upload_pcm_batch(zlhip_engine *e, const zlhip_pcm_source *srcs, int32_t count, int32_t *out_ids);
+/* measurement: device time of the copies into the stage and of the decode launches of the last PCM upload call made with profiling on
+ * (zlhip_set_profiling; HIP events on the engine's stream) */
+int zlhip_debug_upload_pcm_timings(zlhip_engine *e, float *copy_ms, float *decode_ms);
 /* debug: the seek offsets off_k of the sound's last render, one per stretch segment (*count = 0: the stretch did not run) */
 int zlhip_debug_rerender_offsets(zlhip_engine *e, int32_t id, int32_t *out, int32_t capacity, int32_t *count);
 /* measurement: device time of the seek launch and of the synthesis launch of the last re-render call made with profiling on
@@ -386,6 +411,8 @@ const char *zlhip_group_last_error(const zlhip_group *g);
 int  zlhip_group_layout(zlhip_group *g, int32_t *partition, int32_t *first_bus, int32_t *num_buses, int32_t *first_slot, int32_t *slots);
 zlhip_engine *zlhip_group_member(zlhip_group *g, int32_t r);
 int  zlhip_group_sound_upload(zlhip_group *g, const float *left, const float *right, int32_t length, double sample_rate, int32_t *out_id);
+/* zlhip_sound_upload_pcm_batch on every member (broadcast): the ids agree; a failure on one member undoes the others */
+int  zlhip_group_sound_upload_pcm_batch(zlhip_group *g, const zlhip_pcm_source *srcs, int32_t count, int32_t *out_ids);
 int  zlhip_group_sound_release(zlhip_group *g, int32_t id);
 int  zlhip_group_clip_set(zlhip_group *g, int32_t id, const zlhip_clip_params *p);
 int  zlhip_group_sound_rerender_batch(zlhip_group *g, const int32_t *ids, const zlhip_rerender_params *params, int32_t count);

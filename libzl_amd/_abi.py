@@ -106,6 +106,16 @@ class OverviewRequest(C.Structure):
     _fields_ = [("id", C.c_int32), ("first_frame", C.c_int32), ("num_frames", C.c_int32), ("columns", C.c_int32)]
 
 
+PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = 1, 2, 3, 4, 5, 6
+PCM_MAX_CHANNELS = 64
+PCM_BYTES = {PCM_U8: 1, PCM_S16: 2, PCM_S24: 3, PCM_S32: 4, PCM_F32: 4, PCM_F64: 8}
+
+
+class PcmSource(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("length", C.c_int32), ("channels", C.c_int32), ("format", C.c_int32), ("reserved", C.c_int32),
+                ("sample_rate", C.c_double)]
+
+
 class RtCycleTrace(C.Structure):
     _fields_ = [
         ("cycle", C.c_uint64), ("resident", C.c_int32), ("reserved", C.c_int32),
@@ -144,6 +154,9 @@ SIGNATURES = {
     "zlhip_sound_overview": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "zlhip_sound_overview_batch": (C.c_int, [_E, C.POINTER(OverviewRequest), C.c_int32, C.c_void_p, C.c_size_t]),
     "zlhip_debug_overview_timings": (C.c_int, [_E, C.POINTER(C.c_float)]),
+    "zlhip_sound_upload_pcm": (C.c_int, [_E, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_int32)]),
+    "zlhip_sound_upload_pcm_batch": (C.c_int, [_E, C.POINTER(PcmSource), C.c_int32, C.POINTER(C.c_int32)]),
+    "zlhip_debug_upload_pcm_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "zlhip_debug_rerender_offsets": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_debug_rerender_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "zlhip_clip_command_clear": (None, [C.POINTER(ClipCommand)]),
@@ -191,6 +204,7 @@ SIGNATURES = {
     "zlhip_group_layout": (C.c_int, [_E, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "zlhip_group_member": (C.c_void_p, [_E, C.c_int32]),
     "zlhip_group_sound_upload": (C.c_int, [_E, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_int32)]),
+    "zlhip_group_sound_upload_pcm_batch": (C.c_int, [_E, C.POINTER(PcmSource), C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_group_sound_release": (C.c_int, [_E, C.c_int32]),
     "zlhip_group_clip_set": (C.c_int, [_E, C.c_int32, C.POINTER(ClipParams)]),
     "zlhip_group_sound_rerender_batch": (C.c_int, [_E, C.POINTER(C.c_int32), C.POINTER(RerenderParams), C.c_int32]),

@@ -28,6 +28,7 @@
 #include "zl_pair.h"
 #include "zl_plan.h"
 #include "zl_overview.h"
+#include "zl_decode.h"
 #include "zl_render.h"
 #include "zl_stretch.h"
 #include "zl_types.h"
@@ -97,6 +98,15 @@ struct zlhip_engine {
         float *hCols = nullptr; uint32_t *dCols = nullptr; size_t colCap = 0;    // [columns][4]
         hipEvent_t ev[2] = {nullptr, nullptr}; float ms = 0.0f;                 // profiling: around the call's launches (zlhip_debug_overview_timings)
     } ov;
+    // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h): the staging buffer the raw bytes are copied into, a call's piece and
+    // publish records and its verdict words -- allocated by the first PCM call, grown only; an engine that never loads PCM has none
+    struct Pcm {
+        unsigned char *stage = nullptr; size_t stageBytes = 0;
+        ZlDecPiece *dPieces = nullptr; size_t piecesCap = 0;
+        ZlDecPublish *dPub = nullptr; uint32_t *dVerdicts = nullptr; size_t clipsCap = 0;
+        std::vector<hipEvent_t> ev;                                 // profiling: before every pass's copies and every decode launch, behind the last
+        float copyMs = 0.0f, decodeMs = 0.0f;                       // ... of the last call made with profiling on (zlhip_debug_upload_pcm_timings)
+    } pcm;
     ZlSound *dSounds = nullptr; ZlClip *dClips = nullptr;
     ZlVoiceState *dVoices = nullptr;
     // K1 -> K2 records, double buffered so that planning window i+1 overlaps rendering window i
@@ -404,7 +414,8 @@ void zlhip_engine_destroy(zlhip_engine *e)
     if (e->asmStream) (void)hipStreamSynchronize(e->asmStream);
     for (auto &seg : e->arenaSegments) if (seg.p) (void)hipFree(seg.p);
     void *dev[] = { e->arena, e->dSounds, e->dClips, e->dVoices, e->dGain, e->dBus, e->dLevels, e->dLevelState, e->dTrace, e->dPass, e->dPassCache,
-                    e->dStJobs, e->dStList, e->dStOffs, e->ov.dReq, e->ov.dCols };
+                    e->dStJobs, e->dStList, e->dStOffs, e->ov.dReq, e->ov.dCols,
+                    e->pcm.stage, e->pcm.dPieces, e->pcm.dPub, e->pcm.dVerdicts };
     for (void *p : dev) if (p) (void)hipFree(p);
     for (auto &q : e->ps) {
         void *pd[] = { q.vconst, q.runs, q.tsegs, q.hdr, q.seg0, q.seg1, q.ctlP, q.ctlEnv, q.partials, q.ctlNext, q.simConst, q.order };
@@ -435,6 +446,7 @@ void zlhip_engine_destroy(zlhip_engine *e)
     for (void *p : host) if (p) (void)hipHostFree(p);
     for (hipEvent_t ev : e->stEv) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->ov.ev) if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->pcm.ev) if (ev) (void)hipEventDestroy(ev);
     if (e->evJoin) (void)hipEventDestroy(e->evJoin);
     if (e->evPlanTail) (void)hipEventDestroy(e->evPlanTail);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -882,6 +894,163 @@ int zlhip_sound_upload(zlhip_engine *e, const float *left, const float *right, i
     if (rc == ZLHIP_OK) rc = publish_sound(e, *out_id);
     if (rc != ZLHIP_OK) { free_sound_slot(e, *out_id); *out_id = -1; }   // a failed upload keeps neither the slot nor its extent
     return rc;
+}
+
+// ---- clips from raw PCM (zl_decode.h, zl_decode.hip) ---------------------------------------------------------------------
+// The other side of the file boundary: zlhip_bounce writes 16-bit PCM from the render kernel, this reads the bytes of a WAV `data`
+// chunk.  The raw bytes cross the link (half of fp32 for 16-bit files, no host loop over the samples), one decode launch per staging
+// pass writes the arena's layout, pad included, and the call waits for the device once -- whatever the number of clips.
+// ZL_PCM_STAGE_BYTES: the size of the staging buffer, read per call (tests cut clips inside with a small one)
+static uint32_t zl_pcm_stage_switch() { const char *v = std::getenv("ZL_PCM_STAGE_BYTES"); return zl_dec_stage_bytes(v ? std::atoll(v) : (long long)ZL_DEC_STAGE_DEFAULT); }
+
+// (hipMalloc / hipFree wait for the device: other engines' kernels step aside; this engine's has left)
+static int pcm_reserve(zlhip_engine *e, size_t stageBytes, size_t npieces, size_t nclips)
+{
+    zlhip_engine::Pcm &p = e->pcm;
+    if (stageBytes <= p.stageBytes && npieces <= p.piecesCap && nclips <= p.clipsCap) return ZLHIP_OK;
+    ZlQuiesce quiet(e);
+    auto grow = [&](void **ptr, size_t *cap, size_t need, size_t elem) -> bool {
+        if (need <= *cap) return true;
+        if (*ptr) { (void)hipFree(*ptr); e->deviceBytes -= *cap * elem; *ptr = nullptr; *cap = 0; }
+        if (hipMalloc(ptr, need * elem) != hipSuccess) { (void)hipGetLastError(); *ptr = nullptr; return false; }
+        e->deviceBytes += need * elem;
+        *cap = need;
+        return true;
+    };
+    bool ok = grow((void **)&p.stage, &p.stageBytes, stageBytes, 1);
+    ok = ok && grow((void **)&p.dPieces, &p.piecesCap, std::max<size_t>(npieces * 2, 64), sizeof(ZlDecPiece));
+    if (ok && nclips > p.clipsCap) {
+        size_t cap = p.clipsCap, cap2 = p.clipsCap;
+        const size_t n = std::max<size_t>(nclips * 2, 64);
+        ok = grow((void **)&p.dPub, &cap, n, sizeof(ZlDecPublish)) && grow((void **)&p.dVerdicts, &cap2, n, sizeof(uint32_t));
+        p.clipsCap = ok ? n : 0;
+        if (!ok) {
+            if (p.dPub) { (void)hipFree(p.dPub); e->deviceBytes -= cap * sizeof(ZlDecPublish); p.dPub = nullptr; }
+            if (p.dVerdicts) { (void)hipFree(p.dVerdicts); e->deviceBytes -= cap2 * sizeof(uint32_t); p.dVerdicts = nullptr; }
+        }
+    }
+    return ok ? ZLHIP_OK : fail(e, ZLHIP_ERR_CAPACITY, "sound_upload_pcm: no device memory for the staging buffer or the call's records");
+}
+
+int zlhip_sound_upload_pcm_batch(zlhip_engine *e, const zlhip_pcm_source *srcs, int32_t count, int32_t *out_ids)
+{
+    if (!e || count < 0 || (count > 0 && (!srcs || !out_ids))) return ZLHIP_ERR_INVALID;
+    if (count == 0) return ZLHIP_OK;
+    for (int32_t i = 0; i < count; ++i) out_ids[i] = -1;
+    // every argument before the first HIP call
+    for (int32_t i = 0; i < count; ++i) {
+        const zlhip_pcm_source &q = srcs[i];
+        if (!q.frames) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: frames is NULL");
+        if (q.format < ZLHIP_PCM_U8 || q.format > ZLHIP_PCM_F64) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: format outside 1 .. 6");
+        if (q.channels < 1 || q.channels > ZLHIP_PCM_MAX_CHANNELS) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: channels outside 1 .. 64");
+        if (q.length < 1) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: length below 1");
+        if (!(q.sample_rate > 0.0)) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: sample rate not above 0");
+        if (q.reserved != 0) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: reserved is not 0");
+    }
+    // the slots: the first free ones in request order, as consecutive zlhip_sound_upload calls would take them
+    std::vector<int32_t> ids;
+    for (int i = 0; i < e->cfg.max_sounds && (int32_t)ids.size() < count; ++i) if (!e->hc.soundUsed[i]) ids.push_back(i);
+    if ((int32_t)ids.size() < count) return fail(e, ZLHIP_ERR_CAPACITY, "sound_upload_pcm: too few free sound slots for the call");
+    ZL_HIP(e, hipSetDevice(e->device));
+    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }         // (the resident real-time kernel does not see other engines' writes)
+    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }     // see zlhip_sound_upload_device
+    // the extents (all or none: an arena that cannot hold the call keeps nothing; a segment it grew by goes back)
+    std::vector<size_t> off((size_t)count, 0), floats((size_t)count, 0);
+    for (int32_t i = 0; i < count; ++i) {
+        const size_t n = extent_floats(srcs[i].length, zl_dec_out_channels(srcs[i].channels));
+        const int rc = alloc_extent(e, n, &off[(size_t)i]);
+        if (rc != ZLHIP_OK) { for (int32_t k = i - 1; k >= 0; --k) free_extent(e, off[(size_t)k], floats[(size_t)k]); return rc; }
+        floats[(size_t)i] = n;
+    }
+    auto rollback = [&]() { for (int32_t k = count - 1; k >= 0; --k) free_extent(e, off[(size_t)k], floats[(size_t)k]); };
+    // the cut into passes and pieces, the records
+    const uint32_t stageBytes = zl_pcm_stage_switch();
+    std::vector<ZlDecClip> clips((size_t)count);
+    for (int32_t i = 0; i < count; ++i) clips[(size_t)i] = ZlDecClip{ srcs[i].length, srcs[i].channels, srcs[i].format };
+    std::vector<ZlDecPiece> pieces; std::vector<ZlDecPass> passes;
+    zl_dec_plan(clips.data(), count, stageBytes, pieces, passes);
+    for (ZlDecPiece &R : pieces) R.dst = (uint64_t)(uintptr_t)arena_ptr(e, off[(size_t)R.verdict]);
+    std::vector<ZlDecPublish> pub((size_t)count);
+    for (int32_t i = 0; i < count; ++i) {
+        ZlSound s; s.offset = off[(size_t)i]; s.length = srcs[i].length; s.channels = zl_dec_out_channels(srcs[i].channels);
+        s.sample_rate = srcs[i].sample_rate; s.flags = 0; s.pad = 0;
+        pub[(size_t)i] = ZlDecPublish{ s, ids[(size_t)i], zl_dec_is_float(srcs[i].format) ? 1 : 0 };
+    }
+    { const int rc = pcm_reserve(e, stageBytes, pieces.size(), (size_t)count); if (rc != ZLHIP_OK) { rollback(); return rc; } }
+    zlhip_engine::Pcm &P = e->pcm;
+    // everything is decided: from here on only a HIP error fails the call
+    std::vector<uint32_t> verdicts((size_t)count, 0u);
+    const bool prof = e->profiling;
+    const size_t nev = prof ? 2 * passes.size() + 1 : 0;
+    int krc = 0;
+    while (krc == 0 && P.ev.size() < nev) { hipEvent_t ev = nullptr; krc = (int)hipEventCreate(&ev); if (krc == 0) P.ev.push_back(ev); }
+    if (krc == 0) krc = (int)hipMemsetAsync(P.dVerdicts, 0, (size_t)count * sizeof(uint32_t), e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(P.dPieces, pieces.data(), pieces.size() * sizeof(ZlDecPiece), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(P.dPub, pub.data(), pub.size() * sizeof(ZlDecPublish), hipMemcpyHostToDevice, e->stream);
+    for (size_t a = 0; krc == 0 && a < passes.size(); ++a) {
+        const ZlDecPass &ps = passes[a];
+        if (prof) krc = (int)hipEventRecord(P.ev[2 * a], e->stream);
+        for (int32_t k = ps.first_piece; krc == 0 && k < ps.first_piece + ps.npieces; ++k) {
+            const ZlDecPiece &R = pieces[(size_t)k];
+            const unsigned char *src = (const unsigned char *)srcs[R.verdict].frames + zl_dec_source_offset(R);
+            krc = (int)hipMemcpyAsync(P.stage + R.stage_off, src, (size_t)zl_dec_piece_bytes(R), hipMemcpyHostToDevice, e->stream);
+        }
+        if (prof && krc == 0) krc = (int)hipEventRecord(P.ev[2 * a + 1], e->stream);
+        if (krc == 0) krc = zl_launch_pcm_decode(P.dPieces + ps.first_piece, ps.npieces, ps.items, P.stage, P.dVerdicts, e->stream);
+    }
+    if (prof && krc == 0) krc = (int)hipEventRecord(P.ev[2 * passes.size()], e->stream);
+    if (krc == 0) krc = zl_launch_pcm_publish(P.dPub, count, P.dVerdicts, e->dSounds, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(verdicts.data(), P.dVerdicts, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
+    if (krc == 0) { const int w_ = engine_wait(e); if (w_ != ZLHIP_OK) { rollback(); return w_; } }     // the call's one wait
+    if (krc != 0) {
+        e->err = std::string("sound_upload_pcm: ") + hipGetErrorString((hipError_t)krc);
+        (void)hipStreamSynchronize(e->stream);
+        rollback();
+        return ZLHIP_ERR_HIP;
+    }
+    if (prof) {
+        float copy = 0.0f, dec = 0.0f;
+        for (size_t a = 0; a < passes.size(); ++a) {
+            float x = 0.0f, y = 0.0f;
+            ZL_HIP(e, hipEventElapsedTime(&x, P.ev[2 * a], P.ev[2 * a + 1]));
+            ZL_HIP(e, hipEventElapsedTime(&y, P.ev[2 * a + 1], P.ev[2 * a + 2]));
+            copy += x; dec += y;
+        }
+        P.copyMs = copy; P.decodeMs = dec;
+    }
+    // the host's mirror of what the device has published, and every clip's default parameters (applied at the next render call)
+    for (int32_t i = 0; i < count; ++i) {
+        const int id = ids[(size_t)i];
+        ZlSound s = pub[(size_t)i].s;
+        if (!pub[(size_t)i].check || verdicts[(size_t)i] == 0u) s.flags |= ZL_SOUND_FINITE;
+        e->hc.sounds[id] = s;
+        e->hc.soundUsed[id] = 1;
+        e->soundFloats[(size_t)id] = floats[(size_t)i];
+        e->origSounds[(size_t)id] = s;
+        e->renderFloats[(size_t)id] = 0;
+        e->renderOffsets[(size_t)id].clear();
+        zlhip_clip_params p;
+        zlhip_clip_params_default(&p, (float)(s.length / s.sample_rate));
+        e->hc.forget_clip_params(id);                              // (the first edit of a slot carries the whole record)
+        (void)zlhip_clip_set(e, id, &p);
+        out_ids[i] = id;
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_upload_pcm(zlhip_engine *e, const void *frames, int32_t format, int32_t channels, int32_t length, double sample_rate, int32_t *out_id)
+{
+    if (!e || !out_id) return ZLHIP_ERR_INVALID;
+    const zlhip_pcm_source q = { frames, length, channels, format, 0, sample_rate };
+    return zlhip_sound_upload_pcm_batch(e, &q, 1, out_id);
+}
+
+int zlhip_debug_upload_pcm_timings(zlhip_engine *e, float *copy_ms, float *decode_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (copy_ms) *copy_ms = e->pcm.copyMs;
+    if (decode_ms) *decode_ms = e->pcm.decodeMs;
+    return ZLHIP_OK;
 }
 
 int zlhip_sound_release(zlhip_engine *e, int32_t id)

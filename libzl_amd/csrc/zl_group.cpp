@@ -223,6 +223,29 @@ int zlhip_group_sound_upload(zlhip_group *g, const float *left, const float *rig
     return ZLHIP_OK;
 }
 
+int zlhip_group_sound_upload_pcm_batch(zlhip_group *g, const zlhip_pcm_source *srcs, int32_t count, int32_t *out_ids)
+{
+    if (!g || count < 0 || (count > 0 && (!srcs || !out_ids))) return ZLHIP_ERR_INVALID;
+    if (count == 0) return ZLHIP_OK;
+    std::vector<int32_t> ids0((size_t)count, -1), ids((size_t)count, -1);
+    for (int r = 0; r < g->L.n; ++r) {
+        int rc = zlhip_sound_upload_pcm_batch(g->m[(size_t)r], srcs, count, r == 0 ? ids0.data() : ids.data());
+        if (rc == ZLHIP_OK && r > 0 && ids != ids0) {
+            for (int32_t id : ids) (void)zlhip_sound_release(g->m[(size_t)r], id);
+            rc = gfail(g, ZLHIP_ERR_STATE, "member " + std::to_string(r) + " gave other sound ids than member 0: the members' sound tables disagree");
+        } else if (rc != ZLHIP_OK) {
+            rc = member_fail(g, r, rc);                            // (a member's call is all or nothing: it kept nothing)
+        }
+        if (rc != ZLHIP_OK) {
+            for (int q = 0; q < r; ++q) for (int32_t id : ids0) (void)zlhip_sound_release(g->m[(size_t)q], id);
+            for (int32_t i = 0; i < count; ++i) out_ids[i] = -1;
+            return rc;
+        }
+    }
+    for (int32_t i = 0; i < count; ++i) out_ids[i] = ids0[(size_t)i];
+    return ZLHIP_OK;
+}
+
 int zlhip_group_sound_release(zlhip_group *g, int32_t id)
 {
     if (!g) return ZLHIP_ERR_INVALID;

@@ -18,6 +18,10 @@ int zl_launch_passthrough(const void *params_dev, const float *in, float *out, i
 int zl_launch_deliver(const float *bus, void *out, int pcm16, int B, long long in_stride, long long off, long long frames, long long total, hipStream_t s);
 // nonfinite (may be null): a word the kernel sets to 1 when a sample of the upload is NaN or infinite (the caller clears it first)
 int zl_launch_interleave(const float *L, const float *R, float *dst, int length, int pad, uint32_t *nonfinite, hipStream_t s);
+// the PCM upload's decode and publish launches (zl_decode.hip; the records are defined in zl_decode.h)
+struct ZlDecPiece; struct ZlDecPublish;
+int zl_launch_pcm_decode(const ZlDecPiece *pieces, int32_t npieces, int32_t items, const void *stage, uint32_t *verdicts, hipStream_t s);
+int zl_launch_pcm_publish(const ZlDecPublish *recs, int32_t n, const uint32_t *verdicts, ZlSound *table, hipStream_t s);
 int zl_launch_reduce_scan(const float *pieces, int npieces, long long stride, long long units, int N, int off, float *out, ZlUnitLevels *lv, hipStream_t s);
 // the spanning-bus sum of an engine group (zl_k_group_reduce_scan): the members' partial buses [B][2][K*N] in rank order, the
 // root's bus and level table, the pairs (k * B + b) this launch sums

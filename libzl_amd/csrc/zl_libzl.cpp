@@ -237,8 +237,9 @@ uint64_t f32_to_u64_sat(float f)
     return (uint64_t)f;
 }
 
-// call with G.mu held
-ClipAudioSource *make_clip(const float *L, const float *R, int length, double sr, const char *path)
+// call with G.mu held.  upload: the step that puts the clip's source into the engine and gives its sound id (planar fp32 through
+// zlhip_sound_upload, a file's raw PCM through zlhip_sound_upload_pcm, or an id a batch call has already produced)
+template <class Upload> ClipAudioSource *make_clip(int length, double sr, const char *path, Upload upload)
 {
     ClipAudioSource *c = new ClipAudioSource();
     c->filePath = path ? path : "";
@@ -252,7 +253,7 @@ ClipAudioSource *make_clip(const float *L, const float *R, int length, double sr
     set_slices(c, 16);                                             // :204
     if (G.engine) {
         int32_t id = -1;
-        const int rc = zlhip_sound_upload(G.engine, L, R, length, sr, &id);
+        const int rc = upload(&id);
         if (rc == ZLHIP_OK) c->engineClip = id;
         else {
             // the reference logs and carries on (libzl.cpp has no error returns); a clip without a source would be silent
@@ -514,18 +515,22 @@ int render_and_report(uint32_t nframes, const zlhip_clock *clock, float *out_lef
 uint32_t rd32(const unsigned char *p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
 uint16_t rd16(const unsigned char *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
 
-}  // namespace
+// a RIFF/WAVE file in memory: the sample format and where its `data` chunk lies in `buf`
+struct WavFile {
+    std::vector<unsigned char> buf;
+    int fmt = 0, bits = 0, channels = 0; uint32_t rate = 0;        // fmt: 1 integer PCM, 3 IEEE float (the sub-format of WAVE_FORMAT_EXTENSIBLE)
+    const unsigned char *data = nullptr; uint32_t dataBytes = 0;
+    int frames() const { return (int)(dataBytes / (uint32_t)((bits / 8) * channels)); }
+    // the ZLHIP_PCM_* value of the samples
+    int pcm_format() const { return fmt == 3 ? (bits == 32 ? ZLHIP_PCM_F32 : ZLHIP_PCM_F64) : bits == 8 ? ZLHIP_PCM_U8 : bits == 16 ? ZLHIP_PCM_S16 : bits == 24 ? ZLHIP_PCM_S24 : ZLHIP_PCM_S32; }
+};
 
-extern "C" {
-
-// ---- WAV IO -------------------------------------------------------------------------------------
-int libzl_wav_read(const char *path, float **left, float **right, int *length, double *sampleRate)
+// reads the file and walks its chunks; ZLHIP_OK only for the sample formats of the decode side
+int wav_parse(const char *path, WavFile &w)
 {
-    if (!path || !left || !right || !length || !sampleRate) return ZLHIP_ERR_INVALID;
-    *left = *right = nullptr; *length = 0; *sampleRate = 0.0;
     FILE *f = std::fopen(path, "rb");
     if (!f) return ZLHIP_ERR_INVALID;
-    std::vector<unsigned char> buf;
+    std::vector<unsigned char> &buf = w.buf;
     std::fseek(f, 0, SEEK_END);
     const long sz = std::ftell(f);
     std::fseek(f, 0, SEEK_SET);
@@ -549,8 +554,28 @@ int libzl_wav_read(const char *path, float **left, float **right, int *length, d
     if (!data || channels < 1 || rate == 0 || !(fmt == 1 || fmt == 3)) return ZLHIP_ERR_INVALID;
     // sample formats of the decode side: integer PCM 8 / 16 / 24 / 32 bits, IEEE float 32 / 64 bits
     if (!((fmt == 1 && (bits == 8 || bits == 16 || bits == 24 || bits == 32)) || (fmt == 3 && (bits == 32 || bits == 64)))) return ZLHIP_ERR_INVALID;
+    w.fmt = fmt; w.bits = bits; w.channels = channels; w.rate = rate; w.data = data; w.dataBytes = dataBytes;
+    return ZLHIP_OK;
+}
+
+// ZL_PCM_DECODE: 1 (default) = a file's data chunk goes to the engine as raw PCM and is decoded on the device, 0 = decoded on the host
+// (libzl_wav_read) and uploaded as planar fp32; read per call.  The playback data does not depend on it.
+bool pcm_decode_switch() { const char *v = std::getenv("ZL_PCM_DECODE"); return (v ? std::atoi(v) : 1) != 0; }
+
+}  // namespace
+
+extern "C" {
+
+// ---- WAV IO -------------------------------------------------------------------------------------
+int libzl_wav_read(const char *path, float **left, float **right, int *length, double *sampleRate)
+{
+    if (!path || !left || !right || !length || !sampleRate) return ZLHIP_ERR_INVALID;
+    *left = *right = nullptr; *length = 0; *sampleRate = 0.0;
+    WavFile w;
+    { const int rc = wav_parse(path, w); if (rc != ZLHIP_OK) return rc; }
+    const int fmt = w.fmt, bits = w.bits, channels = w.channels; const uint32_t rate = w.rate; const unsigned char *data = w.data;
     const int bytesPer = bits / 8;
-    const int frames = (int)(dataBytes / (uint32_t)(bytesPer * channels));
+    const int frames = w.frames();
     const int outCh = std::min(2, channels);                                   // jmin(2, numChannels), SamplerSynthSound.cpp:45
     float *planes[2] = { (float *)std::malloc(sizeof(float) * (size_t)std::max(frames, 1)),
                          outCh > 1 ? (float *)std::malloc(sizeof(float) * (size_t)std::max(frames, 1)) : nullptr };
@@ -680,24 +705,80 @@ ClipAudioSource *ClipAudioSource_newFromBuffer(const float *left, const float *r
 {
     if (!left || length < 1 || !(sampleRate > 0.0)) return nullptr;
     std::lock_guard<std::mutex> lk(G.mu);
-    return make_clip(left, right, length, sampleRate, name ? name : "");
+    return make_clip(length, sampleRate, name ? name : "", [&](int32_t *id) { return zlhip_sound_upload(G.engine, left, right, length, sampleRate, id); });
 }
 
 ClipAudioSource *ClipAudioSource_new(const char *filepath, bool muted)   // libzl.cpp:118-128, ClipAudioSource.cpp:135-205
 {
-    float *L = nullptr, *R = nullptr; int n = 0; double sr = 0.0;
-    if (libzl_wav_read(filepath, &L, &R, &n, &sr) != ZLHIP_OK || n < 1) {
-        std::fprintf(stderr, "libzl hot path: cannot open %s\n", filepath ? filepath : "(null)");
-        return nullptr;
-    }
-    ClipAudioSource *c;
-    {
+    ClipAudioSource *c = nullptr;
+    WavFile w;
+    if (filepath && pcm_decode_switch() && wav_parse(filepath, w) == ZLHIP_OK && w.channels <= ZLHIP_PCM_MAX_CHANNELS) {
+        // the file's data chunk as it is: no host loop over the samples, half the bytes of fp32 for a 16-bit file
+        const int n = w.frames();
+        if (n < 1) {
+            std::fprintf(stderr, "libzl hot path: cannot open %s\n", filepath);
+            return nullptr;
+        }
         std::lock_guard<std::mutex> lk(G.mu);
-        c = make_clip(L, R, n, sr, filepath);
+        c = make_clip(n, (double)w.rate, filepath, [&](int32_t *id) { return zlhip_sound_upload_pcm(G.engine, w.data, w.pcm_format(), w.channels, n, (double)w.rate, id); });
+    } else {
+        float *L = nullptr, *R = nullptr; int n = 0; double sr = 0.0;
+        if (libzl_wav_read(filepath, &L, &R, &n, &sr) != ZLHIP_OK || n < 1) {
+            std::fprintf(stderr, "libzl hot path: cannot open %s\n", filepath ? filepath : "(null)");
+            return nullptr;
+        }
+        {
+            std::lock_guard<std::mutex> lk(G.mu);
+            c = make_clip(n, sr, filepath, [&](int32_t *id) { return zlhip_sound_upload(G.engine, L, R, n, sr, id); });
+        }
+        libzl_wav_free(L); libzl_wav_free(R);
     }
-    libzl_wav_free(L); libzl_wav_free(R);
     if (c && muted) ClipAudioSource_setVolume(c, -100.0f);         // ClipAudioSource.cpp:178-181
     return c;
+}
+
+int libzl_hotpath_clips_new(const char *const *paths, int count, ClipAudioSource **out)
+{
+    if (count < 0 || (count > 0 && (!paths || !out))) return ZLHIP_ERR_INVALID;
+    for (int i = 0; i < count; ++i) out[i] = nullptr;
+    std::vector<WavFile> files((size_t)count);
+    std::vector<int> batch;                                        // the files that go up in the one PCM call
+    const bool pcm = pcm_decode_switch();
+    for (int i = 0; i < count; ++i) {
+        WavFile &w = files[(size_t)i];
+        if (pcm && paths[i] && wav_parse(paths[i], w) == ZLHIP_OK && w.channels <= ZLHIP_PCM_MAX_CHANNELS && w.frames() >= 1) batch.push_back(i);
+        else w.buf.clear();
+    }
+    int loaded = 0;
+    if (!batch.empty()) {
+        std::lock_guard<std::mutex> lk(G.mu);
+        std::vector<zlhip_pcm_source> srcs(batch.size());
+        std::vector<int32_t> ids(batch.size(), -1);
+        for (size_t k = 0; k < batch.size(); ++k) {
+            const WavFile &w = files[(size_t)batch[k]];
+            srcs[k] = zlhip_pcm_source{ w.data, w.frames(), w.channels, w.pcm_format(), 0, (double)w.rate };
+        }
+        const int rc = G.engine ? zlhip_sound_upload_pcm_batch(G.engine, srcs.data(), (int32_t)srcs.size(), ids.data()) : ZLHIP_OK;
+        if (rc != ZLHIP_OK)
+            std::fprintf(stderr, "libzl hot path: cannot load a bank of %zu clips into the engine: %s (%s)\n", batch.size(), zlhip_strerror(rc), zlhip_last_error(G.engine));
+        for (size_t k = 0; rc == ZLHIP_OK && k < batch.size(); ++k) {
+            const int i = batch[k];
+            out[i] = make_clip(srcs[k].length, srcs[k].sample_rate, paths[i], [&](int32_t *id) { *id = ids[k]; return ZLHIP_OK; });
+            if (out[i]) ++loaded;
+        }
+    }
+    // the host route, clip by clip: ZL_PCM_DECODE=0, or a file the PCM call does not take (ClipAudioSource_new reports what it cannot open)
+    for (int i = 0; i < count; ++i) {
+        if (out[i] || !paths[i] || std::find(batch.begin(), batch.end(), i) != batch.end()) continue;
+        if (!pcm || (wav_parse(paths[i], files[(size_t)i]) == ZLHIP_OK && files[(size_t)i].channels > ZLHIP_PCM_MAX_CHANNELS)) {
+            files[(size_t)i].buf.clear();
+            out[i] = ClipAudioSource_new(paths[i], false);
+            if (out[i]) ++loaded;
+        } else {
+            std::fprintf(stderr, "libzl hot path: cannot open %s\n", paths[i]);
+        }
+    }
+    return loaded;
 }
 
 void ClipAudioSource_destroy(ClipAudioSource *c)                   // libzl.cpp:258-267

@@ -109,6 +109,34 @@ def _overview_split(out, reqs, count):
     return res
 
 
+def _pcm_sources(sources):
+    """(frames, fmt, channels, sample_rate) tuples -> (the C source array, the buffers it points into).  frames: a numpy array
+    (uint8, int16, int32, float32, float64) or raw bytes (S24: three bytes per sample), interleaved; fmt: a ZLHIP_PCM_* value or None
+    to take it from the array's dtype."""
+    by_dtype = {"uint8": _abi.PCM_U8, "int16": _abi.PCM_S16, "int32": _abi.PCM_S32, "float32": _abi.PCM_F32, "float64": _abi.PCM_F64}
+    arr = (_abi.PcmSource * max(1, len(sources)))()
+    keep = []
+    for i, (frames, fmt, channels, sample_rate) in enumerate(sources):
+        if isinstance(frames, (bytes, bytearray, memoryview)):
+            buf = np.frombuffer(bytes(frames), np.uint8)
+        else:
+            buf = np.ascontiguousarray(frames)
+            if buf.dtype.name not in by_dtype:
+                raise TypeError(f"PCM frames of dtype {buf.dtype}: expected uint8, int16, int32, float32, float64 or bytes")
+            if fmt is None:
+                fmt = by_dtype[buf.dtype.name]
+        if fmt not in _abi.PCM_BYTES:
+            raise ValueError(f"PCM format {fmt}")
+        if buf.dtype != np.uint8 and by_dtype[buf.dtype.name] != fmt:
+            raise ValueError(f"PCM format {fmt} does not match frames of dtype {buf.dtype}")
+        frame_bytes = _abi.PCM_BYTES[fmt] * int(channels)
+        if int(channels) < 1 or buf.nbytes % frame_bytes:
+            raise ValueError(f"{buf.nbytes} bytes are no whole number of frames of {channels} channels of format {fmt}")
+        keep.append(buf)
+        arr[i] = _abi.PcmSource(buf.ctypes.data, buf.nbytes // frame_bytes, int(channels), int(fmt), 0, float(sample_rate))
+    return arr, keep
+
+
 @dataclass
 class BatchResult:
     bus: np.ndarray            # [num_buses, 2, nblocks*nframes] float32
@@ -189,6 +217,24 @@ class SamplerSynth:
         out = C.c_int32(-1)
         self._ck(self._lib.zlhip_sound_upload(self._e, left.ctypes.data, rp, left.shape[0], float(sample_rate), C.byref(out)), "sound_upload")
         return out.value
+
+    def register_clip_pcm(self, frames, fmt, channels: int, sample_rate: float) -> int:
+        """A clip from interleaved little-endian PCM -- the bytes of a WAV data chunk -- decoded on the device (zlhip_sound_upload_pcm)."""
+        return self.register_clips_pcm([(frames, fmt, channels, sample_rate)])[0]
+
+    def register_clips_pcm(self, sources: Sequence[tuple]):
+        """[(frames, fmt, channels, sample_rate)] -> clip ids: one call, one wait for the device, all or nothing."""
+        arr, keep = _pcm_sources(sources)
+        ids = (C.c_int32 * max(1, len(sources)))()
+        self._ck(self._lib.zlhip_sound_upload_pcm_batch(self._e, arr, len(sources), ids), "sound_upload_pcm_batch")
+        del keep
+        return [ids[i] for i in range(len(sources))]
+
+    def upload_pcm_timings(self):
+        """(copy_ms, decode_ms) of the last PCM upload made with profiling on"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        self._ck(self._lib.zlhip_debug_upload_pcm_timings(self._e, C.byref(a), C.byref(b)), "debug_upload_pcm_timings")
+        return a.value, b.value
 
     def register_clip_device(self, left_ptr: int, right_ptr: Optional[int], length: int, sample_rate: float) -> int:
         out = C.c_int32(-1)
@@ -568,6 +614,24 @@ class SamplerSynthGroup:
         out = C.c_int32(-1)
         self._ck(self._lib.zlhip_group_sound_upload(self._g, left.ctypes.data, rp, left.shape[0], float(sample_rate), C.byref(out)), "group_sound_upload")
         return out.value
+
+    def register_clip_pcm(self, frames, fmt, channels: int, sample_rate: float) -> int:
+        """A clip from interleaved little-endian PCM -- the bytes of a WAV data chunk -- decoded on the device (zlhip_sound_upload_pcm)."""
+        return self.register_clips_pcm([(frames, fmt, channels, sample_rate)])[0]
+
+    def register_clips_pcm(self, sources: Sequence[tuple]):
+        """[(frames, fmt, channels, sample_rate)] -> clip ids: one call, one wait for the device, all or nothing."""
+        arr, keep = _pcm_sources(sources)
+        ids = (C.c_int32 * max(1, len(sources)))()
+        self._ck(self._lib.zlhip_group_sound_upload_pcm_batch(self._g, arr, len(sources), ids), "group_sound_upload_pcm_batch")
+        del keep
+        return [ids[i] for i in range(len(sources))]
+
+    def upload_pcm_timings(self):
+        """(copy_ms, decode_ms) of the last PCM upload made with profiling on"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        _abi.check(self._lib, C.c_void_p(self.member(0)), self._lib.zlhip_debug_upload_pcm_timings(self.member(0), C.byref(a), C.byref(b)), "debug_upload_pcm_timings")
+        return a.value, b.value
 
     def unregister_clip(self, clip: int):
         self._ck(self._lib.zlhip_group_sound_release(self._g, clip), "group_sound_release")
