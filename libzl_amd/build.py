@@ -20,7 +20,7 @@ LIBDIR = os.path.join(ROOT, "libzl_amd", "lib")
 LIB = os.path.join(LIBDIR, "libzlhip.so")
 
 HIP_SOURCES = ["zl_kernels.hip", "zl_stretch.hip", "zl_overview.hip", "zl_decode.hip", "zl_engine.cpp", "zl_libzl.cpp", "zl_group.cpp"]
-HEADERS = ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_render.h", "zl_kernels.h", "zl_host.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", "zl_overview.h", "zl_decode.h", "zl_group.h", "zl_member.h",
+HEADERS = ["zl_types.h", "zl_arena.h", "zl_plan.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_render.h", "zl_kernels.h", "zl_host.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", "zl_overview.h", "zl_decode.h", "zl_group.h", "zl_member.h",
            os.path.join("..", "..", "include", "zlhip.h"), os.path.join("..", "..", "include", "libzl_hotpath.h")]
 
 
@@ -70,7 +70,7 @@ SOURCE_DEPS = {
     "zl_stretch.hip": ["zl_types.h", "zl_stretch.h"],
     "zl_overview.hip": ["zl_types.h", "zl_overview.h"],
     "zl_decode.hip": ["zl_types.h", "zl_decode.h"],
-    "zl_engine.cpp": ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_stretch.h", "zl_overview.h", "zl_decode.h", os.path.join(_INC, "zlhip.h")],
+    "zl_engine.cpp": ["zl_types.h", "zl_arena.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_stretch.h", "zl_overview.h", "zl_decode.h", os.path.join(_INC, "zlhip.h")],
     "zl_group.cpp": ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_group.h", os.path.join(_INC, "zlhip.h")],
     "zl_libzl.cpp": ["zl_render.h", "zl_types.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h"), os.path.join(_INC, "libzl_hotpath.h")],
 }
@@ -274,6 +274,11 @@ def build_overview_harness(force: bool = False) -> str:
 def build_decode_harness(force: bool = False) -> str:
     """The PCM upload's conversions, its cut into passes and pieces and a lane's work on one group (zl_decode.h)."""
     return _build_harness("zl_decode_host", "decode_host.cpp", ["zl_types.h", "zl_decode.h"], _NO_CONTRACT + ["-Wall"], force)
+
+
+def build_arena_harness(force: bool = False) -> str:
+    """The source arena's allocator: first fit, coalescing, segments (zl_arena.h)."""
+    return _build_harness("zl_arena_host", "arena_host.cpp", ["zl_types.h", "zl_stretch.h", "zl_arena.h"], ["-Wall"], force)
 
 
 def build_launch_harness(force: bool = False) -> str:

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/zlhip.h"
+#include "zl_arena.h"
 #include "zl_host.h"
 #include "zl_kernels.h"
 #include "zl_member.h"
@@ -59,6 +60,14 @@ template <typename T> hipError_t grow_mapped(T **host, T **dev, size_t *cap, siz
     return r;
 }
 
+// a call's records and staging on the device, allocated by the first call that needs them and grown only (grow_buf); an engine that
+// never re-renders, asks for an overview or loads PCM has none.  h: the page-locked host twin, where there is one; cap in elements
+struct GrowBuf { void *d = nullptr, *h = nullptr; size_t cap = 0; };
+enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a call's jobs, the jobs whose stretch runs, their seek offsets
+       ZB_OV_REQ, ZB_OV_COLS,                                 // overviews: a call's request records and its columns [columns][4], with host twins
+       ZB_PCM_STAGE, ZB_PCM_PIECES, ZB_PCM_PUB, ZB_PCM_VERDICTS,   // PCM: the staging buffer for the raw bytes, a call's piece and publish records, its verdict words
+       ZB_COUNT };
+
 }  // namespace
 
 struct zlhip_engine {
@@ -70,40 +79,28 @@ struct zlhip_engine {
     char devname[256] = {0};
 
     // HBM
-    float *arena = nullptr; size_t arenaFloats = 0;
-    // arena allocator: free extents (offset, floats), sorted by offset, neighbours coalesced on release -- clips are
-    // loaded and destroyed freely (SamplerSynth::registerClip / unregisterClip, SamplerSynth.cpp:285-312)
-    std::vector<std::pair<size_t, size_t>> arenaFree;
-    // further arena segments, allocated when a source does not fit any more (clips are loaded freely; 288 GB of HBM): a source in
-    // one of them is addressed like any other, by its float offset from `arena` -- taken modulo 2^64, so a segment below the first
-    // one in the address space has a "negative" offset that the kernels' 64-bit address arithmetic wraps back
-    struct ArenaSegment { float *p; size_t off, floats; };   // off: the segment's float offset from `arena`, modulo 2^64
-    std::vector<ArenaSegment> arenaSegments;
-    size_t arenaSegmentFloats = 0;       // floats in those segments (zlhip_memory_bytes)
-    std::vector<size_t> soundFloats;     // per sound slot: floats its original upload holds in the arena
-    // clip re-render (zlhip_sound_rerender): per sound slot, the original upload -- every render starts from it, as tracktion renders
-    // from the clip's source file -- and the rendered extent the slot plays instead while it has one (hc.sounds holds what it plays)
-    std::vector<ZlSound> origSounds;
-    std::vector<size_t> renderFloats;    // floats of the slot's rendered extent, 0 = it plays its original
-    std::vector<std::vector<int32_t>> renderOffsets;   // the seek offsets of the slot's last render (zlhip_debug_rerender_offsets)
-    ZlStretchJob *dStJobs = nullptr; size_t stJobsCap = 0;      // a call's jobs, the jobs whose stretch runs, their seek offsets
-    int32_t *dStList = nullptr; size_t stListCap = 0;
-    int32_t *dStOffs = nullptr; size_t stOffsCap = 0;
+    float *arena = nullptr;
+    // the arena's allocator (zl_arena.h): the free extents of the first arena and of the further segments, allocated when a source does
+    // not fit any more (clips are loaded freely; 288 GB of HBM).  A source in a segment is addressed like any other, by its float offset
+    // from `arena` modulo 2^64, which the kernels' 64-bit address arithmetic wraps back.  A segment's handle is its device pointer.
+    ZlArena arenaAlloc;
+    // per sound slot, next to hc.sounds (what the slot plays) and hc.soundUsed: the original upload -- every re-render
+    // (zlhip_sound_rerender) starts from it, as tracktion renders from the clip's source file -- and the render it plays instead while it has one
+    struct SoundSlot {
+        ZlSound orig{0, 0, 0, 0.0}; size_t floats = 0;   // the original upload, the floats it holds in the arena
+        size_t renderFloats = 0;         // floats of the slot's rendered extent, 0 = it plays its original
+        std::vector<int32_t> renderOffsets;   // the seek offsets of the slot's last render (zlhip_debug_rerender_offsets)
+    };
+    std::vector<SoundSlot> soundSlots;
+    GrowBuf scratch[ZB_COUNT];           // a call's records and staging (grow_buf)
     hipEvent_t stEv[3] = {nullptr, nullptr, nullptr};     // profiling (zlhip_set_profiling): before the seek, between the launches, after
     float stSeekMs = 0.0f, stSynthMs = 0.0f;             // ... of the last call (zlhip_debug_rerender_timings)
-    // waveform overviews (zlhip_sound_overview; zl_overview.h): a call's request records and its columns, on the device and in
-    // page-locked host memory -- allocated by the first call, grown only; an engine that never asks for an overview has none
+    // waveform overviews (zlhip_sound_overview; zl_overview.h)
     struct Overview {
-        ZlOvRequest *hReq = nullptr, *dReq = nullptr; size_t reqCap = 0;
-        float *hCols = nullptr; uint32_t *dCols = nullptr; size_t colCap = 0;    // [columns][4]
         hipEvent_t ev[2] = {nullptr, nullptr}; float ms = 0.0f;                 // profiling: around the call's launches (zlhip_debug_overview_timings)
     } ov;
-    // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h): the staging buffer the raw bytes are copied into, a call's piece and
-    // publish records and its verdict words -- allocated by the first PCM call, grown only; an engine that never loads PCM has none
+    // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h)
     struct Pcm {
-        unsigned char *stage = nullptr; size_t stageBytes = 0;
-        ZlDecPiece *dPieces = nullptr; size_t piecesCap = 0;
-        ZlDecPublish *dPub = nullptr; uint32_t *dVerdicts = nullptr; size_t clipsCap = 0;
         std::vector<hipEvent_t> ev;                                 // profiling: before every pass's copies and every decode launch, behind the last
         float copyMs = 0.0f, decodeMs = 0.0f;                       // ... of the last call made with profiling on (zlhip_debug_upload_pcm_timings)
     } pcm;
@@ -412,10 +409,9 @@ void zlhip_engine_destroy(zlhip_engine *e)
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     if (e->planStream) (void)hipStreamSynchronize(e->planStream);
     if (e->asmStream) (void)hipStreamSynchronize(e->asmStream);
-    for (auto &seg : e->arenaSegments) if (seg.p) (void)hipFree(seg.p);
-    void *dev[] = { e->arena, e->dSounds, e->dClips, e->dVoices, e->dGain, e->dBus, e->dLevels, e->dLevelState, e->dTrace, e->dPass, e->dPassCache,
-                    e->dStJobs, e->dStList, e->dStOffs, e->ov.dReq, e->ov.dCols,
-                    e->pcm.stage, e->pcm.dPieces, e->pcm.dPub, e->pcm.dVerdicts };
+    for (auto &seg : e->arenaAlloc.segments) if (seg.handle) (void)hipFree(seg.handle);
+    for (auto &b : e->scratch) { if (b.d) (void)hipFree(b.d); if (b.h) (void)hipHostFree(b.h); }
+    void *dev[] = { e->arena, e->dSounds, e->dClips, e->dVoices, e->dGain, e->dBus, e->dLevels, e->dLevelState, e->dTrace, e->dPass, e->dPassCache };
     for (void *p : dev) if (p) (void)hipFree(p);
     for (auto &q : e->ps) {
         void *pd[] = { q.vconst, q.runs, q.tsegs, q.hdr, q.seg0, q.seg1, q.ctlP, q.ctlEnv, q.partials, q.ctlNext, q.simConst, q.order };
@@ -442,7 +438,7 @@ void zlhip_engine_destroy(zlhip_engine *e)
     for (hipEvent_t ev : e->bnc.winEv) if (ev) (void)hipEventDestroy(ev);
     if (e->planStream) (void)hipStreamDestroy(e->planStream);
     if (e->asmStream) (void)hipStreamDestroy(e->asmStream);
-    void *host[] = { e->hBus, e->hLevelState, e->hFan, e->hPassRt, e->hNonFinite, e->ov.hReq, e->ov.hCols };
+    void *host[] = { e->hBus, e->hLevelState, e->hFan, e->hPassRt, e->hNonFinite };
     for (void *p : host) if (p) (void)hipHostFree(p);
     for (hipEvent_t ev : e->stEv) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->ov.ev) if (ev) (void)hipEventDestroy(ev);
@@ -488,14 +484,14 @@ int zlhip_engine_create(const zlhip_config *cfg_in, zlhip_engine **out)
 
     const size_t V = (size_t)e->V, K = (size_t)cfg->max_batch_blocks, N = (size_t)cfg->max_frames, B = (size_t)cfg->num_buses;
     e->maxGroups = cfg->voices_per_task > 0 ? (cfg->voices_per_bus + cfg->voices_per_task - 1) / cfg->voices_per_task : 1;
-    e->arenaFloats = (size_t)(cfg->sound_arena_bytes / sizeof(float));
+    e->arenaAlloc.init((size_t)(cfg->sound_arena_bytes / sizeof(float)));
 
     int rc = ZLHIP_OK;
     auto chk = [&](hipError_t st, const char *what) {
         if (st != hipSuccess && rc == ZLHIP_OK) { e->err = std::string(what) + ": " + hipGetErrorString(st); rc = ZLHIP_ERR_HIP; }
     };
     chk(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate");
-    chk(dalloc(&e->arena, e->arenaFloats + 1024), "arena");     // + 4 KB: wide loads at the end of the last source stay inside
+    chk(dalloc(&e->arena, e->arenaAlloc.arenaFloats + 1024), "arena");     // + 4 KB: wide loads at the end of the last source stay inside
     chk(dalloc(&e->dSounds, (size_t)cfg->max_sounds), "sounds");
     chk(dalloc(&e->dClips, (size_t)cfg->max_sounds), "clips");
     chk(dalloc(&e->dVoices, V), "voices");
@@ -658,11 +654,7 @@ int zlhip_engine_create(const zlhip_config *cfg_in, zlhip_engine **out)
         if (cfg->rt_idle_timeout_us > 0) e->rt.idleTicks = (unsigned long long)cfg->rt_idle_timeout_us * 100ull;   // 100 MHz counter
     }
     e->hc.init(cfg->num_buses, cfg->voices_per_bus, cfg->max_sounds, cfg->playback_sample_rate);
-    e->soundFloats.assign((size_t)cfg->max_sounds, 0);
-    e->origSounds.assign((size_t)cfg->max_sounds, ZlSound{0, 0, 0, 0.0});
-    e->renderFloats.assign((size_t)cfg->max_sounds, 0);
-    e->renderOffsets.assign((size_t)cfg->max_sounds, std::vector<int32_t>());
-    e->arenaFree.assign(1, { (size_t)0, e->arenaFloats & ~(size_t)3 });
+    e->soundSlots.assign((size_t)cfg->max_sounds, zlhip_engine::SoundSlot());
     for (auto &c : e->slots) { std::memset(c.hReports, 0, V * sizeof(ZlReport)); std::memset(c.hStats, 0, sizeof(ZlBatchStats)); }
     e->latest = &e->slots[0];
     e->deviceBytes = g_alloc_bytes;
@@ -683,46 +675,43 @@ void zlhip_clip_params_default(zlhip_clip_params *p, float duration_seconds)
     ZlHostControl::default_clip_params(p, duration_seconds);
 }
 
-// an extent of `floats` floats (a multiple of 4) of the arena: first fit over the free extents, else a further arena segment
-static int alloc_extent(zlhip_engine *e, size_t floats, size_t *out_off)
+// `need` elements of `elem` bytes in a buffer that only grows: one that is too small is freed and one of `new_cap` elements allocated,
+// with a page-locked host twin where `twin`; a failure leaves it empty and the call failed with `what`.  Besides the arena's segments
+// this is the only place after creation that changes deviceBytes.  hipMalloc, hipFree and hipHostFree wait for the device: stopping
+// this engine's resident kernel and asking the others' to step aside (ZlQuiesce) is the caller's part.
+static int grow_buf(zlhip_engine *e, GrowBuf &b, size_t need, size_t elem, size_t new_cap, bool twin, const char *what)
 {
-    // first fit over the free extents (offsets and sizes are multiples of 4 floats, so every source stays aligned)
-    size_t off = (size_t)-1;
-    for (size_t i = 0; i < e->arenaFree.size(); ++i) {
-        if (e->arenaFree[i].second >= floats) {
-            off = e->arenaFree[i].first;
-            e->arenaFree[i].first += floats; e->arenaFree[i].second -= floats;
-            if (e->arenaFree[i].second == 0) e->arenaFree.erase(e->arenaFree.begin() + (long)i);
-            break;
-        }
+    if (need <= b.cap) return ZLHIP_OK;
+    if (b.d) { (void)hipFree(b.d); e->deviceBytes -= b.cap * elem; }
+    if (b.h) (void)hipHostFree(b.h);
+    b = GrowBuf();
+    if ((twin && hipHostMalloc(&b.h, new_cap * elem) != hipSuccess) || hipMalloc(&b.d, new_cap * elem) != hipSuccess) {
+        (void)hipGetLastError();
+        if (b.h) (void)hipHostFree(b.h);
+        b = GrowBuf();
+        return fail(e, ZLHIP_ERR_CAPACITY, what);
     }
-    if (off == (size_t)-1) {
-        // no extent holds it: one more arena segment, at least as large as the first one (and as the source)
-        const size_t segFloats = (std::max(floats, e->arenaFloats) + 3) & ~(size_t)3;
-        if (e->cfg.sound_arena_max_bytes > 0 && (e->arenaFloats + e->arenaSegmentFloats + segFloats) * sizeof(float) > e->cfg.sound_arena_max_bytes)
-            return fail(e, ZLHIP_ERR_CAPACITY, "sound arena full");
-        float *seg = nullptr;
-        if (hipMalloc((void **)&seg, (segFloats + 1024) * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return fail(e, ZLHIP_ERR_CAPACITY, "sound arena full (no memory for another segment)"); }
-        e->arenaSegmentFloats += segFloats;
-        e->deviceBytes += (segFloats + 1024) * sizeof(float);
-        // float offset of the segment from `arena`, modulo 2^64 (exact: both are multiples of 4 bytes)
-        const int64_t diffBytes = (int64_t)((uintptr_t)seg - (uintptr_t)e->arena);
-        off = (size_t)(uint64_t)(diffBytes / 4);
-        e->arenaSegments.push_back({ seg, off, segFloats });
-        if (segFloats > floats) {
-            const std::pair<size_t, size_t> rest(off + floats, segFloats - floats);
-            e->arenaFree.insert(std::lower_bound(e->arenaFree.begin(), e->arenaFree.end(), rest), rest);
-        }
-    }
-    *out_off = off;
+    e->deviceBytes += new_cap * elem;
+    b.cap = new_cap;
     return ZLHIP_OK;
 }
 
-// floats of the arena extent of a source of `length` frames: ZL_ST_PAD zero frames behind it, 16-byte aligned
-static size_t extent_floats(int64_t length, int channels)
+// an extent of `floats` floats (a multiple of 4) of the arena: first fit over the free extents, else a further arena segment
+// (zl_arena.h decides; the device memory of a segment is allocated here)
+static int alloc_extent(zlhip_engine *e, size_t floats, size_t *out_off)
 {
-    const size_t floats = ((size_t)length + ZL_ST_PAD) * (size_t)channels;
-    return (floats + 3) & ~(size_t)3;                             // keep every source 16-byte aligned
+    ZlArena &a = e->arenaAlloc;
+    if (a.take(floats, out_off)) return ZLHIP_OK;
+    const size_t segFloats = a.segment_floats(floats, e->cfg.sound_arena_max_bytes);
+    if (segFloats == 0) return fail(e, ZLHIP_ERR_CAPACITY, "sound arena full");
+    float *seg = nullptr;
+    if (hipMalloc((void **)&seg, (segFloats + 1024) * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return fail(e, ZLHIP_ERR_CAPACITY, "sound arena full (no memory for another segment)"); }
+    e->deviceBytes += (segFloats + 1024) * sizeof(float);
+    // float offset of the segment from `arena`, modulo 2^64 (exact: both are multiples of 4 bytes)
+    const int64_t diffBytes = (int64_t)((uintptr_t)seg - (uintptr_t)e->arena);
+    a.add_segment(seg, (size_t)(uint64_t)(diffBytes / 4), segFloats);
+    (void)a.take(floats, out_off);                                 // (the segment's first floats)
+    return ZLHIP_OK;
 }
 
 // (integer arithmetic: a segment below the first arena in the address space has an offset that wraps -- no pointer ever leaves its allocation)
@@ -731,73 +720,51 @@ static float *arena_ptr(const zlhip_engine *e, uint64_t off)
     return reinterpret_cast<float *>((uintptr_t)e->arena + (uintptr_t)off * sizeof(float));
 }
 
+// an arena extent goes back to the free list.  A later arena segment whose every float is free again goes back to the device (the first
+// arena stays for the engine's life): the caller has waited for the engine and stopped its resident kernel; the free waits for the
+// device: other engines' kernels step aside.
+static void free_extent(zlhip_engine *e, size_t off, size_t n)
+{
+    ZlArena::Segment seg;
+    if (!e->arenaAlloc.give(off, n, &seg)) return;
+    { ZlQuiesce quiet(e); (void)hipFree(seg.handle); }
+    e->deviceBytes -= (seg.floats + 1024) * sizeof(float);
+}
+
+// a free slot takes a new sound, whose upload holds `floats` floats of the arena: it plays that upload
+static void adopt_sound(zlhip_engine *e, int id, const ZlSound &s, size_t floats)
+{
+    e->hc.sounds[id] = s;
+    e->hc.soundUsed[id] = 1;
+    e->soundSlots[(size_t)id] = zlhip_engine::SoundSlot{ s, floats, 0, {} };
+}
+
 static int alloc_sound_slot(zlhip_engine *e, int32_t length, int channels, double sample_rate, int32_t *out_id, float **dst)
 {
     if (length < 1 || !(sample_rate > 0.0) || !out_id) return fail(e, ZLHIP_ERR_INVALID, "bad sound arguments");
     int id = -1;
     for (int i = 0; i < e->cfg.max_sounds; ++i) if (!e->hc.soundUsed[i]) { id = i; break; }
     if (id < 0) return fail(e, ZLHIP_ERR_CAPACITY, "sound table full");
-    const size_t floats = extent_floats(length, channels);
+    const size_t floats = zl_extent_floats(length, channels);
     size_t off = 0;
     { const int rc = alloc_extent(e, floats, &off); if (rc != ZLHIP_OK) return rc; }
     ZlSound s; s.offset = off; s.length = length; s.channels = channels; s.sample_rate = sample_rate; s.flags = 0; s.pad = 0;
     *dst = arena_ptr(e, off);
-    e->hc.sounds[id] = s;
-    e->hc.soundUsed[id] = 1;
-    e->soundFloats[(size_t)id] = floats;
-    e->origSounds[(size_t)id] = s;
-    e->renderFloats[(size_t)id] = 0;
-    e->renderOffsets[(size_t)id].clear();
+    adopt_sound(e, id, s, floats);
     *out_id = id;
     return ZLHIP_OK;
-}
-
-// an arena extent goes back to the free list (coalesced with its neighbours)
-static void free_extent(zlhip_engine *e, size_t off, size_t n)
-{
-    if (n == 0) return;
-    auto it = std::lower_bound(e->arenaFree.begin(), e->arenaFree.end(), std::make_pair(off, (size_t)0));
-    it = e->arenaFree.insert(it, {off, n});
-    if (it + 1 != e->arenaFree.end() && it->first + it->second == (it + 1)->first) { it->second += (it + 1)->second; e->arenaFree.erase(it + 1); }
-    if (it != e->arenaFree.begin() && (it - 1)->first + (it - 1)->second == it->first) {
-        const auto prev = it - 1;                                  // (stays valid: it lies in front of the erased element)
-        prev->second += it->second;
-        e->arenaFree.erase(it);
-        it = prev;
-    }
-    // a later arena segment whose every float is free again goes back to the device (the first arena stays for the engine's life).  The
-    // caller has waited for the engine and stopped its resident kernel; the free waits for the device: other engines' kernels step aside.
-    for (size_t si = 0; si < e->arenaSegments.size(); ++si) {
-        const auto seg = e->arenaSegments[si];
-        if (!(it->first <= seg.off && seg.off + seg.floats <= it->first + it->second)) continue;
-        const std::pair<size_t, size_t> whole = *it;
-        e->arenaFree.erase(it);
-        if (whole.first < seg.off) { const std::pair<size_t, size_t> head(whole.first, seg.off - whole.first); e->arenaFree.insert(std::lower_bound(e->arenaFree.begin(), e->arenaFree.end(), head), head); }
-        if (seg.off + seg.floats < whole.first + whole.second) {
-            const std::pair<size_t, size_t> tail(seg.off + seg.floats, whole.first + whole.second - (seg.off + seg.floats));
-            e->arenaFree.insert(std::lower_bound(e->arenaFree.begin(), e->arenaFree.end(), tail), tail);
-        }
-        { ZlQuiesce quiet(e); (void)hipFree(seg.p); }
-        e->arenaSegmentFloats -= seg.floats;
-        e->deviceBytes -= (seg.floats + 1024) * sizeof(float);
-        e->arenaSegments.erase(e->arenaSegments.begin() + (long)si);
-        break;                                                     // (one extent, at most one whole segment: segments are separate allocations)
-    }
 }
 
 // the arena extents of a sound slot -- its original upload and the render it plays, if any -- go back to the free list; the slot is free again
 static void free_sound_slot(zlhip_engine *e, int id)
 {
-    const size_t off = (size_t)e->origSounds[(size_t)id].offset, n = e->soundFloats[(size_t)id];
-    const size_t roff = (size_t)e->hc.sounds[id].offset, rn = e->renderFloats[(size_t)id];
+    zlhip_engine::SoundSlot slot;
+    std::swap(slot, e->soundSlots[(size_t)id]);
+    const size_t played = (size_t)e->hc.sounds[id].offset;
     e->hc.soundUsed[id] = 0;
     e->hc.sounds[id] = ZlSound{0, 0, 0, 0.0};
-    e->origSounds[(size_t)id] = ZlSound{0, 0, 0, 0.0};
-    e->soundFloats[(size_t)id] = 0;
-    e->renderFloats[(size_t)id] = 0;
-    e->renderOffsets[(size_t)id].clear();
-    free_extent(e, off, n);
-    free_extent(e, roff, rn);
+    free_extent(e, (size_t)slot.orig.offset, slot.floats);
+    free_extent(e, played, slot.renderFloats);
 }
 
 // dev_checked: the extent was written by zl_k_interleave, which leaves its verdict on the samples in *hNonFinite -- read after the wait
@@ -814,7 +781,7 @@ static int publish_sound(zlhip_engine *e, int id, bool dev_checked = false)
     { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
     if (dev_checked && __atomic_load_n(e->hNonFinite, __ATOMIC_ACQUIRE) == 0u) {
         e->hc.sounds[id].flags |= ZL_SOUND_FINITE;
-        e->origSounds[(size_t)id].flags |= ZL_SOUND_FINITE;
+        e->soundSlots[(size_t)id].orig.flags |= ZL_SOUND_FINITE;
         ZL_HIP(e, hipMemcpyAsync(e->dSounds + id, &e->hc.sounds[id], sizeof(ZlSound), hipMemcpyHostToDevice, e->stream));
     }
     e->hc.forget_clip_params(id);                                  // (the first edit of a slot carries the whole record)
@@ -886,7 +853,7 @@ int zlhip_sound_upload(zlhip_engine *e, const float *left, const float *right, i
     else std::memcpy(tmp.data(), left, (size_t)length * sizeof(float));
     if (zl_all_finite(tmp.data(), tmp.size())) {                   // every sample looked at: K2's on-grid form may drop the second tap (zl_render.h)
         e->hc.sounds[*out_id].flags |= ZL_SOUND_FINITE;
-        e->origSounds[(size_t)*out_id].flags |= ZL_SOUND_FINITE;
+        e->soundSlots[(size_t)*out_id].orig.flags |= ZL_SOUND_FINITE;
     }
     hipError_t st = hipMemcpyAsync(dst, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice, e->stream);
     rc = st == hipSuccess ? engine_wait(e) : ZLHIP_ERR_HIP;
@@ -906,30 +873,18 @@ static uint32_t zl_pcm_stage_switch() { const char *v = std::getenv("ZL_PCM_STAG
 // (hipMalloc / hipFree wait for the device: other engines' kernels step aside; this engine's has left)
 static int pcm_reserve(zlhip_engine *e, size_t stageBytes, size_t npieces, size_t nclips)
 {
-    zlhip_engine::Pcm &p = e->pcm;
-    if (stageBytes <= p.stageBytes && npieces <= p.piecesCap && nclips <= p.clipsCap) return ZLHIP_OK;
+    GrowBuf *b = e->scratch;
+    if (stageBytes <= b[ZB_PCM_STAGE].cap && npieces <= b[ZB_PCM_PIECES].cap
+        && nclips <= b[ZB_PCM_PUB].cap && nclips <= b[ZB_PCM_VERDICTS].cap) return ZLHIP_OK;
     ZlQuiesce quiet(e);
-    auto grow = [&](void **ptr, size_t *cap, size_t need, size_t elem) -> bool {
-        if (need <= *cap) return true;
-        if (*ptr) { (void)hipFree(*ptr); e->deviceBytes -= *cap * elem; *ptr = nullptr; *cap = 0; }
-        if (hipMalloc(ptr, need * elem) != hipSuccess) { (void)hipGetLastError(); *ptr = nullptr; return false; }
-        e->deviceBytes += need * elem;
-        *cap = need;
-        return true;
-    };
-    bool ok = grow((void **)&p.stage, &p.stageBytes, stageBytes, 1);
-    ok = ok && grow((void **)&p.dPieces, &p.piecesCap, std::max<size_t>(npieces * 2, 64), sizeof(ZlDecPiece));
-    if (ok && nclips > p.clipsCap) {
-        size_t cap = p.clipsCap, cap2 = p.clipsCap;
-        const size_t n = std::max<size_t>(nclips * 2, 64);
-        ok = grow((void **)&p.dPub, &cap, n, sizeof(ZlDecPublish)) && grow((void **)&p.dVerdicts, &cap2, n, sizeof(uint32_t));
-        p.clipsCap = ok ? n : 0;
-        if (!ok) {
-            if (p.dPub) { (void)hipFree(p.dPub); e->deviceBytes -= cap * sizeof(ZlDecPublish); p.dPub = nullptr; }
-            if (p.dVerdicts) { (void)hipFree(p.dVerdicts); e->deviceBytes -= cap2 * sizeof(uint32_t); p.dVerdicts = nullptr; }
-        }
-    }
-    return ok ? ZLHIP_OK : fail(e, ZLHIP_ERR_CAPACITY, "sound_upload_pcm: no device memory for the staging buffer or the call's records");
+    const char *what = "sound_upload_pcm: no device memory for the staging buffer or the call's records";
+    // (the piece records are measured by their doubled count: a call that grows anything also grows them once it fills more than half)
+    const size_t np = std::max<size_t>(npieces * 2, 64), nc = std::max<size_t>(nclips * 2, 64);
+    int rc = grow_buf(e, b[ZB_PCM_STAGE], stageBytes, 1, stageBytes, false, what);
+    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_PCM_PIECES], np, sizeof(ZlDecPiece), np, false, what);
+    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_PCM_PUB], nclips, sizeof(ZlDecPublish), nc, false, what);
+    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_PCM_VERDICTS], nclips, sizeof(uint32_t), nc, false, what);
+    return rc;
 }
 
 int zlhip_sound_upload_pcm_batch(zlhip_engine *e, const zlhip_pcm_source *srcs, int32_t count, int32_t *out_ids)
@@ -956,13 +911,13 @@ int zlhip_sound_upload_pcm_batch(zlhip_engine *e, const zlhip_pcm_source *srcs, 
     if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }     // see zlhip_sound_upload_device
     // the extents (all or none: an arena that cannot hold the call keeps nothing; a segment it grew by goes back)
     std::vector<size_t> off((size_t)count, 0), floats((size_t)count, 0);
+    auto rollback = [&]() { for (int32_t k = count - 1; k >= 0; --k) free_extent(e, off[(size_t)k], floats[(size_t)k]); };   // (0 floats: nothing taken)
     for (int32_t i = 0; i < count; ++i) {
-        const size_t n = extent_floats(srcs[i].length, zl_dec_out_channels(srcs[i].channels));
+        const size_t n = zl_extent_floats(srcs[i].length, zl_dec_out_channels(srcs[i].channels));
         const int rc = alloc_extent(e, n, &off[(size_t)i]);
-        if (rc != ZLHIP_OK) { for (int32_t k = i - 1; k >= 0; --k) free_extent(e, off[(size_t)k], floats[(size_t)k]); return rc; }
+        if (rc != ZLHIP_OK) { rollback(); return rc; }
         floats[(size_t)i] = n;
     }
-    auto rollback = [&]() { for (int32_t k = count - 1; k >= 0; --k) free_extent(e, off[(size_t)k], floats[(size_t)k]); };
     // the cut into passes and pieces, the records
     const uint32_t stageBytes = zl_pcm_stage_switch();
     std::vector<ZlDecClip> clips((size_t)count);
@@ -978,29 +933,31 @@ int zlhip_sound_upload_pcm_batch(zlhip_engine *e, const zlhip_pcm_source *srcs, 
     }
     { const int rc = pcm_reserve(e, stageBytes, pieces.size(), (size_t)count); if (rc != ZLHIP_OK) { rollback(); return rc; } }
     zlhip_engine::Pcm &P = e->pcm;
+    unsigned char *const stage = (unsigned char *)e->scratch[ZB_PCM_STAGE].d; ZlDecPiece *const dPieces = (ZlDecPiece *)e->scratch[ZB_PCM_PIECES].d;
+    ZlDecPublish *const dPub = (ZlDecPublish *)e->scratch[ZB_PCM_PUB].d; uint32_t *const dVerdicts = (uint32_t *)e->scratch[ZB_PCM_VERDICTS].d;
     // everything is decided: from here on only a HIP error fails the call
     std::vector<uint32_t> verdicts((size_t)count, 0u);
     const bool prof = e->profiling;
     const size_t nev = prof ? 2 * passes.size() + 1 : 0;
     int krc = 0;
     while (krc == 0 && P.ev.size() < nev) { hipEvent_t ev = nullptr; krc = (int)hipEventCreate(&ev); if (krc == 0) P.ev.push_back(ev); }
-    if (krc == 0) krc = (int)hipMemsetAsync(P.dVerdicts, 0, (size_t)count * sizeof(uint32_t), e->stream);
-    if (krc == 0) krc = (int)hipMemcpyAsync(P.dPieces, pieces.data(), pieces.size() * sizeof(ZlDecPiece), hipMemcpyHostToDevice, e->stream);
-    if (krc == 0) krc = (int)hipMemcpyAsync(P.dPub, pub.data(), pub.size() * sizeof(ZlDecPublish), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemsetAsync(dVerdicts, 0, (size_t)count * sizeof(uint32_t), e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dPieces, pieces.data(), pieces.size() * sizeof(ZlDecPiece), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, pub.data(), pub.size() * sizeof(ZlDecPublish), hipMemcpyHostToDevice, e->stream);
     for (size_t a = 0; krc == 0 && a < passes.size(); ++a) {
         const ZlDecPass &ps = passes[a];
         if (prof) krc = (int)hipEventRecord(P.ev[2 * a], e->stream);
         for (int32_t k = ps.first_piece; krc == 0 && k < ps.first_piece + ps.npieces; ++k) {
             const ZlDecPiece &R = pieces[(size_t)k];
             const unsigned char *src = (const unsigned char *)srcs[R.verdict].frames + zl_dec_source_offset(R);
-            krc = (int)hipMemcpyAsync(P.stage + R.stage_off, src, (size_t)zl_dec_piece_bytes(R), hipMemcpyHostToDevice, e->stream);
+            krc = (int)hipMemcpyAsync(stage + R.stage_off, src, (size_t)zl_dec_piece_bytes(R), hipMemcpyHostToDevice, e->stream);
         }
         if (prof && krc == 0) krc = (int)hipEventRecord(P.ev[2 * a + 1], e->stream);
-        if (krc == 0) krc = zl_launch_pcm_decode(P.dPieces + ps.first_piece, ps.npieces, ps.items, P.stage, P.dVerdicts, e->stream);
+        if (krc == 0) krc = zl_launch_pcm_decode(dPieces + ps.first_piece, ps.npieces, ps.items, stage, dVerdicts, e->stream);
     }
     if (prof && krc == 0) krc = (int)hipEventRecord(P.ev[2 * passes.size()], e->stream);
-    if (krc == 0) krc = zl_launch_pcm_publish(P.dPub, count, P.dVerdicts, e->dSounds, e->stream);
-    if (krc == 0) krc = (int)hipMemcpyAsync(verdicts.data(), P.dVerdicts, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
+    if (krc == 0) krc = zl_launch_pcm_publish(dPub, count, dVerdicts, e->dSounds, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(verdicts.data(), dVerdicts, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
     if (krc == 0) { const int w_ = engine_wait(e); if (w_ != ZLHIP_OK) { rollback(); return w_; } }     // the call's one wait
     if (krc != 0) {
         e->err = std::string("sound_upload_pcm: ") + hipGetErrorString((hipError_t)krc);
@@ -1023,12 +980,7 @@ int zlhip_sound_upload_pcm_batch(zlhip_engine *e, const zlhip_pcm_source *srcs, 
         const int id = ids[(size_t)i];
         ZlSound s = pub[(size_t)i].s;
         if (!pub[(size_t)i].check || verdicts[(size_t)i] == 0u) s.flags |= ZL_SOUND_FINITE;
-        e->hc.sounds[id] = s;
-        e->hc.soundUsed[id] = 1;
-        e->soundFloats[(size_t)id] = floats[(size_t)i];
-        e->origSounds[(size_t)id] = s;
-        e->renderFloats[(size_t)id] = 0;
-        e->renderOffsets[(size_t)id].clear();
+        adopt_sound(e, id, s, floats[(size_t)i]);
         zlhip_clip_params p;
         zlhip_clip_params_default(&p, (float)(s.length / s.sample_rate));
         e->hc.forget_clip_params(id);                              // (the first edit of a slot carries the whole record)
@@ -1073,19 +1025,13 @@ int zlhip_sound_release(zlhip_engine *e, int32_t id)
 // back to the arena.  The clip id keeps its slot; a voice playing it reads the new data from its next block at its unchanged position,
 // as the reference's voices read the sound's data pointer and length on every block (SamplerSynthVoice.cpp:186-191).
 // (a call's device records, grown when a call needs more: the free waits for the device, other engines' kernels step aside)
-static int st_reserve(zlhip_engine *e, void **p, size_t *cap, size_t need, size_t elem)
+static int st_reserve(zlhip_engine *e, GrowBuf &b, size_t need, size_t elem)
 {
-    if (need <= *cap) return ZLHIP_OK;
-    if (*p) {
-        { ZlQuiesce quiet(e); (void)hipFree(*p); }
-        e->deviceBytes -= *cap * elem;
-        *p = nullptr; *cap = 0;
-    }
     const size_t n = std::max<size_t>(need, 64);
-    if (hipMalloc(p, n * elem) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return fail(e, ZLHIP_ERR_CAPACITY, "sound_rerender: no device memory for the call's records"); }
-    e->deviceBytes += n * elem;
-    *cap = n;
-    return ZLHIP_OK;
+    const char *what = "sound_rerender: no device memory for the call's records";
+    if (need <= b.cap || !b.d) return grow_buf(e, b, need, elem, n, false, what);      // (nothing to free: no wait for the device)
+    ZlQuiesce quiet(e);
+    return grow_buf(e, b, need, elem, n, false, what);
 }
 
 int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_rerender_params *params, int32_t count)
@@ -1104,7 +1050,7 @@ int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_
             if (seen[(size_t)id]) return fail(e, ZLHIP_ERR_INVALID, "sound_rerender_batch: a clip appears twice");
             seen[(size_t)id] = 1;
             const zlhip_rerender_params &q = params[i];
-            const ZlSound &o = e->origSounds[(size_t)id];
+            const ZlSound &o = e->soundSlots[(size_t)id].orig;
             if (zl_st_geometry(o.sample_rate, o.length, q.gain_db, q.pitch_semitones, q.speed_ratio, &geo[(size_t)i]) != 0)
                 return fail(e, ZLHIP_ERR_INVALID, "sound_rerender: speed outside [0.25, 4], pitch outside [-24, 24], non-finite gain, or a sample rate the stretch cannot take");
             ident[(size_t)i] = zl_st_identity(q.gain_db, q.pitch_semitones, q.speed_ratio) ? 1 : 0;
@@ -1122,9 +1068,9 @@ int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_
     int64_t maxFrames = 0, offs = 0;
     for (int32_t i = 0; i < count; ++i) {
         if (ident[(size_t)i]) continue;
-        const ZlSound &o = e->origSounds[(size_t)ids[i]];
+        const ZlSound &o = e->soundSlots[(size_t)ids[i]].orig;
         const ZlStretchGeom &g = geo[(size_t)i];
-        const size_t floats = extent_floats(g.N, o.channels);
+        const size_t floats = zl_extent_floats(g.N, o.channels);
         const int rc = alloc_extent(e, floats, &newOff[(size_t)i]);
         if (rc != ZLHIP_OK) { rollback(); return rc; }
         newFloats[(size_t)i] = floats;
@@ -1141,22 +1087,24 @@ int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_
     }
     std::vector<int32_t> hOffs((size_t)offs);
     if (!jobs.empty()) {
-        int rc = st_reserve(e, (void **)&e->dStJobs, &e->stJobsCap, jobs.size(), sizeof(ZlStretchJob));
-        if (rc == ZLHIP_OK) rc = st_reserve(e, (void **)&e->dStList, &e->stListCap, std::max<size_t>(seekList.size(), 1), sizeof(int32_t));
-        if (rc == ZLHIP_OK) rc = st_reserve(e, (void **)&e->dStOffs, &e->stOffsCap, std::max<size_t>((size_t)offs, 1), sizeof(int32_t));
+        int rc = st_reserve(e, e->scratch[ZB_ST_JOBS], jobs.size(), sizeof(ZlStretchJob));
+        if (rc == ZLHIP_OK) rc = st_reserve(e, e->scratch[ZB_ST_LIST], std::max<size_t>(seekList.size(), 1), sizeof(int32_t));
+        if (rc == ZLHIP_OK) rc = st_reserve(e, e->scratch[ZB_ST_OFFS], std::max<size_t>((size_t)offs, 1), sizeof(int32_t));
         if (rc != ZLHIP_OK) { rollback(); return rc; }
-        hipError_t st = hipMemcpyAsync(e->dStJobs, jobs.data(), jobs.size() * sizeof(ZlStretchJob), hipMemcpyHostToDevice, e->stream);
+        ZlStretchJob *const dStJobs = (ZlStretchJob *)e->scratch[ZB_ST_JOBS].d;
+        int32_t *const dStList = (int32_t *)e->scratch[ZB_ST_LIST].d, *const dStOffs = (int32_t *)e->scratch[ZB_ST_OFFS].d;
+        hipError_t st = hipMemcpyAsync(dStJobs, jobs.data(), jobs.size() * sizeof(ZlStretchJob), hipMemcpyHostToDevice, e->stream);
         if (st == hipSuccess && !seekList.empty())
-            st = hipMemcpyAsync(e->dStList, seekList.data(), seekList.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+            st = hipMemcpyAsync(dStList, seekList.data(), seekList.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
         int krc = (int)st;
         const bool prof = e->profiling;
         for (int x = 0; prof && krc == 0 && x < 3; ++x) if (!e->stEv[x]) krc = (int)hipEventCreate(&e->stEv[x]);
         if (prof && krc == 0) krc = (int)hipEventRecord(e->stEv[0], e->stream);
-        if (krc == 0) krc = zl_launch_stretch_seek(e->dStJobs, e->dStList, (int)seekList.size(), e->dStOffs, e->stream);
+        if (krc == 0) krc = zl_launch_stretch_seek(dStJobs, dStList, (int)seekList.size(), dStOffs, e->stream);
         if (prof && krc == 0) krc = (int)hipEventRecord(e->stEv[1], e->stream);
-        if (krc == 0) krc = zl_launch_stretch_synth(e->dStJobs, (int)jobs.size(), maxFrames, e->dStOffs, e->stream);
+        if (krc == 0) krc = zl_launch_stretch_synth(dStJobs, (int)jobs.size(), maxFrames, dStOffs, e->stream);
         if (prof && krc == 0) krc = (int)hipEventRecord(e->stEv[2], e->stream);
-        if (krc == 0 && offs > 0) krc = (int)hipMemcpyAsync(hOffs.data(), e->dStOffs, (size_t)offs * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream);
+        if (krc == 0 && offs > 0) krc = (int)hipMemcpyAsync(hOffs.data(), dStOffs, (size_t)offs * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream);
         if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);
         if (prof && krc == 0) {
             krc = (int)hipEventElapsedTime(&e->stSeekMs, e->stEv[0], e->stEv[1]);
@@ -1172,19 +1120,19 @@ int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_
     // the swap: nothing queued can read the extents the clips played until now any more
     for (int32_t i = 0; i < count; ++i) {
         const int32_t id = ids[i];
-        const ZlSound cur = e->hc.sounds[id];
-        free_extent(e, (size_t)cur.offset, e->renderFloats[(size_t)id]);
-        ZlSound s = e->origSounds[(size_t)id];
+        zlhip_engine::SoundSlot &slot = e->soundSlots[(size_t)id];
+        free_extent(e, (size_t)e->hc.sounds[id].offset, slot.renderFloats);
+        ZlSound s = slot.orig;
         // (a rendered extent has not been looked at: it plays without ZL_SOUND_FINITE; identity parameters play the original, with its own flag)
         if (!ident[(size_t)i]) { s.offset = newOff[(size_t)i]; s.length = (int32_t)geo[(size_t)i].N; s.flags &= ~(int32_t)ZL_SOUND_FINITE; }
         e->hc.sounds[id] = s;
-        e->renderFloats[(size_t)id] = newFloats[(size_t)i];
-        e->renderOffsets[(size_t)id].clear();
+        slot.renderFloats = newFloats[(size_t)i];
+        slot.renderOffsets.clear();
     }
     for (size_t j = 0; j < jobs.size(); ++j) {
         const ZlStretchGeom &g = jobs[j].geom;
         if (g.stretch && g.nseg > 0)
-            e->renderOffsets[(size_t)ids[jobClip[j]]].assign(hOffs.begin() + jobs[j].off_base, hOffs.begin() + jobs[j].off_base + g.nseg);
+            e->soundSlots[(size_t)ids[jobClip[j]]].renderOffsets.assign(hOffs.begin() + jobs[j].off_base, hOffs.begin() + jobs[j].off_base + g.nseg);
     }
     for (int32_t i = 0; i < count; ++i)
         ZL_HIP(e, hipMemcpyAsync(e->dSounds + ids[i], &e->hc.sounds[ids[i]], sizeof(ZlSound), hipMemcpyHostToDevice, e->stream));
@@ -1227,39 +1175,14 @@ int zlhip_sound_read(zlhip_engine *e, int32_t id, float *left, float *right, int
 // no device-synchronising HIP call.
 static int ov_reserve(zlhip_engine *e, size_t nreq, size_t ncols)
 {
-    zlhip_engine::Overview &o = e->ov;
-    if (nreq <= o.reqCap && ncols <= o.colCap) return ZLHIP_OK;
+    GrowBuf &req = e->scratch[ZB_OV_REQ], &cols = e->scratch[ZB_OV_COLS];
+    if (nreq <= req.cap && ncols <= cols.cap) return ZLHIP_OK;
     { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }
     ZlQuiesce quiet(e);
-    if (nreq > o.reqCap) {
-        if (o.dReq) { (void)hipFree(o.dReq); e->deviceBytes -= o.reqCap * sizeof(ZlOvRequest); }
-        if (o.hReq) (void)hipHostFree(o.hReq);
-        o.dReq = nullptr; o.hReq = nullptr; o.reqCap = 0;
-        const size_t n = std::max<size_t>(nreq * 2, 64);
-        if (hipHostMalloc((void **)&o.hReq, n * sizeof(ZlOvRequest)) != hipSuccess || hipMalloc((void **)&o.dReq, n * sizeof(ZlOvRequest)) != hipSuccess) {
-            (void)hipGetLastError();
-            if (o.hReq) (void)hipHostFree(o.hReq);
-            o.hReq = nullptr; o.dReq = nullptr;
-            return fail(e, ZLHIP_ERR_CAPACITY, "sound_overview: no memory for the call's requests");
-        }
-        e->deviceBytes += n * sizeof(ZlOvRequest);
-        o.reqCap = n;
-    }
-    if (ncols > o.colCap) {
-        if (o.dCols) { (void)hipFree(o.dCols); e->deviceBytes -= o.colCap * 4 * sizeof(float); }
-        if (o.hCols) (void)hipHostFree(o.hCols);
-        o.dCols = nullptr; o.hCols = nullptr; o.colCap = 0;
-        const size_t n = std::min<size_t>(std::max<size_t>(ncols * 2, ZL_OV_MAX_COLUMNS), ZL_OV_MAX_CALL_COLUMNS);
-        if (hipHostMalloc((void **)&o.hCols, n * 4 * sizeof(float)) != hipSuccess || hipMalloc((void **)&o.dCols, n * 4 * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            if (o.hCols) (void)hipHostFree(o.hCols);
-            o.hCols = nullptr; o.dCols = nullptr;
-            return fail(e, ZLHIP_ERR_CAPACITY, "sound_overview: no memory for the call's columns");
-        }
-        e->deviceBytes += n * 4 * sizeof(float);
-        o.colCap = n;
-    }
-    return ZLHIP_OK;
+    const int rc = grow_buf(e, req, nreq, sizeof(ZlOvRequest), std::max<size_t>(nreq * 2, 64), true, "sound_overview: no memory for the call's requests");
+    if (rc != ZLHIP_OK) return rc;
+    return grow_buf(e, cols, ncols, 4 * sizeof(float), std::min<size_t>(std::max<size_t>(ncols * 2, ZL_OV_MAX_COLUMNS), ZL_OV_MAX_CALL_COLUMNS), true,
+                    "sound_overview: no memory for the call's columns");
 }
 
 int zlhip_sound_overview_batch(zlhip_engine *e, const zlhip_overview_request *reqs, int32_t count, float *out, size_t out_floats)
@@ -1282,12 +1205,14 @@ int zlhip_sound_overview_batch(zlhip_engine *e, const zlhip_overview_request *re
     if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
     { const int rc = ov_reserve(e, (size_t)count, (size_t)columns); if (rc != ZLHIP_OK) return rc; }
     zlhip_engine::Overview &o = e->ov;
+    ZlOvRequest *const hReq = (ZlOvRequest *)e->scratch[ZB_OV_REQ].h, *const dReq = (ZlOvRequest *)e->scratch[ZB_OV_REQ].d;
+    float *const hCols = (float *)e->scratch[ZB_OV_COLS].h; uint32_t *const dCols = (uint32_t *)e->scratch[ZB_OV_COLS].d;
     // the request records: where the extent lies (64-bit, per request: a grown arena's segments are far apart), what to cut it into
     int64_t items = 0; int32_t col = 0;
     for (int32_t i = 0; i < count; ++i) {
         const zlhip_overview_request &q = reqs[i];
         const ZlSound &s = e->hc.sounds[q.id];
-        ZlOvRequest &R = o.hReq[i];
+        ZlOvRequest &R = hReq[i];
         R.src = (uint64_t)(uintptr_t)arena_ptr(e, s.offset);
         R.item_base = items;
         R.first = q.first_frame; R.frames = q.num_frames; R.columns = q.columns;
@@ -1299,16 +1224,16 @@ int zlhip_sound_overview_batch(zlhip_engine *e, const zlhip_overview_request *re
     }
     const bool prof = e->profiling;
     for (int x = 0; prof && x < 2; ++x) if (!o.ev[x]) ZL_HIP(e, hipEventCreate(&o.ev[x]));
-    ZL_HIP(e, hipMemcpyAsync(o.dReq, o.hReq, (size_t)count * sizeof(ZlOvRequest), hipMemcpyHostToDevice, e->stream));
+    ZL_HIP(e, hipMemcpyAsync(dReq, hReq, (size_t)count * sizeof(ZlOvRequest), hipMemcpyHostToDevice, e->stream));
     if (prof) ZL_HIP(e, hipEventRecord(o.ev[0], e->stream));
-    ZL_HIP(e, hipMemsetAsync(o.dCols, 0, (size_t)columns * 4 * sizeof(float), e->stream));
-    ZL_KERNEL(e, zl_launch_overview_reduce(o.dReq, count, items, o.dCols, e->stream));
-    ZL_KERNEL(e, zl_launch_overview_finish(o.dCols, (int32_t)columns, e->stream));
+    ZL_HIP(e, hipMemsetAsync(dCols, 0, (size_t)columns * 4 * sizeof(float), e->stream));
+    ZL_KERNEL(e, zl_launch_overview_reduce(dReq, count, items, dCols, e->stream));
+    ZL_KERNEL(e, zl_launch_overview_finish(dCols, (int32_t)columns, e->stream));
     if (prof) ZL_HIP(e, hipEventRecord(o.ev[1], e->stream));
-    ZL_HIP(e, hipMemcpyAsync(o.hCols, o.dCols, (size_t)columns * 4 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    ZL_HIP(e, hipMemcpyAsync(hCols, dCols, (size_t)columns * 4 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
     if (prof) ZL_HIP(e, hipEventElapsedTime(&o.ms, o.ev[0], o.ev[1]));
-    std::memcpy(out, o.hCols, (size_t)columns * 4 * sizeof(float));
+    std::memcpy(out, hCols, (size_t)columns * 4 * sizeof(float));
     return ZLHIP_OK;
 }
 
@@ -1336,7 +1261,7 @@ int zlhip_debug_rerender_timings(zlhip_engine *e, float *seek_ms, float *synth_m
 int zlhip_debug_rerender_offsets(zlhip_engine *e, int32_t id, int32_t *out, int32_t capacity, int32_t *count)
 {
     if (!e || id < 0 || id >= e->cfg.max_sounds || !e->hc.soundUsed[id]) return ZLHIP_ERR_INVALID;
-    const std::vector<int32_t> &o = e->renderOffsets[(size_t)id];
+    const std::vector<int32_t> &o = e->soundSlots[(size_t)id].renderOffsets;
     if (count) *count = (int32_t)o.size();
     if (!out) return ZLHIP_OK;
     if ((size_t)capacity < o.size()) return fail(e, ZLHIP_ERR_CAPACITY, "debug_rerender_offsets: capacity below the count");
@@ -2513,7 +2438,7 @@ int zlhip_memory_bytes(zlhip_engine *e, uint64_t *total_device_bytes, uint64_t *
 {
     if (!e) return ZLHIP_ERR_INVALID;
     if (total_device_bytes) *total_device_bytes = (uint64_t)e->deviceBytes;
-    if (arena_bytes) *arena_bytes = (uint64_t)(e->arenaFloats + e->arenaSegmentFloats) * sizeof(float);
+    if (arena_bytes) *arena_bytes = (uint64_t)(e->arenaAlloc.arenaFloats + e->arenaAlloc.arenaSegmentFloats) * sizeof(float);
     return ZLHIP_OK;
 }
 

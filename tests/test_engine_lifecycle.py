@@ -374,3 +374,82 @@ def test_device_upload_behind_the_producers_stream(Engine):
     ref, _ = osyn.render_batch(4, 128, clk)
     assert np.array_equal(syn.read_bus().view(np.int32), ref.view(np.int32)) and np.abs(ref).max() > 0.1
     syn.close()
+
+
+def test_the_clip_store_through_a_mixed_life(Engine):
+    """Uploads (fp32 planes; batches of 16-bit and float PCM), re-renders (gain only, half speed, back to the original), overviews and
+    releases in a seeded mix on one small engine: after every step every live clip reads back bit for bit -- an upload as its source
+    data, a re-render as it read straight after the call (tests/test_rerender_gpu.py holds what it must be) -- so no call touches an
+    extent that is not its own.  The live data outgrows the first arena by more than the largest segment, so at least two segments
+    come and go wherever the device puts them; with everything released the arena is the one reserved at creation.  The same
+    sequence a second time finds every scratch buffer large enough: the engine's device memory is what it was before it."""
+    import decode_ref as dr
+    import overview_ref as ovr
+    first = 1 << 16
+    syn = Engine(2, 4, max_frames=128, max_batch_blocks=2, max_sounds=12, sound_arena_bytes=first)
+    bits = lambda x: np.ascontiguousarray(x).view(np.uint32)
+    extent = lambda planes, frames: ((frames + 8) * len(planes) + 3) & ~3          # floats a clip of these planes holds in the arena
+
+    def run(seed):
+        rng = np.random.default_rng(seed)
+        live = {}                                  # clip -> [planes it plays, planes of its upload]; planes: [channels][frames] float32
+        peak_floats = peak_arena = 0
+        for step in range(40):
+            free = 12 - len(live)
+            ops = (["upload"] * 3 + ["pcm"] * 2 if free >= 3 else ["upload"] if free else []) if step < 36 else []
+            if live:
+                ops += ["gain", "slow", "identity", "overview"] + ["release"] * (1 if step < 10 else 3)
+            op = ops[int(rng.integers(0, len(ops)))]
+            pick = lambda: sorted(live)[int(rng.integers(0, len(live)))]
+            if op == "upload":
+                n, stereo = int(rng.integers(300, 6001)), bool(rng.integers(0, 2))
+                L, R = rand_source(rng, n, stereo=stereo)
+                planes = np.stack([L, R]) if stereo else L[None, :]
+                live[syn.register_clip(L, R, 48000.0)] = [planes, planes]
+            elif op == "pcm":
+                srcs, want = [], []
+                for k in range(int(rng.integers(2, 4))):
+                    fmt, ch, n = (dr.S16, dr.F32)[(step + k) % 2], int(rng.integers(1, 3)), int(rng.integers(300, 6001))
+                    raw = dr.random_raw(rng, fmt, ch, n)
+                    srcs.append((raw.view(np.int16 if fmt == dr.S16 else np.float32), fmt, ch, 44100.0))
+                    want.append(dr.decode(raw, fmt, ch))
+                for cid, planes in zip(syn.register_clips_pcm(srcs), want):
+                    assert cid not in live
+                    live[cid] = [planes, planes]
+            elif op in ("gain", "slow", "identity"):
+                cid = pick()
+                syn.rerender_clip(cid, **{"gain": dict(gain_db=-6.0), "slow": dict(speed=0.5), "identity": {}}[op])
+                if op == "identity":
+                    live[cid][0] = live[cid][1]                                  # it plays its upload again
+                else:
+                    L, R = syn.read_clip(cid)
+                    live[cid][0] = np.stack([L, R]) if R is not None else L[None, :]
+                    assert live[cid][0].shape == (live[cid][1].shape[0], live[cid][1].shape[1] * (2 if op == "slow" else 1))
+            elif op == "overview":
+                cids = [pick() for _ in range(int(rng.integers(1, 3)))]
+                for cid, got in zip(cids, syn.clip_overviews([(c, 64) for c in cids])):
+                    assert ovr.same_bits(got, ovr.overview(live[cid][0], 64))
+            else:
+                cid = pick()
+                syn.unregister_clip(cid)
+                del live[cid]
+            for cid, (plays, _) in live.items():
+                L, R = syn.read_clip(cid)
+                assert np.array_equal(bits(L), bits(plays[0])) and (R is None) == (len(plays) == 1), (step, op, cid)
+                assert R is None or np.array_equal(bits(R), bits(plays[1])), (step, op, cid)
+            floats = sum(extent(u, u.shape[1]) + (extent(p, p.shape[1]) if p is not u else 0) for p, u in live.values())
+            arena = syn.memory_bytes()[1]
+            assert arena >= 4 * floats
+            peak_floats, peak_arena = max(peak_floats, floats), max(peak_arena, arena)
+        for cid in sorted(live):
+            syn.unregister_clip(cid)
+        return peak_floats, peak_arena
+
+    peak_floats, peak_arena = run(21)
+    # the largest extent -- a stereo clip of 6000 frames at half speed -- is the largest segment there can be
+    assert peak_floats > first // 4 + extent("LR", 12000) and peak_arena >= 3 * first
+    mem = syn.memory_bytes()
+    assert mem[1] == first
+    assert run(21)[0] == peak_floats                               # the same sequence
+    assert syn.memory_bytes() == mem
+    syn.close()
