@@ -246,6 +246,11 @@ def build_order_harness(force: bool = False) -> str:
     return _build_harness("zl_order_host", "order_host.cpp", ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_host.h", _ZLHIP_H], _NO_CONTRACT + ["-Wall", "-Wno-unused-function"], force)
 
 
+def build_order_summary_harness(force: bool = False) -> str:
+    """The run summary K1o leaves behind the order table (zl_order.h)."""
+    return _build_harness("zl_order_summary_host", "order_summary_host.cpp", ["zl_types.h", "zl_order.h"], ["-Wall", "-Wno-unused-function"], force)
+
+
 def build_ongrid_harness(force: bool = False) -> str:
     """K2's on-grid form (zl_render.h)."""
     return _build_harness("zl_ongrid_host", "ongrid_host.cpp", ["zl_types.h", "zl_render.h"], _NO_CONTRACT + ["-Wall", "-Wno-unused-function"], force)

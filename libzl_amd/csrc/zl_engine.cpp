@@ -115,7 +115,7 @@ struct zlhip_engine {
         unsigned long long ctlBase = 0;                   // host side: past every value the counter can have reached
         ZlSimConst *simConst = nullptr;
         float *partials = nullptr;
-        int32_t *order = nullptr; size_t orderInts = 0;  // K2's phase order of the window's blocks (K1o): [z-slots][K], allocated on first use
+        int32_t *order = nullptr; size_t orderInts = 0;  // K2's phase order of the window's blocks (K1o): [z-slots][K] and the run summary behind it (zl_order_ints), allocated on first use
         hipEvent_t planned = nullptr, rendered = nullptr, k1done = nullptr;
         hipEvent_t renderedEv = nullptr; // the event that marks the end of the last rendering from this set (rendered, or a profiling event)
         bool used = false;               // `rendered` has been recorded at least once
@@ -1584,6 +1584,9 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
     // ---- K2 with two frames per lane (zl_pair.h): ZL_K2_PAIR 0 = never, 1 = auto (default: every playing voice cheap to plan, the
     //      voices whose interior blocks are on-grid), 2 = wherever the launch shape allows (tests, A/B); read per call
     const int pairMode = [] { const char *v = std::getenv("ZL_K2_PAIR"); return v ? std::atoi(v) : 1; }();
+    // ---- the pair kernels' staging without the run lists (zl_order.h): ZL_K2_STAGE_NORUN 1 = in the blocks behind the last
+    //      inline run of the bus's voices (default), 0 = never (K1o then leaves run_end = INT_MAX); read per call
+    const int stageNorun = [] { const char *v = std::getenv("ZL_K2_STAGE_NORUN"); return v ? (std::atoi(v) != 0 ? 1 : 0) : 1; }();
     // offline bounce, direct delivery: K2 itself also stores the finished bus into the caller's page-locked host buffer
     const bool direct = e->bnc.sink.on && e->bnc.sink.hostDev && A.groups == 1;
     // ---- which kernel a window of K blocks gets, its grid, and what follows from it (zl_launch.h) ----
@@ -1598,7 +1601,7 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
     };
     {
         size_t need = 0;
-        for (const auto &wk : wins) { const ZlK2Launch L = k2Launch(wk.second, true); if (L.order) need = std::max(need, (size_t)L.gz * (size_t)wk.second); }
+        for (const auto &wk : wins) { const ZlK2Launch L = k2Launch(wk.second, true); if (L.order) need = std::max(need, zl_order_ints((int)L.gz, wk.second, e->V)); }   // the table and its tail
         if (need > e->ps[0].orderInts || (e->ps[1].hdr != nullptr && need > e->ps[1].orderInts)) {
             ZlQuiesce quiet(e);                                    // (as for the trace buffer: hipFree waits for the whole device)
             for (auto &q : e->ps) {
@@ -1674,12 +1677,12 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
             ZL_HIP(e, hipEventRecord(q.k1done, ps));
             ZL_HIP(e, hipStreamWaitEvent(e->asmStream, q.k1done, 0));
             ZL_KERNEL(e, zl_launch_assemble(Aw, e->asmStream));
-            if (L.order) ZL_KERNEL(e, zl_launch_order(Aw, q.order, (int)L.gz, e->asmStream));
+            if (L.order) ZL_KERNEL(e, zl_launch_order(Aw, q.order, (int)L.gz, stageNorun, e->asmStream));
             ZL_HIP(e, hipEventRecord(q.planned, e->asmStream));
             ZL_HIP(e, hipStreamWaitEvent(s, q.planned, 0));
         } else {
             if (!Aw.fuse_assemble) ZL_KERNEL(e, zl_launch_assemble(Aw, ps));
-            if (L.order) ZL_KERNEL(e, zl_launch_order(Aw, q.order, (int)L.gz, ps));
+            if (L.order) ZL_KERNEL(e, zl_launch_order(Aw, q.order, (int)L.gz, stageNorun, ps));
             if (ps != s) {
                 ZL_HIP(e, hipEventRecord(q.planned, ps));
                 ZL_HIP(e, hipStreamWaitEvent(s, q.planned, 0));

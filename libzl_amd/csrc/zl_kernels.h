@@ -7,7 +7,7 @@
 int zl_launch_apply_ops(const ZlBatch &A, hipStream_t s);
 int zl_launch_plan(const ZlBatch &A, int force_slow, hipStream_t s);
 int zl_launch_assemble(const ZlBatch &A, hipStream_t s);
-int zl_launch_order(const ZlBatch &A, int32_t *order, int nslots, hipStream_t s);   // K1o: order[nslots][A.K]
+int zl_launch_order(const ZlBatch &A, int32_t *order, int nslots, int norun, hipStream_t s);   // K1o: order[nslots][A.K] and the tail (zl_order_ints)
 const ZlK2Switches &zl_k2_switches();
 int zl_launch_render(const ZlBatch &A, const ZlK2Launch &L, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);   // L = zl_k2_launch(...)
 int zl_launch_finalize(const ZlBatch &A, const float *bus_in, hipStream_t s);

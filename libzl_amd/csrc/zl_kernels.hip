@@ -166,20 +166,27 @@ __global__ void __launch_bounds__(64) zl_k1c_assemble(const ZlBatch A, int block
 // workgroup per z-slot: a counting sort over at most ZL_ORDER_MAXBKT buckets in LDS.  It runs beside a rendering K2 (the
 // planner's free wave slot, 9 KB of LDS), so it is small: 4 waves, a few us.  Without a key voice, or when the window is no
 // longer than the key voice's pass, the slot's order is the identity.
-__global__ void __launch_bounds__(256) zl_k1o_order(const ZlBatch A, int32_t *order)
+__global__ void __launch_bounds__(256) zl_k1o_order(const ZlBatch A, int32_t *order, int norun)
 {
     __shared__ int s_hist[ZL_ORDER_MAXBKT];
     __shared__ int s_part[256];
-    __shared__ int s_key;
+    __shared__ int s_key, s_end;
     const int tid = threadIdx.x, K = A.K;
     int vb, ve;
     zl_order_slot_voices((int)blockIdx.x, A.NB, A.VPB, A.V, vb, ve);
     int32_t *out = order + (size_t)blockIdx.x * K;
-    if (tid == 0) s_key = INT_MAX;
+    if (tid == 0) { s_key = INT_MAX; s_end = 0; }
     __syncthreads();
-    for (int v = vb + tid; v < ve; v += 256)
+    // the same pass over the slot's run lists leaves the tail behind the table (zl_order.h): the slot's run_end -- INT_MAX with
+    // ZL_K2_STAGE_NORUN=0: staging then fetches the run lists in every block -- and each voice's dead_from, dense
+    for (int v = vb + tid; v < ve; v += 256) {
         if (zl_order_is_key(A.runs[v], K)) atomicMin(&s_key, v);
+        const int e = zl_order_run_end(A.runs[v]);
+        if (e > 0) atomicMax(&s_end, e);
+        order[zl_order_tail_dead((int)gridDim.x, K, v)] = A.runs[v].dead_from;
+    }
     __syncthreads();
+    if (tid == 0) order[zl_order_tail_run_end((int)gridDim.x, K, (int)blockIdx.x)] = norun ? s_end : INT_MAX;
     ZlOrderKey key;
     if (s_key == INT_MAX || !zl_order_setup(A.runs[s_key], K, A.N, key)) {
         for (int k = tid; k < K; k += 256) out[k] = k;
@@ -1131,7 +1138,11 @@ static __device__ __forceinline__ void zl_k2_chunk(const ZlBatch &A, const ZlBlo
 // zl_k_rt_loop<0, wide>'s from 402 to 338 with 20 -> 12 bytes of scratch.  K2 sits at the SGPR limit: any change to its text moves the allocation.)
 // The record of voice vb + i in block kk (i >= nv: a slot behind the pass's last voice, which gets the neutral record); every load the record
 // may need is issued at once.
-static __device__ __forceinline__ void zl_k2_stage_load(const ZlBatch &A, int kk, int vb, int i, int nv, ZlVoiceConst &vc, ZlBlockPlan &pl)
+// RUNS = false: a block that no inline run of the workgroup's voices reaches (k >= run_end, the word K1o leaves behind the order table,
+// zl_order.h).  The run list -- 160 of the 240 bytes of a voice-block, every lane in cache lines of its own -- is not touched: cov is
+// false, and dead_from comes from the dense copy in the table's tail (dead_tail[v], one coalesced load).  The rest is the same text.
+template <bool RUNS>
+static __device__ __forceinline__ void zl_k2_stage_load(const ZlBatch &A, int kk, int vb, int i, int nv, ZlVoiceConst &vc, ZlBlockPlan &pl, const int32_t *dead_tail)
 {
     const int N = A.N, V = A.V;
     zl_plan_clear(pl);
@@ -1148,14 +1159,16 @@ static __device__ __forceinline__ void zl_k2_stage_load(const ZlBatch &A, int kk
             const size_t pidx = (size_t)kk * V + (size_t)(vb + i);
             const ZlPlanHdr ph = A.plan_hdr[pidx];
             const ZlPlanSeg0 ps = A.plan_seg0[pidx];
-            const int rn = rl->n, dead = rl->dead_from;
+            const int rn = RUNS ? rl->n : 0, dead = RUNS ? rl->dead_from : dead_tail[vb + i];
             bool cov = false; double rP = 0.0, rstep = 0.0; int rk0 = 0;
+            if (RUNS) {
 #pragma unroll
-            for (int j = 0; j < ZL_MAXRUNS; ++j) {
-                const ZlRun r = rl->r[j];
-                const bool hit = !cov && j < rn && kk >= r.k0 && kk < r.k1;
-                rP = hit ? r.P : rP; rstep = hit ? r.step : rstep; rk0 = hit ? r.k0 : rk0;
-                cov = cov || hit;
+                for (int j = 0; j < ZL_MAXRUNS; ++j) {
+                    const ZlRun r = rl->r[j];
+                    const bool hit = !cov && j < rn && kk >= r.k0 && kk < r.k1;
+                    rP = hit ? r.P : rP; rstep = hit ? r.step : rstep; rk0 = hit ? r.k0 : rk0;
+                    cov = cov || hit;
+                }
             }
             if (kk < dead) {
                 pl.flags = cov ? (int32_t)ZL_PLAN_ACTIVE : ph.flags; pl.n_active = cov ? N : ph.n_active; pl.nseg = cov ? 1 : ph.nseg;
@@ -1784,6 +1797,9 @@ static __device__ __forceinline__ void zl_k2_pair_body(const ZlBatch &A)
     const int v0 = bus * A.VPB, vlim = (bus + 1) * A.VPB;
     const int v1 = (v0 + A.G < vlim) ? v0 + A.G : vlim;
     const bool wantPeak = __builtin_amdgcn_readfirstlane((int)(A.k0 + k == A.Ktot - 1)) != 0;
+    // the tail K1o leaves behind the table: from block run_end on, no voice of this bus has an inline run -- staging leaves the run lists alone
+    const int32_t *dead_tail = ORD ? A.order + zl_order_tail_dead((int)gridDim.z, A.K, 0) : nullptr;
+    const bool norun = ORD && __builtin_amdgcn_readfirstlane((int)(k >= A.order[zl_order_tail_run_end((int)gridDim.z, A.K, (int)bz)])) != 0;
 
     float accL0 = 0.0f, accR0 = 0.0f, accL1 = 0.0f, accR1 = 0.0f;
     for (int vb = v0; vb < v1; vb += CH) {
@@ -1792,7 +1808,8 @@ static __device__ __forceinline__ void zl_k2_pair_body(const ZlBatch &A)
         for (int i = threadIdx.x; i < CH; i += blockDim.x) {
             ZlVoiceConst vc;
             ZlBlockPlan pl;
-            zl_k2_stage_load(A, k, vb, i, nv, vc, pl);
+            if (norun) zl_k2_stage_load<false>(A, k, vb, i, nv, vc, pl, dead_tail);
+            else       zl_k2_stage_load<true>(A, k, vb, i, nv, vc, pl, nullptr);
             const int cls = zl_k2_stage_class<MODE>(A, vc, pl);
             s_unit[i] = zl_unit_record<MODE>(A, vc, pl, cls);
             s_vc[i] = vc;
@@ -2495,9 +2512,9 @@ int zl_launch_assemble(const ZlBatch &A, hipStream_t s)
     return 0;
 }
 
-int zl_launch_order(const ZlBatch &A, int32_t *order, int nslots, hipStream_t s)
+int zl_launch_order(const ZlBatch &A, int32_t *order, int nslots, int norun, hipStream_t s)
 {
-    hipLaunchKernelGGL(zl_k1o_order, dim3(nslots), dim3(256), 0, s, A, order);
+    hipLaunchKernelGGL(zl_k1o_order, dim3(nslots), dim3(256), 0, s, A, order, norun);
     ZL_LAUNCH_CHECK();
     return 0;
 }

@@ -48,6 +48,32 @@ ZL_HD inline int zl_order_bucket(const ZlOrderKey &key, int k)
     return (int)(p / key.width);
 }
 
+// ---- the slot's summary of its voices' inline runs, kept behind the order table.  K1o reads every run list of its slot anyway; the
+// pair kernel's staging (zl_k2_stage_load) fetches a voice's run list only where an inline run can cover the block.
+//   order[nslots * K + z]           run_end of z-slot z: no voice of the slot has an inline run that reaches block run_end or later
+//   order[nslots * K + nslots + v]  runs[v].dead_from, dense: a staging wave reads its voices' words with one coalesced load
+// first block behind the voice's last inline run; 0: it has none
+ZL_HD inline int zl_order_run_end(const ZlRunList &rl)
+{
+    int e = 0;
+    for (int j = 0; j < ZL_MAXRUNS; ++j) if (j < rl.n && rl.r[j].k1 > e) e = rl.r[j].k1;
+    return e;
+}
+
+// ... and of the voices [vb, ve) of a slot.  on = 0 (ZL_K2_STAGE_NORUN=0): INT_MAX, every block fetches the run lists
+ZL_HD inline int zl_order_slot_run_end(const ZlRunList *runs, int vb, int ve, int on)
+{
+    if (!on) return 0x7fffffff;
+    int e = 0;
+    for (int v = vb; v < ve; ++v) { const int ev = zl_order_run_end(runs[v]); e = ev > e ? ev : e; }
+    return e;
+}
+
+ZL_HD inline size_t zl_order_tail_run_end(int nslots, int K, int z) { return (size_t)nslots * (size_t)K + (size_t)z; }
+ZL_HD inline size_t zl_order_tail_dead(int nslots, int K, int v) { return (size_t)nslots * (size_t)K + (size_t)nslots + (size_t)v; }
+// ints of the order buffer of a window: the table and the tail
+ZL_HD inline size_t zl_order_ints(int nslots, int K, int V) { return (size_t)nslots * (size_t)K + (size_t)nslots + (size_t)V; }
+
 // the launch shapes K2 can take an order in: one block per workgroup (not the 64- / 128-frame batch forms), no mix groups, not staged
 inline bool zl_order_shape(int groups, int staged, int nblocks, int nframes)
 {
