@@ -183,6 +183,15 @@ int  libzl_hotpath_clip_waveform(ClipAudioSource *c, float start_seconds, float 
  * zlhip status for bad arguments).  ZL_PCM_DECODE=0 (read per call) and files with more than ZLHIP_PCM_MAX_CHANNELS channels take
  * ClipAudioSource_new's host decode, clip by clip; the playback data is bit-identical either way. */
 int  libzl_hotpath_clips_new(const char *const *paths, int count, ClipAudioSource **out);
+/* Convert clips to the engine's sample rate on the device, band-limited, in ONE zlhip_sound_convert_rate_batch call: from then on they
+ * play as unit-step sources (the on-grid path) instead of through the pitched path.  Build-defined and opt-in: the reference resamples
+ * while it plays, so a converted clip no longer reproduces its bits.  A clip the conversion does not take -- NULL, not in the engine,
+ * re-rendered by setPitch / setSpeedRatio / setGain, or at a ratio beyond the limits (zlhip.h) -- stays as it is and plays pitched.
+ * ClipAudioSource_getDuration, the start, the length and the slices are seconds and do not change.  Convert before playing.
+ * Returns how many of the clips are at the engine's rate afterwards, or a negative zlhip status (every clip is as it was then).
+ * ZL_LOAD_CONVERT=1 (read per call, default 0) makes ClipAudioSource_new and libzl_hotpath_clips_new convert what they loaded; the
+ * clips of one libzl_hotpath_clips_new call go in one batch.  With 0 the loaders do exactly what they did before. */
+int  libzl_hotpath_clips_convert(ClipAudioSource *const *clips, int count);
 /* minimal RIFF/WAVE IO (decode side of SamplerSynthSound.cpp:28-59; record side of AudioLevels.cpp:35-119) */
 int  libzl_wav_read(const char *path, float **left, float **right, int *length, double *sampleRate);  /* malloc'd planes; free with libzl_wav_free */
 void libzl_wav_free(float *plane);

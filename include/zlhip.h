@@ -37,7 +37,8 @@ extern "C" {
  * 3: new entry points only (a caller built against 2 keeps working): zlhip_render_fanout (the JackPassthrough fan-out on the
  *    real-time cycle), zlhip_rt_residency, zlhip_rt_last_cycle; the resident real-time kernel takes any period (blocks longer than 256 frames too).
  *    Later additions, still 3 (new entry points only): the engine group (zlhip_group_*), zlhip_sound_overview / _batch (waveform overviews),
- *    zlhip_sound_upload_pcm / _batch (clips from raw PCM, decoded on the device). */
+ *    zlhip_sound_upload_pcm / _batch (clips from raw PCM, decoded on the device), zlhip_sound_convert_rate / _batch (clips converted to
+ *    another sample rate on the device, band-limited), zlhip_resample_design, zlhip_sound_info_get, zlhip_debug_sound_extent. */
 #define ZLHIP_ABI_VERSION 3
 
 /* status codes */
@@ -268,6 +269,43 @@ int zlhip_debug_rerender_offsets(zlhip_engine *e, int32_t id, int32_t *out, int3
 /* measurement: device time of the seek launch and of the synthesis launch of the last re-render call made with profiling on
  * (zlhip_set_profiling; HIP events on the engine's stream) */
 int zlhip_debug_rerender_timings(zlhip_engine *e, float *seek_ms, float *synth_ms);
+/* Sample-rate conversion: a clip whose rate differs from the engine's plays through the pitched voice path
+ *   (an fp64 position per frame, two taps, no anti-alias filter); converted to the engine's rate it is a unit-step source and takes
+ *   the on-grid path.  The conversion is build-defined -- the reference resamples while it plays (SamplerSynthVoice.cpp:104), so a
+ *   converted clip no longer reproduces the reference's bits for that file -- and therefore opt-in: nothing converts unless asked.
+ *   Definition: rates are integer-valued, in [1000, 768000]; g = gcd(fs, ft), L = ft / g, M = fs / g.  A Kaiser-windowed sinc
+ *   (beta 10, cutoff 0.95 of the lower Nyquist, 32 / min(1, L/M) input frames a side), one row per phase, rows of unit sum, fp32;
+ *   the clip gets N = ceil(length * L / M) frames, each the sum of its taps in fp32 -- a rounded multiply, then a rounded add, in tap
+ *   order, samples outside the clip +0.  Mono stays mono.  ZL_SOUND_FINITE is decided on the device from the output.
+ *   Limits: L <= 2048, M <= 8 L, L * (taps rounded up to 4) <= 262144, N + 8 <= INT32_MAX: anything else is ZLHIP_ERR_INVALID,
+ *   as are ids not in use or repeated and count < 0 -- all decided before the first HIP call.  target_rate == 0 means the engine's
+ *   playback_sample_rate.  A clip that currently plays a re-render is ZLHIP_ERR_STATE (re-render it with gain 0, pitch 0, speed 1
+ *   first); an arena that cannot hold the whole call is ZLHIP_ERR_CAPACITY.  All or nothing: on any error every clip is as it was.
+ *   A clip already at the target rate is skipped (no launch, no copy), whatever that rate is.
+ *   The converted extent becomes the clip's ORIGINAL: later re-renders start from it, the old original goes back to the arena.
+ *   Synchronisation is zlhip_sound_rerender's: the resident kernel leaves, queued batches finish, the table entry switches at a block
+ *   boundary; one launch converts every clip of the call, one publishes, and the call waits once.
+ *   Side effects: the sound's sample rate changes, so a note started later steps at the new rate.  Clip parameters are seconds and
+ *   keep their meaning; duration_seconds stays.  A voice that plays the clip DURING the call keeps its frame position and step: that is
+ *   safe (as after a re-render that shortens the clip) but musically wrong -- convert before playing.
+ *   The filter tables live on the device, one per (L, M) ever asked for, until the engine is destroyed; zlhip_memory_bytes counts them.
+ *   A table is made by the first call that asks for its ratio; a call that fails frees the tables it added. */
+int zlhip_sound_convert_rate(zlhip_engine *e, int32_t id, double target_rate);
+int zlhip_sound_convert_rate_batch(zlhip_engine *e, const int32_t *ids, int32_t count, double target_rate);
+/* The filter of a ratio, on the host (no engine, no device): *L, *M, *taps and *row_floats (taps rounded up to a multiple of 4) and,
+ * where table != NULL, the L rows of row_floats floats (zeros in the pad).  table == NULL asks for the sizes only; table_floats below
+ * L * row_floats is ZLHIP_ERR_CAPACITY, a ratio beyond the limits ZLHIP_ERR_INVALID.  The engine builds its device tables with this code. */
+int zlhip_resample_design(double source_rate, double target_rate, int32_t *L, int32_t *M, int32_t *taps, int32_t *row_floats,
+                          float *table, size_t table_floats);
+/* What a sound slot plays now: frames, channels, rate; finite = ZL_SOUND_FINITE is set; rendered = it plays a re-render. */
+typedef struct zlhip_sound_info { int32_t length, channels; double sample_rate; int32_t finite, rendered; } zlhip_sound_info;
+int zlhip_sound_info_get(zlhip_engine *e, int32_t id, zlhip_sound_info *out);
+/* debug: the sound's playback extent as it lies in the arena -- interleaved (or mono), the 8 zero frames behind the last frame and the
+ * floats up to the 16-byte boundary included.  *floats receives the extent's size; out == NULL asks for the size only; capacity below it
+ * is ZLHIP_ERR_CAPACITY.  Synchronisation is zlhip_sound_read's. */
+int zlhip_debug_sound_extent(zlhip_engine *e, int32_t id, float *out, size_t capacity, size_t *floats);
+/* measurement: device time of the last conversion call made with profiling on (HIP events around the call's two launches) */
+int zlhip_debug_convert_timings(zlhip_engine *e, float *device_ms);
 
 /* ---- commands ------------------------------------------------------------------------------ */
 void zlhip_clip_command_clear(zlhip_clip_command *c);           /* ClipCommand.h:74-91 */
@@ -416,6 +454,10 @@ int  zlhip_group_sound_upload_pcm_batch(zlhip_group *g, const zlhip_pcm_source *
 int  zlhip_group_sound_release(zlhip_group *g, int32_t id);
 int  zlhip_group_clip_set(zlhip_group *g, int32_t id, const zlhip_clip_params *p);
 int  zlhip_group_sound_rerender_batch(zlhip_group *g, const int32_t *ids, const zlhip_rerender_params *params, int32_t count);
+/* zlhip_sound_convert_rate_batch on every member, in member order.  The members hold the same clips in arenas that are alike, so a call
+ * that is invalid, refused or does not fit fails on member 0 and changes nothing.  A failure on a later member (a HIP error) converts
+ * nothing back: the members before it hold the converted clips, it and the ones behind it the old ones; the error names the member. */
+int  zlhip_group_sound_convert_rate_batch(zlhip_group *g, const int32_t *ids, int32_t count, double target_rate);
 /* zlhip_sound_overview / _batch: every member holds every sound, member 0 answers */
 int  zlhip_group_sound_overview(zlhip_group *g, int32_t id, int32_t first_frame, int32_t num_frames, int32_t columns, float *out);
 int  zlhip_group_sound_overview_batch(zlhip_group *g, const zlhip_overview_request *reqs, int32_t count, float *out, size_t out_floats);

@@ -116,6 +116,10 @@ class PcmSource(C.Structure):
                 ("sample_rate", C.c_double)]
 
 
+class SoundInfo(C.Structure):
+    _fields_ = [("length", C.c_int32), ("channels", C.c_int32), ("sample_rate", C.c_double), ("finite", C.c_int32), ("rendered", C.c_int32)]
+
+
 class RtCycleTrace(C.Structure):
     _fields_ = [
         ("cycle", C.c_uint64), ("resident", C.c_int32), ("reserved", C.c_int32),
@@ -159,6 +163,12 @@ SIGNATURES = {
     "zlhip_debug_upload_pcm_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "zlhip_debug_rerender_offsets": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_debug_rerender_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "zlhip_sound_convert_rate": (C.c_int, [_E, C.c_int32, C.c_double]),
+    "zlhip_sound_convert_rate_batch": (C.c_int, [_E, C.POINTER(C.c_int32), C.c_int32, C.c_double]),
+    "zlhip_resample_design": (C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_size_t]),
+    "zlhip_sound_info_get": (C.c_int, [_E, C.c_int32, C.POINTER(SoundInfo)]),
+    "zlhip_debug_convert_timings": (C.c_int, [_E, C.POINTER(C.c_float)]),
+    "zlhip_debug_sound_extent": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "zlhip_clip_command_clear": (None, [C.POINTER(ClipCommand)]),
     "zlhip_handle_command": (C.c_int, [_E, C.POINTER(ClipCommand), C.c_uint64]),
     "zlhip_handle_commands": (C.c_int, [_E, C.POINTER(ClipCommand), C.c_int32, C.c_uint64, C.POINTER(C.c_int32)]),
@@ -208,6 +218,7 @@ SIGNATURES = {
     "zlhip_group_sound_release": (C.c_int, [_E, C.c_int32]),
     "zlhip_group_clip_set": (C.c_int, [_E, C.c_int32, C.POINTER(ClipParams)]),
     "zlhip_group_sound_rerender_batch": (C.c_int, [_E, C.POINTER(C.c_int32), C.POINTER(RerenderParams), C.c_int32]),
+    "zlhip_group_sound_convert_rate_batch": (C.c_int, [_E, C.POINTER(C.c_int32), C.c_int32, C.c_double]),
     "zlhip_group_sound_overview": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "zlhip_group_sound_overview_batch": (C.c_int, [_E, C.POINTER(OverviewRequest), C.c_int32, C.c_void_p, C.c_size_t]),
     "zlhip_group_handle_commands": (C.c_int, [_E, C.POINTER(ClipCommand), C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

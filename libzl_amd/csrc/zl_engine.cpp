@@ -29,6 +29,7 @@
 #include "zl_pair.h"
 #include "zl_plan.h"
 #include "zl_overview.h"
+#include "zl_resample.h"
 #include "zl_decode.h"
 #include "zl_render.h"
 #include "zl_stretch.h"
@@ -66,6 +67,7 @@ struct GrowBuf { void *d = nullptr, *h = nullptr; size_t cap = 0; };
 enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a call's jobs, the jobs whose stretch runs, their seek offsets
        ZB_OV_REQ, ZB_OV_COLS,                                 // overviews: a call's request records and its columns [columns][4], with host twins
        ZB_PCM_STAGE, ZB_PCM_PIECES, ZB_PCM_PUB, ZB_PCM_VERDICTS,   // PCM: the staging buffer for the raw bytes, a call's piece and publish records, its verdict words
+       ZB_RS_JOBS, ZB_RS_PUB, ZB_RS_VERDICTS,                // rate conversion: a call's job and publish records, its verdict words
        ZB_COUNT };
 
 }  // namespace
@@ -104,6 +106,12 @@ struct zlhip_engine {
         std::vector<hipEvent_t> ev;                                 // profiling: before every pass's copies and every decode launch, behind the last
         float copyMs = 0.0f, decodeMs = 0.0f;                       // ... of the last call made with profiling on (zlhip_debug_upload_pcm_timings)
     } pcm;
+    // clips converted to another rate (zlhip_sound_convert_rate; zl_resample.h): the filter tables on the device, one per (L, M) ever asked for
+    struct Resample {
+        struct Table { int32_t L = 0, M = 0; float *d = nullptr; size_t floats = 0; std::vector<float> pending; };   // pending: the host copy, until the call that made the table has waited
+        std::vector<Table> tables;
+        hipEvent_t ev[2] = {nullptr, nullptr}; float ms = 0.0f;                 // profiling: around the call's launches (zlhip_debug_convert_timings)
+    } rs;
     ZlSound *dSounds = nullptr; ZlClip *dClips = nullptr;
     ZlVoiceState *dVoices = nullptr;
     // K1 -> K2 records, double buffered so that planning window i+1 overlaps rendering window i
@@ -411,6 +419,8 @@ void zlhip_engine_destroy(zlhip_engine *e)
     if (e->asmStream) (void)hipStreamSynchronize(e->asmStream);
     for (auto &seg : e->arenaAlloc.segments) if (seg.handle) (void)hipFree(seg.handle);
     for (auto &b : e->scratch) { if (b.d) (void)hipFree(b.d); if (b.h) (void)hipHostFree(b.h); }
+    for (auto &t : e->rs.tables) if (t.d) (void)hipFree(t.d);
+    for (hipEvent_t ev : e->rs.ev) if (ev) (void)hipEventDestroy(ev);
     void *dev[] = { e->arena, e->dSounds, e->dClips, e->dVoices, e->dGain, e->dBus, e->dLevels, e->dLevelState, e->dTrace, e->dPass, e->dPassCache };
     for (void *p : dev) if (p) (void)hipFree(p);
     for (auto &q : e->ps) {
@@ -1143,6 +1153,239 @@ int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_
 int zlhip_sound_rerender(zlhip_engine *e, int32_t id, const zlhip_rerender_params *params)
 {
     return zlhip_sound_rerender_batch(e, &id, params, 1);
+}
+
+// ---- sample-rate conversion (zl_resample.h, zl_resample.hip) --------------------------------------------------------------
+// A clip whose rate differs from the engine's plays through the pitched voice path; converted once, band-limited, it is a unit-step
+// integer-position source and K2 takes its on-grid form.  Every clip of the call is converted from its original upload into a new
+// arena extent by ONE launch, a second one publishes the sound-table entries (ZL_SOUND_FINITE from the device's verdict), and the
+// call waits once.  Synchronisation is zlhip_sound_rerender's: the resident kernel has left and every queued batch has finished before
+// anything is written.  The converted extent becomes the slot's original: later re-renders start from it.
+int zlhip_resample_design(double source_rate, double target_rate, int32_t *L, int32_t *M, int32_t *taps, int32_t *row_floats, float *table, size_t table_floats)
+{
+    ZlRsGeom g;
+    if (zl_rs_geometry(source_rate, target_rate, &g) != 0) return ZLHIP_ERR_INVALID;
+    if (L) *L = g.L;
+    if (M) *M = g.M;
+    if (taps) *taps = g.taps;
+    if (row_floats) *row_floats = g.row;
+    if (!table) return ZLHIP_OK;
+    if (table_floats < (size_t)g.L * (size_t)g.row) return ZLHIP_ERR_CAPACITY;
+    zl_rs_design(g, table);
+    return ZLHIP_OK;
+}
+
+// the device table of a ratio: made by the first call that asks for the ratio, before the call takes anything from the arena, and cached
+// for the engine's life once that call has succeeded -- a call that fails frees the tables it added (hipMalloc and hipFree wait for the
+// device: other engines' kernels step aside).  The copy is queued on the engine's stream in front of the call's launches and shares
+// the call's one wait: the host copy lives until then.
+static int rs_table(zlhip_engine *e, const ZlRsGeom &g, float **out)
+{
+    for (const auto &t : e->rs.tables) if (t.L == g.L && t.M == g.M) { *out = t.d; return ZLHIP_OK; }
+    e->rs.tables.emplace_back();
+    zlhip_engine::Resample::Table &t = e->rs.tables.back();
+    t.L = g.L; t.M = g.M; t.floats = (size_t)g.L * (size_t)g.row;
+    t.pending.resize(t.floats);
+    zl_rs_design(g, t.pending.data());
+    bool ok;
+    { ZlQuiesce quiet(e); ok = hipMalloc((void **)&t.d, t.floats * sizeof(float)) == hipSuccess; }
+    if (!ok) { (void)hipGetLastError(); e->rs.tables.pop_back(); return fail(e, ZLHIP_ERR_CAPACITY, "sound_convert_rate: no device memory for the filter table"); }
+    if (hipMemcpyAsync(t.d, t.pending.data(), t.floats * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(e->stream);
+        { ZlQuiesce quiet(e); (void)hipFree(t.d); }
+        e->rs.tables.pop_back();
+        return fail(e, ZLHIP_ERR_HIP, "sound_convert_rate: the filter table did not reach the device");
+    }
+    e->deviceBytes += t.floats * sizeof(float);
+    *out = t.d;
+    return ZLHIP_OK;
+}
+// after a wait for the engine's stream: the tables' host copies are no longer read
+static void rs_tables_settled(zlhip_engine *e) { for (auto &t : e->rs.tables) std::vector<float>().swap(t.pending); }
+// a failed call: the engine's stream runs dry, the tables behind the first `keep` go back to the device
+static void rs_tables_undo(zlhip_engine *e, size_t keep)
+{
+    (void)hipStreamSynchronize(e->stream);
+    rs_tables_settled(e);
+    while (e->rs.tables.size() > keep) {
+        { ZlQuiesce quiet(e); (void)hipFree(e->rs.tables.back().d); }
+        e->deviceBytes -= e->rs.tables.back().floats * sizeof(float);
+        e->rs.tables.pop_back();
+    }
+}
+
+static int rs_reserve(zlhip_engine *e, size_t njobs)
+{
+    GrowBuf *b = e->scratch;
+    if (njobs <= b[ZB_RS_JOBS].cap && njobs <= b[ZB_RS_PUB].cap && njobs <= b[ZB_RS_VERDICTS].cap) return ZLHIP_OK;
+    ZlQuiesce quiet(e);
+    const char *what = "sound_convert_rate: no device memory for the call's records";
+    const size_t n = std::max<size_t>(njobs * 2, 64);
+    int rc = grow_buf(e, b[ZB_RS_JOBS], njobs, sizeof(ZlRsJob), n, false, what);
+    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_RS_PUB], njobs, sizeof(ZlRsPublish), n, false, what);
+    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_RS_VERDICTS], njobs, sizeof(uint32_t), n, false, what);
+    return rc;
+}
+
+int zlhip_sound_convert_rate_batch(zlhip_engine *e, const int32_t *ids, int32_t count, double target_rate)
+{
+    if (!e || count < 0 || (count > 0 && !ids)) return ZLHIP_ERR_INVALID;
+    if (count == 0) return ZLHIP_OK;
+    const double ft = target_rate == 0.0 ? e->cfg.playback_sample_rate : target_rate;
+    // validate everything before the first HIP call
+    std::vector<ZlRsGeom> geo((size_t)count);
+    std::vector<int64_t> outN((size_t)count, 0);
+    std::vector<char> skip((size_t)count, 0);
+    {
+        std::vector<char> seen((size_t)e->cfg.max_sounds, 0);
+        int64_t wgs = 0;
+        for (int32_t i = 0; i < count; ++i) {
+            const int32_t id = ids[i];
+            if (id < 0 || id >= e->cfg.max_sounds || !e->hc.soundUsed[id]) return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate: no such sound");
+            if (seen[(size_t)id]) return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate_batch: a clip appears twice");
+            seen[(size_t)id] = 1;
+        }
+        for (int32_t i = 0; i < count; ++i) {
+            const ZlSound &o = e->soundSlots[(size_t)ids[i]].orig;
+            skip[(size_t)i] = o.sample_rate == ft ? 1 : 0;           // (already at the rate, whatever the rate: nothing to check, nothing to do)
+            if (skip[(size_t)i]) continue;
+            if (zl_rs_geometry(o.sample_rate, ft, &geo[(size_t)i]) != 0)
+                return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate: a rate that is no integer in [1000, 768000], or a ratio beyond L <= 2048, M <= 8 L, 262144 table floats");
+            outN[(size_t)i] = zl_rs_out_frames(geo[(size_t)i], o.length);
+            if (outN[(size_t)i] < 1) return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate: the converted clip would exceed 2^31 - 9 frames");
+            wgs += zl_rs_job_wgs((int32_t)outN[(size_t)i]);
+        }
+        if (wgs > (int64_t)INT32_MAX) return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate_batch: more than 2^31 - 1 workgroups in one call");
+        for (int32_t i = 0; i < count; ++i)
+            if (!skip[(size_t)i] && e->soundSlots[(size_t)ids[i]].renderFloats != 0)
+                return fail(e, ZLHIP_ERR_STATE, "sound_convert_rate: the clip plays a re-render (re-render it with gain 0, pitch 0, speed 1 first)");
+    }
+    int32_t njobs = 0;
+    for (int32_t i = 0; i < count; ++i) njobs += skip[(size_t)i] ? 0 : 1;
+    if (njobs == 0) return ZLHIP_OK;                               // every clip is at the target rate already: no launch, no copy
+    ZL_HIP(e, hipSetDevice(e->device));
+    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }         // the sound table and the arena change under the resident kernel otherwise
+    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }     // queued batches still read the table
+
+    // the filter tables of the call's ratios first; a call that fails frees the ones it added
+    const size_t tables0 = e->rs.tables.size();
+    std::vector<float *> tables((size_t)count, nullptr);
+    for (int32_t i = 0; i < count; ++i) {
+        if (skip[(size_t)i]) continue;
+        const int rc = rs_table(e, geo[(size_t)i], &tables[(size_t)i]);
+        if (rc != ZLHIP_OK) { rs_tables_undo(e, tables0); return rc; }
+    }
+    // the new extents (all or none: an arena that cannot hold the call leaves every clip as it was)
+    std::vector<size_t> newOff((size_t)count, 0), newFloats((size_t)count, 0);
+    auto rollback = [&]() {
+        rs_tables_undo(e, tables0);
+        for (int32_t i = count - 1; i >= 0; --i) free_extent(e, newOff[(size_t)i], newFloats[(size_t)i]);
+    };
+    for (int32_t i = 0; i < count; ++i) {
+        if (skip[(size_t)i]) continue;
+        const size_t floats = zl_extent_floats(outN[(size_t)i], e->soundSlots[(size_t)ids[i]].orig.channels);
+        const int rc = alloc_extent(e, floats, &newOff[(size_t)i]);
+        if (rc != ZLHIP_OK) { rollback(); return rc; }
+        newFloats[(size_t)i] = floats;
+    }
+    std::vector<ZlRsJob> jobs; std::vector<ZlRsPublish> pub;
+    int32_t wgs = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        if (skip[(size_t)i]) continue;
+        const ZlSound &o = e->soundSlots[(size_t)ids[i]].orig;
+        const ZlRsGeom &g = geo[(size_t)i];
+        float *const table = tables[(size_t)i];
+        ZlRsJob J; std::memset(&J, 0, sizeof J);
+        J.src = (uint64_t)(uintptr_t)arena_ptr(e, o.offset);
+        J.dst = (uint64_t)(uintptr_t)arena_ptr(e, newOff[(size_t)i]);
+        J.table = (uint64_t)(uintptr_t)table;
+        J.len = o.length; J.N = (int32_t)outN[(size_t)i]; J.channels = o.channels;
+        J.L = g.L; J.M = g.M; J.half = g.half; J.taps = g.taps; J.row = g.row;
+        J.wg_base = wgs; J.verdict = (int32_t)jobs.size();
+        wgs += zl_rs_job_wgs(J.N);
+        ZlSound s = o; s.offset = newOff[(size_t)i]; s.length = J.N; s.sample_rate = ft; s.flags &= ~(int32_t)ZL_SOUND_FINITE;
+        pub.push_back(ZlRsPublish{ s, ids[i], J.verdict });
+        jobs.push_back(J);
+    }
+    { const int rc = rs_reserve(e, jobs.size()); if (rc != ZLHIP_OK) { rollback(); return rc; } }
+    ZlRsJob *const dJobs = (ZlRsJob *)e->scratch[ZB_RS_JOBS].d; ZlRsPublish *const dPub = (ZlRsPublish *)e->scratch[ZB_RS_PUB].d;
+    uint32_t *const dVerdicts = (uint32_t *)e->scratch[ZB_RS_VERDICTS].d;
+    // everything is decided: from here on only a HIP error fails the call
+    std::vector<uint32_t> verdicts(jobs.size(), 0u);
+    const bool prof = e->profiling;
+    int krc = 0;
+    for (int x = 0; prof && krc == 0 && x < 2; ++x) if (!e->rs.ev[x]) krc = (int)hipEventCreate(&e->rs.ev[x]);
+    if (krc == 0) krc = (int)hipMemsetAsync(dVerdicts, 0, jobs.size() * sizeof(uint32_t), e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dJobs, jobs.data(), jobs.size() * sizeof(ZlRsJob), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, pub.data(), pub.size() * sizeof(ZlRsPublish), hipMemcpyHostToDevice, e->stream);
+    if (prof && krc == 0) krc = (int)hipEventRecord(e->rs.ev[0], e->stream);
+    if (krc == 0) krc = zl_launch_resample(dJobs, (int32_t)jobs.size(), wgs, dVerdicts, e->stream);
+    if (krc == 0) krc = zl_launch_resample_publish(dPub, (int32_t)pub.size(), dVerdicts, e->dSounds, e->stream);
+    if (prof && krc == 0) krc = (int)hipEventRecord(e->rs.ev[1], e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(verdicts.data(), dVerdicts, jobs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
+    if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);      // the call's one wait
+    if (prof && krc == 0) krc = (int)hipEventElapsedTime(&e->rs.ms, e->rs.ev[0], e->rs.ev[1]);
+    if (krc != 0) {
+        e->err = std::string("sound_convert_rate: ") + hipGetErrorString((hipError_t)krc);
+        (void)hipStreamSynchronize(e->stream);
+        // (the table entries the device may have switched go back to what the host's mirror holds)
+        for (const ZlRsPublish &p : pub) (void)hipMemcpy(e->dSounds + p.id, &e->hc.sounds[p.id], sizeof(ZlSound), hipMemcpyHostToDevice);
+        rollback();
+        return ZLHIP_ERR_HIP;
+    }
+    e->outstanding = false;
+    rs_tables_settled(e);
+    // the swap on the host: the converted extent is the slot's original from now on, the old one goes back to the arena
+    for (const ZlRsPublish &p : pub) {
+        zlhip_engine::SoundSlot &slot = e->soundSlots[(size_t)p.id];
+        const size_t oldOff = (size_t)slot.orig.offset, oldFloats = slot.floats;
+        ZlSound s = p.s;
+        if (verdicts[(size_t)p.verdict] == 0u) s.flags |= ZL_SOUND_FINITE;
+        int32_t i = 0;
+        while (ids[i] != p.id) ++i;
+        slot.orig = s; slot.floats = newFloats[(size_t)i];
+        slot.renderOffsets.clear();
+        e->hc.sounds[p.id] = s;
+        free_extent(e, oldOff, oldFloats);
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_convert_rate(zlhip_engine *e, int32_t id, double target_rate)
+{
+    return zlhip_sound_convert_rate_batch(e, &id, 1, target_rate);
+}
+
+int zlhip_sound_info_get(zlhip_engine *e, int32_t id, zlhip_sound_info *out)
+{
+    if (!e || !out || id < 0 || id >= e->cfg.max_sounds || !e->hc.soundUsed[id]) return ZLHIP_ERR_INVALID;
+    const ZlSound &s = e->hc.sounds[id];
+    out->length = s.length; out->channels = s.channels; out->sample_rate = s.sample_rate;
+    out->finite = (s.flags & ZL_SOUND_FINITE) ? 1 : 0;
+    out->rendered = e->soundSlots[(size_t)id].renderFloats != 0 ? 1 : 0;
+    return ZLHIP_OK;
+}
+
+int zlhip_debug_sound_extent(zlhip_engine *e, int32_t id, float *out, size_t capacity, size_t *floats)
+{
+    if (!e || id < 0 || id >= e->cfg.max_sounds || !e->hc.soundUsed[id]) return ZLHIP_ERR_INVALID;
+    const ZlSound s = e->hc.sounds[id];
+    const size_t n = zl_extent_floats(s.length, s.channels);
+    if (floats) *floats = n;
+    if (!out) return ZLHIP_OK;
+    if (capacity < n) return fail(e, ZLHIP_ERR_CAPACITY, "debug_sound_extent: capacity below the extent's floats");
+    ZL_HIP(e, hipSetDevice(e->device));
+    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    ZL_HIP(e, hipMemcpyAsync(out, arena_ptr(e, s.offset), n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    return engine_wait(e);
+}
+
+int zlhip_debug_convert_timings(zlhip_engine *e, float *device_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (device_ms) *device_ms = e->rs.ms;
+    return ZLHIP_OK;
 }
 
 int zlhip_sound_read(zlhip_engine *e, int32_t id, float *left, float *right, int32_t capacity, int32_t *length)

@@ -278,6 +278,17 @@ int zlhip_group_sound_rerender_batch(zlhip_group *g, const int32_t *ids, const z
     return ZLHIP_OK;
 }
 
+int zlhip_group_sound_convert_rate_batch(zlhip_group *g, const int32_t *ids, int32_t count, double target_rate)
+{
+    if (!g) return ZLHIP_ERR_INVALID;
+    // (the members hold the same clips in arenas that are alike: a call that is invalid or does not fit fails on member 0 and leaves every member as it was)
+    for (int r = 0; r < g->L.n; ++r) {
+        const int rc = zlhip_sound_convert_rate_batch(g->m[(size_t)r], ids, count, target_rate);
+        if (rc != ZLHIP_OK) return member_fail(g, r, rc);
+    }
+    return ZLHIP_OK;
+}
+
 // sounds are broadcast: every member holds the same playback data, member 0 answers
 int zlhip_group_sound_overview_batch(zlhip_group *g, const zlhip_overview_request *reqs, int32_t count, float *out, size_t out_floats)
 {

@@ -708,6 +708,52 @@ ClipAudioSource *ClipAudioSource_newFromBuffer(const float *left, const float *r
     return make_clip(length, sampleRate, name ? name : "", [&](int32_t *id) { return zlhip_sound_upload(G.engine, left, right, length, sampleRate, id); });
 }
 
+// ZL_LOAD_CONVERT: 1 = the loaders convert what they loaded to the engine's rate (zlhip_sound_convert_rate_batch); 0 (default) = a clip
+// keeps its file's rate and plays pitched, bit for bit as the reference would; read per call
+static bool load_convert_switch() { const char *v = std::getenv("ZL_LOAD_CONVERT"); return (v ? std::atoi(v) : 0) != 0; }
+
+// call with G.mu held.  The clips the conversion takes -- loaded into the engine, not playing a re-render, at a ratio inside the
+// limits -- go in ONE batch call; the others stay as they are and play pitched.  Returns how many clips are at the engine's rate
+// afterwards, or a negative zlhip status when the call itself failed (every clip is as it was then).
+static int clips_convert(ClipAudioSource *const *clips, int count)
+{
+    if (!G.engine) return ZLHIP_ERR_STATE;
+    zlhip_config dflt; zlhip_config_default(&dflt);
+    const double rate = G.cfgSet ? G.cfg.playback_sample_rate : dflt.playback_sample_rate;
+    std::vector<int32_t> ids; std::vector<ClipAudioSource *> taken;
+    int atRate = 0;
+    for (int i = 0; i < count; ++i) {
+        ClipAudioSource *c = clips[i];
+        zlhip_sound_info info;
+        if (!c || c->engineClip < 0 || zlhip_sound_info_get(G.engine, c->engineClip, &info) != ZLHIP_OK) continue;
+        if (std::find(taken.begin(), taken.end(), c) != taken.end()) continue;
+        if (info.sample_rate == rate && !info.rendered) { ++atRate; continue; }
+        if (info.rendered || zlhip_resample_design(info.sample_rate, rate, nullptr, nullptr, nullptr, nullptr, nullptr, 0) != ZLHIP_OK) continue;
+        ids.push_back(c->engineClip); taken.push_back(c);
+    }
+    if (ids.empty()) return atRate;
+    const int rc = zlhip_sound_convert_rate_batch(G.engine, ids.data(), (int32_t)ids.size(), rate);
+    if (rc != ZLHIP_OK) {
+        std::fprintf(stderr, "libzl hot path: cannot convert %zu clips to %g Hz: %s (%s)\n", ids.size(), rate, zlhip_strerror(rc), zlhip_last_error(G.engine));
+        return rc;
+    }
+    for (ClipAudioSource *c : taken) {
+        zlhip_sound_info info;
+        if (zlhip_sound_info_get(G.engine, c->engineClip, &info) != ZLHIP_OK) continue;
+        // (seconds keep their meaning: the duration, the start, the length and the slices stay; frames are counted at the new rate)
+        c->sourceSampleRate = info.sample_rate; c->lengthFrames = info.length;
+        ++atRate;
+    }
+    return atRate;
+}
+
+int libzl_hotpath_clips_convert(ClipAudioSource *const *clips, int count)
+{
+    if (count < 0 || (count > 0 && !clips)) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    return clips_convert(clips, count);
+}
+
 ClipAudioSource *ClipAudioSource_new(const char *filepath, bool muted)   // libzl.cpp:118-128, ClipAudioSource.cpp:135-205
 {
     ClipAudioSource *c = nullptr;
@@ -733,6 +779,7 @@ ClipAudioSource *ClipAudioSource_new(const char *filepath, bool muted)   // libz
         }
         libzl_wav_free(L); libzl_wav_free(R);
     }
+    if (c && load_convert_switch()) { std::lock_guard<std::mutex> lk(G.mu); (void)clips_convert(&c, 1); }   // (a clip the conversion does not take stays as loaded)
     if (c && muted) ClipAudioSource_setVolume(c, -100.0f);         // ClipAudioSource.cpp:178-181
     return c;
 }
@@ -778,6 +825,8 @@ int libzl_hotpath_clips_new(const char *const *paths, int count, ClipAudioSource
             std::fprintf(stderr, "libzl hot path: cannot open %s\n", paths[i]);
         }
     }
+    // (the clips the host route loaded have been converted one by one, by ClipAudioSource_new: they are skipped here)
+    if (loaded > 0 && load_convert_switch()) { std::lock_guard<std::mutex> lk(G.mu); (void)clips_convert(out, count); }
     return loaded;
 }
 

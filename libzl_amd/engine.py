@@ -274,6 +274,34 @@ class SamplerSynth:
         params = (RerenderParams * n)(*[RerenderParams(g[i], p[i], s[i], 0) for i in range(n)])
         self._ck(self._lib.zlhip_sound_rerender_batch(self._e, ids, params, n), "sound_rerender_batch")
 
+    def convert_clips(self, clips: Sequence[int], target_rate: Optional[float] = None):
+        """Convert the clips to `target_rate` (None: the engine's playback rate) on the device, band-limited, in one call
+        (zlhip_sound_convert_rate_batch): from then on they play as unit-step sources.  Opt-in: a converted clip no longer reproduces
+        the reference's bits for its file.  All or nothing; a clip already at the rate is skipped."""
+        n = len(clips)
+        ids = (C.c_int32 * max(1, n))(*clips)
+        self._ck(self._lib.zlhip_sound_convert_rate_batch(self._e, ids, n, float(target_rate or 0.0)), "sound_convert_rate_batch")
+
+    def clip_info(self, clip: int) -> dict:
+        """What the clip plays now: length, channels, sample_rate, finite (ZL_SOUND_FINITE), rendered (it plays a re-render)"""
+        i = _abi.SoundInfo()
+        self._ck(self._lib.zlhip_sound_info_get(self._e, clip, C.byref(i)), "sound_info_get")
+        return {"length": i.length, "channels": i.channels, "sample_rate": i.sample_rate, "finite": bool(i.finite), "rendered": bool(i.rendered)}
+
+    def clip_extent(self, clip: int) -> np.ndarray:
+        """debug: the clip's playback extent as it lies in the arena, the zero frames behind the last frame included (zlhip_debug_sound_extent)"""
+        n = C.c_size_t(0)
+        self._ck(self._lib.zlhip_debug_sound_extent(self._e, clip, None, 0, C.byref(n)), "debug_sound_extent")
+        out = np.empty(n.value, np.float32)
+        self._ck(self._lib.zlhip_debug_sound_extent(self._e, clip, out.ctypes.data, out.size, None), "debug_sound_extent")
+        return out
+
+    def convert_timings(self) -> float:
+        """device ms of the last conversion call made with profiling on (set_profiling)"""
+        a = C.c_float(0.0)
+        self._ck(self._lib.zlhip_debug_convert_timings(self._e, C.byref(a)), "debug_convert_timings")
+        return a.value
+
     def read_clip(self, clip: int):
         """The clip's current playback data: (left, right) float32, right None for a mono clip (zlhip_sound_read)."""
         n = C.c_int32(0)
@@ -655,6 +683,19 @@ class SamplerSynthGroup:
 
     def rerender_clip(self, clip: int, gain_db: float = 0.0, pitch: float = 0.0, speed: float = 1.0):
         self.rerender_clips([clip], gain_db, pitch, speed)
+
+    def convert_clips(self, clips: Sequence[int], target_rate: Optional[float] = None):
+        """SamplerSynth.convert_clips on every member (zlhip_group_sound_convert_rate_batch)"""
+        n = len(clips)
+        ids = (C.c_int32 * max(1, n))(*clips)
+        self._ck(self._lib.zlhip_group_sound_convert_rate_batch(self._g, ids, n, float(target_rate or 0.0)), "group_sound_convert_rate_batch")
+
+    def clip_info(self, clip: int) -> dict:
+        """SamplerSynth.clip_info: every member holds every clip, member 0 answers"""
+        i = _abi.SoundInfo()
+        m0 = C.c_void_p(self.member(0))
+        _abi.check(self._lib, m0, self._lib.zlhip_sound_info_get(m0, clip, C.byref(i)), "sound_info_get")
+        return {"length": i.length, "channels": i.channels, "sample_rate": i.sample_rate, "finite": bool(i.finite), "rendered": bool(i.rendered)}
 
     def clip_length(self, clip: int) -> int:
         n = C.c_int32(0)
