@@ -177,6 +177,15 @@ int    ClipAudioSource_engineClip(ClipAudioSource *c);                          
  * data; end_seconds <= start_seconds or an end beyond the data means "to the end".  1 <= columns <= ZLHIP_OVERVIEW_MAX_COLUMNS.
  * Returns 0 or a negative zlhip status (out is not written then).  The painting stays the host's. */
 int  libzl_hotpath_clip_waveform(ClipAudioSource *c, float start_seconds, float end_seconds, int columns, float *out);
+/* Slice the clip at its transients (build-defined: the reference's setSlices only divides evenly, ClipAudioSource.cpp:495-528).  The
+ * transients of the clip's current playback data between its start and its start + length -- in frames, cast as SamplerSynthSound
+ * does (SamplerSynthSound.cpp:96-104) -- are found on the device (zlhip_sound_onsets with its defaults and max_onsets = the number of
+ * slices asked for: with more transients than slices the strongest stay).  Slice 0 is 0.0; an onset nearer to the region's start than
+ * (min_gap_hops + 1) * hop_frames frames is slice 0 itself and is dropped; every other onset becomes
+ * (double)(frame - start) / (double)(stop - start).  At most min(max_slices, ZLHIP_MAX_SLICES) entries; `slices` becomes the table's
+ * length, as setSlicePositions does (ClipAudioSource.cpp:535-543), and the table is published like ClipAudioSource_setSlices.
+ * Returns the number of slices, or a negative zlhip status that leaves the clip as it was. */
+int  libzl_hotpath_clip_slice_at_transients(ClipAudioSource *c, int max_slices);
 /* A bank of clips in one engine call: every file is read, their `data` chunks go to the engine as raw PCM in ONE
  * zlhip_sound_upload_pcm_batch call (decoded on the device, one wait for the whole bank).  out[i] is the clip of paths[i], or NULL
  * for a file that cannot be opened or decoded -- it does not fail the others.  Returns the number of clips loaded (or a negative

@@ -38,7 +38,8 @@ extern "C" {
  *    real-time cycle), zlhip_rt_residency, zlhip_rt_last_cycle; the resident real-time kernel takes any period (blocks longer than 256 frames too).
  *    Later additions, still 3 (new entry points only): the engine group (zlhip_group_*), zlhip_sound_overview / _batch (waveform overviews),
  *    zlhip_sound_upload_pcm / _batch (clips from raw PCM, decoded on the device), zlhip_sound_convert_rate / _batch (clips converted to
- *    another sample rate on the device, band-limited), zlhip_resample_design, zlhip_sound_info_get, zlhip_debug_sound_extent. */
+ *    another sample rate on the device, band-limited), zlhip_resample_design, zlhip_sound_info_get, zlhip_debug_sound_extent, zlhip_sound_onsets / _batch (a clip's transients, found on
+ *    the device), zlhip_onset_resolve. */
 #define ZLHIP_ABI_VERSION 3
 
 /* status codes */
@@ -240,6 +241,36 @@ int zlhip_sound_overview_batch(zlhip_engine *e, const zlhip_overview_request *re
 /* measurement: device time of the last overview call made with profiling on (zlhip_set_profiling; HIP events on the engine's stream
  * around the call's launches) */
 int zlhip_debug_overview_timings(zlhip_engine *e, float *device_ms);
+/* Transients: the frames at which a sampler slices a loop (a build-defined extension, the reference has no
+ * transient detection) -- found on the device in the sound's CURRENT playback data.  Everything behind the 16-bit quantisation
+ * q = clamp(rint(4096 v), +-32767) (NaN -> 0) is integer arithmetic, so the result does not depend on any order of evaluation:
+ *   E[h]: the sum of q^2 over the channels and the frames of hop h (hop_frames frames from first_frame on, the last hop cut at the
+ *   request's end), E[-1] = 0; F = hop_frames * channels * gate^2; L(x) = 64 p + floor((x - 2^p) * 64 / 2^p), p = floor(log2 x);
+ *   N[h] = max(0, L(E[h] + F) - L(E[h-1] + F)).  Hop h is a candidate if N[h] >= threshold, N[h] > N[j] for the min_gap_hops hops
+ *   before it and N[h] >= N[j] for the min_gap_hops hops behind it.  More than max_onsets candidates: those with the largest N stay,
+ *   equal N goes to the earlier hop.  A kept hop's onset is the start of the first sub-block of hop_frames / 16 frames, from one hop
+ *   before h to the end of h, whose energy e has 4 e > E[h-1] + F; else the hop's first frame.
+ *   out: the onsets (frame counted from the sound's first frame, strength = N[h]) in ascending frame order; *count / counts[i]: how
+ *   many.  The requests of a batch are packed one behind the other, in request order, without gaps.
+ *   A field given as 0 takes its default (zlhip_onset_resolve with the sound's sample rate): hop_frames = 16 * clamp(rint(rate / 3000),
+ *   4, 256), gate = 8, threshold = 128, min_gap_hops = max(1, ceil(0.05 * rate / hop_frames)), max_onsets = 128.
+ *   Limits: hop_frames a multiple of 16 in [64, 4096], gate in [1, 32767], threshold in [1, 4096], min_gap_hops in [1, 1024],
+ *   max_onsets in [1, ZLHIP_ONSET_MAX_ONSETS], num_frames >= 1, first_frame >= 0, first_frame + num_frames <= the sound's length, at
+ *   most 65536 hops per request and 4194304 per call, nreq >= 0: anything else is ZLHIP_ERR_INVALID; capacity below the sum of the
+ *   resolved max_onsets is ZLHIP_ERR_CAPACITY.  On any error out and counts are not written; one bad request fails the call.
+ *   A call is two kernel launches whatever its size, waits once and moves 8 bytes per onset and 4 per request to the host.  It runs
+ *   on the engine's stream behind what is queued there and the resident real-time kernel keeps running, like zlhip_sound_overview. */
+#define ZLHIP_ONSET_MAX_ONSETS 1024
+typedef struct zlhip_onset_request { int32_t id, first_frame, num_frames, hop_frames, gate, threshold, min_gap_hops, max_onsets; } zlhip_onset_request;
+typedef struct zlhip_onset { int32_t frame, strength; } zlhip_onset;
+/* host only: fills the fields given as 0 and checks every limit that does not need the sound; a refused request is left as it was */
+int zlhip_onset_resolve(double sample_rate, zlhip_onset_request *r);
+int zlhip_sound_onsets(zlhip_engine *e, const zlhip_onset_request *r, zlhip_onset *out, int32_t capacity, int32_t *count);
+int zlhip_sound_onsets_batch(zlhip_engine *e, const zlhip_onset_request *reqs, int32_t nreq, zlhip_onset *out, size_t capacity, int32_t *counts);
+/* E and N of request `request` of the last call (energy / strength: [capacity], may be NULL to ask for *hops only) */
+int zlhip_debug_onset_hops(zlhip_engine *e, int32_t request, uint64_t *energy, int32_t *strength, int32_t capacity, int32_t *hops);
+/* measurement: device time of the energy pass and of the rest of the last call made with profiling on */
+int zlhip_debug_onset_timings(zlhip_engine *e, float *energy_ms, float *rest_ms);
 /* Clips from raw PCM.  `frames` is host memory, pageable or page-locked: `length` frames of `channels`
  *   interleaved little-endian samples, exactly the bytes of a WAV `data` chunk.  They are copied raw into a device staging buffer and
  *   decoded there into the arena's layout; one decode launch serves each staging pass and the call waits for the device once.
@@ -461,6 +492,8 @@ int  zlhip_group_sound_convert_rate_batch(zlhip_group *g, const int32_t *ids, in
 /* zlhip_sound_overview / _batch: every member holds every sound, member 0 answers */
 int  zlhip_group_sound_overview(zlhip_group *g, int32_t id, int32_t first_frame, int32_t num_frames, int32_t columns, float *out);
 int  zlhip_group_sound_overview_batch(zlhip_group *g, const zlhip_overview_request *reqs, int32_t count, float *out, size_t out_floats);
+/* zlhip_sound_onsets_batch: member 0 answers */
+int  zlhip_group_sound_onsets_batch(zlhip_group *g, const zlhip_onset_request *reqs, int32_t nreq, zlhip_onset *out, size_t capacity, int32_t *counts);
 /* zlhip_handle_commands_voices over the whole synth (taken, voices optional) */
 int  zlhip_group_handle_commands(zlhip_group *g, const zlhip_clip_command *cmds, int32_t count, uint64_t current_tick, int32_t *taken,
                                  int32_t *voices);

@@ -106,6 +106,18 @@ class OverviewRequest(C.Structure):
     _fields_ = [("id", C.c_int32), ("first_frame", C.c_int32), ("num_frames", C.c_int32), ("columns", C.c_int32)]
 
 
+ONSET_MAX_ONSETS = 1024
+
+
+class OnsetRequest(C.Structure):
+    _fields_ = [("id", C.c_int32), ("first_frame", C.c_int32), ("num_frames", C.c_int32), ("hop_frames", C.c_int32), ("gate", C.c_int32),
+                ("threshold", C.c_int32), ("min_gap_hops", C.c_int32), ("max_onsets", C.c_int32)]
+
+
+class Onset(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("strength", C.c_int32)]
+
+
 PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = 1, 2, 3, 4, 5, 6
 PCM_MAX_CHANNELS = 64
 PCM_BYTES = {PCM_U8: 1, PCM_S16: 2, PCM_S24: 3, PCM_S32: 4, PCM_F32: 4, PCM_F64: 8}
@@ -158,6 +170,11 @@ SIGNATURES = {
     "zlhip_sound_overview": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "zlhip_sound_overview_batch": (C.c_int, [_E, C.POINTER(OverviewRequest), C.c_int32, C.c_void_p, C.c_size_t]),
     "zlhip_debug_overview_timings": (C.c_int, [_E, C.POINTER(C.c_float)]),
+    "zlhip_onset_resolve": (C.c_int, [C.c_double, C.POINTER(OnsetRequest)]),
+    "zlhip_sound_onsets": (C.c_int, [_E, C.POINTER(OnsetRequest), C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zlhip_sound_onsets_batch": (C.c_int, [_E, C.POINTER(OnsetRequest), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "zlhip_debug_onset_hops": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zlhip_debug_onset_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "zlhip_sound_upload_pcm": (C.c_int, [_E, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_int32)]),
     "zlhip_sound_upload_pcm_batch": (C.c_int, [_E, C.POINTER(PcmSource), C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_debug_upload_pcm_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -221,6 +238,7 @@ SIGNATURES = {
     "zlhip_group_sound_convert_rate_batch": (C.c_int, [_E, C.POINTER(C.c_int32), C.c_int32, C.c_double]),
     "zlhip_group_sound_overview": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "zlhip_group_sound_overview_batch": (C.c_int, [_E, C.POINTER(OverviewRequest), C.c_int32, C.c_void_p, C.c_size_t]),
+    "zlhip_group_sound_onsets_batch": (C.c_int, [_E, C.POINTER(OnsetRequest), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "zlhip_group_handle_commands": (C.c_int, [_E, C.POINTER(ClipCommand), C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "zlhip_group_start_voice": (C.c_int, [_E, C.c_int32, C.c_int32, C.POINTER(ClipCommand), C.c_uint64]),
     "zlhip_group_stop_voice": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_int]),

@@ -28,6 +28,7 @@
 #include "zl_order.h"
 #include "zl_pair.h"
 #include "zl_plan.h"
+#include "zl_onset.h"
 #include "zl_overview.h"
 #include "zl_resample.h"
 #include "zl_decode.h"
@@ -68,6 +69,7 @@ enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a ca
        ZB_OV_REQ, ZB_OV_COLS,                                 // overviews: a call's request records and its columns [columns][4], with host twins
        ZB_PCM_STAGE, ZB_PCM_PIECES, ZB_PCM_PUB, ZB_PCM_VERDICTS,   // PCM: the staging buffer for the raw bytes, a call's piece and publish records, its verdict words
        ZB_RS_JOBS, ZB_RS_PUB, ZB_RS_VERDICTS,                // rate conversion: a call's job and publish records, its verdict words
+       ZB_ON_REQ, ZB_ON_E, ZB_ON_N, ZB_ON_PS,                // transients: a call's request records (with a host twin), and per hop E, N and the windows' running maxima
        ZB_COUNT };
 
 }  // namespace
@@ -101,6 +103,13 @@ struct zlhip_engine {
     struct Overview {
         hipEvent_t ev[2] = {nullptr, nullptr}; float ms = 0.0f;                 // profiling: around the call's launches (zlhip_debug_overview_timings)
     } ov;
+    // transients (zlhip_sound_onsets; zl_onset.h)
+    struct Onset {
+        int32_t *hCounts = nullptr, *dCounts = nullptr; size_t countsCap = 0;   // a call's counts and onsets, in host memory mapped into the device:
+        ZlOnOnset *hOut = nullptr, *dOut = nullptr; size_t outCap = 0;         // the pick kernel writes what it found there and nothing else crosses
+        std::vector<std::pair<int32_t, int32_t>> last;                          // per request of the last call: its first hop, its hops (zlhip_debug_onset_hops)
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; float energyMs = 0.0f, restMs = 0.0f;   // profiling (zlhip_debug_onset_timings)
+    } on;
     // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h)
     struct Pcm {
         std::vector<hipEvent_t> ev;                                 // profiling: before every pass's copies and every decode launch, behind the last
@@ -452,6 +461,9 @@ void zlhip_engine_destroy(zlhip_engine *e)
     for (void *p : host) if (p) (void)hipHostFree(p);
     for (hipEvent_t ev : e->stEv) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->ov.ev) if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->on.ev) if (ev) (void)hipEventDestroy(ev);
+    if (e->on.hCounts) (void)hipHostFree(e->on.hCounts);
+    if (e->on.hOut) (void)hipHostFree(e->on.hOut);
     for (hipEvent_t ev : e->pcm.ev) if (ev) (void)hipEventDestroy(ev);
     if (e->evJoin) (void)hipEventDestroy(e->evJoin);
     if (e->evPlanTail) (void)hipEventDestroy(e->evPlanTail);
@@ -1490,6 +1502,127 @@ int zlhip_debug_overview_timings(zlhip_engine *e, float *device_ms)
 {
     if (!e) return ZLHIP_ERR_INVALID;
     if (device_ms) *device_ms = e->ov.ms;
+    return ZLHIP_OK;
+}
+
+// ---- transients (zl_onset.h, zl_onset.hip) ---------------------------------------------------------------------------------
+// Where a sampler slices a loop.  The synchronisation and the buffers are the overviews': the call runs on the engine's stream behind
+// what is queued there and leaves the resident real-time kernel alone; its buffers are allocated by the first call and grow only.
+// The counts and the onsets are written by the pick kernel into host memory mapped into the device, so only what was found crosses.
+int zlhip_onset_resolve(double sample_rate, zlhip_onset_request *r)
+{
+    if (!r || r->first_frame < 0 || r->num_frames < 1) return ZLHIP_ERR_INVALID;
+    zlhip_onset_request q = *r;
+    if (zl_on_resolve(sample_rate, &q.hop_frames, &q.gate, &q.threshold, &q.min_gap_hops, &q.max_onsets) != 0) return ZLHIP_ERR_INVALID;
+    if (zl_on_hops(q.num_frames, q.hop_frames) > ZL_ON_MAX_HOPS) return ZLHIP_ERR_INVALID;
+    *r = q;
+    return ZLHIP_OK;
+}
+
+static int on_reserve(zlhip_engine *e, size_t nreq, size_t hops, size_t nout)
+{
+    GrowBuf *b = e->scratch; zlhip_engine::Onset &o = e->on;
+    if (nreq <= b[ZB_ON_REQ].cap && hops <= b[ZB_ON_E].cap && hops <= b[ZB_ON_N].cap && hops <= b[ZB_ON_PS].cap && nreq <= o.countsCap && nout <= o.outCap)
+        return ZLHIP_OK;
+    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }
+    ZlQuiesce quiet(e);
+    const char *what = "sound_onsets: no memory for the call's buffers";
+    const size_t hcap = std::min<size_t>(std::max<size_t>(hops * 2, 4096), ZL_ON_MAX_CALL_HOPS);
+    int rc = grow_buf(e, b[ZB_ON_REQ], nreq, sizeof(ZlOnRequest), std::max<size_t>(nreq * 2, 64), true, what);
+    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_ON_E], hops, sizeof(uint64_t), hcap, false, what);
+    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_ON_N], hops, sizeof(int32_t), hcap, false, what);
+    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_ON_PS], hops, sizeof(uint32_t), hcap, false, what);
+    if (rc != ZLHIP_OK) return rc;
+    ZL_HIP(e, grow_mapped(&o.hCounts, &o.dCounts, &o.countsCap, std::max<size_t>(nreq, 32)));
+    ZL_HIP(e, grow_mapped(&o.hOut, &o.dOut, &o.outCap, std::max<size_t>(nout, 512)));
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_onsets_batch(zlhip_engine *e, const zlhip_onset_request *reqs, int32_t nreq, zlhip_onset *out, size_t capacity, int32_t *counts)
+{
+    if (!e || nreq < 0 || (nreq > 0 && (!reqs || !out || !counts))) return ZLHIP_ERR_INVALID;
+    if (nreq == 0) return ZLHIP_OK;
+    // validate and resolve everything before anything is written and before the first HIP call
+    std::vector<zlhip_onset_request> res((size_t)nreq);
+    int64_t hops = 0; size_t nout = 0;
+    for (int32_t i = 0; i < nreq; ++i) {
+        zlhip_onset_request &q = res[(size_t)i];
+        q = reqs[i];
+        if (q.id < 0 || q.id >= e->cfg.max_sounds || !e->hc.soundUsed[q.id]) return fail(e, ZLHIP_ERR_INVALID, "sound_onsets: no such sound");
+        const ZlSound &s = e->hc.sounds[q.id];
+        if (zlhip_onset_resolve(s.sample_rate, &q) != ZLHIP_OK) return fail(e, ZLHIP_ERR_INVALID, "sound_onsets: a field of the request is outside its limits");
+        if ((int64_t)q.first_frame + q.num_frames > s.length) return fail(e, ZLHIP_ERR_INVALID, "sound_onsets: the frames do not lie inside the sound's playback data");
+        hops += zl_on_hops(q.num_frames, q.hop_frames);
+        if (hops > ZL_ON_MAX_CALL_HOPS) return fail(e, ZLHIP_ERR_INVALID, "sound_onsets_batch: more than 4194304 hops in one call");
+        nout += (size_t)q.max_onsets;
+    }
+    if (capacity < nout) return fail(e, ZLHIP_ERR_CAPACITY, "sound_onsets: out holds fewer onsets than the requests' max_onsets");
+    ZL_HIP(e, hipSetDevice(e->device));
+    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    { const int rc = on_reserve(e, (size_t)nreq, (size_t)hops, nout); if (rc != ZLHIP_OK) return rc; }
+    zlhip_engine::Onset &o = e->on;
+    ZlOnRequest *const hReq = (ZlOnRequest *)e->scratch[ZB_ON_REQ].h, *const dReq = (ZlOnRequest *)e->scratch[ZB_ON_REQ].d;
+    uint64_t *const dE = (uint64_t *)e->scratch[ZB_ON_E].d; int32_t *const dN = (int32_t *)e->scratch[ZB_ON_N].d; uint32_t *const dPs = (uint32_t *)e->scratch[ZB_ON_PS].d;
+    o.last.clear();
+    int32_t hop0 = 0, out0 = 0;
+    for (int32_t i = 0; i < nreq; ++i) {
+        const zlhip_onset_request &q = res[(size_t)i];
+        const ZlSound &s = e->hc.sounds[q.id];
+        ZlOnRequest &R = hReq[i];
+        R.src = (uint64_t)(uintptr_t)arena_ptr(e, s.offset);
+        R.floor_ = zl_on_floor(q.hop_frames, s.channels, q.gate);
+        R.first = q.first_frame; R.frames = q.num_frames; R.hop = q.hop_frames; R.channels = s.channels;
+        R.hops = (int32_t)zl_on_hops(q.num_frames, q.hop_frames);
+        R.hop_base = hop0;
+        R.threshold = q.threshold; R.min_gap = q.min_gap_hops; R.max_onsets = q.max_onsets;
+        R.out_base = out0;
+        o.last.emplace_back(hop0, R.hops);
+        hop0 += R.hops; out0 += q.max_onsets;
+    }
+    const bool prof = e->profiling;
+    for (int x = 0; prof && x < 3; ++x) if (!o.ev[x]) ZL_HIP(e, hipEventCreate(&o.ev[x]));
+    ZL_HIP(e, hipMemcpyAsync(dReq, hReq, (size_t)nreq * sizeof(ZlOnRequest), hipMemcpyHostToDevice, e->stream));
+    if (prof) ZL_HIP(e, hipEventRecord(o.ev[0], e->stream));
+    ZL_KERNEL(e, zl_launch_onset_energy(dReq, nreq, hops, dE, e->stream));
+    if (prof) ZL_HIP(e, hipEventRecord(o.ev[1], e->stream));
+    ZL_KERNEL(e, zl_launch_onset_pick(dReq, nreq, dE, dN, dPs, o.dCounts, o.dOut, e->stream));
+    if (prof) ZL_HIP(e, hipEventRecord(o.ev[2], e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    if (prof) { ZL_HIP(e, hipEventElapsedTime(&o.energyMs, o.ev[0], o.ev[1])); ZL_HIP(e, hipEventElapsedTime(&o.restMs, o.ev[1], o.ev[2])); }
+    size_t at = 0;
+    for (int32_t i = 0; i < nreq; ++i) {
+        const int32_t n = o.hCounts[i];
+        std::memcpy(out + at, o.hOut + hReq[i].out_base, (size_t)n * sizeof(zlhip_onset));
+        counts[i] = n;
+        at += (size_t)n;
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_onsets(zlhip_engine *e, const zlhip_onset_request *r, zlhip_onset *out, int32_t capacity, int32_t *count)
+{
+    if (capacity < 0) return ZLHIP_ERR_INVALID;
+    return zlhip_sound_onsets_batch(e, r, 1, out, (size_t)capacity, count);
+}
+
+int zlhip_debug_onset_hops(zlhip_engine *e, int32_t request, uint64_t *energy, int32_t *strength, int32_t capacity, int32_t *hops)
+{
+    if (!e || request < 0 || (size_t)request >= e->on.last.size()) return ZLHIP_ERR_INVALID;
+    const int32_t base = e->on.last[(size_t)request].first, n = e->on.last[(size_t)request].second;
+    if (hops) *hops = n;
+    if (!energy && !strength) return ZLHIP_OK;
+    if (capacity < n) return fail(e, ZLHIP_ERR_CAPACITY, "debug_onset_hops: capacity below the request's hops");
+    ZL_HIP(e, hipSetDevice(e->device));
+    if (energy) ZL_HIP(e, hipMemcpyAsync(energy, (const uint64_t *)e->scratch[ZB_ON_E].d + base, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    if (strength) ZL_HIP(e, hipMemcpyAsync(strength, (const int32_t *)e->scratch[ZB_ON_N].d + base, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    return engine_wait(e);
+}
+
+int zlhip_debug_onset_timings(zlhip_engine *e, float *energy_ms, float *rest_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (energy_ms) *energy_ms = e->on.energyMs;
+    if (rest_ms) *rest_ms = e->on.restMs;
     return ZLHIP_OK;
 }
 

@@ -937,6 +937,44 @@ int libzl_hotpath_clip_waveform(ClipAudioSource *c, float start_seconds, float e
     return zlhip_sound_overview(G.engine, c->engineClip, (int32_t)a, (int32_t)(b - a), columns, out);
 }
 
+// A sampler plays a loop from the keyboard slice by slice (sliceForMidiNote, getStartPosition(slice) .. getStopPosition(slice)), and the
+// only table setSlices can make is an even division, which cuts through the hits.  Here: the clip's transients, found on the device in
+// the data it plays now (zlhip_sound_onsets, defaults), become its slice table, as setSlicePositions would set it
+// (ClipAudioSource.cpp:535-543: `slices` becomes the table's length).  Build-defined: the reference has no transient detection.
+int libzl_hotpath_clip_slice_at_transients(ClipAudioSource *c, int max_slices)
+{
+    if (!c || max_slices < 1) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    if (!G.engine || c->engineClip < 0) return ZLHIP_ERR_STATE;
+    zlhip_sound_info info;
+    { const int rc = zlhip_sound_info_get(G.engine, c->engineClip, &info); if (rc != ZLHIP_OK) return rc; }
+    float startSec, lengthSec;
+    { std::lock_guard<std::mutex> sl(c->setMu); startSec = c->startPositionInSeconds; lengthSec = c->lengthInSeconds; }
+    // the region in frames, cast as SamplerSynthSound::startPosition / stopPosition do (SamplerSynthSound.cpp:96-104), cut to the data
+    auto frame = [&](float seconds) -> int64_t {
+        const double f = (double)seconds * info.sample_rate;
+        return !(f > 0.0) ? 0 : (f >= (double)info.length ? (int64_t)info.length : (int64_t)f);
+    };
+    const int64_t start = frame(startSec), stop = frame(startSec + lengthSec);
+    if (stop <= start) return ZLHIP_ERR_INVALID;
+    const int cap = std::min(max_slices, (int)ZLHIP_MAX_SLICES);
+    // with more transients than slices the strongest stay (the select rule of the request)
+    zlhip_onset_request q = { c->engineClip, (int32_t)start, (int32_t)(stop - start), 0, 0, 0, 0, cap };
+    if (zlhip_onset_resolve(info.sample_rate, &q) != ZLHIP_OK) return ZLHIP_ERR_INVALID;
+    std::vector<zlhip_onset> on((size_t)q.max_onsets);
+    int32_t n = 0;
+    { const int rc = zlhip_sound_onsets(G.engine, &q, on.data(), q.max_onsets, &n); if (rc != ZLHIP_OK) return rc; }
+    std::vector<double> table(1, 0.0);
+    const int64_t head = (int64_t)(q.min_gap_hops + 1) * q.hop_frames;         // an onset this near to the region's start is slice 0 itself
+    for (int32_t i = 0; i < n && (int)table.size() < cap; ++i)
+        if (on[(size_t)i].frame - start >= head) table.push_back((double)(on[(size_t)i].frame - start) / (double)(stop - start));
+    std::lock_guard<std::mutex> sl(c->setMu);
+    c->slicePositions = table;
+    c->slices = (int)table.size();
+    publish_params(c);
+    return c->slices;
+}
+
 void ClipAudioSource_setVolume(ClipAudioSource *c, float vol)      // ClipAudioSource.cpp:313-326
 {
     std::lock_guard<std::mutex> sl(c->setMu);

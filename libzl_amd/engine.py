@@ -109,6 +109,35 @@ def _overview_split(out, reqs, count):
     return res
 
 
+def _onset_requests(requests, length_of):
+    """(clip[, first_frame[, num_frames[, hop[, gate[, threshold[, min_gap[, max_onsets]]]]]]]) tuples -> the C request array and the
+    onsets `out` must hold; num_frames None / missing = to the end of the clip, every other field 0 / missing = its default"""
+    reqs = (_abi.OnsetRequest * max(1, len(requests)))()
+    capacity = 0
+    for i, r in enumerate(requests):
+        r = tuple(r) if isinstance(r, (tuple, list)) else (r,)
+        clip = int(r[0])
+        first = int(r[1]) if len(r) > 1 else 0
+        n = r[2] if len(r) > 2 else None
+        rest = [int(v) for v in r[3:8]] + [0] * (8 - max(3, len(r)))
+        reqs[i] = _abi.OnsetRequest(clip, first, int(length_of(clip) - first if n is None else n), *rest)
+        capacity += rest[4] if rest[4] > 0 else 128                # (zl_onset.h: the default of max_onsets)
+    return reqs, capacity
+
+
+def _onsets_call(fn, handle, requests, length_of):
+    """one zlhip_sound_onsets_batch-shaped call -> one int32 [count, 2] array (frame, strength) per request; (status, arrays)"""
+    reqs, capacity = _onset_requests(requests, length_of)
+    out = np.zeros((max(capacity, 1), 2), np.int32)
+    counts = np.zeros(max(1, len(requests)), np.int32)
+    rc = fn(handle, reqs, len(requests), out.ctypes.data, capacity, counts.ctypes.data)
+    res, at = [], 0
+    for i in range(len(requests)):
+        res.append(out[at:at + counts[i]])
+        at += int(counts[i])
+    return rc, res
+
+
 def _pcm_sources(sources):
     """(frames, fmt, channels, sample_rate) tuples -> (the C source array, the buffers it points into).  frames: a numpy array
     (uint8, int16, int32, float32, float64) or raw bytes (S24: three bytes per sample), interleaved; fmt: a ZLHIP_PCM_* value or None
@@ -330,6 +359,34 @@ class SamplerSynth:
         out = np.empty((total, 4), np.float32)
         self._ck(self._lib.zlhip_sound_overview_batch(self._e, reqs, len(requests), out.ctypes.data, out.size), "sound_overview_batch")
         return _overview_split(out, reqs, len(requests))
+
+    def clip_onsets(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, hop: int = 0, gate: int = 0, threshold: int = 0,
+                    min_gap: int = 0, max_onsets: int = 0) -> np.ndarray:
+        """The transients of the clip's current playback data over [first_frame, first_frame + num_frames) (None: to the end), found on
+        the device (zlhip_sound_onsets): int32 [count, 2] = (frame, strength) in ascending frame order.  A field
+        given as 0 takes its default (zlhip_onset_resolve).  Where a sampler slices a loop."""
+        return self.clip_onsets_batch([(clip, first_frame, num_frames, hop, gate, threshold, min_gap, max_onsets)])[0]
+
+    def clip_onsets_batch(self, requests: Sequence[tuple]):
+        """Several requests in one call (zlhip_sound_onsets_batch: two launches whatever the count).  requests: tuples
+        (clip[, first_frame[, num_frames[, hop[, gate[, threshold[, min_gap[, max_onsets]]]]]]]); one int32 [count, 2] array each."""
+        rc, res = _onsets_call(self._lib.zlhip_sound_onsets_batch, self._e, requests, self.clip_length)
+        self._ck(rc, "sound_onsets_batch")
+        return res
+
+    def onset_hops(self, request: int = 0):
+        """debug: (E uint64 [hops], N int32 [hops]) of request `request` of the last onsets call"""
+        n = C.c_int32(0)
+        self._ck(self._lib.zlhip_debug_onset_hops(self._e, request, None, None, 0, C.byref(n)), "debug_onset_hops")
+        E = np.zeros(n.value, np.uint64); N = np.zeros(n.value, np.int32)
+        self._ck(self._lib.zlhip_debug_onset_hops(self._e, request, E.ctypes.data, N.ctypes.data, n.value, C.byref(n)), "debug_onset_hops")
+        return E, N
+
+    def onset_timings(self):
+        """device ms of the energy pass and of the rest of the last onsets call made with profiling on (set_profiling)"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        self._ck(self._lib.zlhip_debug_onset_timings(self._e, C.byref(a), C.byref(b)), "debug_onset_timings")
+        return a.value, b.value
 
     def overview_timings(self) -> float:
         """device ms of the last overview call made with profiling on (set_profiling)"""
@@ -713,6 +770,16 @@ class SamplerSynthGroup:
         out = np.empty((total, 4), np.float32)
         self._ck(self._lib.zlhip_group_sound_overview_batch(self._g, reqs, len(requests), out.ctypes.data, out.size), "group_sound_overview_batch")
         return _overview_split(out, reqs, len(requests))
+
+    def clip_onsets(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, hop: int = 0, gate: int = 0, threshold: int = 0,
+                    min_gap: int = 0, max_onsets: int = 0) -> np.ndarray:
+        """SamplerSynth.clip_onsets: every member holds every clip, member 0 answers (zlhip_group_sound_onsets_batch)"""
+        return self.clip_onsets_batch([(clip, first_frame, num_frames, hop, gate, threshold, min_gap, max_onsets)])[0]
+
+    def clip_onsets_batch(self, requests: Sequence[tuple]):
+        rc, res = _onsets_call(self._lib.zlhip_group_sound_onsets_batch, self._g, requests, self.clip_length)
+        self._ck(rc, "group_sound_onsets_batch")
+        return res
 
     # -- commands (global buses, slots and midi channels) --------------------------------------
     def handle_clip_commands(self, cmds: Sequence[ClipCommand], current_tick: int = 0, want_voices: bool = False):
