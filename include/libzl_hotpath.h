@@ -186,6 +186,17 @@ int  libzl_hotpath_clip_waveform(ClipAudioSource *c, float start_seconds, float 
  * length, as setSlicePositions does (ClipAudioSource.cpp:535-543), and the table is published like ClipAudioSource_setSlices.
  * Returns the number of slices, or a negative zlhip status that leaves the clip as it was. */
 int  libzl_hotpath_clip_slice_at_transients(ClipAudioSource *c, int max_slices);
+/* The clip's tempo (build-defined: the reference has no tempo estimate; setLength(beat, bpm) and setSpeedRatio take one the caller
+ * must know).  Estimated on the device (zlhip_sound_tempo, hop_frames at its default) over the clip's current playback data between its
+ * start and its start + length, in frames as for libzl_hotpath_clip_slice_at_transients.  bpm_min / bpm_max of 0 take 75 / 150.
+ * *bpm = 0 (and *confidence = 0) means "no tempo": silence, or a region too short for the range; that is not an error.  Returns 0 or a
+ * negative zlhip status (nothing is written then). */
+int  libzl_hotpath_clip_tempo(ClipAudioSource *c, float bpm_min, float bpm_max, float *bpm, float *confidence);
+/* Fit the clip to target_bpm: detects as libzl_hotpath_clip_tempo(c, 0, 0, ...) over the data the clip plays now and sets the speed
+ * ratio (float)(target_bpm * current speed ratio / detected) through ClipAudioSource_setSpeedRatio's path (its clamp to [0.25, 4]
+ * stays; a re-render starts from the original upload, hence the current ratio in the product).  *ratio_out: the ratio now in effect.
+ * Returns 1, or 0 where there is no tempo or the confidence is below min_confidence (nothing changes then), or a negative status. */
+int  libzl_hotpath_clip_match_tempo(ClipAudioSource *c, float target_bpm, float min_confidence, float *ratio_out);
 /* A bank of clips in one engine call: every file is read, their `data` chunks go to the engine as raw PCM in ONE
  * zlhip_sound_upload_pcm_batch call (decoded on the device, one wait for the whole bank).  out[i] is the clip of paths[i], or NULL
  * for a file that cannot be opened or decoded -- it does not fail the others.  Returns the number of clips loaded (or a negative

@@ -39,7 +39,7 @@ extern "C" {
  *    Later additions, still 3 (new entry points only): the engine group (zlhip_group_*), zlhip_sound_overview / _batch (waveform overviews),
  *    zlhip_sound_upload_pcm / _batch (clips from raw PCM, decoded on the device), zlhip_sound_convert_rate / _batch (clips converted to
  *    another sample rate on the device, band-limited), zlhip_resample_design, zlhip_sound_info_get, zlhip_debug_sound_extent, zlhip_sound_onsets / _batch (a clip's transients, found on
- *    the device), zlhip_onset_resolve. */
+ *    the device), zlhip_onset_resolve, zlhip_sound_tempo / _batch (a clip's tempo, estimated on the device), zlhip_tempo_resolve. */
 #define ZLHIP_ABI_VERSION 3
 
 /* status codes */
@@ -271,6 +271,41 @@ int zlhip_sound_onsets_batch(zlhip_engine *e, const zlhip_onset_request *reqs, i
 int zlhip_debug_onset_hops(zlhip_engine *e, int32_t request, uint64_t *energy, int32_t *strength, int32_t capacity, int32_t *hops);
 /* measurement: device time of the energy pass and of the rest of the last call made with profiling on */
 int zlhip_debug_onset_timings(zlhip_engine *e, float *energy_ms, float *rest_ms);
+/* Tempo: how fast a loop is (a build-defined extension, the reference has no tempo estimate) -- estimated on the
+ * device in the sound's CURRENT playback data.  The samples are read once, by the transients' energy pass; everything behind it is
+ * integer arithmetic, so the result does not depend on any order of evaluation:
+ *   E[h] as for zlhip_sound_onsets; R[h] = floor(sqrt(E[h])), R[-1] = 0; s = max(0, bitlength(max R) - 16);
+ *   W[h] = max(0, R[h] - R[h-1]) >> s; sum = the sum of W.  l_min = max(1, ceil(60 rate / (hop_frames bpm_max))),
+ *   l_max = floor(60 rate / (hop_frames bpm_min)), cap = (hops - 1) / 2, l_max = min(l_max, cap).
+ *   A[l] = the sum over h >= l of W[h] W[h-l], for l = 0 and l in [max(1, l_min - 1), min(8 l_max + 8, cap + 1)].
+ *   Lag a beats lag b iff A[a] (hops - b) > A[b] (hops - a); equal goes to the smaller lag.  lag_coarse = the best lag in
+ *   [l_min, l_max]; then, with m = lag_coarse and doublings = 0: while doublings < 3 and 2m + 1 <= cap, m = the best of
+ *   {2m-1, 2m, 2m+1} and doublings += 1; lag_fine = m, acf_lo / mid / hi = A[m-1], A[m], A[m+1], acf_zero = A[0].
+ *   The host derives, in double: y_d = A[m+d] / (hops - m - d); den = (y- - 2 y0) + y+; delta = (y- - y+) / (2 den) if den < 0 else 0,
+ *   clamped to +-0.5; period = (m + delta) / 2^doublings; bpm = 60 rate / (hop_frames period); mu = sum / hops;
+ *   confidence = (y0 - mu^2) / (A[0] / hops - mu^2), 0 where that denominator is not positive.
+ *   No tempo -- l_min > l_max (the frames are too few for the range) or A[0] == 0 (silence) -- is not an error: every field is 0
+ *   except hops, shift, sum and acf_zero.
+ *   A field given as 0 takes its default (zlhip_tempo_resolve with the sound's sample rate): hop_frames as for the transients,
+ *   bpm_min = 75, bpm_max = 150 (one octave makes the answer unambiguous).
+ *   Limits: hop_frames a multiple of 16 in [64, 4096]; bpm_min and bpm_max finite, 20 <= bpm_min < bpm_max <= 400; l_max <= 1024
+ *   before the cut to cap; num_frames >= 1, first_frame >= 0, first_frame + num_frames <= the sound's length; at most 65536 hops per
+ *   request and 4194304 per call; nreq >= 0: anything else is ZLHIP_ERR_INVALID.  On any error out is not written; one bad request
+ *   fails the call.
+ *   A call is four kernel launches whatever its size, behind one copy of the request records; it waits once and 72 bytes per request
+ *   come back.  It runs on the engine's stream behind what is queued there and the resident real-time kernel keeps running. */
+typedef struct zlhip_tempo_request { int32_t id, first_frame, num_frames, hop_frames; float bpm_min, bpm_max; } zlhip_tempo_request;
+typedef struct zlhip_tempo { float bpm, confidence; int32_t lag_coarse, lag_fine, doublings, shift, hops, reserved;
+                             uint64_t acf_lo, acf_mid, acf_hi, acf_zero, sum; } zlhip_tempo;
+/* host only: fills the fields given as 0 and checks every limit that does not need the sound; a refused request is left as it was */
+int zlhip_tempo_resolve(double sample_rate, zlhip_tempo_request *r);
+int zlhip_sound_tempo(zlhip_engine *e, const zlhip_tempo_request *r, zlhip_tempo *out);
+int zlhip_sound_tempo_batch(zlhip_engine *e, const zlhip_tempo_request *reqs, int32_t nreq, zlhip_tempo *out);
+/* W and A of request `request` of the last call: flux [hops], acf [lags] = A[first_lag ...] (either may be NULL; both NULL asks for
+ * *hops, *first_lag and *lags only; capacity: the elements each array given holds).  A[0] is the record's acf_zero. */
+int zlhip_debug_tempo_acf(zlhip_engine *e, int32_t request, uint16_t *flux, uint64_t *acf, int32_t capacity, int32_t *hops, int32_t *first_lag, int32_t *lags);
+/* measurement: device time of the energy pass, of the autocorrelation kernel and of the rest of the last call made with profiling on */
+int zlhip_debug_tempo_timings(zlhip_engine *e, float *energy_ms, float *acf_ms, float *rest_ms);
 /* Clips from raw PCM.  `frames` is host memory, pageable or page-locked: `length` frames of `channels`
  *   interleaved little-endian samples, exactly the bytes of a WAV `data` chunk.  They are copied raw into a device staging buffer and
  *   decoded there into the arena's layout; one decode launch serves each staging pass and the call waits for the device once.
@@ -494,6 +529,8 @@ int  zlhip_group_sound_overview(zlhip_group *g, int32_t id, int32_t first_frame,
 int  zlhip_group_sound_overview_batch(zlhip_group *g, const zlhip_overview_request *reqs, int32_t count, float *out, size_t out_floats);
 /* zlhip_sound_onsets_batch: member 0 answers */
 int  zlhip_group_sound_onsets_batch(zlhip_group *g, const zlhip_onset_request *reqs, int32_t nreq, zlhip_onset *out, size_t capacity, int32_t *counts);
+/* zlhip_sound_tempo_batch: member 0 answers */
+int  zlhip_group_sound_tempo_batch(zlhip_group *g, const zlhip_tempo_request *reqs, int32_t nreq, zlhip_tempo *out);
 /* zlhip_handle_commands_voices over the whole synth (taken, voices optional) */
 int  zlhip_group_handle_commands(zlhip_group *g, const zlhip_clip_command *cmds, int32_t count, uint64_t current_tick, int32_t *taken,
                                  int32_t *voices);

@@ -118,6 +118,17 @@ class Onset(C.Structure):
     _fields_ = [("frame", C.c_int32), ("strength", C.c_int32)]
 
 
+class TempoRequest(C.Structure):
+    _fields_ = [("id", C.c_int32), ("first_frame", C.c_int32), ("num_frames", C.c_int32), ("hop_frames", C.c_int32), ("bpm_min", C.c_float),
+                ("bpm_max", C.c_float)]
+
+
+class Tempo(C.Structure):
+    _fields_ = [("bpm", C.c_float), ("confidence", C.c_float), ("lag_coarse", C.c_int32), ("lag_fine", C.c_int32), ("doublings", C.c_int32),
+                ("shift", C.c_int32), ("hops", C.c_int32), ("reserved", C.c_int32), ("acf_lo", C.c_uint64), ("acf_mid", C.c_uint64),
+                ("acf_hi", C.c_uint64), ("acf_zero", C.c_uint64), ("sum", C.c_uint64)]
+
+
 PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = 1, 2, 3, 4, 5, 6
 PCM_MAX_CHANNELS = 64
 PCM_BYTES = {PCM_U8: 1, PCM_S16: 2, PCM_S24: 3, PCM_S32: 4, PCM_F32: 4, PCM_F64: 8}
@@ -175,6 +186,11 @@ SIGNATURES = {
     "zlhip_sound_onsets_batch": (C.c_int, [_E, C.POINTER(OnsetRequest), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "zlhip_debug_onset_hops": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_debug_onset_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "zlhip_tempo_resolve": (C.c_int, [C.c_double, C.POINTER(TempoRequest)]),
+    "zlhip_sound_tempo": (C.c_int, [_E, C.POINTER(TempoRequest), C.POINTER(Tempo)]),
+    "zlhip_sound_tempo_batch": (C.c_int, [_E, C.POINTER(TempoRequest), C.c_int32, C.POINTER(Tempo)]),
+    "zlhip_debug_tempo_acf": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "zlhip_debug_tempo_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "zlhip_sound_upload_pcm": (C.c_int, [_E, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_int32)]),
     "zlhip_sound_upload_pcm_batch": (C.c_int, [_E, C.POINTER(PcmSource), C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_debug_upload_pcm_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -239,6 +255,7 @@ SIGNATURES = {
     "zlhip_group_sound_overview": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "zlhip_group_sound_overview_batch": (C.c_int, [_E, C.POINTER(OverviewRequest), C.c_int32, C.c_void_p, C.c_size_t]),
     "zlhip_group_sound_onsets_batch": (C.c_int, [_E, C.POINTER(OnsetRequest), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "zlhip_group_sound_tempo_batch": (C.c_int, [_E, C.POINTER(TempoRequest), C.c_int32, C.POINTER(Tempo)]),
     "zlhip_group_handle_commands": (C.c_int, [_E, C.POINTER(ClipCommand), C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "zlhip_group_start_voice": (C.c_int, [_E, C.c_int32, C.c_int32, C.POINTER(ClipCommand), C.c_uint64]),
     "zlhip_group_stop_voice": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_int]),

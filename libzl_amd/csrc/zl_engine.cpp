@@ -29,6 +29,7 @@
 #include "zl_pair.h"
 #include "zl_plan.h"
 #include "zl_onset.h"
+#include "zl_tempo.h"
 #include "zl_overview.h"
 #include "zl_resample.h"
 #include "zl_decode.h"
@@ -70,6 +71,7 @@ enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a ca
        ZB_PCM_STAGE, ZB_PCM_PIECES, ZB_PCM_PUB, ZB_PCM_VERDICTS,   // PCM: the staging buffer for the raw bytes, a call's piece and publish records, its verdict words
        ZB_RS_JOBS, ZB_RS_PUB, ZB_RS_VERDICTS,                // rate conversion: a call's job and publish records, its verdict words
        ZB_ON_REQ, ZB_ON_E, ZB_ON_N, ZB_ON_PS,                // transients: a call's request records (with a host twin), and per hop E, N and the windows' running maxima
+       ZB_TP_REQ, ZB_TP_E, ZB_TP_W, ZB_TP_A, ZB_TP_STAT,      // tempo: a call's request records (the energy pass's and the tempo kernels', one host twin), per hop E and W, per lag A, per request the flux's statistics
        ZB_COUNT };
 
 }  // namespace
@@ -110,6 +112,13 @@ struct zlhip_engine {
         std::vector<std::pair<int32_t, int32_t>> last;                          // per request of the last call: its first hop, its hops (zlhip_debug_onset_hops)
         hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; float energyMs = 0.0f, restMs = 0.0f;   // profiling (zlhip_debug_onset_timings)
     } on;
+    // tempo (zlhip_sound_tempo; zl_tempo.h)
+    struct Tempo {
+        ZlTpResult *hOut = nullptr, *dOut = nullptr; size_t outCap = 0;         // a call's integer records, in host memory mapped into the device
+        struct Last { int32_t hop_base, hops, acf_base, first_lag, nlags; };
+        std::vector<Last> last;                                                 // per request of the last call (zlhip_debug_tempo_acf)
+        hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; float energyMs = 0.0f, acfMs = 0.0f, restMs = 0.0f;   // profiling (zlhip_debug_tempo_timings)
+    } tp;
     // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h)
     struct Pcm {
         std::vector<hipEvent_t> ev;                                 // profiling: before every pass's copies and every decode launch, behind the last
@@ -464,6 +473,8 @@ void zlhip_engine_destroy(zlhip_engine *e)
     for (hipEvent_t ev : e->on.ev) if (ev) (void)hipEventDestroy(ev);
     if (e->on.hCounts) (void)hipHostFree(e->on.hCounts);
     if (e->on.hOut) (void)hipHostFree(e->on.hOut);
+    for (hipEvent_t ev : e->tp.ev) if (ev) (void)hipEventDestroy(ev);
+    if (e->tp.hOut) (void)hipHostFree(e->tp.hOut);
     for (hipEvent_t ev : e->pcm.ev) if (ev) (void)hipEventDestroy(ev);
     if (e->evJoin) (void)hipEventDestroy(e->evJoin);
     if (e->evPlanTail) (void)hipEventDestroy(e->evPlanTail);
@@ -1623,6 +1634,143 @@ int zlhip_debug_onset_timings(zlhip_engine *e, float *energy_ms, float *rest_ms)
     if (!e) return ZLHIP_ERR_INVALID;
     if (energy_ms) *energy_ms = e->on.energyMs;
     if (rest_ms) *rest_ms = e->on.restMs;
+    return ZLHIP_OK;
+}
+
+// ---- tempo (zl_tempo.h, zl_tempo.hip) --------------------------------------------------------------------------------------
+// How fast a loop is.  The samples are read once, by the transients' energy kernel; the flux, the autocorrelation and the pick are
+// integer arithmetic on one word per hop.  Synchronisation and buffers as for the transients: the call runs on the engine's stream
+// behind what is queued there and leaves the resident real-time kernel alone; its buffers are allocated by the first call and grow
+// only.  The integer records are written by the pick kernel into host memory mapped into the device; bpm and confidence are derived
+// here (zl_tp_finish).
+int zlhip_tempo_resolve(double sample_rate, zlhip_tempo_request *r)
+{
+    if (!r || r->first_frame < 0 || r->num_frames < 1) return ZLHIP_ERR_INVALID;
+    zlhip_tempo_request q = *r;
+    if (zl_tp_resolve(sample_rate, &q.hop_frames, &q.bpm_min, &q.bpm_max) != 0) return ZLHIP_ERR_INVALID;
+    if (zl_on_hops(q.num_frames, q.hop_frames) > ZL_TP_MAX_HOPS) return ZLHIP_ERR_INVALID;
+    *r = q;
+    return ZLHIP_OK;
+}
+
+static const size_t kTpRecordBytes = sizeof(ZlOnRequest) + sizeof(ZlTpRequest);     // per request: the energy pass's record and the tempo kernels'
+
+static int tp_reserve(zlhip_engine *e, size_t nreq, size_t hops, size_t lags)
+{
+    GrowBuf *b = e->scratch; zlhip_engine::Tempo &t = e->tp;
+    if (nreq <= b[ZB_TP_REQ].cap && hops <= b[ZB_TP_E].cap && hops <= b[ZB_TP_W].cap && lags <= b[ZB_TP_A].cap && nreq <= b[ZB_TP_STAT].cap && nreq <= t.outCap)
+        return ZLHIP_OK;
+    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }
+    ZlQuiesce quiet(e);
+    const char *what = "sound_tempo: no memory for the call's buffers";
+    const size_t hcap = std::min<size_t>(std::max<size_t>(hops * 2, 4096), ZL_TP_MAX_CALL_HOPS);
+    const size_t rcap = std::max<size_t>(nreq * 2, 64);
+    int rc = grow_buf(e, b[ZB_TP_REQ], nreq, kTpRecordBytes, rcap, true, what);
+    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_TP_E], hops, sizeof(uint64_t), hcap, false, what);
+    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_TP_W], hops, sizeof(uint16_t), hcap, false, what);
+    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_TP_A], lags, sizeof(uint64_t), std::max<size_t>(lags * 2, 4096), false, what);
+    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_TP_STAT], nreq, sizeof(ZlTpStat), rcap, false, what);
+    if (rc != ZLHIP_OK) return rc;
+    ZL_HIP(e, grow_mapped(&t.hOut, &t.dOut, &t.outCap, std::max<size_t>(nreq, 32)));
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_tempo_batch(zlhip_engine *e, const zlhip_tempo_request *reqs, int32_t nreq, zlhip_tempo *out)
+{
+    static_assert(sizeof(zlhip_tempo) == sizeof(ZlTpResult), "the device writes zlhip_tempo's layout");
+    if (!e || nreq < 0 || (nreq > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
+    if (nreq == 0) return ZLHIP_OK;
+    // validate and resolve everything before anything is written and before the first HIP call
+    std::vector<zlhip_tempo_request> res((size_t)nreq);
+    std::vector<ZlTpRequest> geo((size_t)nreq);
+    int64_t hops = 0, lags = 0, items = 0;
+    for (int32_t i = 0; i < nreq; ++i) {
+        zlhip_tempo_request &q = res[(size_t)i];
+        q = reqs[i];
+        if (q.id < 0 || q.id >= e->cfg.max_sounds || !e->hc.soundUsed[q.id]) return fail(e, ZLHIP_ERR_INVALID, "sound_tempo: no such sound");
+        const ZlSound &s = e->hc.sounds[q.id];
+        if (zlhip_tempo_resolve(s.sample_rate, &q) != ZLHIP_OK) return fail(e, ZLHIP_ERR_INVALID, "sound_tempo: a field of the request is outside its limits");
+        if ((int64_t)q.first_frame + q.num_frames > s.length) return fail(e, ZLHIP_ERR_INVALID, "sound_tempo: the frames do not lie inside the sound's playback data");
+        ZlTpRequest &T = geo[(size_t)i];
+        double lmin, lmax;
+        zl_tp_lags(s.sample_rate, q.hop_frames, q.bpm_min, q.bpm_max, &lmin, &lmax);
+        zl_tp_geometry(&T, (int32_t)zl_on_hops(q.num_frames, q.hop_frames), lmin, lmax);
+        T.hop_base = (int32_t)hops; T.acf_base = (int32_t)lags; T.item_base = (int32_t)items;
+        hops += T.hops; lags += T.nlags; items += zl_tp_items(T);
+        if (hops > ZL_TP_MAX_CALL_HOPS) return fail(e, ZLHIP_ERR_INVALID, "sound_tempo_batch: more than 4194304 hops in one call");
+    }
+    ZL_HIP(e, hipSetDevice(e->device));
+    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    { const int rc = tp_reserve(e, (size_t)nreq, (size_t)hops, (size_t)lags); if (rc != ZLHIP_OK) return rc; }
+    zlhip_engine::Tempo &t = e->tp;
+    char *const hRec = (char *)e->scratch[ZB_TP_REQ].h, *const dRec = (char *)e->scratch[ZB_TP_REQ].d;
+    ZlOnRequest *const hOn = (ZlOnRequest *)hRec, *const dOn = (ZlOnRequest *)dRec;
+    ZlTpRequest *const hTp = (ZlTpRequest *)(hRec + (size_t)nreq * sizeof(ZlOnRequest)), *const dTp = (ZlTpRequest *)(dRec + (size_t)nreq * sizeof(ZlOnRequest));
+    uint64_t *const dE = (uint64_t *)e->scratch[ZB_TP_E].d; uint16_t *const dW = (uint16_t *)e->scratch[ZB_TP_W].d;
+    uint64_t *const dA = (uint64_t *)e->scratch[ZB_TP_A].d; ZlTpStat *const dStat = (ZlTpStat *)e->scratch[ZB_TP_STAT].d;
+    t.last.clear();
+    for (int32_t i = 0; i < nreq; ++i) {
+        const zlhip_tempo_request &q = res[(size_t)i];
+        const ZlSound &s = e->hc.sounds[q.id];
+        const ZlTpRequest &T = geo[(size_t)i];
+        ZlOnRequest &R = hOn[i];
+        std::memset(&R, 0, sizeof(R));
+        R.src = (uint64_t)(uintptr_t)arena_ptr(e, s.offset);
+        R.first = q.first_frame; R.frames = q.num_frames; R.hop = q.hop_frames; R.channels = s.channels;
+        R.hops = T.hops; R.hop_base = T.hop_base;
+        hTp[i] = T;
+        t.last.push_back({T.hop_base, T.hops, T.acf_base, T.first_lag, T.nlags});
+    }
+    const bool prof = e->profiling;
+    for (int x = 0; prof && x < 5; ++x) if (!t.ev[x]) ZL_HIP(e, hipEventCreate(&t.ev[x]));
+    ZL_HIP(e, hipMemcpyAsync(dRec, hRec, (size_t)nreq * kTpRecordBytes, hipMemcpyHostToDevice, e->stream));
+    if (prof) ZL_HIP(e, hipEventRecord(t.ev[0], e->stream));
+    ZL_KERNEL(e, zl_launch_onset_energy(dOn, nreq, hops, dE, e->stream));
+    if (prof) ZL_HIP(e, hipEventRecord(t.ev[1], e->stream));
+    ZL_KERNEL(e, zl_launch_tempo_flux(dTp, nreq, dE, dW, dA, dStat, e->stream));
+    if (prof) ZL_HIP(e, hipEventRecord(t.ev[2], e->stream));
+    ZL_KERNEL(e, zl_launch_tempo_acf(dTp, nreq, items, dW, dA, e->stream));
+    if (prof) ZL_HIP(e, hipEventRecord(t.ev[3], e->stream));
+    ZL_KERNEL(e, zl_launch_tempo_pick(dTp, nreq, dA, dStat, t.dOut, e->stream));
+    if (prof) ZL_HIP(e, hipEventRecord(t.ev[4], e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    if (prof) {
+        float flux = 0.0f, pick = 0.0f;
+        ZL_HIP(e, hipEventElapsedTime(&t.energyMs, t.ev[0], t.ev[1])); ZL_HIP(e, hipEventElapsedTime(&flux, t.ev[1], t.ev[2]));
+        ZL_HIP(e, hipEventElapsedTime(&t.acfMs, t.ev[2], t.ev[3])); ZL_HIP(e, hipEventElapsedTime(&pick, t.ev[3], t.ev[4]));
+        t.restMs = flux + pick;
+    }
+    for (int32_t i = 0; i < nreq; ++i) {
+        ZlTpResult r = t.hOut[i];
+        zl_tp_finish(e->hc.sounds[res[(size_t)i].id].sample_rate, res[(size_t)i].hop_frames, &r);
+        std::memcpy(&out[i], &r, sizeof(r));
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_tempo(zlhip_engine *e, const zlhip_tempo_request *r, zlhip_tempo *out) { return zlhip_sound_tempo_batch(e, r, 1, out); }
+
+int zlhip_debug_tempo_acf(zlhip_engine *e, int32_t request, uint16_t *flux, uint64_t *acf, int32_t capacity, int32_t *hops, int32_t *first_lag, int32_t *lags)
+{
+    if (!e || request < 0 || (size_t)request >= e->tp.last.size()) return ZLHIP_ERR_INVALID;
+    const zlhip_engine::Tempo::Last &l = e->tp.last[(size_t)request];
+    if (hops) *hops = l.hops;
+    if (first_lag) *first_lag = l.first_lag;
+    if (lags) *lags = l.nlags;
+    if (!flux && !acf) return ZLHIP_OK;
+    if ((flux && capacity < l.hops) || (acf && capacity < l.nlags)) return fail(e, ZLHIP_ERR_CAPACITY, "debug_tempo_acf: capacity below the request's hops or lags");
+    ZL_HIP(e, hipSetDevice(e->device));
+    if (flux) ZL_HIP(e, hipMemcpyAsync(flux, (const uint16_t *)e->scratch[ZB_TP_W].d + l.hop_base, (size_t)l.hops * sizeof(uint16_t), hipMemcpyDeviceToHost, e->stream));
+    if (acf && l.nlags > 0) ZL_HIP(e, hipMemcpyAsync(acf, (const uint64_t *)e->scratch[ZB_TP_A].d + l.acf_base, (size_t)l.nlags * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    return engine_wait(e);
+}
+
+int zlhip_debug_tempo_timings(zlhip_engine *e, float *energy_ms, float *acf_ms, float *rest_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (energy_ms) *energy_ms = e->tp.energyMs;
+    if (acf_ms) *acf_ms = e->tp.acfMs;
+    if (rest_ms) *rest_ms = e->tp.restMs;
     return ZLHIP_OK;
 }
 

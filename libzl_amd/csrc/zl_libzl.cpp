@@ -892,11 +892,16 @@ static void clip_rerender(ClipAudioSource *c)                      // call with 
         std::fprintf(stderr, "libzl hot path: cannot re-render %s: %s (%s)\n", c->filePath.c_str(), zlhip_strerror(rc), zlhip_last_error(G.engine));
 }
 
+static void clip_set_speed_ratio(ClipAudioSource *c, float v)      // call with G.mu held
+{
+    { std::lock_guard<std::mutex> sl(c->setMu); c->speedRatio = std::min(std::max(ZL_ST_SPEED_MIN, v), ZL_ST_SPEED_MAX); }
+    clip_rerender(c);
+}
+
 void ClipAudioSource_setSpeedRatio(ClipAudioSource *c, float v)    // :292-303
 {
     std::lock_guard<std::mutex> lk(G.mu);
-    { std::lock_guard<std::mutex> sl(c->setMu); c->speedRatio = std::min(std::max(ZL_ST_SPEED_MIN, v), ZL_ST_SPEED_MAX); }
-    clip_rerender(c);
+    clip_set_speed_ratio(c, v);
 }
 
 void ClipAudioSource_setPitch(ClipAudioSource *c, float v)         // :279-290
@@ -973,6 +978,55 @@ int libzl_hotpath_clip_slice_at_transients(ClipAudioSource *c, int max_slices)
     c->slices = (int)table.size();
     publish_params(c);
     return c->slices;
+}
+
+// A sampler must know how fast a loop is before it can fit it to the session: setLength(beat, bpm) and setSpeedRatio both take a
+// tempo the caller already knows.  Here: the tempo of the data the clip plays now between its start and its start + length, estimated
+// on the device (zlhip_sound_tempo).  Build-defined: the reference has no tempo estimate.
+static int clip_tempo(ClipAudioSource *c, float bpm_min, float bpm_max, zlhip_tempo *t)      // call with G.mu held
+{
+    if (!G.engine || c->engineClip < 0) return ZLHIP_ERR_STATE;
+    zlhip_sound_info info;
+    { const int rc = zlhip_sound_info_get(G.engine, c->engineClip, &info); if (rc != ZLHIP_OK) return rc; }
+    float startSec, lengthSec;
+    { std::lock_guard<std::mutex> sl(c->setMu); startSec = c->startPositionInSeconds; lengthSec = c->lengthInSeconds; }
+    // the region in frames, cast as SamplerSynthSound::startPosition / stopPosition do (SamplerSynthSound.cpp:96-104), cut to the data
+    auto frame = [&](float seconds) -> int64_t {
+        const double f = (double)seconds * info.sample_rate;
+        return !(f > 0.0) ? 0 : (f >= (double)info.length ? (int64_t)info.length : (int64_t)f);
+    };
+    const int64_t start = frame(startSec), stop = frame(startSec + lengthSec);
+    if (stop <= start) return ZLHIP_ERR_INVALID;
+    const zlhip_tempo_request q = { c->engineClip, (int32_t)start, (int32_t)(stop - start), 0, bpm_min, bpm_max };
+    return zlhip_sound_tempo(G.engine, &q, t);
+}
+
+int libzl_hotpath_clip_tempo(ClipAudioSource *c, float bpm_min, float bpm_max, float *bpm, float *confidence)
+{
+    if (!c) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    zlhip_tempo t;
+    { const int rc = clip_tempo(c, bpm_min, bpm_max, &t); if (rc != ZLHIP_OK) return rc; }
+    if (bpm) *bpm = t.bpm;
+    if (confidence) *confidence = t.confidence;
+    return ZLHIP_OK;
+}
+
+// Fit the clip to the session's tempo: detect over the data it plays now, then re-render at the speed ratio that brings the detected
+// tempo to the target.  A re-render starts from the original upload, so the new ratio is target * current ratio / detected.
+int libzl_hotpath_clip_match_tempo(ClipAudioSource *c, float target_bpm, float min_confidence, float *ratio_out)
+{
+    if (!c || !(target_bpm > 0.0f) || !(target_bpm <= FLT_MAX)) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    zlhip_tempo t;
+    { const int rc = clip_tempo(c, 0.0f, 0.0f, &t); if (rc != ZLHIP_OK) return rc; }
+    if (!(t.bpm > 0.0f) || !(t.confidence >= min_confidence)) return 0;
+    float current;
+    { std::lock_guard<std::mutex> sl(c->setMu); current = c->speedRatio; }
+    const float ratio = (float)((double)target_bpm * (double)current / (double)t.bpm);
+    clip_set_speed_ratio(c, ratio);
+    if (ratio_out) { std::lock_guard<std::mutex> sl(c->setMu); *ratio_out = c->speedRatio; }
+    return 1;
 }
 
 void ClipAudioSource_setVolume(ClipAudioSource *c, float vol)      // ClipAudioSource.cpp:313-326

@@ -138,6 +138,26 @@ def _onsets_call(fn, handle, requests, length_of):
     return rc, res
 
 
+TEMPO_FIELDS = tuple(name for name, _ in _abi.Tempo._fields_ if name != "reserved")
+
+
+def _tempo_call(fn, handle, requests, length_of):
+    """one zlhip_sound_tempo_batch-shaped call over (clip[, first_frame[, num_frames[, hop[, bpm_min[, bpm_max]]]]]) tuples (num_frames
+    None / missing = to the end of the clip, every other field 0 / missing = its default) -> (status, one dict of zlhip_tempo's fields
+    per request)"""
+    reqs = (_abi.TempoRequest * max(1, len(requests)))()
+    for i, r in enumerate(requests):
+        r = tuple(r) if isinstance(r, (tuple, list)) else (r,)
+        clip = int(r[0])
+        first = int(r[1]) if len(r) > 1 else 0
+        n = r[2] if len(r) > 2 else None
+        reqs[i] = _abi.TempoRequest(clip, first, int(length_of(clip) - first if n is None else n), int(r[3]) if len(r) > 3 else 0,
+                                    float(r[4]) if len(r) > 4 else 0.0, float(r[5]) if len(r) > 5 else 0.0)
+    out = (_abi.Tempo * max(1, len(requests)))()
+    rc = fn(handle, reqs, len(requests), out)
+    return rc, [{k: getattr(out[i], k) for k in TEMPO_FIELDS} for i in range(len(requests))]
+
+
 def _pcm_sources(sources):
     """(frames, fmt, channels, sample_rate) tuples -> (the C source array, the buffers it points into).  frames: a numpy array
     (uint8, int16, int32, float32, float64) or raw bytes (S24: three bytes per sample), interleaved; fmt: a ZLHIP_PCM_* value or None
@@ -387,6 +407,34 @@ class SamplerSynth:
         a, b = C.c_float(0.0), C.c_float(0.0)
         self._ck(self._lib.zlhip_debug_onset_timings(self._e, C.byref(a), C.byref(b)), "debug_onset_timings")
         return a.value, b.value
+
+    def clip_tempo(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, hop: int = 0, bpm_min: float = 0.0, bpm_max: float = 0.0) -> dict:
+        """The tempo of the clip's current playback data over [first_frame, first_frame + num_frames) (None: to the end), estimated on
+        the device (zlhip_sound_tempo): a dict of zlhip_tempo's fields -- bpm, confidence and the integers they
+        derive from.  bpm == 0 means "no tempo" (silence, or too short for the range).  A field given as 0 takes its default
+        (zlhip_tempo_resolve: 75 to 150 bpm)."""
+        return self.clip_tempo_batch([(clip, first_frame, num_frames, hop, bpm_min, bpm_max)])[0]
+
+    def clip_tempo_batch(self, requests: Sequence[tuple]):
+        """Several requests in one call (zlhip_sound_tempo_batch: four launches whatever the count).  requests: tuples
+        (clip[, first_frame[, num_frames[, hop[, bpm_min[, bpm_max]]]]]); one dict each."""
+        rc, res = _tempo_call(self._lib.zlhip_sound_tempo_batch, self._e, requests, self.clip_length)
+        self._ck(rc, "sound_tempo_batch")
+        return res
+
+    def tempo_acf(self, request: int = 0):
+        """debug: (W uint16 [hops], first_lag, A uint64 [lags] from first_lag on) of request `request` of the last tempo call"""
+        n, f, l = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._ck(self._lib.zlhip_debug_tempo_acf(self._e, request, None, None, 0, C.byref(n), C.byref(f), C.byref(l)), "debug_tempo_acf")
+        W = np.zeros(n.value, np.uint16); A = np.zeros(l.value, np.uint64)
+        self._ck(self._lib.zlhip_debug_tempo_acf(self._e, request, W.ctypes.data, A.ctypes.data, max(n.value, l.value), C.byref(n), C.byref(f), C.byref(l)), "debug_tempo_acf")
+        return W, f.value, A
+
+    def tempo_timings(self):
+        """device ms of the energy pass, the autocorrelation kernel and the rest of the last tempo call made with profiling on"""
+        a, b, c = C.c_float(0.0), C.c_float(0.0), C.c_float(0.0)
+        self._ck(self._lib.zlhip_debug_tempo_timings(self._e, C.byref(a), C.byref(b), C.byref(c)), "debug_tempo_timings")
+        return a.value, b.value, c.value
 
     def overview_timings(self) -> float:
         """device ms of the last overview call made with profiling on (set_profiling)"""
@@ -779,6 +827,15 @@ class SamplerSynthGroup:
     def clip_onsets_batch(self, requests: Sequence[tuple]):
         rc, res = _onsets_call(self._lib.zlhip_group_sound_onsets_batch, self._g, requests, self.clip_length)
         self._ck(rc, "group_sound_onsets_batch")
+        return res
+
+    def clip_tempo(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, hop: int = 0, bpm_min: float = 0.0, bpm_max: float = 0.0) -> dict:
+        """SamplerSynth.clip_tempo: every member holds every clip, member 0 answers (zlhip_group_sound_tempo_batch)"""
+        return self.clip_tempo_batch([(clip, first_frame, num_frames, hop, bpm_min, bpm_max)])[0]
+
+    def clip_tempo_batch(self, requests: Sequence[tuple]):
+        rc, res = _tempo_call(self._lib.zlhip_group_sound_tempo_batch, self._g, requests, self.clip_length)
+        self._ck(rc, "group_sound_tempo_batch")
         return res
 
     # -- commands (global buses, slots and midi channels) --------------------------------------
