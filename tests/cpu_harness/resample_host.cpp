@@ -40,6 +40,27 @@ int64_t zl_rs_host_out_frames(double fs, double ft, int64_t len)
 
 int64_t zl_rs_host_extent_floats(int64_t N, int32_t channels) { return (int64_t)zl_rs_extent_floats(N, channels); }
 
+int32_t zl_rs_host_stage_frames(void) { return ZL_RS_STAGE_FRAMES; }
+
+// zl_rs_position of output frame j and zl_rs_span of workgroup w for a clip of `len` source frames (int64: the two functions read the
+// job's N and ratio, not its len, so a length beyond what a job record holds still walks them to the end of the range).
+// out: N, i, p, first, count.  -1 on a bad ratio, -3 where zl_rs_out_frames answers 0.
+int zl_rs_host_walk(double fs, double ft, int64_t len, int64_t j, int32_t w, int64_t *out)
+{
+    ZlRsGeom g;
+    if (zl_rs_geometry(fs, ft, &g) != 0) return -1;
+    const int64_t N = zl_rs_out_frames(g, len);
+    if (N < 1) return -3;
+    ZlRsJob J = {};
+    J.len = len > (int64_t)INT32_MAX ? INT32_MAX : (int32_t)len; J.N = (int32_t)N; J.channels = 1;
+    J.L = g.L; J.M = g.M; J.half = g.half; J.taps = g.taps; J.row = g.row;
+    int64_t i, first; int32_t p, count;
+    zl_rs_position(J, j, &i, &p);
+    zl_rs_span(J, w, &first, &count);
+    out[0] = N; out[1] = i; out[2] = p; out[3] = first; out[4] = count;
+    return 0;
+}
+
 // the header's own table (the tests feed the LIBRARY's, and hold this one against it)
 int zl_rs_host_design(double fs, double ft, float *table)
 {

@@ -1,6 +1,7 @@
 """The sample-rate conversion restated in numpy, independently of libzl_amd/csrc/zl_resample.h: the ratio, the
 Kaiser-windowed sinc table (np.sinc, np.i0, in double) and the convolution (vectorised over the output frames; per tap one fp32
-multiply, then one fp32 add, in tap order).  The tests hold the header's host build and the kernel against it."""
+multiply, then one fp32 add, in tap order), and in Python integers a frame's position and the span of input frames a workgroup of 256
+output frames stages.  The tests hold the header's host build and the kernel against it."""
 from math import gcd
 
 import numpy as np
@@ -54,6 +55,30 @@ def design(fs, ft):
 def out_frames(fs, ft, length):
     L, M = geometry(fs, ft)[:2]
     return (int(length) * L + M - 1) // M
+
+
+WG = 256                                                          # output frames of a workgroup
+STAGE_FRAMES = (WG - 1) * 8 + 512 + 1                             # what a workgroup stages at most: M <= 8 L, T <= 512
+
+
+def position(fs, ft, j):
+    """(i, p) of output frame j, in Python integers"""
+    L, M = geometry(fs, ft)[:2]
+    return (j * M) // L, (j * M) % L
+
+
+def span(fs, ft, N, w):
+    """(first, count): the input frames workgroup w of a clip of N output frames stages"""
+    L, M, half, taps, _ = geometry(fs, ft)
+    j0 = w * WG
+    j1 = min(j0 + WG, N) - 1
+    return (j0 * M) // L - half + 1, (j1 * M) // L - (j0 * M) // L + taps
+
+
+def staged_counts(fs, ft, length):
+    """the staged count of every workgroup of a clip of `length` source frames"""
+    N = out_frames(fs, ft, length)
+    return [span(fs, ft, N, w)[1] for w in range((N + WG - 1) // WG)]
 
 
 def lengths_for(fs, ft, N):

@@ -2,7 +2,9 @@
 (tests/resample_ref.py); the host build of libzl_amd/csrc/zl_resample.h (tests/cpu_harness/resample_host.cpp walks a clip the way
 the kernel does, with the library's table) against the restatement bit for bit, with every float of the extent written exactly once
 and no read outside the clip's own floats (the harness reads the source through an accessor that checks the index against the
-buffer); what the definition does to sines (it guards the design constants, not the kernel); the new kernels' resources and what the C-ABI answers without a GPU.  tests/test_resample_gpu.py holds the kernel itself to the restatement."""
+buffer); what the definition does to sines (it guards the design constants, not the kernel); the new kernels' resources and what the C-ABI answers without a GPU; the header's position and span at the far end of the range
+(j * M beyond 2^31) against Python integers.  tests/test_resample_gpu.py and tests/test_resample_geometry_gpu.py hold the kernel itself
+to the restatement."""
 import ctypes as C
 import os
 
@@ -18,11 +20,19 @@ f32, u32 = np.float32, np.uint32
 # (fs, ft) -> what the issue states about the ratio
 RATIOS = {
     (44100, 48000): {"L": 160, "M": 147, "T": 64},
-    (48000, 44100): {"T": 70},
+    (48000, 44100): {"L": 147, "M": 160, "T": 70},
     (96000, 48000): {"L": 1, "T": 128},
     (8000, 48000): {"L": 6, "M": 1},
     (22050, 48000): {"L": 320},
     (192000, 44100): {"T": 280},
+    # the geometries of tests/test_resample_geometry_gpu.py: an odd `half` while downsampling, M = 8 L (the staging at its limit),
+    # L at its limit, the table at its limit (2048 * 128 = 262144 floats), the lowest and the highest accepted rate
+    (88200, 48000): {"L": 80, "M": 147, "T": 118},
+    (384000, 48000): {"L": 1, "M": 8, "T": 512},
+    (51175, 51200): {"L": 2048, "M": 2047, "T": 64},
+    (102375, 51200): {"L": 2048, "M": 4095, "T": 128},
+    (1000, 6000): {"L": 6, "M": 1, "T": 64},
+    (768000, 96000): {"L": 1, "M": 8, "T": 512},
 }
 
 _h = None
@@ -43,6 +53,10 @@ def harness():
         l.zl_rs_host_design.argtypes = [C.c_double, C.c_double, C.c_void_p]
         l.zl_rs_host_convert.restype = C.c_int64
         l.zl_rs_host_convert.argtypes = [C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.zl_rs_host_stage_frames.restype = C.c_int32
+        l.zl_rs_host_stage_frames.argtypes = []
+        l.zl_rs_host_walk.restype = C.c_int
+        l.zl_rs_host_walk.argtypes = [C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
         _h = l
     return _h
 
@@ -136,7 +150,8 @@ def run_harness(fs, ft, table, x, src_floats=None):
 
 
 def lengths(fs, ft):
-    out = [1, 2, 63, 64, 65, 1000]
+    half, T = rr.geometry(fs, ft)[2:4]
+    out = [1, 2, 63, 64, 65, 1000, half - 1, half, half + 1, T + 1]   # (shorter than the filter: both ends of the taps hang outside)
     for N in (255, 256, 257, 513):                                 # the workgroup edges
         out += rr.lengths_for(fs, ft, N)
     return sorted(set(out))
@@ -162,6 +177,76 @@ def test_harness_matches_the_restatement_bit_for_bit(built, fs, ft, ch):
     # count); an upsampling ratio skips counts (1:6 gives multiples of 6): there a count on either side of the edge
     for N in (255, 256, 257, 513):
         assert N in counts or (ft > fs and any(c < N for c in counts if c > N - 8) and any(c > N for c in counts if c < N + 8)), (fs, ft, N, sorted(counts))
+
+
+def walk(fs, ft, length, j, w):
+    """(rc, N, i, p, first, count) of the header's zl_rs_out_frames, zl_rs_position(j) and zl_rs_span(w)"""
+    out = (C.c_int64 * 5)()
+    rc = harness().zl_rs_host_walk(fs, ft, length, j, w, out)
+    return (rc,) + tuple(out)
+
+
+def test_the_staging_reaches_its_limit_at_eight_to_one_and_never_passes_it(built):
+    """M = 8 L, T = 512: a full workgroup stages 255 * 8 + 512 = 2552 frames, one below ZL_RS_STAGE_FRAMES.  The harness answers -2
+    where a span is longer than the stage or a lane's taps leave it"""
+    fs, ft = 384000, 48000
+    assert harness().zl_rs_host_stage_frames() == rr.STAGE_FRAMES == 2553
+    table = library_table(fs, ft)[4]
+    rng = np.random.default_rng(17)
+    counts = []
+    for n in lengths(fs, ft) + [8 * 256 * 3 + 5]:
+        N = rr.out_frames(fs, ft, n)
+        got, writes, refused, verdict = run_harness(fs, ft, table, source(rng, n, 2))
+        assert refused == 0 and np.all(writes == 1), (n, refused)   # (-2 is not 0)
+        for w in range((N + rr.WG - 1) // rr.WG):
+            rc, hN, _, _, first, count = walk(fs, ft, n, 0, w)
+            assert rc == 0 and hN == N and (first, count) == rr.span(fs, ft, N, w), (n, w)
+            counts.append(count)
+    assert max(counts) == rr.STAGE_FRAMES - 1, max(counts)
+    # no accepted ratio passes it: the span of a full workgroup is floor(255 M / L) + T at most
+    for (a, b) in RATIOS:
+        L, M, half, T, _ = rr.geometry(a, b)
+        assert (255 * M) // L + 1 + T <= rr.STAGE_FRAMES, (a, b)
+
+
+INT32_MAX = 2 ** 31 - 1
+
+
+@pytest.mark.parametrize("fs,ft", [(384000, 48000), (51175, 51200), (44100, 48000)])
+def test_position_and_span_at_the_far_end_of_the_range(built, fs, ft):
+    """the longest clip the definition takes (N + 8 <= INT32_MAX; j * M passes 2^31, which no small device shape reaches): the
+    header's position and span against Python integers at the first, a middle and the last workgroup, every lane's first tap inside
+    the staged span, and zl_rs_out_frames answering 0 one frame beyond"""
+    L, M, half, T, _ = rr.geometry(fs, ft)
+    n = ((INT32_MAX - 8) * M) // L
+    while (n * L + M - 1) // M + 8 > INT32_MAX:
+        n -= 1
+    while ((n + 1) * L + M - 1) // M + 8 <= INT32_MAX:
+        n += 1
+    N = (n * L + M - 1) // M
+    if M >= L:
+        assert N + 8 == INT32_MAX                                  # (a ratio that goes down reaches every count)
+    else:
+        assert INT32_MAX - 8 - (L + M - 1) // M < N <= INT32_MAX - 8
+    assert harness().zl_rs_host_out_frames(fs, ft, n) == N
+    assert harness().zl_rs_host_out_frames(fs, ft, n + 1) == 0 and walk(fs, ft, n + 1, 0, 0)[0] == -3
+    wgs = (N + rr.WG - 1) // rr.WG
+    assert (N - 1) * M > 2 ** 31
+    for w in (0, wgs // 2, wgs - 1):
+        first, count = rr.span(fs, ft, N, w)
+        assert 0 < count <= rr.STAGE_FRAMES
+        j0, j1 = w * rr.WG, min((w + 1) * rr.WG, N) - 1
+        assert j1 == N - 1 or w < wgs - 1
+        for j in sorted({j0, j0 + 1, (j0 + j1) // 2, j1 - 1, j1}):
+            rc, hN, i, p, hfirst, hcount = walk(fs, ft, n, j, w)
+            assert rc == 0 and hN == N
+            assert (i, p) == rr.position(fs, ft, j), (w, j)
+            assert (hfirst, hcount) == (first, count), (w, j)
+            o = i - half + 1 - hfirst
+            assert 0 <= o and o + T <= hcount, (w, j, o)
+        # the last input frame a lane of the last workgroup reads lies at most `half` behind the clip
+        if w == wgs - 1:
+            assert first + count - 1 <= n - 1 + half
 
 
 def test_the_harness_refuses_a_read_outside_the_buffer_it_was_given(built):

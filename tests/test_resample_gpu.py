@@ -87,10 +87,11 @@ def uploaded_extent_is(s, cid, x):
     return same(s.clip_extent(cid)[:n], rr.extent(x)[:n])
 
 
-def set_loop(s, cid, frames):
-    """the clip's parameters with a loop of 750 frames (ClipAudioSource::setLength(0.04 beats, 120 bpm) = 1/64 s): with the default
-    length -- the whole clip, no beat length -- a looping voice under a stopped SyncTimer holds its first frame"""
-    p = s.default_clip_params(frames / float(FT))
+def set_loop(s, cid, frames, rate=float(FT)):
+    """the clip's parameters with a loop of 750 frames (ClipAudioSource::setLength(0.04 beats, 120 bpm) = 1/64 s; `rate`: the engine's,
+    where it is not 48000): with the default length -- the whole clip, no beat length -- a looping voice under a stopped SyncTimer
+    holds its first frame"""
+    p = s.default_clip_params(frames / rate)
     p.length_seconds = 0.015625
     p.length_in_beats = 0.04
     s.set_clip_params(cid, p)
@@ -169,14 +170,15 @@ def test_the_frames_behind_a_converted_clip_are_zero_and_the_neighbours_unharmed
 
 
 # ---- playback -------------------------------------------------------------------------------------------------------------------
-def play_pair(s, converted, twin, blocks=8, loop=True):
-    """clip `converted` on bus 0, clip `twin` on bus 1, one voice each, the same command: (bus [2][2][frames], peaks, levels, reports)"""
+def play_pair(s, converted, twin, blocks=8, loop=True, rate=float(FT)):
+    """clip `converted` on bus 0, clip `twin` on bus 1, one voice each, the same command: (bus [2][2][frames], peaks, levels, reports);
+    `rate`: the engine's, where it is not 48000"""
     from scenario import engine_cmd, play_cmd
     from libzl_amd.engine import synthetic_clocks
     for bus, cid in ((0, converted), (1, twin)):
-        set_loop(s, cid, s.clip_info(cid)["length"])
+        set_loop(s, cid, s.clip_info(cid)["length"], rate)
         assert s.handle_clip_command(engine_cmd(**play_cmd(cid, midi_channel=bus - 2, loop=loop, note=60, volume=0.8)), 0) == 1
-    s.render_batch(blocks, 256, synthetic_clocks(blocks, 256, float(FT)))
+    s.render_batch(blocks, 256, synthetic_clocks(blocks, 256, rate))
     bus = s.read_bus()
     peaks = s.block_peaks()
     lv = s.levels_tick()
