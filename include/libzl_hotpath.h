@@ -197,6 +197,17 @@ int  libzl_hotpath_clip_tempo(ClipAudioSource *c, float bpm_min, float bpm_max, 
  * stays; a re-render starts from the original upload, hence the current ratio in the product).  *ratio_out: the ratio now in effect.
  * Returns 1, or 0 where there is no tempo or the confidence is below min_confidence (nothing changes then), or a negative status. */
 int  libzl_hotpath_clip_match_tempo(ClipAudioSource *c, float target_bpm, float min_confidence, float *ratio_out);
+/* The clip's pitch (build-defined: the reference has no pitch detection; ClipAudioSource_setRootNote takes a note the caller must
+ * know).  Detected on the device (zlhip_sound_pitch, every other field at its default) over the clip's current playback data between
+ * its start and its start + length, in frames as for libzl_hotpath_clip_tempo.  f_min / f_max of 0 take 55 / 1760 Hz.  *note is the
+ * fractional MIDI note.  *hz = 0 (and *note = *confidence = 0) means "no pitch": silence, noise, a drum hit, or a region shorter than
+ * one analysis frame; that is not an error.  A note above f_max comes back an octave low.  Returns 0 or a negative zlhip status
+ * (nothing is written then). */
+int  libzl_hotpath_clip_pitch(ClipAudioSource *c, float f_min, float f_max, float *hz, float *note, float *confidence);
+/* Set the clip's root note from its pitch: detects as libzl_hotpath_clip_pitch(c, 0, 0, ...) and sets root_note = clamp(rint(note), 0,
+ * 127) through ClipAudioSource_setRootNote's path, so the next startNote uses it.  *root_note_out: the note set.  Returns 1, or 0 where
+ * there is no pitch or the confidence is below min_confidence (nothing changes then, *root_note_out included), or a negative status. */
+int  libzl_hotpath_clip_detect_root_note(ClipAudioSource *c, float min_confidence, int *root_note_out);
 /* A bank of clips in one engine call: every file is read, their `data` chunks go to the engine as raw PCM in ONE
  * zlhip_sound_upload_pcm_batch call (decoded on the device, one wait for the whole bank).  out[i] is the clip of paths[i], or NULL
  * for a file that cannot be opened or decoded -- it does not fail the others.  Returns the number of clips loaded (or a negative

@@ -39,7 +39,8 @@ extern "C" {
  *    Later additions, still 3 (new entry points only): the engine group (zlhip_group_*), zlhip_sound_overview / _batch (waveform overviews),
  *    zlhip_sound_upload_pcm / _batch (clips from raw PCM, decoded on the device), zlhip_sound_convert_rate / _batch (clips converted to
  *    another sample rate on the device, band-limited), zlhip_resample_design, zlhip_sound_info_get, zlhip_debug_sound_extent, zlhip_sound_onsets / _batch (a clip's transients, found on
- *    the device), zlhip_onset_resolve, zlhip_sound_tempo / _batch (a clip's tempo, estimated on the device), zlhip_tempo_resolve. */
+ *    the device), zlhip_onset_resolve, zlhip_sound_tempo / _batch (a clip's tempo, estimated on the device), zlhip_tempo_resolve,
+ *    zlhip_sound_pitch / _batch (a clip's pitch, detected on the device), zlhip_pitch_resolve. */
 #define ZLHIP_ABI_VERSION 3
 
 /* status codes */
@@ -306,6 +307,49 @@ int zlhip_sound_tempo_batch(zlhip_engine *e, const zlhip_tempo_request *reqs, in
 int zlhip_debug_tempo_acf(zlhip_engine *e, int32_t request, uint16_t *flux, uint64_t *acf, int32_t capacity, int32_t *hops, int32_t *first_lag, int32_t *lags);
 /* measurement: device time of the energy pass, of the autocorrelation kernel and of the rest of the last call made with profiling on */
 int zlhip_debug_tempo_timings(zlhip_engine *e, float *energy_ms, float *acf_ms, float *rest_ms);
+/* Pitch: what note a clip is (a build-defined extension, the reference has no pitch detection) -- detected on
+ * the device in the sound's CURRENT playback data: YIN's difference function, cumulative-mean normalisation and absolute threshold,
+ * in integers behind the 16-bit quantisation, so the result does not depend on any order of evaluation:
+ *   t_min = max(2, ceil(rate / f_max)), t_max = floor(rate / f_min); W = window; a frame needs L = W + t_max + 1 samples.
+ *   num_frames < L: no frames.  Otherwise hop = W, K = (num_frames - L) / hop + 1; K > max_frames: K = max_frames and
+ *   hop = (num_frames - L) / (max_frames - 1) (max_frames 1: K = 1); frame k starts at first_frame + k hop.
+ *   m[f] = the sum over the channels of clamp(rint(4096 v), +-32767) (NaN -> 0); e = the sum of m^2 over the frame's first W samples;
+ *   e < W channels gate^2: the frame is silent.  sh = max(0, bitlength(max |m| over the L samples) - 12), x = m >> sh (arithmetic).
+ *   d[t] = the sum over j < W of (x[j] - x[j + t])^2 for t in [1, t_max + 1]; C[t] = d[1] + ... + d[t].
+ *   t0 = the smallest t in [t_min, t_max] with d[t] t 1024 < threshold C[t] (uint64); none: the frame is unvoiced.
+ *   The frame's lag = the first t >= t0 with t = t_max or d[t + 1] >= d[t]; clarity = L(C[lag] + 1) - L(d[lag] lag + 1), L the
+ *   transients' level (a log2 in 1/64 octaves).  A frame's record (zlhip_pitch_frame): lag, clarity, shift, flag (0 voiced, 1 silent,
+ *   2 unvoiced), d_lo / d_mid / d_hi = d[lag - 1], d[lag], d[lag + 1], cum = C[lag]; silent and unvoiced frames: 0 except shift, flag.
+ *   The vote: voiced = the voiced frames, t_med = their lower median lag, a frame is consistent if |lag - t_med| <= t_med >> 5,
+ *   the representative (`frame`) is the consistent frame with the largest clarity, equal values go to the earlier frame; lag, shift,
+ *   clarity, d_lo, d_mid, d_hi, cum are its record's.
+ *   The host derives, in double: den = (d_lo - 2 d_mid) + d_hi; delta = (d_lo - d_hi) / (2 den) if den > 0 else 0, clamped to
+ *   +-0.5; hz = rate / (lag + delta); note = 69 + 12 log2(hz / 440); root_note = clamp(rint(note), 0, 127);
+ *   cents = 100 (note - root_note); confidence = consistent / frames.
+ *   No pitch -- no frames (num_frames < L) or no voiced frame (silence, noise, a drum hit) -- is not an error: every field is 0
+ *   except frames.  A note above f_max comes back an octave (or more) low: choose f_max above the material.
+ *   A field given as 0 takes its default (zlhip_pitch_resolve with the sound's sample rate): f_min = 55, f_max = 1760,
+ *   threshold = 154 (0.15), gate = 8, max_frames = 64, window = min(4096, roundup(2 t_max, 64)).
+ *   Limits: window a multiple of 64 in [256, 4096]; t_max + 1 <= min(2048, window); f_min and f_max finite,
+ *   20 <= f_min < f_max < rate / 2; threshold in [1, 1024]; gate in [1, 32767]; max_frames in [1, 256]; num_frames >= 1,
+ *   first_frame >= 0, first_frame + num_frames <= the sound's length; at most 65536 analysis frames per call; nreq >= 0: anything
+ *   else is ZLHIP_ERR_INVALID.  On any error out is not written; one bad request fails the call.
+ *   A call is three kernel launches whatever its size, behind one copy of the request records; it waits once and 80 bytes per request
+ *   come back.  It runs on the engine's stream behind what is queued there and the resident real-time kernel keeps running. */
+typedef struct zlhip_pitch_request { int32_t id, first_frame, num_frames, window, max_frames; float f_min, f_max; int32_t threshold, gate; } zlhip_pitch_request;
+typedef struct zlhip_pitch { float hz, note, cents, confidence; int32_t root_note, frames, voiced, consistent, frame, lag, shift, clarity;
+                             uint64_t d_lo, d_mid, d_hi, cum; } zlhip_pitch;
+typedef struct zlhip_pitch_frame { int32_t lag, clarity, shift, flag; uint64_t d_lo, d_mid, d_hi, cum; } zlhip_pitch_frame;
+/* host only: fills the fields given as 0 and checks every limit that does not need the sound; a refused request is left as it was */
+int zlhip_pitch_resolve(double sample_rate, zlhip_pitch_request *r);
+int zlhip_sound_pitch(zlhip_engine *e, const zlhip_pitch_request *r, zlhip_pitch *out);
+int zlhip_sound_pitch_batch(zlhip_engine *e, const zlhip_pitch_request *reqs, int32_t nreq, zlhip_pitch *out);
+/* the frame records of request `request` of the last call (records: [capacity], may be NULL to ask for *frames only) */
+int zlhip_debug_pitch_frames(zlhip_engine *e, int32_t request, zlhip_pitch_frame *records, int32_t capacity, int32_t *frames);
+/* d[1 .. t_max + 1] of frame `frame` of request `request` of the last call (d: [capacity], may be NULL to ask for *lags = t_max + 1 only) */
+int zlhip_debug_pitch_diff(zlhip_engine *e, int32_t request, int32_t frame, uint64_t *d, int32_t capacity, int32_t *lags);
+/* measurement: device time of the difference-function kernel and of the rest of the last call made with profiling on */
+int zlhip_debug_pitch_timings(zlhip_engine *e, float *diff_ms, float *rest_ms);
 /* Clips from raw PCM.  `frames` is host memory, pageable or page-locked: `length` frames of `channels`
  *   interleaved little-endian samples, exactly the bytes of a WAV `data` chunk.  They are copied raw into a device staging buffer and
  *   decoded there into the arena's layout; one decode launch serves each staging pass and the call waits for the device once.
@@ -531,6 +575,8 @@ int  zlhip_group_sound_overview_batch(zlhip_group *g, const zlhip_overview_reque
 int  zlhip_group_sound_onsets_batch(zlhip_group *g, const zlhip_onset_request *reqs, int32_t nreq, zlhip_onset *out, size_t capacity, int32_t *counts);
 /* zlhip_sound_tempo_batch: member 0 answers */
 int  zlhip_group_sound_tempo_batch(zlhip_group *g, const zlhip_tempo_request *reqs, int32_t nreq, zlhip_tempo *out);
+/* zlhip_sound_pitch_batch: member 0 answers */
+int  zlhip_group_sound_pitch_batch(zlhip_group *g, const zlhip_pitch_request *reqs, int32_t nreq, zlhip_pitch *out);
 /* zlhip_handle_commands_voices over the whole synth (taken, voices optional) */
 int  zlhip_group_handle_commands(zlhip_group *g, const zlhip_clip_command *cmds, int32_t count, uint64_t current_tick, int32_t *taken,
                                  int32_t *voices);

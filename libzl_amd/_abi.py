@@ -123,6 +123,23 @@ class TempoRequest(C.Structure):
                 ("bpm_max", C.c_float)]
 
 
+class PitchRequest(C.Structure):
+    _fields_ = [("id", C.c_int32), ("first_frame", C.c_int32), ("num_frames", C.c_int32), ("window", C.c_int32), ("max_frames", C.c_int32),
+                ("f_min", C.c_float), ("f_max", C.c_float), ("threshold", C.c_int32), ("gate", C.c_int32)]
+
+
+class Pitch(C.Structure):
+    _fields_ = [("hz", C.c_float), ("note", C.c_float), ("cents", C.c_float), ("confidence", C.c_float), ("root_note", C.c_int32),
+                ("frames", C.c_int32), ("voiced", C.c_int32), ("consistent", C.c_int32), ("frame", C.c_int32), ("lag", C.c_int32),
+                ("shift", C.c_int32), ("clarity", C.c_int32), ("d_lo", C.c_uint64), ("d_mid", C.c_uint64), ("d_hi", C.c_uint64),
+                ("cum", C.c_uint64)]
+
+
+class PitchFrame(C.Structure):
+    _fields_ = [("lag", C.c_int32), ("clarity", C.c_int32), ("shift", C.c_int32), ("flag", C.c_int32), ("d_lo", C.c_uint64),
+                ("d_mid", C.c_uint64), ("d_hi", C.c_uint64), ("cum", C.c_uint64)]
+
+
 class Tempo(C.Structure):
     _fields_ = [("bpm", C.c_float), ("confidence", C.c_float), ("lag_coarse", C.c_int32), ("lag_fine", C.c_int32), ("doublings", C.c_int32),
                 ("shift", C.c_int32), ("hops", C.c_int32), ("reserved", C.c_int32), ("acf_lo", C.c_uint64), ("acf_mid", C.c_uint64),
@@ -191,6 +208,12 @@ SIGNATURES = {
     "zlhip_sound_tempo_batch": (C.c_int, [_E, C.POINTER(TempoRequest), C.c_int32, C.POINTER(Tempo)]),
     "zlhip_debug_tempo_acf": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "zlhip_debug_tempo_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "zlhip_pitch_resolve": (C.c_int, [C.c_double, C.POINTER(PitchRequest)]),
+    "zlhip_sound_pitch": (C.c_int, [_E, C.POINTER(PitchRequest), C.POINTER(Pitch)]),
+    "zlhip_sound_pitch_batch": (C.c_int, [_E, C.POINTER(PitchRequest), C.c_int32, C.POINTER(Pitch)]),
+    "zlhip_debug_pitch_frames": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zlhip_debug_pitch_diff": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zlhip_debug_pitch_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "zlhip_sound_upload_pcm": (C.c_int, [_E, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_int32)]),
     "zlhip_sound_upload_pcm_batch": (C.c_int, [_E, C.POINTER(PcmSource), C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_debug_upload_pcm_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -256,6 +279,7 @@ SIGNATURES = {
     "zlhip_group_sound_overview_batch": (C.c_int, [_E, C.POINTER(OverviewRequest), C.c_int32, C.c_void_p, C.c_size_t]),
     "zlhip_group_sound_onsets_batch": (C.c_int, [_E, C.POINTER(OnsetRequest), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "zlhip_group_sound_tempo_batch": (C.c_int, [_E, C.POINTER(TempoRequest), C.c_int32, C.POINTER(Tempo)]),
+    "zlhip_group_sound_pitch_batch": (C.c_int, [_E, C.POINTER(PitchRequest), C.c_int32, C.POINTER(Pitch)]),
     "zlhip_group_handle_commands": (C.c_int, [_E, C.POINTER(ClipCommand), C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "zlhip_group_start_voice": (C.c_int, [_E, C.c_int32, C.c_int32, C.POINTER(ClipCommand), C.c_uint64]),
     "zlhip_group_stop_voice": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_int]),

@@ -30,6 +30,7 @@
 #include "zl_plan.h"
 #include "zl_onset.h"
 #include "zl_tempo.h"
+#include "zl_pitch.h"
 #include "zl_overview.h"
 #include "zl_resample.h"
 #include "zl_decode.h"
@@ -72,6 +73,7 @@ enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a ca
        ZB_RS_JOBS, ZB_RS_PUB, ZB_RS_VERDICTS,                // rate conversion: a call's job and publish records, its verdict words
        ZB_ON_REQ, ZB_ON_E, ZB_ON_N, ZB_ON_PS,                // transients: a call's request records (with a host twin), and per hop E, N and the windows' running maxima
        ZB_TP_REQ, ZB_TP_E, ZB_TP_W, ZB_TP_A, ZB_TP_STAT,      // tempo: a call's request records (the energy pass's and the tempo kernels', one host twin), per hop E and W, per lag A, per request the flux's statistics
+       ZB_PT_REQ, ZB_PT_D, ZB_PT_STAT, ZB_PT_FRAME,           // pitch: a call's request records (with a host twin), per frame and lag d, per frame the diff kernel's statistics and the frame records
        ZB_COUNT };
 
 }  // namespace
@@ -119,6 +121,13 @@ struct zlhip_engine {
         std::vector<Last> last;                                                 // per request of the last call (zlhip_debug_tempo_acf)
         hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; float energyMs = 0.0f, acfMs = 0.0f, restMs = 0.0f;   // profiling (zlhip_debug_tempo_timings)
     } tp;
+    // pitch (zlhip_sound_pitch; zl_pitch.h)
+    struct Pitch {
+        ZlPtResult *hOut = nullptr, *dOut = nullptr; size_t outCap = 0;         // a call's integer records, in host memory mapped into the device
+        struct Last { int64_t d_base; int32_t frame_base, frames, nd; };
+        std::vector<Last> last;                                                 // per request of the last call (zlhip_debug_pitch_frames / _diff)
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; float diffMs = 0.0f, restMs = 0.0f;   // profiling (zlhip_debug_pitch_timings)
+    } pt;
     // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h)
     struct Pcm {
         std::vector<hipEvent_t> ev;                                 // profiling: before every pass's copies and every decode launch, behind the last
@@ -475,6 +484,8 @@ void zlhip_engine_destroy(zlhip_engine *e)
     if (e->on.hOut) (void)hipHostFree(e->on.hOut);
     for (hipEvent_t ev : e->tp.ev) if (ev) (void)hipEventDestroy(ev);
     if (e->tp.hOut) (void)hipHostFree(e->tp.hOut);
+    for (hipEvent_t ev : e->pt.ev) if (ev) (void)hipEventDestroy(ev);
+    if (e->pt.hOut) (void)hipHostFree(e->pt.hOut);
     for (hipEvent_t ev : e->pcm.ev) if (ev) (void)hipEventDestroy(ev);
     if (e->evJoin) (void)hipEventDestroy(e->evJoin);
     if (e->evPlanTail) (void)hipEventDestroy(e->evPlanTail);
@@ -1771,6 +1782,137 @@ int zlhip_debug_tempo_timings(zlhip_engine *e, float *energy_ms, float *acf_ms, 
     if (energy_ms) *energy_ms = e->tp.energyMs;
     if (acf_ms) *acf_ms = e->tp.acfMs;
     if (rest_ms) *rest_ms = e->tp.restMs;
+    return ZLHIP_OK;
+}
+
+// ---- pitch (zl_pitch.h, zl_pitch.hip) --------------------------------------------------------------------------------------
+// What note a clip is.  The diff kernel reads the analysed frames' samples and leaves d per frame and lag; the pick and the vote are
+// integer arithmetic on it.  Synchronisation and buffers as for the transients and the tempo: the call runs on the engine's stream
+// behind what is queued there and leaves the resident real-time kernel alone; its buffers are allocated by the first call and grow
+// only.  The integer records are written by the vote kernel into host memory mapped into the device; hz, note, root_note, cents and
+// confidence are derived here (zl_pt_finish).
+int zlhip_pitch_resolve(double sample_rate, zlhip_pitch_request *r)
+{
+    if (!r || r->first_frame < 0 || r->num_frames < 1) return ZLHIP_ERR_INVALID;
+    zlhip_pitch_request q = *r;
+    if (zl_pt_resolve(sample_rate, &q.window, &q.max_frames, &q.f_min, &q.f_max, &q.threshold, &q.gate) != 0) return ZLHIP_ERR_INVALID;
+    *r = q;
+    return ZLHIP_OK;
+}
+
+static int pt_reserve(zlhip_engine *e, size_t nreq, size_t frames, size_t words)
+{
+    GrowBuf *b = e->scratch; zlhip_engine::Pitch &t = e->pt;
+    if (nreq <= b[ZB_PT_REQ].cap && words <= b[ZB_PT_D].cap && frames <= b[ZB_PT_STAT].cap && frames <= b[ZB_PT_FRAME].cap && nreq <= t.outCap)
+        return ZLHIP_OK;
+    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }
+    ZlQuiesce quiet(e);
+    const char *what = "sound_pitch: no memory for the call's buffers";
+    const size_t fcap = std::min<size_t>(std::max<size_t>(frames * 2, 256), ZL_PT_MAX_CALL_FRAMES);
+    int rc = grow_buf(e, b[ZB_PT_REQ], nreq, sizeof(ZlPtRequest), std::max<size_t>(nreq * 2, 64), true, what);
+    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_PT_D], words, sizeof(uint64_t), std::max<size_t>(words + words / 2, 65536), false, what);
+    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_PT_STAT], frames, sizeof(ZlPtStat), fcap, false, what);
+    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_PT_FRAME], frames, sizeof(ZlPtFrame), fcap, false, what);
+    if (rc != ZLHIP_OK) return rc;
+    ZL_HIP(e, grow_mapped(&t.hOut, &t.dOut, &t.outCap, std::max<size_t>(nreq, 32)));
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_pitch_batch(zlhip_engine *e, const zlhip_pitch_request *reqs, int32_t nreq, zlhip_pitch *out)
+{
+    static_assert(sizeof(zlhip_pitch) == sizeof(ZlPtResult), "the device writes zlhip_pitch's layout");
+    static_assert(sizeof(zlhip_pitch_frame) == sizeof(ZlPtFrame), "the device writes zlhip_pitch_frame's layout");
+    if (!e || nreq < 0 || (nreq > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
+    if (nreq == 0) return ZLHIP_OK;
+    // validate and resolve everything before anything is written and before the first HIP call
+    std::vector<ZlPtRequest> geo((size_t)nreq);
+    std::vector<double> rate((size_t)nreq);
+    int64_t frames = 0, words = 0, items = 0;
+    for (int32_t i = 0; i < nreq; ++i) {
+        zlhip_pitch_request q = reqs[i];
+        if (q.id < 0 || q.id >= e->cfg.max_sounds || !e->hc.soundUsed[q.id]) return fail(e, ZLHIP_ERR_INVALID, "sound_pitch: no such sound");
+        const ZlSound &s = e->hc.sounds[q.id];
+        if (zlhip_pitch_resolve(s.sample_rate, &q) != ZLHIP_OK) return fail(e, ZLHIP_ERR_INVALID, "sound_pitch: a field of the request is outside its limits");
+        if ((int64_t)q.first_frame + q.num_frames > s.length) return fail(e, ZLHIP_ERR_INVALID, "sound_pitch: the frames do not lie inside the sound's playback data");
+        ZlPtRequest &R = geo[(size_t)i];
+        double tmin, tmax;
+        zl_pt_lags(s.sample_rate, q.f_min, q.f_max, &tmin, &tmax);
+        R.src = 0;                                                 // (the address: behind pt_reserve, with the other HIP-side state)
+        R.floor_ = (uint64_t)q.window * (uint64_t)s.channels * (uint64_t)q.gate * (uint64_t)q.gate;
+        R.first = q.first_frame; R.channels = s.channels;
+        R.window = q.window; R.tmin = (int32_t)tmin; R.tmax = (int32_t)tmax; R.threshold = q.threshold;
+        zl_pt_frames(q.num_frames, R.window, R.tmax, q.max_frames, &R.frames, &R.hop);
+        R.d_base = words; R.frame_base = (int32_t)frames; R.item_base = (int32_t)items;
+        rate[(size_t)i] = s.sample_rate;
+        frames += R.frames; words += (int64_t)R.frames * zl_pt_nd(R); items += zl_pt_items(R);
+        if (frames > ZL_PT_MAX_CALL_FRAMES) return fail(e, ZLHIP_ERR_INVALID, "sound_pitch_batch: more than 65536 analysis frames in one call");
+    }
+    ZL_HIP(e, hipSetDevice(e->device));
+    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    { const int rc = pt_reserve(e, (size_t)nreq, (size_t)frames, (size_t)words); if (rc != ZLHIP_OK) return rc; }
+    zlhip_engine::Pitch &t = e->pt;
+    ZlPtRequest *const hReq = (ZlPtRequest *)e->scratch[ZB_PT_REQ].h, *const dReq = (ZlPtRequest *)e->scratch[ZB_PT_REQ].d;
+    uint64_t *const dD = (uint64_t *)e->scratch[ZB_PT_D].d; ZlPtStat *const dStat = (ZlPtStat *)e->scratch[ZB_PT_STAT].d;
+    ZlPtFrame *const dFrame = (ZlPtFrame *)e->scratch[ZB_PT_FRAME].d;
+    t.last.clear();
+    for (int32_t i = 0; i < nreq; ++i) {
+        ZlPtRequest &R = hReq[i];
+        R = geo[(size_t)i];
+        R.src = (uint64_t)(uintptr_t)arena_ptr(e, e->hc.sounds[reqs[i].id].offset);
+        t.last.push_back({R.d_base, R.frame_base, R.frames, zl_pt_nd(R)});
+    }
+    const bool prof = e->profiling;
+    for (int x = 0; prof && x < 3; ++x) if (!t.ev[x]) ZL_HIP(e, hipEventCreate(&t.ev[x]));
+    ZL_HIP(e, hipMemcpyAsync(dReq, hReq, (size_t)nreq * sizeof(ZlPtRequest), hipMemcpyHostToDevice, e->stream));
+    if (prof) ZL_HIP(e, hipEventRecord(t.ev[0], e->stream));
+    ZL_KERNEL(e, zl_launch_pitch_diff(dReq, nreq, items, dD, dStat, e->stream));
+    if (prof) ZL_HIP(e, hipEventRecord(t.ev[1], e->stream));
+    ZL_KERNEL(e, zl_launch_pitch_pick(dReq, nreq, frames, dD, dStat, dFrame, e->stream));
+    ZL_KERNEL(e, zl_launch_pitch_vote(dReq, nreq, dFrame, t.dOut, e->stream));
+    if (prof) ZL_HIP(e, hipEventRecord(t.ev[2], e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    if (prof) { ZL_HIP(e, hipEventElapsedTime(&t.diffMs, t.ev[0], t.ev[1])); ZL_HIP(e, hipEventElapsedTime(&t.restMs, t.ev[1], t.ev[2])); }
+    for (int32_t i = 0; i < nreq; ++i) {
+        ZlPtResult r = t.hOut[i];
+        zl_pt_finish(rate[(size_t)i], &r);
+        std::memcpy(&out[i], &r, sizeof(r));
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_pitch(zlhip_engine *e, const zlhip_pitch_request *r, zlhip_pitch *out) { return zlhip_sound_pitch_batch(e, r, 1, out); }
+
+int zlhip_debug_pitch_frames(zlhip_engine *e, int32_t request, zlhip_pitch_frame *records, int32_t capacity, int32_t *frames)
+{
+    if (!e || request < 0 || (size_t)request >= e->pt.last.size()) return ZLHIP_ERR_INVALID;
+    const zlhip_engine::Pitch::Last &l = e->pt.last[(size_t)request];
+    if (frames) *frames = l.frames;
+    if (!records) return ZLHIP_OK;
+    if (capacity < l.frames) return fail(e, ZLHIP_ERR_CAPACITY, "debug_pitch_frames: capacity below the request's frames");
+    if (l.frames == 0) return ZLHIP_OK;
+    ZL_HIP(e, hipSetDevice(e->device));
+    ZL_HIP(e, hipMemcpyAsync(records, (const ZlPtFrame *)e->scratch[ZB_PT_FRAME].d + l.frame_base, (size_t)l.frames * sizeof(ZlPtFrame), hipMemcpyDeviceToHost, e->stream));
+    return engine_wait(e);
+}
+
+int zlhip_debug_pitch_diff(zlhip_engine *e, int32_t request, int32_t frame, uint64_t *d, int32_t capacity, int32_t *lags)
+{
+    if (!e || request < 0 || (size_t)request >= e->pt.last.size()) return ZLHIP_ERR_INVALID;
+    const zlhip_engine::Pitch::Last &l = e->pt.last[(size_t)request];
+    if (lags) *lags = l.nd;
+    if (!d) return ZLHIP_OK;
+    if (frame < 0 || frame >= l.frames) return fail(e, ZLHIP_ERR_INVALID, "debug_pitch_diff: no such frame");
+    if (capacity < l.nd) return fail(e, ZLHIP_ERR_CAPACITY, "debug_pitch_diff: capacity below the request's lags");
+    ZL_HIP(e, hipSetDevice(e->device));
+    ZL_HIP(e, hipMemcpyAsync(d, (const uint64_t *)e->scratch[ZB_PT_D].d + l.d_base + (int64_t)frame * l.nd, (size_t)l.nd * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    return engine_wait(e);
+}
+
+int zlhip_debug_pitch_timings(zlhip_engine *e, float *diff_ms, float *rest_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (diff_ms) *diff_ms = e->pt.diffMs;
+    if (rest_ms) *rest_ms = e->pt.restMs;
     return ZLHIP_OK;
 }
 

@@ -1029,6 +1029,53 @@ int libzl_hotpath_clip_match_tempo(ClipAudioSource *c, float target_bpm, float m
     return 1;
 }
 
+// A bank of pitched one-shots plays out of tune until every sample's root note is known: ClipAudioSource_setRootNote takes a note
+// the caller must already know.  Here: the pitch of the data the clip plays now between its start and its start + length, detected on
+// the device (zlhip_sound_pitch).  Build-defined: the reference has no pitch detection.
+static int clip_pitch(ClipAudioSource *c, float f_min, float f_max, zlhip_pitch *t)      // call with G.mu held
+{
+    if (!G.engine || c->engineClip < 0) return ZLHIP_ERR_STATE;
+    zlhip_sound_info info;
+    { const int rc = zlhip_sound_info_get(G.engine, c->engineClip, &info); if (rc != ZLHIP_OK) return rc; }
+    float startSec, lengthSec;
+    { std::lock_guard<std::mutex> sl(c->setMu); startSec = c->startPositionInSeconds; lengthSec = c->lengthInSeconds; }
+    // the region in frames, cast as for libzl_hotpath_clip_tempo
+    auto frame = [&](float seconds) -> int64_t {
+        const double f = (double)seconds * info.sample_rate;
+        return !(f > 0.0) ? 0 : (f >= (double)info.length ? (int64_t)info.length : (int64_t)f);
+    };
+    const int64_t start = frame(startSec), stop = frame(startSec + lengthSec);
+    if (stop <= start) return ZLHIP_ERR_INVALID;
+    const zlhip_pitch_request q = { c->engineClip, (int32_t)start, (int32_t)(stop - start), 0, 0, f_min, f_max, 0, 0 };
+    return zlhip_sound_pitch(G.engine, &q, t);
+}
+
+int libzl_hotpath_clip_pitch(ClipAudioSource *c, float f_min, float f_max, float *hz, float *note, float *confidence)
+{
+    if (!c) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    zlhip_pitch t;
+    { const int rc = clip_pitch(c, f_min, f_max, &t); if (rc != ZLHIP_OK) return rc; }
+    if (hz) *hz = t.hz;
+    if (note) *note = t.note;
+    if (confidence) *confidence = t.confidence;
+    return ZLHIP_OK;
+}
+
+// Set the clip's root note from the pitch of the data it plays now: the same lock and the same publish_params as
+// ClipAudioSource_setRootNote, so the next startNote plays at 2^((midi_note - root_note) / 12) of the detected note.
+int libzl_hotpath_clip_detect_root_note(ClipAudioSource *c, float min_confidence, int *root_note_out)
+{
+    if (!c) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    zlhip_pitch t;
+    { const int rc = clip_pitch(c, 0.0f, 0.0f, &t); if (rc != ZLHIP_OK) return rc; }
+    if (!(t.hz > 0.0f) || !(t.confidence >= min_confidence)) return 0;
+    ClipAudioSource_setRootNote(c, t.root_note);
+    if (root_note_out) *root_note_out = t.root_note;
+    return 1;
+}
+
 void ClipAudioSource_setVolume(ClipAudioSource *c, float vol)      // ClipAudioSource.cpp:313-326
 {
     std::lock_guard<std::mutex> sl(c->setMu);

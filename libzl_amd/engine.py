@@ -138,6 +138,28 @@ def _onsets_call(fn, handle, requests, length_of):
     return rc, res
 
 
+PITCH_FIELDS = tuple(name for name, _ in _abi.Pitch._fields_)
+PITCH_FRAME_FIELDS = tuple(name for name, _ in _abi.PitchFrame._fields_)
+_PITCH_KEYS = ("first_frame", "num_frames", "window", "max_frames", "f_min", "f_max", "threshold", "gate")
+
+
+def _pitch_call(fn, handle, requests, length_of):
+    """one zlhip_sound_pitch_batch-shaped call over (clip[, first_frame[, num_frames[, window[, max_frames[, f_min[, f_max[, threshold[, gate]]]]]]]])
+    tuples, or dicts with "clip" and any of those keys (num_frames None / missing = to the end of the clip, every other field 0 / missing =
+    its default) -> (status, one dict of zlhip_pitch's fields per request)"""
+    reqs = (_abi.PitchRequest * max(1, len(requests)))()
+    for i, r in enumerate(requests):
+        if isinstance(r, dict):
+            r = (r["clip"],) + tuple(r.get(k, None if k == "num_frames" else 0) for k in _PITCH_KEYS)
+        r = tuple(r) if isinstance(r, (tuple, list)) else (r,)
+        r = r + (0, None, 0, 0, 0.0, 0.0, 0, 0)[len(r) - 1:]
+        clip, first = int(r[0]), int(r[1])
+        reqs[i] = _abi.PitchRequest(clip, first, int(length_of(clip) - first if r[2] is None else r[2]), int(r[3]), int(r[4]), float(r[5]), float(r[6]), int(r[7]), int(r[8]))
+    out = (_abi.Pitch * max(1, len(requests)))()
+    rc = fn(handle, reqs, len(requests), out)
+    return rc, [{k: getattr(out[i], k) for k in PITCH_FIELDS} for i in range(len(requests))]
+
+
 TEMPO_FIELDS = tuple(name for name, _ in _abi.Tempo._fields_ if name != "reserved")
 
 
@@ -435,6 +457,43 @@ class SamplerSynth:
         a, b, c = C.c_float(0.0), C.c_float(0.0), C.c_float(0.0)
         self._ck(self._lib.zlhip_debug_tempo_timings(self._e, C.byref(a), C.byref(b), C.byref(c)), "debug_tempo_timings")
         return a.value, b.value, c.value
+
+    def clip_pitch(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, window: int = 0, max_frames: int = 0, f_min: float = 0.0,
+                   f_max: float = 0.0, threshold: int = 0, gate: int = 0) -> dict:
+        """The pitch of the clip's current playback data over [first_frame, first_frame + num_frames) (None: to the end), detected on the
+        device (zlhip_sound_pitch): a dict of zlhip_pitch's fields -- hz, note, cents, confidence, root_note and the
+        integers they derive from.  hz == 0 means "no pitch" (silence, noise, or shorter than one analysis frame).  A field given as 0
+        takes its default (zlhip_pitch_resolve: 55 to 1760 Hz, up to 64 frames).  A note above f_max comes back an octave low."""
+        return self.clip_pitch_batch([(clip, first_frame, num_frames, window, max_frames, f_min, f_max, threshold, gate)])[0]
+
+    def clip_pitch_batch(self, requests: Sequence):
+        """Several requests in one call (zlhip_sound_pitch_batch: three launches whatever the count).  requests: tuples
+        (clip[, first_frame[, num_frames[, window[, max_frames[, f_min[, f_max[, threshold[, gate]]]]]]]]) or dicts; one dict each."""
+        rc, res = _pitch_call(self._lib.zlhip_sound_pitch_batch, self._e, requests, self.clip_length)
+        self._ck(rc, "sound_pitch_batch")
+        return res
+
+    def pitch_frames(self, request: int = 0):
+        """debug: the frame records (dicts of zlhip_pitch_frame's fields) of request `request` of the last pitch call"""
+        n = C.c_int32(0)
+        self._ck(self._lib.zlhip_debug_pitch_frames(self._e, request, None, 0, C.byref(n)), "debug_pitch_frames")
+        recs = (_abi.PitchFrame * max(1, n.value))()
+        self._ck(self._lib.zlhip_debug_pitch_frames(self._e, request, C.addressof(recs), n.value, C.byref(n)), "debug_pitch_frames")
+        return [{k: getattr(recs[i], k) for k in PITCH_FRAME_FIELDS} for i in range(n.value)]
+
+    def pitch_diff(self, request: int = 0, frame: int = 0):
+        """debug: d[1 .. t_max + 1] (uint64) of frame `frame` of request `request` of the last pitch call"""
+        n = C.c_int32(0)
+        self._ck(self._lib.zlhip_debug_pitch_diff(self._e, request, frame, None, 0, C.byref(n)), "debug_pitch_diff")
+        d = np.zeros(n.value, np.uint64)
+        self._ck(self._lib.zlhip_debug_pitch_diff(self._e, request, frame, d.ctypes.data, n.value, C.byref(n)), "debug_pitch_diff")
+        return d
+
+    def pitch_timings(self):
+        """device ms of the difference-function kernel and of the rest of the last pitch call made with profiling on"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        self._ck(self._lib.zlhip_debug_pitch_timings(self._e, C.byref(a), C.byref(b)), "debug_pitch_timings")
+        return a.value, b.value
 
     def overview_timings(self) -> float:
         """device ms of the last overview call made with profiling on (set_profiling)"""
@@ -836,6 +895,16 @@ class SamplerSynthGroup:
     def clip_tempo_batch(self, requests: Sequence[tuple]):
         rc, res = _tempo_call(self._lib.zlhip_group_sound_tempo_batch, self._g, requests, self.clip_length)
         self._ck(rc, "group_sound_tempo_batch")
+        return res
+
+    def clip_pitch(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, window: int = 0, max_frames: int = 0, f_min: float = 0.0,
+                   f_max: float = 0.0, threshold: int = 0, gate: int = 0) -> dict:
+        """SamplerSynth.clip_pitch: every member holds every clip, member 0 answers (zlhip_group_sound_pitch_batch)"""
+        return self.clip_pitch_batch([(clip, first_frame, num_frames, window, max_frames, f_min, f_max, threshold, gate)])[0]
+
+    def clip_pitch_batch(self, requests: Sequence):
+        rc, res = _pitch_call(self._lib.zlhip_group_sound_pitch_batch, self._g, requests, self.clip_length)
+        self._ck(rc, "group_sound_pitch_batch")
         return res
 
     # -- commands (global buses, slots and midi channels) --------------------------------------
