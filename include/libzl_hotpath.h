@@ -208,6 +208,23 @@ int  libzl_hotpath_clip_pitch(ClipAudioSource *c, float f_min, float f_max, floa
  * 127) through ClipAudioSource_setRootNote's path, so the next startNote uses it.  *root_note_out: the note set.  Returns 1, or 0 where
  * there is no pitch or the confidence is below min_confidence (nothing changes then, *root_note_out included), or a negative status. */
 int  libzl_hotpath_clip_detect_root_note(ClipAudioSource *c, float min_confidence, int *root_note_out);
+/* The clip's loudness (build-defined: the reference has no loudness measurement; ClipAudioSource_setGain takes a dB value the caller
+ * must know).  Measured on the device (zlhip_sound_loudness, sub_frames at its default) over the clip's current playback data between
+ * its start and its start + length, in frames as for libzl_hotpath_clip_pitch.  *lufs: the integrated loudness of ITU-R BS.1770-4 /
+ * EBU R 128; *peak_db: 20 log10 of the largest sample peak (not a true peak).  Returns 1, or 0 for "no loudness" -- silence, or
+ * nothing above -70 LUFS; *lufs is -inf then -- or a negative zlhip status (nothing is written then). */
+int  libzl_hotpath_clip_loudness(ClipAudioSource *c, double *lufs, float *peak_db);
+/* Bring the clip to target_lufs: measures as libzl_hotpath_clip_loudness, delta = target_lufs - lufs, held so that the sample peak
+ * stays at or below ceiling_db (delta = min(delta, ceiling_db - 20 log10(peak))), and sets the gain (float)(current gain + delta)
+ * through ClipAudioSource_setGain's path (a re-render starts from the original upload and the measured data already carries the
+ * current gain, hence the sum).  *gain_db_out: the gain now in effect.  Returns 1, or 0 where there is no loudness (nothing changes
+ * then), or a negative status; a NaN target or ceiling is ZLHIP_ERR_INVALID. */
+int  libzl_hotpath_clip_normalize(ClipAudioSource *c, float target_lufs, float ceiling_db, float *gain_db_out);
+/* Level a bank: ONE zlhip_sound_loudness_batch call for all clips and ONE zlhip_sound_rerender_batch call for those that change.  A
+ * clip that is NULL, not in the engine or without loudness stays as it is; gains_out[i] (may be NULL) is clip i's gain afterwards (0
+ * for NULL).  Duplicate clips are ZLHIP_ERR_INVALID.  If the re-render fails every clip and every stored gain is as it was.  Returns
+ * the number of clips levelled, or a negative status. */
+int  libzl_hotpath_clips_level(ClipAudioSource **clips, int count, float target_lufs, float ceiling_db, float *gains_out);
 /* A bank of clips in one engine call: every file is read, their `data` chunks go to the engine as raw PCM in ONE
  * zlhip_sound_upload_pcm_batch call (decoded on the device, one wait for the whole bank).  out[i] is the clip of paths[i], or NULL
  * for a file that cannot be opened or decoded -- it does not fail the others.  Returns the number of clips loaded (or a negative

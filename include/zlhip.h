@@ -40,7 +40,8 @@ extern "C" {
  *    zlhip_sound_upload_pcm / _batch (clips from raw PCM, decoded on the device), zlhip_sound_convert_rate / _batch (clips converted to
  *    another sample rate on the device, band-limited), zlhip_resample_design, zlhip_sound_info_get, zlhip_debug_sound_extent, zlhip_sound_onsets / _batch (a clip's transients, found on
  *    the device), zlhip_onset_resolve, zlhip_sound_tempo / _batch (a clip's tempo, estimated on the device), zlhip_tempo_resolve,
- *    zlhip_sound_pitch / _batch (a clip's pitch, detected on the device), zlhip_pitch_resolve. */
+ *    zlhip_sound_pitch / _batch (a clip's pitch, detected on the device), zlhip_pitch_resolve, zlhip_sound_loudness / _batch (a clip's
+ *    loudness, measured on the device), zlhip_loudness_resolve, zlhip_loudness_design. */
 #define ZLHIP_ABI_VERSION 3
 
 /* status codes */
@@ -350,6 +351,45 @@ int zlhip_debug_pitch_frames(zlhip_engine *e, int32_t request, zlhip_pitch_frame
 int zlhip_debug_pitch_diff(zlhip_engine *e, int32_t request, int32_t frame, uint64_t *d, int32_t capacity, int32_t *lags);
 /* measurement: device time of the difference-function kernel and of the rest of the last call made with profiling on */
 int zlhip_debug_pitch_timings(zlhip_engine *e, float *diff_ms, float *rest_ms);
+/* Loudness: how loud a clip is (a build-defined extension, the reference has no loudness measurement) -- the
+ * integrated loudness of ITU-R BS.1770-4 / EBU R 128 and the sample peak of the sound's CURRENT playback data, measured on the device:
+ *   K-weighting: two biquads per channel (a high shelf, the RLB high-pass), designed for the sound's rate in double
+ *   (zlhip_loudness_design: coeffs[0..4] = the shelf's b0 b1 b2 a1 a2, coeffs[5..9] = the high-pass's 1 -2 1 a1 a2; at 48 kHz BS.1770's
+ *   tables), run in double as transposed direct form II, o = b0 v + s1; s1 = (b1 v - a1 o) + s2; s2 = b2 v - a2 o, one IEEE operation
+ *   per operator.  A non-finite sample is 0; subnormals are kept.
+ *   sub = sub_frames (given as 0: floor(rate 0.1 + 0.5), 100 ms); S = num_frames / sub whole sub-blocks.  Sub-block k is filtered from
+ *   zero state at the start of sub-block k - 1 (sub-block 0: at first_frame) and its own outputs are squared and summed per channel in
+ *   sample order: a zlhip_loudness_sub per sub-block, sum[2] and peak[2] (max |v| over its finite samples; the last one also scans
+ *   the remainder behind the S whole sub-blocks for the peak); a mono sound leaves sum[1] = peak[1] = 0.  Against one serial pass the
+ *   warm-up changes a sub-block's sum by less than 1e-10 relative.
+ *   u[k] = sum[0] + sum[1]; the blocks j = 0 .. S - 4: z_j = (((u[j] + u[j+1]) + u[j+2]) + u[j+3]) / (4 sub), 400 ms with 75 % overlap.
+ *   S < 4 (a one-shot shorter than 400 ms): the sub-blocks are ceil(num_frames / sub), the last one partial, and there is one block
+ *   over the whole region, z_0 = (u[0] + u[1] + ...) / num_frames.
+ *   The blocks with z_j > 1.1724653045822981e-07 (-70 LUFS) pass the absolute gate, above_absolute of them; relative_gate = their
+ *   mean / 10; the blocks above both gates, above_relative of them, give mean_square = their mean and
+ *   lufs = -0.691 + 10 log10(mean_square).  No block above -70 LUFS -- silence -- is not an error: lufs = -inf, mean_square =
+ *   relative_gate = 0, above_absolute = above_relative = 0.  peak[c] is the largest sample peak of channel c; sub_blocks and blocks
+ *   count what was summed.
+ *   Limits: num_frames >= 1, first_frame >= 0, first_frame + num_frames <= the sound's length; sub_frames 0 or in [16, 131072]; at
+ *   most 65536 sub-blocks per request and 1048576 per call; nreq >= 0: anything else is ZLHIP_ERR_INVALID.  On any error out is not
+ *   written; one bad request fails the call.
+ *   A call is one kernel launch whatever its size, behind one copy of the request records; it waits once and 24 bytes per sub-block
+ *   come back.  It runs on the engine's stream behind what is queued there and the resident real-time kernel keeps running.
+ *   Not provided: true peak (the peak is the sample peak: leave headroom), loudness range, momentary / short-term meters (the
+ *   sub-block sums are there through zlhip_debug_loudness_subs), channel weights beyond stereo. */
+typedef struct zlhip_loudness_request { int32_t id, first_frame, num_frames, sub_frames; } zlhip_loudness_request;
+typedef struct zlhip_loudness { double lufs, mean_square, relative_gate; float peak[2]; int32_t sub_blocks, blocks, above_absolute, above_relative; } zlhip_loudness;
+typedef struct zlhip_loudness_sub { double sum[2]; float peak[2]; } zlhip_loudness_sub;
+/* host only: fills sub_frames given as 0 and checks every limit that does not need the sound; a refused request is left as it was */
+int zlhip_loudness_resolve(double sample_rate, zlhip_loudness_request *r);
+/* host only: the ten K-weighting coefficients for a sample rate (coeffs: [10]) */
+int zlhip_loudness_design(double sample_rate, double *coeffs);
+int zlhip_sound_loudness(zlhip_engine *e, const zlhip_loudness_request *r, zlhip_loudness *out);
+int zlhip_sound_loudness_batch(zlhip_engine *e, const zlhip_loudness_request *reqs, int32_t nreq, zlhip_loudness *out);
+/* the sub-block records of request `request` of the last call (records: [capacity], may be NULL to ask for *count only) */
+int zlhip_debug_loudness_subs(zlhip_engine *e, int32_t request, zlhip_loudness_sub *records, int32_t capacity, int32_t *count);
+/* measurement: device time of the kernel of the last call made with profiling on */
+int zlhip_debug_loudness_timings(zlhip_engine *e, float *kernel_ms);
 /* Clips from raw PCM.  `frames` is host memory, pageable or page-locked: `length` frames of `channels`
  *   interleaved little-endian samples, exactly the bytes of a WAV `data` chunk.  They are copied raw into a device staging buffer and
  *   decoded there into the arena's layout; one decode launch serves each staging pass and the call waits for the device once.
@@ -577,6 +617,8 @@ int  zlhip_group_sound_onsets_batch(zlhip_group *g, const zlhip_onset_request *r
 int  zlhip_group_sound_tempo_batch(zlhip_group *g, const zlhip_tempo_request *reqs, int32_t nreq, zlhip_tempo *out);
 /* zlhip_sound_pitch_batch: member 0 answers */
 int  zlhip_group_sound_pitch_batch(zlhip_group *g, const zlhip_pitch_request *reqs, int32_t nreq, zlhip_pitch *out);
+/* zlhip_sound_loudness_batch: member 0 answers */
+int  zlhip_group_sound_loudness_batch(zlhip_group *g, const zlhip_loudness_request *reqs, int32_t nreq, zlhip_loudness *out);
 /* zlhip_handle_commands_voices over the whole synth (taken, voices optional) */
 int  zlhip_group_handle_commands(zlhip_group *g, const zlhip_clip_command *cmds, int32_t count, uint64_t current_tick, int32_t *taken,
                                  int32_t *voices);

@@ -140,6 +140,19 @@ class PitchFrame(C.Structure):
                 ("d_mid", C.c_uint64), ("d_hi", C.c_uint64), ("cum", C.c_uint64)]
 
 
+class LoudnessRequest(C.Structure):
+    _fields_ = [("id", C.c_int32), ("first_frame", C.c_int32), ("num_frames", C.c_int32), ("sub_frames", C.c_int32)]
+
+
+class Loudness(C.Structure):
+    _fields_ = [("lufs", C.c_double), ("mean_square", C.c_double), ("relative_gate", C.c_double), ("peak", C.c_float * 2),
+                ("sub_blocks", C.c_int32), ("blocks", C.c_int32), ("above_absolute", C.c_int32), ("above_relative", C.c_int32)]
+
+
+class LoudnessSub(C.Structure):
+    _fields_ = [("sum", C.c_double * 2), ("peak", C.c_float * 2)]
+
+
 class Tempo(C.Structure):
     _fields_ = [("bpm", C.c_float), ("confidence", C.c_float), ("lag_coarse", C.c_int32), ("lag_fine", C.c_int32), ("doublings", C.c_int32),
                 ("shift", C.c_int32), ("hops", C.c_int32), ("reserved", C.c_int32), ("acf_lo", C.c_uint64), ("acf_mid", C.c_uint64),
@@ -214,6 +227,12 @@ SIGNATURES = {
     "zlhip_debug_pitch_frames": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_debug_pitch_diff": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_debug_pitch_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "zlhip_loudness_resolve": (C.c_int, [C.c_double, C.POINTER(LoudnessRequest)]),
+    "zlhip_loudness_design": (C.c_int, [C.c_double, C.POINTER(C.c_double)]),
+    "zlhip_sound_loudness": (C.c_int, [_E, C.POINTER(LoudnessRequest), C.POINTER(Loudness)]),
+    "zlhip_sound_loudness_batch": (C.c_int, [_E, C.POINTER(LoudnessRequest), C.c_int32, C.POINTER(Loudness)]),
+    "zlhip_debug_loudness_subs": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zlhip_debug_loudness_timings": (C.c_int, [_E, C.POINTER(C.c_float)]),
     "zlhip_sound_upload_pcm": (C.c_int, [_E, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_int32)]),
     "zlhip_sound_upload_pcm_batch": (C.c_int, [_E, C.POINTER(PcmSource), C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_debug_upload_pcm_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -280,6 +299,7 @@ SIGNATURES = {
     "zlhip_group_sound_onsets_batch": (C.c_int, [_E, C.POINTER(OnsetRequest), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "zlhip_group_sound_tempo_batch": (C.c_int, [_E, C.POINTER(TempoRequest), C.c_int32, C.POINTER(Tempo)]),
     "zlhip_group_sound_pitch_batch": (C.c_int, [_E, C.POINTER(PitchRequest), C.c_int32, C.POINTER(Pitch)]),
+    "zlhip_group_sound_loudness_batch": (C.c_int, [_E, C.POINTER(LoudnessRequest), C.c_int32, C.POINTER(Loudness)]),
     "zlhip_group_handle_commands": (C.c_int, [_E, C.POINTER(ClipCommand), C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "zlhip_group_start_voice": (C.c_int, [_E, C.c_int32, C.c_int32, C.POINTER(ClipCommand), C.c_uint64]),
     "zlhip_group_stop_voice": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_int]),

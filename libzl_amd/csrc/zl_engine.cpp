@@ -31,6 +31,7 @@
 #include "zl_onset.h"
 #include "zl_tempo.h"
 #include "zl_pitch.h"
+#include "zl_loudness.h"
 #include "zl_overview.h"
 #include "zl_resample.h"
 #include "zl_decode.h"
@@ -74,6 +75,7 @@ enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a ca
        ZB_ON_REQ, ZB_ON_E, ZB_ON_N, ZB_ON_PS,                // transients: a call's request records (with a host twin), and per hop E, N and the windows' running maxima
        ZB_TP_REQ, ZB_TP_E, ZB_TP_W, ZB_TP_A, ZB_TP_STAT,      // tempo: a call's request records (the energy pass's and the tempo kernels', one host twin), per hop E and W, per lag A, per request the flux's statistics
        ZB_PT_REQ, ZB_PT_D, ZB_PT_STAT, ZB_PT_FRAME,           // pitch: a call's request records (with a host twin), per frame and lag d, per frame the diff kernel's statistics and the frame records
+       ZB_LD_REQ,                                             // loudness: a call's request records (with a host twin)
        ZB_COUNT };
 
 }  // namespace
@@ -128,6 +130,13 @@ struct zlhip_engine {
         std::vector<Last> last;                                                 // per request of the last call (zlhip_debug_pitch_frames / _diff)
         hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; float diffMs = 0.0f, restMs = 0.0f;   // profiling (zlhip_debug_pitch_timings)
     } pt;
+    // loudness (zlhip_sound_loudness; zl_loudness.h)
+    struct Loudness {
+        ZlLdSub *hOut = nullptr, *dOut = nullptr; size_t outCap = 0;            // a call's sub-block records, in host memory mapped into the device
+        struct Last { int32_t item_base, items; };
+        std::vector<Last> last;                                                 // per request of the last call (zlhip_debug_loudness_subs)
+        hipEvent_t ev[2] = {nullptr, nullptr}; float kernelMs = 0.0f;           // profiling (zlhip_debug_loudness_timings)
+    } ld;
     // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h)
     struct Pcm {
         std::vector<hipEvent_t> ev;                                 // profiling: before every pass's copies and every decode launch, behind the last
@@ -486,6 +495,8 @@ void zlhip_engine_destroy(zlhip_engine *e)
     if (e->tp.hOut) (void)hipHostFree(e->tp.hOut);
     for (hipEvent_t ev : e->pt.ev) if (ev) (void)hipEventDestroy(ev);
     if (e->pt.hOut) (void)hipHostFree(e->pt.hOut);
+    for (hipEvent_t ev : e->ld.ev) if (ev) (void)hipEventDestroy(ev);
+    if (e->ld.hOut) (void)hipHostFree(e->ld.hOut);
     for (hipEvent_t ev : e->pcm.ev) if (ev) (void)hipEventDestroy(ev);
     if (e->evJoin) (void)hipEventDestroy(e->evJoin);
     if (e->evPlanTail) (void)hipEventDestroy(e->evPlanTail);
@@ -1913,6 +1924,113 @@ int zlhip_debug_pitch_timings(zlhip_engine *e, float *diff_ms, float *rest_ms)
     if (!e) return ZLHIP_ERR_INVALID;
     if (diff_ms) *diff_ms = e->pt.diffMs;
     if (rest_ms) *rest_ms = e->pt.restMs;
+    return ZLHIP_OK;
+}
+
+// ---- loudness (zl_loudness.h, zl_loudness.hip) -----------------------------------------------------------------------------
+// How loud a clip is: BS.1770's integrated loudness and the sample peak.  The kernel filters and sums the sub-blocks, one lane each,
+// and writes their records into host memory mapped into the device; the blocks, the gates and lufs are derived here (zl_ld_finish).
+// Synchronisation and buffers as for the transients, the tempo and the pitch: the call runs on the engine's stream behind what is
+// queued there and leaves the resident real-time kernel alone; its buffers are allocated by the first call and grow only.
+int zlhip_loudness_design(double sample_rate, double *coeffs)
+{
+    if (!coeffs) return ZLHIP_ERR_INVALID;
+    double c[10];
+    if (zl_ld_design(sample_rate, c) != 0) return ZLHIP_ERR_INVALID;
+    std::memcpy(coeffs, c, sizeof(c));
+    return ZLHIP_OK;
+}
+
+int zlhip_loudness_resolve(double sample_rate, zlhip_loudness_request *r)
+{
+    if (!r) return ZLHIP_ERR_INVALID;
+    int32_t sub = r->sub_frames;
+    if (zl_ld_resolve(sample_rate, r->first_frame, r->num_frames, &sub) != 0) return ZLHIP_ERR_INVALID;
+    r->sub_frames = sub;
+    return ZLHIP_OK;
+}
+
+static int ld_reserve(zlhip_engine *e, size_t nreq, size_t items)
+{
+    GrowBuf *b = e->scratch; zlhip_engine::Loudness &t = e->ld;
+    if (nreq <= b[ZB_LD_REQ].cap && items <= t.outCap) return ZLHIP_OK;
+    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }
+    ZlQuiesce quiet(e);
+    const int rc = grow_buf(e, b[ZB_LD_REQ], nreq, sizeof(ZlLdRequest), std::max<size_t>(nreq * 2, 64), true, "sound_loudness: no memory for the call's buffers");
+    if (rc != ZLHIP_OK) return rc;
+    ZL_HIP(e, grow_mapped(&t.hOut, &t.dOut, &t.outCap, std::max<size_t>(items, 512)));
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_loudness_batch(zlhip_engine *e, const zlhip_loudness_request *reqs, int32_t nreq, zlhip_loudness *out)
+{
+    static_assert(sizeof(zlhip_loudness) == sizeof(ZlLdResult), "zl_ld_finish writes zlhip_loudness's layout");
+    static_assert(sizeof(zlhip_loudness_sub) == sizeof(ZlLdSub) && sizeof(ZlLdSub) == 24, "the device writes zlhip_loudness_sub's layout");
+    if (!e || nreq < 0 || (nreq > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
+    if (nreq == 0) return ZLHIP_OK;
+    // validate and resolve everything before anything is written and before the first HIP call
+    std::vector<ZlLdRequest> geo((size_t)nreq);
+    int64_t items = 0;
+    for (int32_t i = 0; i < nreq; ++i) {
+        zlhip_loudness_request q = reqs[i];
+        if (q.id < 0 || q.id >= e->cfg.max_sounds || !e->hc.soundUsed[q.id]) return fail(e, ZLHIP_ERR_INVALID, "sound_loudness: no such sound");
+        const ZlSound &s = e->hc.sounds[q.id];
+        ZlLdRequest &R = geo[(size_t)i];
+        if (zlhip_loudness_resolve(s.sample_rate, &q) != ZLHIP_OK || zl_ld_design(s.sample_rate, R.c) != 0)
+            return fail(e, ZLHIP_ERR_INVALID, "sound_loudness: a field of the request is outside its limits");
+        if ((int64_t)q.first_frame + q.num_frames > s.length) return fail(e, ZLHIP_ERR_INVALID, "sound_loudness: the frames do not lie inside the sound's playback data");
+        R.src = 0;                                                 // (the address: behind ld_reserve, with the other HIP-side state)
+        R.first = q.first_frame; R.frames = q.num_frames; R.sub = q.sub_frames; R.channels = s.channels;
+        R.items = (int32_t)zl_ld_items(q.num_frames, q.sub_frames); R.item_base = (int32_t)items;
+        items += R.items;
+        if (items > ZL_LD_MAX_CALL_ITEMS) return fail(e, ZLHIP_ERR_INVALID, "sound_loudness_batch: more than 1048576 sub-blocks in one call");
+    }
+    ZL_HIP(e, hipSetDevice(e->device));
+    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    { const int rc = ld_reserve(e, (size_t)nreq, (size_t)items); if (rc != ZLHIP_OK) return rc; }
+    zlhip_engine::Loudness &t = e->ld;
+    ZlLdRequest *const hReq = (ZlLdRequest *)e->scratch[ZB_LD_REQ].h, *const dReq = (ZlLdRequest *)e->scratch[ZB_LD_REQ].d;
+    t.last.clear();
+    for (int32_t i = 0; i < nreq; ++i) {
+        ZlLdRequest &R = hReq[i];
+        R = geo[(size_t)i];
+        R.src = (uint64_t)(uintptr_t)arena_ptr(e, e->hc.sounds[reqs[i].id].offset);
+        t.last.push_back({R.item_base, R.items});
+    }
+    const bool prof = e->profiling;
+    for (int x = 0; prof && x < 2; ++x) if (!t.ev[x]) ZL_HIP(e, hipEventCreate(&t.ev[x]));
+    ZL_HIP(e, hipMemcpyAsync(dReq, hReq, (size_t)nreq * sizeof(ZlLdRequest), hipMemcpyHostToDevice, e->stream));
+    if (prof) ZL_HIP(e, hipEventRecord(t.ev[0], e->stream));
+    ZL_KERNEL(e, zl_launch_loudness(dReq, nreq, (int32_t)items, t.dOut, e->stream));
+    if (prof) ZL_HIP(e, hipEventRecord(t.ev[1], e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    if (prof) ZL_HIP(e, hipEventElapsedTime(&t.kernelMs, t.ev[0], t.ev[1]));
+    for (int32_t i = 0; i < nreq; ++i) {
+        const ZlLdRequest &R = geo[(size_t)i];
+        ZlLdResult r;
+        zl_ld_finish(t.hOut + R.item_base, R.frames, R.sub, &r);
+        std::memcpy(&out[i], &r, sizeof(r));
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_loudness(zlhip_engine *e, const zlhip_loudness_request *r, zlhip_loudness *out) { return zlhip_sound_loudness_batch(e, r, 1, out); }
+
+int zlhip_debug_loudness_subs(zlhip_engine *e, int32_t request, zlhip_loudness_sub *records, int32_t capacity, int32_t *count)
+{
+    if (!e || request < 0 || (size_t)request >= e->ld.last.size()) return ZLHIP_ERR_INVALID;
+    const zlhip_engine::Loudness::Last &l = e->ld.last[(size_t)request];
+    if (count) *count = l.items;
+    if (!records) return ZLHIP_OK;
+    if (capacity < l.items) return fail(e, ZLHIP_ERR_CAPACITY, "debug_loudness_subs: capacity below the request's sub-blocks");
+    std::memcpy(records, e->ld.hOut + l.item_base, (size_t)l.items * sizeof(ZlLdSub));      // (the call has waited: the records are in host memory)
+    return ZLHIP_OK;
+}
+
+int zlhip_debug_loudness_timings(zlhip_engine *e, float *kernel_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (kernel_ms) *kernel_ms = e->ld.kernelMs;
     return ZLHIP_OK;
 }
 

@@ -911,12 +911,17 @@ void ClipAudioSource_setPitch(ClipAudioSource *c, float v)         // :279-290
     clip_rerender(c);
 }
 
-void ClipAudioSource_setGain(ClipAudioSource *c, float db)         // :305-311
+static void clip_set_gain(ClipAudioSource *c, float db)            // call with G.mu held
 {
-    std::lock_guard<std::mutex> lk(G.mu);
     if (db != db) return;
     { std::lock_guard<std::mutex> sl(c->setMu); c->gainDb = std::min(std::max(-FLT_MAX, db), FLT_MAX); }
     clip_rerender(c);
+}
+
+void ClipAudioSource_setGain(ClipAudioSource *c, float db)         // :305-311
+{
+    std::lock_guard<std::mutex> lk(G.mu);
+    clip_set_gain(c, db);
 }
 
 // WaveFormItem::paint draws the clip's thumbnail between m_start and qMin(m_end, total length) seconds (WaveFormItem.cpp:130-139).
@@ -1074,6 +1079,109 @@ int libzl_hotpath_clip_detect_root_note(ClipAudioSource *c, float min_confidence
     ClipAudioSource_setRootNote(c, t.root_note);
     if (root_note_out) *root_note_out = t.root_note;
     return 1;
+}
+
+// A freshly loaded bank is unusable until its clips sit at one level: ClipAudioSource_setGain takes a dB value the caller must already
+// know, and the sample peak is not loudness.  Here: the integrated loudness (BS.1770 / EBU R 128) and the sample peak of the data the
+// clip plays now between its start and its start + length, measured on the device (zlhip_sound_loudness).
+// Build-defined: the reference has no loudness measurement.
+static int clip_loudness_request(ClipAudioSource *c, zlhip_loudness_request *q)      // call with G.mu held
+{
+    if (!G.engine || c->engineClip < 0) return ZLHIP_ERR_STATE;
+    zlhip_sound_info info;
+    { const int rc = zlhip_sound_info_get(G.engine, c->engineClip, &info); if (rc != ZLHIP_OK) return rc; }
+    float startSec, lengthSec;
+    { std::lock_guard<std::mutex> sl(c->setMu); startSec = c->startPositionInSeconds; lengthSec = c->lengthInSeconds; }
+    // the region in frames, cast as for libzl_hotpath_clip_pitch
+    auto frame = [&](float seconds) -> int64_t {
+        const double f = (double)seconds * info.sample_rate;
+        return !(f > 0.0) ? 0 : (f >= (double)info.length ? (int64_t)info.length : (int64_t)f);
+    };
+    const int64_t start = frame(startSec), stop = frame(startSec + lengthSec);
+    if (stop <= start) return ZLHIP_ERR_INVALID;
+    *q = zlhip_loudness_request{ c->engineClip, (int32_t)start, (int32_t)(stop - start), 0 };
+    return ZLHIP_OK;
+}
+
+static float loudness_peak(const zlhip_loudness &l) { return std::max(l.peak[0], l.peak[1]); }
+
+// the gain that brings a measured clip to the target, held under the ceiling: the measured data already carries the current gain and
+// a re-render starts from the original upload, hence the sum
+static float level_gain(const zlhip_loudness &l, float current_db, float target_lufs, float ceiling_db)
+{
+    double delta = (double)target_lufs - l.lufs;
+    const float peak = loudness_peak(l);
+    if (peak > 0.0f) delta = std::min(delta, (double)ceiling_db - 20.0 * std::log10((double)peak));
+    return (float)((double)current_db + delta);
+}
+
+int libzl_hotpath_clip_loudness(ClipAudioSource *c, double *lufs, float *peak_db)
+{
+    if (!c) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    zlhip_loudness_request q; zlhip_loudness l;
+    { const int rc = clip_loudness_request(c, &q); if (rc != ZLHIP_OK) return rc; }
+    { const int rc = zlhip_sound_loudness(G.engine, &q, &l); if (rc != ZLHIP_OK) return rc; }
+    if (lufs) *lufs = l.lufs;
+    if (peak_db) *peak_db = (float)(20.0 * std::log10((double)loudness_peak(l)));      // (a peak of 0: -inf)
+    return l.above_absolute > 0 ? 1 : 0;
+}
+
+int libzl_hotpath_clip_normalize(ClipAudioSource *c, float target_lufs, float ceiling_db, float *gain_db_out)
+{
+    if (!c || target_lufs != target_lufs || ceiling_db != ceiling_db) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    zlhip_loudness_request q; zlhip_loudness l;
+    { const int rc = clip_loudness_request(c, &q); if (rc != ZLHIP_OK) return rc; }
+    { const int rc = zlhip_sound_loudness(G.engine, &q, &l); if (rc != ZLHIP_OK) return rc; }
+    if (l.above_absolute == 0) return 0;
+    float current;
+    { std::lock_guard<std::mutex> sl(c->setMu); current = c->gainDb; }
+    clip_set_gain(c, level_gain(l, current, target_lufs, ceiling_db));
+    if (gain_db_out) { std::lock_guard<std::mutex> sl(c->setMu); *gain_db_out = c->gainDb; }
+    return 1;
+}
+
+// A whole bank: ONE zlhip_sound_loudness_batch and ONE zlhip_sound_rerender_batch for the clips that change.
+int libzl_hotpath_clips_level(ClipAudioSource **clips, int count, float target_lufs, float ceiling_db, float *gains_out)
+{
+    if (count < 0 || (count > 0 && !clips) || target_lufs != target_lufs || ceiling_db != ceiling_db) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    if (!G.engine) return ZLHIP_ERR_STATE;
+    for (int i = 0; i < count; ++i)
+        for (int j = 0; clips[i] && j < i; ++j) if (clips[j] == clips[i]) return ZLHIP_ERR_INVALID;
+    std::vector<int> who; std::vector<zlhip_loudness_request> reqs;
+    for (int i = 0; i < count; ++i) {
+        zlhip_loudness_request q;
+        if (!clips[i] || clip_loudness_request(clips[i], &q) != ZLHIP_OK) continue;      // NULL or not in the engine: stays as it is
+        who.push_back(i); reqs.push_back(q);
+    }
+    std::vector<zlhip_loudness> res(reqs.size());
+    if (!reqs.empty()) { const int rc = zlhip_sound_loudness_batch(G.engine, reqs.data(), (int32_t)reqs.size(), res.data()); if (rc != ZLHIP_OK) return rc; }
+    std::vector<float> gains((size_t)count, 0.0f), before((size_t)count, 0.0f);
+    for (int i = 0; i < count; ++i) if (clips[i]) { std::lock_guard<std::mutex> sl(clips[i]->setMu); gains[(size_t)i] = before[(size_t)i] = clips[i]->gainDb; }
+    std::vector<int> changed; std::vector<int32_t> ids; std::vector<zlhip_rerender_params> params;
+    for (size_t n = 0; n < who.size(); ++n) {
+        if (res[n].above_absolute == 0) continue;                  // no loudness: stays as it is
+        ClipAudioSource *c = clips[who[n]];
+        const float g = level_gain(res[n], before[(size_t)who[n]], target_lufs, ceiling_db);
+        if (g != g) continue;
+        zlhip_rerender_params p;
+        std::lock_guard<std::mutex> sl(c->setMu);
+        c->gainDb = std::min(std::max(-FLT_MAX, g), FLT_MAX);
+        gains[(size_t)who[n]] = c->gainDb;
+        p.gain_db = c->gainDb; p.pitch_semitones = c->pitchChange; p.speed_ratio = c->speedRatio; p.reserved = 0;
+        changed.push_back(who[n]); ids.push_back(c->engineClip); params.push_back(p);
+    }
+    if (!ids.empty()) {
+        const int rc = zlhip_sound_rerender_batch(G.engine, ids.data(), params.data(), (int32_t)ids.size());
+        if (rc != ZLHIP_OK) {                                      // all or nothing: every clip plays what it played, so every gain goes back
+            for (int i : changed) { std::lock_guard<std::mutex> sl(clips[i]->setMu); clips[i]->gainDb = before[(size_t)i]; }
+            return rc;
+        }
+    }
+    if (gains_out) for (int i = 0; i < count; ++i) gains_out[i] = gains[(size_t)i];
+    return (int)changed.size();
 }
 
 void ClipAudioSource_setVolume(ClipAudioSource *c, float vol)      // ClipAudioSource.cpp:313-326

@@ -160,6 +160,26 @@ def _pitch_call(fn, handle, requests, length_of):
     return rc, [{k: getattr(out[i], k) for k in PITCH_FIELDS} for i in range(len(requests))]
 
 
+LOUDNESS_FIELDS = tuple(name for name, _ in _abi.Loudness._fields_)
+
+
+def _loudness_call(fn, handle, requests, length_of):
+    """one zlhip_sound_loudness_batch-shaped call over (clip[, first_frame[, num_frames[, sub_frames]]]) tuples, or dicts with "clip" and any
+    of those keys (num_frames None / missing = to the end of the clip, sub_frames 0 / missing = 100 ms) -> (status, one dict of
+    zlhip_loudness's fields per request; peak is a pair)"""
+    reqs = (_abi.LoudnessRequest * max(1, len(requests)))()
+    for i, r in enumerate(requests):
+        if isinstance(r, dict):
+            r = (r["clip"], r.get("first_frame", 0), r.get("num_frames"), r.get("sub_frames", 0))
+        r = tuple(r) if isinstance(r, (tuple, list)) else (r,)
+        r = r + (0, None, 0)[len(r) - 1:]
+        clip, first = int(r[0]), int(r[1])
+        reqs[i] = _abi.LoudnessRequest(clip, first, int(length_of(clip) - first if r[2] is None else r[2]), int(r[3]))
+    out = (_abi.Loudness * max(1, len(requests)))()
+    rc = fn(handle, reqs, len(requests), out)
+    return rc, [{k: (tuple(out[i].peak) if k == "peak" else getattr(out[i], k)) for k in LOUDNESS_FIELDS} for i in range(len(requests))]
+
+
 TEMPO_FIELDS = tuple(name for name, _ in _abi.Tempo._fields_ if name != "reserved")
 
 
@@ -494,6 +514,34 @@ class SamplerSynth:
         a, b = C.c_float(0.0), C.c_float(0.0)
         self._ck(self._lib.zlhip_debug_pitch_timings(self._e, C.byref(a), C.byref(b)), "debug_pitch_timings")
         return a.value, b.value
+
+    def clip_loudness(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, sub_frames: int = 0) -> dict:
+        """The integrated loudness (ITU-R BS.1770-4 / EBU R 128) and the sample peak of the clip's current playback data over
+        [first_frame, first_frame + num_frames) (None: to the end), measured on the device (zlhip_sound_loudness):
+        a dict of zlhip_loudness's fields -- lufs, mean_square, relative_gate, peak (a pair), sub_blocks, blocks, above_absolute,
+        above_relative.  above_absolute == 0 (lufs == -inf) means "no loudness": silence, or nothing above -70 LUFS."""
+        return self.clip_loudness_batch([(clip, first_frame, num_frames, sub_frames)])[0]
+
+    def clip_loudness_batch(self, requests: Sequence):
+        """Several requests in one call (zlhip_sound_loudness_batch: one launch whatever the count).  requests: tuples
+        (clip[, first_frame[, num_frames[, sub_frames]]]) or dicts; one dict each."""
+        rc, res = _loudness_call(self._lib.zlhip_sound_loudness_batch, self._e, requests, self.clip_length)
+        self._ck(rc, "sound_loudness_batch")
+        return res
+
+    def loudness_subs(self, request: int = 0):
+        """debug: the sub-block records of request `request` of the last loudness call -> (sum [n, 2] float64, peak [n, 2] float32)"""
+        n = C.c_int32(0)
+        self._ck(self._lib.zlhip_debug_loudness_subs(self._e, request, None, 0, C.byref(n)), "debug_loudness_subs")
+        recs = np.zeros(max(1, n.value), np.dtype([("sum", np.float64, 2), ("peak", np.float32, 2)]))
+        self._ck(self._lib.zlhip_debug_loudness_subs(self._e, request, recs.ctypes.data, n.value, C.byref(n)), "debug_loudness_subs")
+        return recs["sum"][:n.value].copy(), recs["peak"][:n.value].copy()
+
+    def loudness_timings(self) -> float:
+        """device ms of the kernel of the last loudness call made with profiling on"""
+        a = C.c_float(0.0)
+        self._ck(self._lib.zlhip_debug_loudness_timings(self._e, C.byref(a)), "debug_loudness_timings")
+        return a.value
 
     def overview_timings(self) -> float:
         """device ms of the last overview call made with profiling on (set_profiling)"""
@@ -905,6 +953,15 @@ class SamplerSynthGroup:
     def clip_pitch_batch(self, requests: Sequence):
         rc, res = _pitch_call(self._lib.zlhip_group_sound_pitch_batch, self._g, requests, self.clip_length)
         self._ck(rc, "group_sound_pitch_batch")
+        return res
+
+    def clip_loudness(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, sub_frames: int = 0) -> dict:
+        """SamplerSynth.clip_loudness: every member holds every clip, member 0 answers (zlhip_group_sound_loudness_batch)"""
+        return self.clip_loudness_batch([(clip, first_frame, num_frames, sub_frames)])[0]
+
+    def clip_loudness_batch(self, requests: Sequence):
+        rc, res = _loudness_call(self._lib.zlhip_group_sound_loudness_batch, self._g, requests, self.clip_length)
+        self._ck(rc, "group_sound_loudness_batch")
         return res
 
     # -- commands (global buses, slots and midi channels) --------------------------------------

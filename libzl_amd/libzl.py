@@ -99,6 +99,9 @@ SIGNATURES = {
     "libzl_hotpath_clip_match_tempo": (C.c_int, [_P, C.c_float, C.c_float, C.POINTER(C.c_float)]),
     "libzl_hotpath_clip_pitch": (C.c_int, [_P, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "libzl_hotpath_clip_detect_root_note": (C.c_int, [_P, C.c_float, C.POINTER(C.c_int)]),
+    "libzl_hotpath_clip_loudness": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_float)]),
+    "libzl_hotpath_clip_normalize": (C.c_int, [_P, C.c_float, C.c_float, C.POINTER(C.c_float)]),
+    "libzl_hotpath_clips_level": (C.c_int, [C.POINTER(_P), C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float)]),
     "libzl_wav_read": (C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "libzl_hotpath_clips_new": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.POINTER(_P)]),
     "libzl_hotpath_clips_convert": (C.c_int, [C.POINTER(_P), C.c_int]),
