@@ -18,6 +18,7 @@ import numpy as np
 from numpy.lib.stride_tricks import sliding_window_view
 
 f32 = np.float32
+MAX_WINDOW = 4608          # W + O, the longest seek window a render may have
 
 
 def geometry(sr: float, length: int, gain_db: float, pitch: float, speed: float) -> dict:
@@ -35,6 +36,11 @@ def geometry(sr: float, length: int, gain_db: float, pitch: float, speed: float)
     S = math.floor(sr * seq_ms / 1000)
     W = math.floor(sr * seek_ms / 1000)
     stretch = tau != 1.0
+    # a source the stretch cannot take: the sequence must be longer than the overlap it is cross-faded over (rates below 425 Hz at
+    # tau >= 2), there must be a candidate to seek over, and the seek window W + O must fit the 4608 frames the seek stages per
+    # channel (rates from 204850 Hz at tau <= 0.5).  Where the stretch does not run there is nothing to reject
+    if stretch and (S <= O or W < 1 or W + O > MAX_WINDOW):
+        raise ValueError("a sample rate the stretch cannot take")
     N1 = math.floor(length / tau) if stretch else length
     nseg = -(-N1 // (S - O)) if stretch else 0
     return dict(r=r, tau=tau, N=N, N1=N1, O=O, S=S, W=W, nseg=nseg, stretch=stretch, resample=bool(pitch != 0),

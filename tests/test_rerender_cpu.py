@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 
 import stretch_ref as sr_
-from rerender_cases import GAINS, PITCHES, RATES, SPEEDS, cases, lengths, same_bits, source
+from rerender_cases import (GAINS, LAST_FRAME_CASES, PITCHES, RATES, SPEEDS, TIE_SPEED, cases, edge_cases, edge_id, holds_ties,
+                            last_frame_source, lengths, same_bits, source, tie_cases, tie_source)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
@@ -52,16 +53,101 @@ def test_geometry_matches_the_restatement(host):
         assert host.zlst_geometry(48000.0, 1000, *bad, geo.ctypes.data) == -1, bad
 
 
+def test_geometry_limits(host):
+    """what the stretch accepts and rejects at the ends of the sample-rate range, host build and restatement alike: the seek window
+    W + O may be 4608 frames and no more, the sequence must be longer than the overlap, and neither matters where the stretch
+    does not run (tau == 1)"""
+    def both(sr, speed, pitch):
+        geo = np.zeros(9, np.int64)
+        rc = host.zlst_geometry(sr, 1000, 0.0, pitch, speed, geo.ctypes.data)
+        try:
+            g = sr_.geometry(sr, 1000, 0.0, pitch, speed)
+        except ValueError:
+            assert rc == -1, (sr, speed, pitch)
+            return None
+        assert rc == 0, (sr, speed, pitch)
+        assert list(geo[:8]) == [g["N"], g["N1"], g["nseg"], g["O"], g["S"], g["W"], int(g["stretch"]), int(g["resample"])]
+        return g
+
+    g = both(204800.0, 0.5, 0.0)
+    assert g is not None and (g["W"], g["O"]) == (4096, 512) and g["W"] + g["O"] == sr_.MAX_WINDOW == 4608
+    assert both(204850.0, 0.5, 0.0) is None                        # W = 4097
+    assert int(np.floor(204850.0 * 20.0 / 1000.0)) == 4097
+    g = both(204850.0, 2.0, 12.0)                                  # tau == 1: the stretch does not run
+    assert g is not None and not g["stretch"] and g["nseg"] == 0 and g["resample"]
+    g = both(204850.0, 2.0, 0.0)
+    assert g is not None and g["stretch"] and g["W"] == 3072
+    assert both(400.0, 4.0, 0.0) is None                           # S = 16 = O
+    assert int(np.floor(400.0 * 40.0 / 1000.0)) == 16
+    g = both(425.0, 4.0, 0.0)
+    assert g is not None and (g["S"], g["O"], g["W"]) == (17, 16, 6)
+    assert both(400.0, 4.0, 24.0) is not None                      # (tau == 1 again, at the low end)
+
+
+def test_the_edge_cases_hold_the_geometries_they_are_there_for():
+    """so that the list does not decay: from the restatement's geometry alone"""
+    seen = {}
+    for (sr, ch, speed, pitch, gain, length, kind) in EDGE:
+        g = sr_.geometry(sr, length, gain, pitch, speed)
+        seen.setdefault((sr, speed, pitch), []).append((g, length, ch, kind))
+    assert all(sorted(c for _, _, c, _ in v) in ([1, 2], [1, 1, 1, 1, 2, 2, 2, 2]) for v in seen.values())    # mono and stereo each
+    geo = {k: v[0][0] for k, v in seen.items()}
+    g = geo[(425.0, 4.0, 0.0)]
+    assert (g["O"], g["S"] - g["O"], g["W"]) == (16, 1, 6) and g["nseg"] > 4
+    g = geo[(500.0, 0.5, 0.0)]
+    assert g["O"] == 16 and g["S"] - g["O"] > g["O"] and g["W"] == 10 and g["nseg"] > 4
+    assert geo[(2000.0, 2.0, 7.0)]["W"] == 34 and geo[(8000.0, 0.5, 0.0)]["W"] == 160
+    assert geo[(47250.0, 1.25, 3.0)]["O"] == 376 and int(47250 * 0.008) == 378
+    assert geo[(37800.0, 0.8, -5.0)]["O"] == 296 and int(37800 * 0.008) == 302
+    for k in ((2000.0, 2.0, 7.0), (8000.0, 0.5, 0.0), (47250.0, 1.25, 3.0), (37800.0, 0.8, -5.0)):
+        assert geo[k]["nseg"] == 5 and geo[k]["N1"] - 4 * (geo[k]["S"] - geo[k]["O"]) < 16, k      # four segments and a few frames
+    for k in ((204800.0, 0.5, 0.0), (204800.0, 0.25, 0.0)):
+        assert geo[k]["W"] + geo[k]["O"] == 4096 + 512 == sr_.MAX_WINDOW and geo[k]["nseg"] >= 3
+    for k in ((96000.0, 1.25, 0.0), (96000.0, 0.8, 3.0)):
+        assert geo[k]["O"] == 512 and all(kind == "rail" for _, _, _, kind in seen[k])
+    rail = source(96000.0, 2, 30000, seed=1, kind="rail")
+    assert set(np.unique(sr_.quantise(rail))) == {-32767, 32767}
+    L = geo[(48000.0, 0.5, 0.0)]["S"] - geo[(48000.0, 0.5, 0.0)]["O"]
+    assert [(g["nseg"], g["N1"]) for g, _, c, _ in seen[(48000.0, 0.5, 0.0)] if c == 1] == [(1, L - 2), (1, L), (2, L + 2), (2, 2 * L)]
+    assert [g["N"] + 8 for g, _, c, _ in seen[(48000.0, 1.0, 3.0)] if c == 1] == [256, 257, 512, 513]
+    assert all(g["stretch"] for g, _, _, _ in seen[(48000.0, 1.0, 3.0)])
+
+
 GRID = cases()
+EDGE = edge_cases()
 
 
-@pytest.mark.parametrize("sr,ch,speed,pitch,gain,length", GRID, ids=[f"{int(c[0])}-{c[1]}ch-s{c[2]}-p{c[3]}-g{c[4]}-n{c[5]}" for c in GRID])
-def test_host_build_equals_the_restatement(host, sr, ch, speed, pitch, gain, length):
-    src = source(sr, ch, length, seed=length + 7 * ch)
+@pytest.mark.parametrize("sr,ch,speed,pitch,gain,length,kind", [c + ("noise",) for c in GRID] + EDGE,
+                         ids=[f"{int(c[0])}-{c[1]}ch-s{c[2]}-p{c[3]}-g{c[4]}-n{c[5]}" for c in GRID] + ["edge-" + edge_id(c) for c in EDGE])
+def test_host_build_equals_the_restatement(host, sr, ch, speed, pitch, gain, length, kind):
+    src = source(sr, ch, length, seed=length + 7 * ch, kind=kind)
     ref, roffs = sr_.render(src, sr, gain, pitch, speed)
     out, offs = host_render(host, src, sr, gain, pitch, speed)
     assert same_bits(out, ref), np.flatnonzero((out != ref).any(axis=0))[:10]
     assert np.array_equal(offs.astype(np.int64), roffs)
+    if kind == "rail" or sr == 204800.0:
+        assert roffs.any()                                         # (the scores differ: the seek has something to decide)
+
+
+@pytest.mark.parametrize("sr,ch,period", tie_cases(), ids=[f"{int(c[0])}-{c[1]}ch-P{c[2]}" for c in tie_cases()])
+def test_periodic_clips_tie_and_the_smallest_offset_wins(host, sr, ch, period):
+    """candidates a period apart score the same to the bit; the host build and the restatement take the first of them"""
+    src = tie_source(sr, ch, period)
+    ref, roffs = sr_.render(src, sr, 0.0, 0.0, TIE_SPEED)
+    out, offs = host_render(host, src, sr, 0.0, 0.0, TIE_SPEED)
+    assert same_bits(out, ref) and np.array_equal(offs.astype(np.int64), roffs)
+    assert same_bits(src[:, period:], src[:, :-period])
+    holds_ties(sr, period, roffs)
+
+
+@pytest.mark.parametrize("sr,pitch,speed", LAST_FRAME_CASES)
+@pytest.mark.parametrize("ch", [1, 2])
+def test_the_last_staged_frame_decides_a_seek(host, sr, pitch, speed, ch):
+    src = last_frame_source(sr, ch, pitch, speed)
+    ref, roffs = sr_.render(src, sr, 0.0, pitch, speed)
+    out, offs = host_render(host, src, sr, 0.0, pitch, speed)
+    assert same_bits(out, ref) and np.array_equal(offs.astype(np.int64), roffs)
+    assert roffs[1] == 0 and roffs[2] == sr_.geometry(sr, src.shape[1], 0.0, pitch, speed)["W"] - 1
 
 
 @pytest.mark.parametrize("kind", ["zeros", "special"])
