@@ -271,6 +271,13 @@ def build_pair_harness(force: bool = False) -> str:
     return _build_harness("zl_pair_host", "pair_host.cpp", ["zl_pair.h"], ["-Wall"], force)
 
 
+def build_pair_wrap_harness(force: bool = False) -> str:
+    """The pair kernels' on-grid form for blocks with one loop restart (zl_render.h: zl_voice_ongrid2, zl_ongrid2_lane), with the host planner."""
+    plan_host = os.path.join("..", "..", "tests", "cpu_harness", "plan_host.cpp")        # (included by the harness for its ZlSim)
+    return _build_harness("zl_pair_wrap_host", "pair_wrap_host.cpp", ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_host.h", _ZLHIP_H, plan_host],
+                          _NO_CONTRACT + ["-Wall", "-Wno-unused-function"], force)
+
+
 def build_group_harness(force: bool = False) -> str:
     """The engine group's partition arithmetic and command routing (zl_group.h)."""
     return _build_harness("zl_group_host", "group_host.cpp", ["zl_types.h", "zl_plan.h", "zl_host.h", "zl_group.h", _ZLHIP_H], _NO_CONTRACT + ["-Wall", "-Wno-unused-function"], force)

@@ -826,7 +826,15 @@ static void free_sound_slot(zlhip_engine *e, int id)
 // that is here anyway; a finite source then gets ZL_SOUND_FINITE (the table entry goes to the device once more, in stream order)
 // ZL_K2_ONGRID: 0 = K2 never takes the one-tap form of on-grid unit-step chunks, 1 = wherever its condition holds (default); read per call
 // (A/B runs of one build, tests that compare both forms).  Results do not depend on it.
-static int zl_ongrid_switch() { const char *v = std::getenv("ZL_K2_ONGRID"); return (v ? std::atoi(v) : 1) != 0 ? 1 : 0; }
+// ZL_K2_PAIR_WRAP: 0 = a voice-block that holds a loop restart is never on-grid (the two-tap chunk functions, as before), 1 = the pair kernels
+// take it on the one-tap path where zl_voice_ongrid2 holds (default); read per call like the other.  It travels in bit 1 of ZlBatch::ongrid
+// (ZL_ONGRID_WRAP, zl_render.h) and only with bit 0: whoever asks "on or off" sees what it saw before.
+static int zl_ongrid_switch()
+{
+    const char *v = std::getenv("ZL_K2_ONGRID"), *w = std::getenv("ZL_K2_PAIR_WRAP");
+    if ((v ? std::atoi(v) : 1) == 0) return 0;
+    return ZL_ONGRID_ON | ((w ? std::atoi(w) : 1) != 0 ? ZL_ONGRID_WRAP : 0);
+}
 
 static int publish_sound(zlhip_engine *e, int id, bool dev_checked = false)
 {

@@ -365,7 +365,8 @@ typedef float zl_f2 __attribute__((ext_vector_type(2)));
 // The gain products are read in the Hermite mode only, and no voice is on-grid there (zl_voice_ongrid): in every other mode their
 // eight bytes hold, for a voice classed on-grid, the byte address of the block's frame 0 in the arena (zl_unit_record) -- the one
 // thing the on-grid chunks read of the voice besides its pan pair.
-struct ZlUnit { int ipos; float alpha; union { struct { float gpl, gpr; }; uint64_t addr0; }; };
+// (alt: a voice-block with one loop restart on the grid, zl_k2_stage_unit)
+struct ZlUnit { int ipos; union { float alpha; int alt; }; union { struct { float gpl, gpr; }; uint64_t addr0; }; };
 static_assert(sizeof(ZlUnit) == 16, "one 16-byte LDS record per voice");
 
 // the ZlUnit of a staged voice-block (cls: zl_k2_stage_class).  addr0 = arena + 4 src_offset + 8 ipos (4 ipos mono) in 64-bit unsigned
@@ -754,6 +755,71 @@ static __device__ __forceinline__ void zl_k2_chunk_ongrid_pair(const ZlBatch &A,
             if ((threadIdx.x & 63) == 0 && pk > 0.0f) atomicMax(&A.reports[vfirst + i].peak_bits, __float_as_uint(pk));
         }
     }
+}
+
+// The pair chunk whose voices are all on-grid and at least one of them RESTARTS ITS LOOP inside the block (chunk class 256: zl_render.h,
+// zl_voice_ongrid2).  Frame f of such a voice reads P0 + f below n1 and P1 + (f - n1) from n1 on, both from the same source; the other voices
+// of the chunk have n1 = INT_MAX.  Per voice the lane issues the pair's 16-byte load from the segment of its first frame and one 8-byte load
+// for the frame a pair that straddles an odd n1 takes from the second segment -- every other lane repeats its own first frame there, so no
+// address leaves the source (zl_ongrid2_lane).  Both loads go from the source's first byte with a 32-bit byte offset: the two segments
+// lie on either side of each other, and a source is shorter than 4 GiB (zl_k2_stage_class).  Straight-line like zl_k2_chunk_ongrid_pair:
+// every load in flight before the first mix, then zl_mix_acc_ongrid_pk per frame in voice order into the same four accumulators.  The
+// call's last block (the report path) keeps the two-tap chunk functions.
+#ifndef ZL_K2_U_PAIR_WRAP
+#define ZL_K2_U_PAIR_WRAP 8  // voices per pass of this chunk (6 data registers a voice); 8 or 4
+#endif
+template <bool MONO, int U>
+static __device__ __forceinline__ void zl_k2_chunk_ongrid_pair_wrap(const ZlBatch &A, const ZlBlockPlan *s_plan, const ZlVoiceConst *s_vc, const ZlUnit *s_unit,
+                                                                     int c0, int f0, float &accL0, float &accR0, float &accL1, float &accR1)
+{
+    zl_f4a8 x4[MONO ? 1 : U];
+    zl_f2   y2[MONO ? 1 : U];
+    zl_f2   x2[MONO ? U : 1];
+    float   y1[MONO ? U : 1];
+    zl_f2 pan[U];
+    bool straddle[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int i = c0 + u;
+        const ZlWrapLane w = zl_ongrid2_lane(s_unit[i].ipos, s_unit[i].alt, s_plan[i].n1, f0);
+        const uint64_t so = s_vc[i].src_offset << 2;
+        const uint64_t src = (uint64_t)reinterpret_cast<uintptr_t>(A.arena)
+                           + (((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(so >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)so));
+        const uint32_t ox = (uint32_t)w.x << (MONO ? 2 : 3), oy = (uint32_t)w.y << (MONO ? 2 : 3);
+        if (MONO) { x2[u] = zl_k2_ongrid_load<zl_f2a4b>(src, ox); y1[u] = zl_k2_ongrid_load<float>(src, oy); }
+        else      { x4[u] = zl_k2_ongrid_load<zl_f4a8>(src, ox);  y2[u] = zl_k2_ongrid_load<zl_f2>(src, oy); }
+        pan[u] = *reinterpret_cast<const zl_f2 *>(&s_vc[i].lpan);
+        straddle[u] = w.straddle;
+    }
+    __builtin_amdgcn_sched_barrier(0);                            // (all loads in flight before the first mix)
+    if (!ZL_K2_ONGRID_PK) {                                       // the scalar text of the same frames, as in zl_k2_chunk_ongrid_pair
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float a0 = MONO ? x2[u].x : x4[u].x, b0 = MONO ? x2[u].x : x4[u].y;
+            const float a1 = MONO ? (straddle[u] ? y1[u] : x2[u].y) : (straddle[u] ? y2[u].x : x4[u].z);
+            const float b1 = MONO ? a1 : (straddle[u] ? y2[u].y : x4[u].w);
+            float l0, r0, l1, r1;
+            zl_mix_frame_ongrid(a0, b0, pan[u].x, pan[u].y, l0, r0);
+            zl_mix_frame_ongrid(a1, b1, pan[u].x, pan[u].y, l1, r1);
+            accL0 += l0; accR0 += r0;                             // :218-221 (index shift applied at the store)
+            accL1 += l1; accR1 += r1;
+        }
+        return;
+    }
+    zl_f2 acc0 = {accL0, accR0}, acc1 = {accL1, accR1};
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (MONO) {
+            const zl_f2 d = {x2[u].x, straddle[u] ? y1[u] : x2[u].y};
+            zl_mix_acc_ongrid_pk<1>(acc0, d, pan[u]);
+            zl_mix_acc_ongrid_pk<2>(acc1, d, pan[u]);
+        } else {
+            const zl_f2 d1 = {straddle[u] ? y2[u].x : x4[u].z, straddle[u] ? y2[u].y : x4[u].w};
+            zl_mix_acc_ongrid_pk<0>(acc0, __builtin_shufflevector(x4[u], x4[u], 0, 1), pan[u]);
+            zl_mix_acc_ongrid_pk<0>(acc1, d1, pan[u]);
+        }
+    }
+    accL0 = acc0.x; accR0 = acc0.y; accL1 = acc1.x; accR1 = acc1.y;
 }
 
 // UNIT + INT chunks with SHARED taps (ZL_K2_UNIT_SHARE=1): at the playback rate inside an exact run, lane f + 1's first tap IS lane
@@ -1206,8 +1272,25 @@ static __device__ __forceinline__ int zl_k2_stage_class(const ZlBatch &A, const 
         // 128 = "on-grid": a unit-step interior block from an integer position of a source known to be finite -- alpha = 0 in
         // every frame, the second tap only adds a signed zero (zl_render.h): zl_k2_chunk_ongrid mixes it from one tap
         cls |= zl_voice_ongrid(MODE, A.ongrid, true, (cls & 32) != 0, interior, pl.P0, pl.step, vc.pad[0]) ? 128 : 0;
+        // 256 = "on-grid with one loop restart": two unit-step segments from integer positions, every tap of both inside the source
+        // (zl_render.h, zl_voice_ongrid2): zl_k2_chunk_ongrid_pair_wrap mixes each frame from the first tap of its own segment
+        cls |= zl_voice_ongrid2(MODE, A.ongrid, vc.pad[0], cls & 3, pl.n_active, pl.flags, true, pl.nseg, pl.n1, N, pl.step, pl.step1, pl.P0, pl.P1,
+                                vc.sample_duration) ? 256 : 0;
     }
     return cls;
+}
+
+// ... its ZlUnit: zl_unit_record's, and for a voice-block of class 256, whose record no chunk function reads (a chunk with a two-segment
+// voice is never UNIT), alt = P1 - n1 in the place of alpha -- what zl_ongrid2_lane adds to a frame of the second segment.  An on-grid
+// voice of one segment has alpha = +0.0f there, which reads as alt = 0.  zl_unit_record is shared with zl_k2_body and gets the class
+// without bit 256: given a wider range of its argument, the compiler writes the `cls & 128` test of EVERY caller another way, and
+// zl_k2_body's kernels are to keep their instructions.
+template <uint32_t MODE>
+static __device__ __forceinline__ ZlUnit zl_k2_stage_unit(const ZlBatch &A, const ZlVoiceConst &vc, const ZlBlockPlan &pl, int cls)
+{
+    ZlUnit un = zl_unit_record<MODE>(A, vc, pl, cls & 255);
+    if (cls & 256) un.alt = (int)pl.P1 - pl.n1;
+    return un;
 }
 
 // ... and the class of each chunk of U voices of the pass, from the classes of the wave's 64 voices (voice i of the pass = this lane's)
@@ -1218,6 +1301,8 @@ static __device__ __forceinline__ void zl_k2_stage_chunks(int cls, int i, int *s
     // mono (ballots over the wave's 64 voices)
     const unsigned long long m1 = __ballot(cls & 1), m2 = __ballot(cls & 2), m4 = __ballot(cls & 4), m8 = __ballot(cls & 8),
                              m16 = __ballot(cls & 16), m32 = __ballot(cls & 32), m64 = __ballot(cls & 64), m128 = __ballot(cls & 128);
+    // 256 = every voice on-grid in either form (voice bits 128, 256), one source layout, and at least one voice with a loop restart
+    const unsigned long long m256 = __ballot(cls & 256), many = __ballot(cls & 384);
     const int lane = i & 63;
     if (lane < 64 / U) {
         const unsigned long long full = (1ull << U) - 1ull;
@@ -1225,7 +1310,8 @@ static __device__ __forceinline__ void zl_k2_stage_chunks(int cls, int i, int *s
         const unsigned long long mono = (m16 >> sh) & full;
         const int cc = (((m1 >> sh) & full) ? 1 : 0) | (((m2 >> sh) & full) ? 2 : 0) | (((m8 >> sh) & full) ? 8 : 0)
                      | (((((m4 >> sh) & full) == full) && (mono == 0 || mono == full)) ? 4 : 0) | (mono == full ? 16 : 0)
-                     | ((((m32 >> sh) & full) == full) ? 32 : 0) | ((((m64 >> sh) & full) == full) ? 64 : 0) | ((((m128 >> sh) & full) == full) ? 128 : 0);
+                     | ((((m32 >> sh) & full) == full) ? 32 : 0) | ((((m64 >> sh) & full) == full) ? 64 : 0) | ((((m128 >> sh) & full) == full) ? 128 : 0)
+                     | (((((many >> sh) & full) == full) && ((m256 >> sh) & full) != 0 && (mono == 0 || mono == full)) ? 256 : 0);
         s_chunk[(i >> 6) * (64 / U) + lane] = cc;
     }
 }
@@ -1775,8 +1861,9 @@ template <bool ORD>
 static __device__ __forceinline__ void zl_k2_pair_body(const ZlBatch &A)
 {
     constexpr uint32_t MODE = 0;
-    constexpr int U = ZL_K2_U, UP = ZL_K2_U_PAIR, CH = ZL_K2_CHUNK;
+    constexpr int U = ZL_K2_U, UP = ZL_K2_U_PAIR, UW = ZL_K2_U_PAIR_WRAP, CH = ZL_K2_CHUNK;
     static_assert(UP == U || 2 * UP == U, "the pair chunk walks a chunk class of U voices whole or in halves");
+    static_assert(UW == U || 2 * UW == U, "and so does the chunk with loop restarts");
     __shared__ ZlBlockPlan  s_plan[CH];
     __shared__ ZlVoiceConst s_vc[CH];
     __shared__ int s_cls[CH];                         // per voice: 1 = plays this block, 2 = per-frame control
@@ -1811,7 +1898,7 @@ static __device__ __forceinline__ void zl_k2_pair_body(const ZlBatch &A)
             if (norun) zl_k2_stage_load<false>(A, k, vb, i, nv, vc, pl, dead_tail);
             else       zl_k2_stage_load<true>(A, k, vb, i, nv, vc, pl, nullptr);
             const int cls = zl_k2_stage_class<MODE>(A, vc, pl);
-            s_unit[i] = zl_unit_record<MODE>(A, vc, pl, cls);
+            s_unit[i] = zl_k2_stage_unit<MODE>(A, vc, pl, cls);
             s_vc[i] = vc;
             s_plan[i] = pl;
             s_cls[i] = cls;
@@ -1831,6 +1918,13 @@ static __device__ __forceinline__ void zl_k2_pair_body(const ZlBatch &A)
                     }
                     else if (cc & 16) zl_k2_chunk_ongrid_pair<true, UP, false>(A, s_vc, s_unit, c0 + h, vb, f0, accL0, accR0, accL1, accR1);
                     else              zl_k2_chunk_ongrid_pair<false, UP, false>(A, s_vc, s_unit, c0 + h, vb, f0, accL0, accR0, accL1, accR1);
+                }
+            } else if ((cc & 256) && !wantPeak) {
+                // every voice on-grid, one or more of them with a loop restart inside the block (not in the call's last block)
+#pragma unroll
+                for (int h = 0; h < U; h += UW) {
+                    if (cc & 16) zl_k2_chunk_ongrid_pair_wrap<true, UW>(A, s_plan, s_vc, s_unit, c0 + h, f0, accL0, accR0, accL1, accR1);
+                    else         zl_k2_chunk_ongrid_pair_wrap<false, UW>(A, s_plan, s_vc, s_unit, c0 + h, f0, accL0, accR0, accL1, accR1);
                 }
             } else {
                 // the other classes: zl_k2_body's dispatch, one frame of the lane after the other

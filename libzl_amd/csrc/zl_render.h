@@ -104,6 +104,42 @@ ZL_HD inline bool zl_voice_ongrid(uint32_t mode, int enabled, bool simple, bool 
         && (mode & (ZL_MODE_HERMITE | ZL_MODE_FIX_GAIN)) == 0;
 }
 
+// The same for a block that holds ONE loop restart (two segments): both segments of a clip at its own pitch and rate are unit-step runs
+// from integer positions, so alpha = 0 in every frame of both and each frame is zl_mix_frame_ongrid on the first tap of its own segment --
+// frame f reads position P0 + f below n1 and P1 + (f - n1) from n1 on.  `ongrid` is ZlBatch::ongrid: bit 0 the on-grid form, bit 1 this
+// one (ZL_K2_PAIR_WRAP).  cls / n_active / plan_flags / gains_finite: the voice plays the whole block (cls == 1: no per-frame control) in
+// sustain with a finite gain product.  Every tap of both segments lies inside the source: the first segment's last frame is n1 - 1, the
+// second's is N - 1.
+#define ZL_ONGRID_ON   1
+#define ZL_ONGRID_WRAP 2
+ZL_HD inline bool zl_voice_ongrid2(uint32_t mode, int ongrid, int sound_flags, int cls, int n_active, int plan_flags, bool gains_finite,
+                                   int nseg, int n1, int N, double step, double step1, double P0, double P1, int sample_duration)
+{
+    return (ongrid & ZL_ONGRID_ON) != 0 && (ongrid & ZL_ONGRID_WRAP) != 0 && (mode & (ZL_MODE_HERMITE | ZL_MODE_FIX_GAIN)) == 0
+        && (sound_flags & ZL_SOUND_FINITE) != 0
+        && cls == 1 && n_active == N && (plan_flags & ZL_PLAN_ENV) == 0 && gains_finite
+        && nseg == 2 && n1 > 0 && n1 < N
+        && step == 1.0 && step1 == 1.0
+        && P0 >= 0.0 && P0 < 1073741824.0 && P0 == (double)(int)P0 && P1 >= 0.0 && P1 < 1073741824.0 && P1 == (double)(int)P1
+        && P0 + (double)(n1 - 1) < (double)sample_duration && P1 + (double)(N - 1 - n1) < (double)sample_duration;
+}
+
+// What a lane of the two-frames-per-lane kernels reads of such a voice (zl_kernels.hip, zl_k2_chunk_ongrid_pair_wrap).  The lane renders
+// frames f0 (even) and f0 + 1.  ipos = P0 and alt = P1 - n1 as integers (alt may be negative: it is only added to frames >= n1), both in
+// source frames; a single-segment on-grid voice of the same chunk has n1 = INT_MAX.  x = the source frame of a two-frame load (frames x
+// and x + 1), y = the source frame of a one-frame load; frame f0 is x's first frame, frame f0 + 1 is y where `straddle` (f0 + 1 == n1: one
+// frame from each segment) and x's second frame otherwise.  Where the lane does not straddle y = x, a frame it reads anyway: no lane
+// reads in front of P1, and a straddling lane's unused frame x + 1 = P0 + n1 <= sample_duration is the source's own.
+struct ZlWrapLane { int x, y; bool straddle; };
+ZL_HD inline ZlWrapLane zl_ongrid2_lane(int ipos, int alt, int n1, int f0)
+{
+    ZlWrapLane w;
+    w.x = (f0 >= n1 ? alt : ipos) + f0;
+    w.straddle = f0 + 1 == n1;
+    w.y = w.straddle ? alt + f0 + 1 : w.x;
+    return w;
+}
+
 // :208-211 on the one tap (x0l, x0r) of an on-grid frame; a mono source passes x0r = x0l (r = l, :205)
 ZL_HD inline void zl_mix_frame_ongrid(float x0l, float x0r, float lpan, float rpan, float &lout, float &rout)
 {

@@ -86,8 +86,12 @@ def main() -> int:
         for blk in cand:
             ops = collections.Counter(re.sub(r"_e(32|64)$", "", i.split()[0]) for i in blk if i.startswith("v_"))
             nload = sum(i.startswith("global_load") for i in blk)
-            print(f"  block of {len(blk)} instructions ending in {blk[-1].split()[0]}: {nload} loads, {sum(i.startswith('ds_read') for i in blk)} LDS reads, "
-                  f"{sum(i.startswith('s_') for i in blk)} scalar, {sum(ops.values())} VALU = {sum(ops.values()) / (nload * frames):.1f} per voice-wave")
+            # a voice is one load of the chunk's width; the pair chunk with loop restarts (zl_k2_chunk_ongrid_pair_wrap) issues a narrower second
+            # load per voice, for the frame of a pair that straddles the restart
+            nvoice = sum(i.startswith(load + " ") for i in blk)
+            what = f"{nload} loads" if nload == nvoice else f"{nload} loads ({nvoice} voices, {nload - nvoice} straddle loads: the chunk with loop restarts)"
+            print(f"  block of {len(blk)} instructions ending in {blk[-1].split()[0]}: {what}, {sum(i.startswith('ds_read') for i in blk)} LDS reads, "
+                  f"{sum(i.startswith('s_') for i in blk)} scalar, {sum(ops.values())} VALU = {sum(ops.values()) / (nvoice * frames):.1f} per voice-wave")
             print("    " + ", ".join(f"{n} {o}" for o, n in sorted(ops.items(), key=lambda kv: (-kv[1], kv[0]))))
             if "--dump" in sys.argv:
                 print("\n".join("        " + i for i in blk))
