@@ -6,67 +6,11 @@ synchronisation, a group of one, and two devices when there are two."""
 import numpy as np
 import pytest
 
+from group_cases import assert_same_bus, assert_same_levels, assert_same_reports, check_against, group
 from libzl_amd import MODE_FAITHFUL, MODE_FIX_DELAY, MODE_HERMITE, SamplerSynth, SamplerSynthGroup
 from scenario import Scene, compare_runs, engine_cmd, play_cmd, rand_source, random_scene, run_backend, run_oracle, snapshot_clip
 
 pytestmark = pytest.mark.gpu
-
-LEVEL_FIELDS = ("peak_a", "peak_b", "peak_a_hold_signal", "peak_b_hold_signal", "peak_db_a", "peak_db_b", "combined_db", "hold_db_a",
-                "hold_db_b", "rms_a", "rms_b")
-REPORT_FIELDS = ("playing", "valid", "gain", "progress", "clip", "source_sample_position")
-
-
-def group(devices, partition, **extra):
-    return lambda **kw: SamplerSynthGroup(devices, partition=partition, **kw, **extra)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
-
-
-def assert_same_bus(a, b, what):
-    assert a.shape == b.shape, what
-    assert np.array_equal(bits(a), bits(b)), f"{what}: max abs diff {np.abs(a - b).max()} at {np.argwhere(a != b)[:3].tolist()}"
-
-
-def assert_same_reports(r1, r2, V, what):
-    for v in range(V):
-        for f in REPORT_FIELDS:
-            x, y = getattr(r1[v], f), getattr(r2[v], f)
-            assert np.array(x).tobytes() == np.array(y).tobytes(), f"{what}: voice {v} {f}: {x} vs {y}"
-
-
-def assert_same_levels(l1, l2, B, what):
-    for b in range(B):
-        for f in LEVEL_FIELDS:
-            x, y = getattr(l1[b], f), getattr(l2[b], f)
-            assert np.float32(x).tobytes() == np.float32(y).tobytes() if isinstance(x, float) else x == y, f"{what}: bus {b} {f}: {x} vs {y}"
-
-
-def meters(syn, K, hold):
-    """every block's levels (the hold bus kept across the ticks) and the block peaks of the last call"""
-    return [syn.levels_tick(block_index=k, with_hold_bus=hold) for k in range(K)], syn.block_peaks()
-
-
-def check_against(sc, factory, batch=1 << 30, hold=1):
-    """run the scene on the oracle, one engine and the group; bus, reports, levels and peaks must agree bit for bit"""
-    ref, orep, osyn = run_oracle(sc, batch=batch)
-    one, rep1, syn1, _ = run_backend(sc, SamplerSynth, batch=batch)
-    grp, repg, syng, _ = run_backend(sc, factory, batch=batch)
-    V = sc.num_buses * sc.voices_per_bus
-    compare_runs(ref, orep, osyn, grp, repg, V)
-    assert_same_bus(one, grp, "group vs one engine")
-    assert_same_reports(rep1, repg, V, "group vs one engine")
-    K = syn1._last[0]
-    lv1, pk1 = meters(syn1, K, hold)
-    lvg, pkg = meters(syng, K, hold)
-    for k in range(K):
-        assert_same_levels(lv1[k], lvg[k], sc.num_buses, f"levels, block {k}")
-    assert np.array_equal(pk1, pkg)
-    assert any(lv1[-1][b].rms_a > 0 for b in range(sc.num_buses))
-    syn1.close()
-    syng.close()
-    return grp
 
 
 @pytest.mark.parametrize("devices", [[0, 0], [0, 0, 0]])
