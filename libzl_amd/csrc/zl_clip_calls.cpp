@@ -1,0 +1,1033 @@
+// zl_clip_calls.cpp -- the clip services of include/zlhip.h: loading from raw PCM, re-render, rate conversion, and the five analyses
+// (waveform overviews, transients, tempo, pitch, loudness).  Every one is a call on a loaded clip that validates everything before its
+// first HIP call, reserves buffers that only grow, queues its launches on the engine's stream and waits once.  What they share is
+// written once, below; the engine itself -- arena, sound slots, rendering, the resident kernel -- is zl_engine.cpp.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+
+#include "zl_engine_impl.h"
+#include "zl_decode.h"
+#include "zl_loudness.h"
+#include "zl_onset.h"
+#include "zl_overview.h"
+#include "zl_pitch.h"
+#include "zl_resample.h"
+#include "zl_stretch.h"
+#include "zl_tempo.h"
+
+// ---- what every service does ---------------------------------------------------------------------------------------------------
+static int fail_in(zlhip_engine *e, int code, const char *svc, const char *msg) { return fail(e, code, (std::string(svc) + ": " + msg).c_str()); }
+
+static int check_sound(zlhip_engine *e, const char *svc, int32_t id)
+{
+    return id < 0 || id >= e->cfg.max_sounds || !e->hc.soundUsed[id] ? fail_in(e, ZLHIP_ERR_INVALID, svc, "no such sound") : ZLHIP_OK;
+}
+
+// An analysis request: its sound exists, its fields are inside their limits (`resolve` fills the defaults in and returns what is wrong,
+// or nullptr), its window lies inside the data the sound plays.  In that order, before the first HIP call.
+template <typename Q, typename Resolve> static int check_request(zlhip_engine *e, const char *svc, Q &q, Resolve resolve)
+{
+    { const int rc = check_sound(e, svc, q.id); if (rc != ZLHIP_OK) return rc; }
+    const ZlSound &s = e->hc.sounds[q.id];
+    if (const char *wrong = resolve(s)) return fail_in(e, ZLHIP_ERR_INVALID, svc, wrong);
+    if (q.first_frame < 0 || q.num_frames < 1 || (int64_t)q.first_frame + q.num_frames > s.length)
+        return fail_in(e, ZLHIP_ERR_INVALID, svc, "the frames do not lie inside the sound's playback data");
+    return ZLHIP_OK;
+}
+static const char *const kOutsideLimits = "a field of the request is outside its limits";
+
+// A call's buffers: `need` elements of `elem` bytes in scratch[buf], a too small one replaced by one of `new_cap` (grow_buf); where
+// anything is replaced, a buffer is measured by `regrow` instead, if given.  And its results in mapped host memory.
+struct ZlBufNeed { int buf; size_t need, elem, new_cap; bool twin; const char *what; size_t regrow = 0; };
+struct ZlMapNeed { void *mapped; size_t cap, need; hipError_t (*grow)(void *, size_t); };
+template <typename T> static ZlMapNeed mapped_need(ZlMapped<T> &m, size_t need) { return { &m, m.cap, need, [](void *p, size_t n) { return ((ZlMapped<T> *)p)->grow(n); } }; }
+// hipMalloc, hipFree and hipHostFree wait for resident kernels, so the buffers are allocated by the first call and grow only: a call
+// that fits them makes no device-synchronising HIP call.  One that does not stops this engine's kernel first (stop; a call that has
+// stopped it already passes false) and has the others' step aside.
+static int reserve(zlhip_engine *e, bool stop, std::initializer_list<ZlBufNeed> bufs, std::initializer_list<ZlMapNeed> maps = {})
+{
+    bool fits = true;
+    for (const ZlBufNeed &b : bufs) fits = fits && b.need <= e->scratch[b.buf].cap;
+    for (const ZlMapNeed &m : maps) fits = fits && m.need <= m.cap;
+    if (fits) return ZLHIP_OK;
+    if (stop) { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }
+    ZlQuiesce quiet(e);
+    for (const ZlBufNeed &b : bufs) {
+        const int rc = grow_buf(e, e->scratch[b.buf], b.regrow ? b.regrow : b.need, b.elem, b.new_cap, b.twin, b.what);
+        if (rc != ZLHIP_OK) return rc;
+    }
+    for (const ZlMapNeed &m : maps) ZL_HIP(e, m.grow(m.mapped, m.need));
+    return ZLHIP_OK;
+}
+
+extern "C" {
+
+// ---- clips from raw PCM (zl_decode.h, zl_decode.hip) ---------------------------------------------------------------------
+// The other side of the file boundary: zlhip_bounce writes 16-bit PCM from the render kernel, this reads the bytes of a WAV `data`
+// chunk.  The raw bytes cross the link (half of fp32 for 16-bit files, no host loop over the samples), one decode launch per staging
+// pass writes the arena's layout, pad included, and the call waits for the device once -- whatever the number of clips.
+// ZL_PCM_STAGE_BYTES: the size of the staging buffer, read per call (tests cut clips inside with a small one)
+static uint32_t zl_pcm_stage_switch() { const char *v = std::getenv("ZL_PCM_STAGE_BYTES"); return zl_dec_stage_bytes(v ? std::atoll(v) : (long long)ZL_DEC_STAGE_DEFAULT); }
+
+int zlhip_sound_upload_pcm_batch(zlhip_engine *e, const zlhip_pcm_source *srcs, int32_t count, int32_t *out_ids)
+{
+    if (!e || count < 0 || (count > 0 && (!srcs || !out_ids))) return ZLHIP_ERR_INVALID;
+    if (count == 0) return ZLHIP_OK;
+    for (int32_t i = 0; i < count; ++i) out_ids[i] = -1;
+    // every argument before the first HIP call
+    for (int32_t i = 0; i < count; ++i) {
+        const zlhip_pcm_source &q = srcs[i];
+        if (!q.frames) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: frames is NULL");
+        if (q.format < ZLHIP_PCM_U8 || q.format > ZLHIP_PCM_F64) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: format outside 1 .. 6");
+        if (q.channels < 1 || q.channels > ZLHIP_PCM_MAX_CHANNELS) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: channels outside 1 .. 64");
+        if (q.length < 1) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: length below 1");
+        if (!(q.sample_rate > 0.0)) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: sample rate not above 0");
+        if (q.reserved != 0) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: reserved is not 0");
+    }
+    // the slots: the first free ones in request order, as consecutive zlhip_sound_upload calls would take them
+    std::vector<int32_t> ids;
+    for (int i = 0; i < e->cfg.max_sounds && (int32_t)ids.size() < count; ++i) if (!e->hc.soundUsed[i]) ids.push_back(i);
+    if ((int32_t)ids.size() < count) return fail(e, ZLHIP_ERR_CAPACITY, "sound_upload_pcm: too few free sound slots for the call");
+    { const int rc = call_begin(e, true); if (rc != ZLHIP_OK) return rc; }     // (an extent freed earlier may be handed out again here)
+    // the extents (all or none: an arena that cannot hold the call keeps nothing; a segment it grew by goes back)
+    std::vector<size_t> off((size_t)count, 0), floats((size_t)count, 0);
+    auto rollback = [&]() { for (int32_t k = count - 1; k >= 0; --k) free_extent(e, off[(size_t)k], floats[(size_t)k]); };   // (0 floats: nothing taken)
+    for (int32_t i = 0; i < count; ++i) {
+        const size_t n = zl_extent_floats(srcs[i].length, zl_dec_out_channels(srcs[i].channels));
+        const int rc = alloc_extent(e, n, &off[(size_t)i]);
+        if (rc != ZLHIP_OK) { rollback(); return rc; }
+        floats[(size_t)i] = n;
+    }
+    // the cut into passes and pieces, the records
+    const uint32_t stageBytes = zl_pcm_stage_switch();
+    std::vector<ZlDecClip> clips((size_t)count);
+    for (int32_t i = 0; i < count; ++i) clips[(size_t)i] = ZlDecClip{ srcs[i].length, srcs[i].channels, srcs[i].format };
+    std::vector<ZlDecPiece> pieces; std::vector<ZlDecPass> passes;
+    zl_dec_plan(clips.data(), count, stageBytes, pieces, passes);
+    for (ZlDecPiece &R : pieces) R.dst = (uint64_t)(uintptr_t)arena_ptr(e, off[(size_t)R.verdict]);
+    std::vector<ZlDecPublish> pub((size_t)count);
+    for (int32_t i = 0; i < count; ++i) {
+        ZlSound s; s.offset = off[(size_t)i]; s.length = srcs[i].length; s.channels = zl_dec_out_channels(srcs[i].channels);
+        s.sample_rate = srcs[i].sample_rate; s.flags = 0; s.pad = 0;
+        pub[(size_t)i] = ZlDecPublish{ s, ids[(size_t)i], zl_dec_is_float(srcs[i].format) ? 1 : 0 };
+    }
+    // (the piece records are measured by their doubled count: a call that grows anything also grows them once it fills more than half)
+    const char *what = "sound_upload_pcm: no device memory for the staging buffer or the call's records";
+    const size_t np = std::max<size_t>(pieces.size() * 2, 64), nc = std::max<size_t>((size_t)count * 2, 64);
+    const int rsv = reserve(e, false, { { ZB_PCM_STAGE, stageBytes, 1, stageBytes, false, what }, { ZB_PCM_PIECES, pieces.size(), sizeof(ZlDecPiece), np, false, what, np },
+                                       { ZB_PCM_PUB, (size_t)count, sizeof(ZlDecPublish), nc, false, what }, { ZB_PCM_VERDICTS, (size_t)count, sizeof(uint32_t), nc, false, what } });
+    if (rsv != ZLHIP_OK) { rollback(); return rsv; }
+    zlhip_engine::Pcm &P = e->pcm;
+    unsigned char *const stage = (unsigned char *)e->scratch[ZB_PCM_STAGE].d; ZlDecPiece *const dPieces = (ZlDecPiece *)e->scratch[ZB_PCM_PIECES].d;
+    ZlDecPublish *const dPub = (ZlDecPublish *)e->scratch[ZB_PCM_PUB].d; uint32_t *const dVerdicts = (uint32_t *)e->scratch[ZB_PCM_VERDICTS].d;
+    // everything is decided: from here on only a HIP error fails the call
+    std::vector<uint32_t> verdicts((size_t)count, 0u);
+    const bool prof = e->profiling;
+    const size_t nev = prof ? 2 * passes.size() + 1 : 0;
+    int krc = 0;
+    while (krc == 0 && P.ev.size() < nev) { hipEvent_t ev = nullptr; krc = (int)hipEventCreate(&ev); if (krc == 0) P.ev.push_back(ev); }
+    if (krc == 0) krc = (int)hipMemsetAsync(dVerdicts, 0, (size_t)count * sizeof(uint32_t), e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dPieces, pieces.data(), pieces.size() * sizeof(ZlDecPiece), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, pub.data(), pub.size() * sizeof(ZlDecPublish), hipMemcpyHostToDevice, e->stream);
+    for (size_t a = 0; krc == 0 && a < passes.size(); ++a) {
+        const ZlDecPass &ps = passes[a];
+        if (prof) krc = (int)hipEventRecord(P.ev[2 * a], e->stream);
+        for (int32_t k = ps.first_piece; krc == 0 && k < ps.first_piece + ps.npieces; ++k) {
+            const ZlDecPiece &R = pieces[(size_t)k];
+            const unsigned char *src = (const unsigned char *)srcs[R.verdict].frames + zl_dec_source_offset(R);
+            krc = (int)hipMemcpyAsync(stage + R.stage_off, src, (size_t)zl_dec_piece_bytes(R), hipMemcpyHostToDevice, e->stream);
+        }
+        if (prof && krc == 0) krc = (int)hipEventRecord(P.ev[2 * a + 1], e->stream);
+        if (krc == 0) krc = zl_launch_pcm_decode(dPieces + ps.first_piece, ps.npieces, ps.items, stage, dVerdicts, e->stream);
+    }
+    if (prof && krc == 0) krc = (int)hipEventRecord(P.ev[2 * passes.size()], e->stream);
+    if (krc == 0) krc = zl_launch_pcm_publish(dPub, count, dVerdicts, e->dSounds, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(verdicts.data(), dVerdicts, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
+    if (krc == 0) { const int w_ = engine_wait(e); if (w_ != ZLHIP_OK) { rollback(); return w_; } }     // the call's one wait
+    if (krc != 0) {
+        e->err = std::string("sound_upload_pcm: ") + hipGetErrorString((hipError_t)krc);
+        (void)hipStreamSynchronize(e->stream);
+        rollback();
+        return ZLHIP_ERR_HIP;
+    }
+    if (prof) {
+        float copy = 0.0f, dec = 0.0f;
+        for (size_t a = 0; a < passes.size(); ++a) {
+            float x = 0.0f, y = 0.0f;
+            ZL_HIP(e, hipEventElapsedTime(&x, P.ev[2 * a], P.ev[2 * a + 1]));
+            ZL_HIP(e, hipEventElapsedTime(&y, P.ev[2 * a + 1], P.ev[2 * a + 2]));
+            copy += x; dec += y;
+        }
+        P.copyMs = copy; P.decodeMs = dec;
+    }
+    // the host's mirror of what the device has published, and every clip's default parameters (applied at the next render call)
+    for (int32_t i = 0; i < count; ++i) {
+        const int id = ids[(size_t)i];
+        ZlSound s = pub[(size_t)i].s;
+        if (!pub[(size_t)i].check || verdicts[(size_t)i] == 0u) s.flags |= ZL_SOUND_FINITE;
+        adopt_sound(e, id, s, floats[(size_t)i]);
+        zlhip_clip_params p;
+        zlhip_clip_params_default(&p, (float)(s.length / s.sample_rate));
+        e->hc.forget_clip_params(id);                              // (the first edit of a slot carries the whole record)
+        (void)zlhip_clip_set(e, id, &p);
+        out_ids[i] = id;
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_upload_pcm(zlhip_engine *e, const void *frames, int32_t format, int32_t channels, int32_t length, double sample_rate, int32_t *out_id)
+{
+    if (!e || !out_id) return ZLHIP_ERR_INVALID;
+    const zlhip_pcm_source q = { frames, length, channels, format, 0, sample_rate };
+    return zlhip_sound_upload_pcm_batch(e, &q, 1, out_id);
+}
+
+int zlhip_debug_upload_pcm_timings(zlhip_engine *e, float *copy_ms, float *decode_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (copy_ms) *copy_ms = e->pcm.copyMs;
+    if (decode_ms) *decode_ms = e->pcm.decodeMs;
+    return ZLHIP_OK;
+}
+
+// ---- clip re-render (zl_stretch.h, zl_stretch.hip) ----------------------------------------------------------------------
+// ClipAudioSource::setPitch / setSpeedRatio / setGain re-render the clip's playback file from its source and the sound reloads it
+// (ClipAudioSource.cpp:279-311,404-413, SamplerSynthSound.cpp:28-68).  Here: every clip of the call is rendered from its ORIGINAL
+// upload into a new arena extent (one seek launch, one synthesis launch for the call), then the sound table entries switch -- at a
+// block boundary: the resident kernel has left and every queued batch has finished -- and the extents the clips played before go
+// back to the arena.  The clip id keeps its slot; a voice playing it reads the new data from its next block at its unchanged position,
+// as the reference's voices read the sound's data pointer and length on every block (SamplerSynthVoice.cpp:186-191).
+// (a call's device records, grown when a call needs more: the free waits for the device, other engines' kernels step aside)
+static int st_reserve(zlhip_engine *e, GrowBuf &b, size_t need, size_t elem)
+{
+    const size_t n = std::max<size_t>(need, 64);
+    const char *what = "sound_rerender: no device memory for the call's records";
+    if (need <= b.cap || !b.d) return grow_buf(e, b, need, elem, n, false, what);      // (nothing to free: no wait for the device)
+    ZlQuiesce quiet(e);
+    return grow_buf(e, b, need, elem, n, false, what);
+}
+
+int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_rerender_params *params, int32_t count)
+{
+    if (!e || count < 0 || (count > 0 && (!ids || !params))) return ZLHIP_ERR_INVALID;
+    if (count == 0) return ZLHIP_OK;
+    if (count > 65535) return fail(e, ZLHIP_ERR_INVALID, "sound_rerender_batch: more than 65535 clips in one call");
+    // validate everything before anything changes
+    std::vector<ZlStretchGeom> geo((size_t)count);
+    std::vector<char> ident((size_t)count, 0);
+    {
+        std::vector<char> seen((size_t)e->cfg.max_sounds, 0);
+        for (int32_t i = 0; i < count; ++i) {
+            const int32_t id = ids[i];
+            { const int rc = check_sound(e, "sound_rerender", id); if (rc != ZLHIP_OK) return rc; }
+            if (seen[(size_t)id]) return fail(e, ZLHIP_ERR_INVALID, "sound_rerender_batch: a clip appears twice");
+            seen[(size_t)id] = 1;
+            const zlhip_rerender_params &q = params[i];
+            const ZlSound &o = e->soundSlots[(size_t)id].orig;
+            if (zl_st_geometry(o.sample_rate, o.length, q.gain_db, q.pitch_semitones, q.speed_ratio, &geo[(size_t)i]) != 0)
+                return fail(e, ZLHIP_ERR_INVALID, "sound_rerender: speed outside [0.25, 4], pitch outside [-24, 24], non-finite gain, or a sample rate the stretch cannot take");
+            ident[(size_t)i] = zl_st_identity(q.gain_db, q.pitch_semitones, q.speed_ratio) ? 1 : 0;
+        }
+    }
+    { const int rc = call_begin(e, true); if (rc != ZLHIP_OK) return rc; }
+
+    // the new extents (all or none: an arena that cannot hold the call leaves every clip as it was)
+    std::vector<size_t> newOff((size_t)count, 0), newFloats((size_t)count, 0);
+    auto rollback = [&]() { for (int32_t i = 0; i < count; ++i) free_extent(e, newOff[(size_t)i], newFloats[(size_t)i]); };
+    std::vector<ZlStretchJob> jobs;
+    std::vector<int32_t> seekList, jobClip;
+    int64_t maxFrames = 0, offs = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        if (ident[(size_t)i]) continue;
+        const ZlSound &o = e->soundSlots[(size_t)ids[i]].orig;
+        const ZlStretchGeom &g = geo[(size_t)i];
+        const size_t floats = zl_extent_floats(g.N, o.channels);
+        const int rc = alloc_extent(e, floats, &newOff[(size_t)i]);
+        if (rc != ZLHIP_OK) { rollback(); return rc; }
+        newFloats[(size_t)i] = floats;
+        ZlStretchJob J; std::memset(&J, 0, sizeof J);
+        J.geom = g;
+        J.src = (uint64_t)(uintptr_t)arena_ptr(e, o.offset);
+        J.dst = (uint64_t)(uintptr_t)arena_ptr(e, newOff[(size_t)i]);
+        J.channels = o.channels;
+        J.off_base = offs;
+        if (g.stretch && g.nseg > 0) { seekList.push_back((int32_t)jobs.size()); offs += g.nseg; }
+        maxFrames = std::max(maxFrames, g.N);
+        jobs.push_back(J);
+        jobClip.push_back(i);
+    }
+    std::vector<int32_t> hOffs((size_t)offs);
+    if (!jobs.empty()) {
+        int rc = st_reserve(e, e->scratch[ZB_ST_JOBS], jobs.size(), sizeof(ZlStretchJob));
+        if (rc == ZLHIP_OK) rc = st_reserve(e, e->scratch[ZB_ST_LIST], std::max<size_t>(seekList.size(), 1), sizeof(int32_t));
+        if (rc == ZLHIP_OK) rc = st_reserve(e, e->scratch[ZB_ST_OFFS], std::max<size_t>((size_t)offs, 1), sizeof(int32_t));
+        if (rc != ZLHIP_OK) { rollback(); return rc; }
+        ZlStretchJob *const dStJobs = (ZlStretchJob *)e->scratch[ZB_ST_JOBS].d;
+        int32_t *const dStList = (int32_t *)e->scratch[ZB_ST_LIST].d, *const dStOffs = (int32_t *)e->scratch[ZB_ST_OFFS].d;
+        hipError_t st = hipMemcpyAsync(dStJobs, jobs.data(), jobs.size() * sizeof(ZlStretchJob), hipMemcpyHostToDevice, e->stream);
+        if (st == hipSuccess && !seekList.empty())
+            st = hipMemcpyAsync(dStList, seekList.data(), seekList.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+        int krc = (int)st;
+        zlhip_engine::Rerender &t = e->st;
+        t.timer.on = e->profiling;
+        if (krc == 0) krc = (int)t.timer.mark(0, e->stream);
+        if (krc == 0) krc = zl_launch_stretch_seek(dStJobs, dStList, (int)seekList.size(), dStOffs, e->stream);
+        if (krc == 0) krc = (int)t.timer.mark(1, e->stream);
+        if (krc == 0) krc = zl_launch_stretch_synth(dStJobs, (int)jobs.size(), maxFrames, dStOffs, e->stream);
+        if (krc == 0) krc = (int)t.timer.mark(2, e->stream);
+        if (krc == 0 && offs > 0) krc = (int)hipMemcpyAsync(hOffs.data(), dStOffs, (size_t)offs * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream);
+        if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);
+        if (krc == 0) krc = (int)t.timer.elapsed(0, 1, &t.seekMs);
+        if (krc == 0) krc = (int)t.timer.elapsed(1, 2, &t.synthMs);
+        if (krc != 0) {
+            e->err = std::string("sound_rerender: ") + hipGetErrorString((hipError_t)krc);
+            (void)hipStreamSynchronize(e->stream);
+            rollback();
+            return ZLHIP_ERR_HIP;
+        }
+    }
+    // the swap: nothing queued can read the extents the clips played until now any more
+    for (int32_t i = 0; i < count; ++i) {
+        const int32_t id = ids[i];
+        zlhip_engine::SoundSlot &slot = e->soundSlots[(size_t)id];
+        free_extent(e, (size_t)e->hc.sounds[id].offset, slot.renderFloats);
+        ZlSound s = slot.orig;
+        // (a rendered extent has not been looked at: it plays without ZL_SOUND_FINITE; identity parameters play the original, with its own flag)
+        if (!ident[(size_t)i]) { s.offset = newOff[(size_t)i]; s.length = (int32_t)geo[(size_t)i].N; s.flags &= ~(int32_t)ZL_SOUND_FINITE; }
+        e->hc.sounds[id] = s;
+        slot.renderFloats = newFloats[(size_t)i];
+        slot.renderOffsets.clear();
+    }
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        const ZlStretchGeom &g = jobs[j].geom;
+        if (g.stretch && g.nseg > 0)
+            e->soundSlots[(size_t)ids[jobClip[j]]].renderOffsets.assign(hOffs.begin() + jobs[j].off_base, hOffs.begin() + jobs[j].off_base + g.nseg);
+    }
+    for (int32_t i = 0; i < count; ++i)
+        ZL_HIP(e, hipMemcpyAsync(e->dSounds + ids[i], &e->hc.sounds[ids[i]], sizeof(ZlSound), hipMemcpyHostToDevice, e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_rerender(zlhip_engine *e, int32_t id, const zlhip_rerender_params *params)
+{
+    return zlhip_sound_rerender_batch(e, &id, params, 1);
+}
+
+// ---- sample-rate conversion (zl_resample.h, zl_resample.hip) --------------------------------------------------------------
+// A clip whose rate differs from the engine's plays through the pitched voice path; converted once, band-limited, it is a unit-step
+// integer-position source and K2 takes its on-grid form.  Every clip of the call is converted from its original upload into a new
+// arena extent by ONE launch, a second one publishes the sound-table entries (ZL_SOUND_FINITE from the device's verdict), and the
+// call waits once.  Synchronisation is zlhip_sound_rerender's: the resident kernel has left and every queued batch has finished before
+// anything is written.  The converted extent becomes the slot's original: later re-renders start from it.
+int zlhip_resample_design(double source_rate, double target_rate, int32_t *L, int32_t *M, int32_t *taps, int32_t *row_floats, float *table, size_t table_floats)
+{
+    ZlRsGeom g;
+    if (zl_rs_geometry(source_rate, target_rate, &g) != 0) return ZLHIP_ERR_INVALID;
+    if (L) *L = g.L;
+    if (M) *M = g.M;
+    if (taps) *taps = g.taps;
+    if (row_floats) *row_floats = g.row;
+    if (!table) return ZLHIP_OK;
+    if (table_floats < (size_t)g.L * (size_t)g.row) return ZLHIP_ERR_CAPACITY;
+    zl_rs_design(g, table);
+    return ZLHIP_OK;
+}
+
+// the device table of a ratio: made by the first call that asks for the ratio, before the call takes anything from the arena, and cached
+// for the engine's life once that call has succeeded -- a call that fails frees the tables it added (hipMalloc and hipFree wait for the
+// device: other engines' kernels step aside).  The copy is queued on the engine's stream in front of the call's launches and shares
+// the call's one wait: the host copy lives until then.
+static int rs_table(zlhip_engine *e, const ZlRsGeom &g, float **out)
+{
+    for (const auto &t : e->rs.tables) if (t.L == g.L && t.M == g.M) { *out = t.d; return ZLHIP_OK; }
+    e->rs.tables.emplace_back();
+    zlhip_engine::Resample::Table &t = e->rs.tables.back();
+    t.L = g.L; t.M = g.M; t.floats = (size_t)g.L * (size_t)g.row;
+    t.pending.resize(t.floats);
+    zl_rs_design(g, t.pending.data());
+    bool ok;
+    { ZlQuiesce quiet(e); ok = hipMalloc((void **)&t.d, t.floats * sizeof(float)) == hipSuccess; }
+    if (!ok) { (void)hipGetLastError(); e->rs.tables.pop_back(); return fail(e, ZLHIP_ERR_CAPACITY, "sound_convert_rate: no device memory for the filter table"); }
+    if (hipMemcpyAsync(t.d, t.pending.data(), t.floats * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(e->stream);
+        { ZlQuiesce quiet(e); (void)hipFree(t.d); }
+        e->rs.tables.pop_back();
+        return fail(e, ZLHIP_ERR_HIP, "sound_convert_rate: the filter table did not reach the device");
+    }
+    e->deviceBytes += t.floats * sizeof(float);
+    *out = t.d;
+    return ZLHIP_OK;
+}
+// after a wait for the engine's stream: the tables' host copies are no longer read
+static void rs_tables_settled(zlhip_engine *e) { for (auto &t : e->rs.tables) std::vector<float>().swap(t.pending); }
+// a failed call: the engine's stream runs dry, the tables behind the first `keep` go back to the device
+static void rs_tables_undo(zlhip_engine *e, size_t keep)
+{
+    (void)hipStreamSynchronize(e->stream);
+    rs_tables_settled(e);
+    while (e->rs.tables.size() > keep) {
+        { ZlQuiesce quiet(e); (void)hipFree(e->rs.tables.back().d); }
+        e->deviceBytes -= e->rs.tables.back().floats * sizeof(float);
+        e->rs.tables.pop_back();
+    }
+}
+
+int zlhip_sound_convert_rate_batch(zlhip_engine *e, const int32_t *ids, int32_t count, double target_rate)
+{
+    if (!e || count < 0 || (count > 0 && !ids)) return ZLHIP_ERR_INVALID;
+    if (count == 0) return ZLHIP_OK;
+    const double ft = target_rate == 0.0 ? e->cfg.playback_sample_rate : target_rate;
+    // validate everything before the first HIP call
+    std::vector<ZlRsGeom> geo((size_t)count);
+    std::vector<int64_t> outN((size_t)count, 0);
+    std::vector<char> skip((size_t)count, 0);
+    {
+        std::vector<char> seen((size_t)e->cfg.max_sounds, 0);
+        int64_t wgs = 0;
+        for (int32_t i = 0; i < count; ++i) {
+            const int32_t id = ids[i];
+            { const int rc = check_sound(e, "sound_convert_rate", id); if (rc != ZLHIP_OK) return rc; }
+            if (seen[(size_t)id]) return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate_batch: a clip appears twice");
+            seen[(size_t)id] = 1;
+        }
+        for (int32_t i = 0; i < count; ++i) {
+            const ZlSound &o = e->soundSlots[(size_t)ids[i]].orig;
+            skip[(size_t)i] = o.sample_rate == ft ? 1 : 0;           // (already at the rate, whatever the rate: nothing to check, nothing to do)
+            if (skip[(size_t)i]) continue;
+            if (zl_rs_geometry(o.sample_rate, ft, &geo[(size_t)i]) != 0)
+                return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate: a rate that is no integer in [1000, 768000], or a ratio beyond L <= 2048, M <= 8 L, 262144 table floats");
+            outN[(size_t)i] = zl_rs_out_frames(geo[(size_t)i], o.length);
+            if (outN[(size_t)i] < 1) return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate: the converted clip would exceed 2^31 - 9 frames");
+            wgs += zl_rs_job_wgs((int32_t)outN[(size_t)i]);
+        }
+        if (wgs > (int64_t)INT32_MAX) return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate_batch: more than 2^31 - 1 workgroups in one call");
+        for (int32_t i = 0; i < count; ++i)
+            if (!skip[(size_t)i] && e->soundSlots[(size_t)ids[i]].renderFloats != 0)
+                return fail(e, ZLHIP_ERR_STATE, "sound_convert_rate: the clip plays a re-render (re-render it with gain 0, pitch 0, speed 1 first)");
+    }
+    int32_t njobs = 0;
+    for (int32_t i = 0; i < count; ++i) njobs += skip[(size_t)i] ? 0 : 1;
+    if (njobs == 0) return ZLHIP_OK;                               // every clip is at the target rate already: no launch, no copy
+    { const int rc = call_begin(e, true); if (rc != ZLHIP_OK) return rc; }
+
+    // the filter tables of the call's ratios first; a call that fails frees the ones it added
+    const size_t tables0 = e->rs.tables.size();
+    std::vector<float *> tables((size_t)count, nullptr);
+    for (int32_t i = 0; i < count; ++i) {
+        if (skip[(size_t)i]) continue;
+        const int rc = rs_table(e, geo[(size_t)i], &tables[(size_t)i]);
+        if (rc != ZLHIP_OK) { rs_tables_undo(e, tables0); return rc; }
+    }
+    // the new extents (all or none: an arena that cannot hold the call leaves every clip as it was)
+    std::vector<size_t> newOff((size_t)count, 0), newFloats((size_t)count, 0);
+    auto rollback = [&]() {
+        rs_tables_undo(e, tables0);
+        for (int32_t i = count - 1; i >= 0; --i) free_extent(e, newOff[(size_t)i], newFloats[(size_t)i]);
+    };
+    for (int32_t i = 0; i < count; ++i) {
+        if (skip[(size_t)i]) continue;
+        const size_t floats = zl_extent_floats(outN[(size_t)i], e->soundSlots[(size_t)ids[i]].orig.channels);
+        const int rc = alloc_extent(e, floats, &newOff[(size_t)i]);
+        if (rc != ZLHIP_OK) { rollback(); return rc; }
+        newFloats[(size_t)i] = floats;
+    }
+    std::vector<ZlRsJob> jobs; std::vector<ZlRsPublish> pub;
+    int32_t wgs = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        if (skip[(size_t)i]) continue;
+        const ZlSound &o = e->soundSlots[(size_t)ids[i]].orig;
+        const ZlRsGeom &g = geo[(size_t)i];
+        float *const table = tables[(size_t)i];
+        ZlRsJob J; std::memset(&J, 0, sizeof J);
+        J.src = (uint64_t)(uintptr_t)arena_ptr(e, o.offset);
+        J.dst = (uint64_t)(uintptr_t)arena_ptr(e, newOff[(size_t)i]);
+        J.table = (uint64_t)(uintptr_t)table;
+        J.len = o.length; J.N = (int32_t)outN[(size_t)i]; J.channels = o.channels;
+        J.L = g.L; J.M = g.M; J.half = g.half; J.taps = g.taps; J.row = g.row;
+        J.wg_base = wgs; J.verdict = (int32_t)jobs.size();
+        wgs += zl_rs_job_wgs(J.N);
+        ZlSound s = o; s.offset = newOff[(size_t)i]; s.length = J.N; s.sample_rate = ft; s.flags &= ~(int32_t)ZL_SOUND_FINITE;
+        pub.push_back(ZlRsPublish{ s, ids[i], J.verdict });
+        jobs.push_back(J);
+    }
+    const char *what = "sound_convert_rate: no device memory for the call's records";
+    const size_t nj = jobs.size(), n = std::max<size_t>(nj * 2, 64);
+    const int rsv = reserve(e, false, { { ZB_RS_JOBS, nj, sizeof(ZlRsJob), n, false, what }, { ZB_RS_PUB, nj, sizeof(ZlRsPublish), n, false, what },
+                                       { ZB_RS_VERDICTS, nj, sizeof(uint32_t), n, false, what } });
+    if (rsv != ZLHIP_OK) { rollback(); return rsv; }
+    ZlRsJob *const dJobs = (ZlRsJob *)e->scratch[ZB_RS_JOBS].d; ZlRsPublish *const dPub = (ZlRsPublish *)e->scratch[ZB_RS_PUB].d;
+    uint32_t *const dVerdicts = (uint32_t *)e->scratch[ZB_RS_VERDICTS].d;
+    // everything is decided: from here on only a HIP error fails the call
+    std::vector<uint32_t> verdicts(jobs.size(), 0u);
+    e->rs.timer.on = e->profiling;
+    int krc = (int)hipMemsetAsync(dVerdicts, 0, jobs.size() * sizeof(uint32_t), e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dJobs, jobs.data(), jobs.size() * sizeof(ZlRsJob), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, pub.data(), pub.size() * sizeof(ZlRsPublish), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)e->rs.timer.mark(0, e->stream);
+    if (krc == 0) krc = zl_launch_resample(dJobs, (int32_t)jobs.size(), wgs, dVerdicts, e->stream);
+    if (krc == 0) krc = zl_launch_resample_publish(dPub, (int32_t)pub.size(), dVerdicts, e->dSounds, e->stream);
+    if (krc == 0) krc = (int)e->rs.timer.mark(1, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(verdicts.data(), dVerdicts, jobs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
+    if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);      // the call's one wait
+    if (krc == 0) krc = (int)e->rs.timer.elapsed(0, 1, &e->rs.ms);
+    if (krc != 0) {
+        e->err = std::string("sound_convert_rate: ") + hipGetErrorString((hipError_t)krc);
+        (void)hipStreamSynchronize(e->stream);
+        // (the table entries the device may have switched go back to what the host's mirror holds)
+        for (const ZlRsPublish &p : pub) (void)hipMemcpy(e->dSounds + p.id, &e->hc.sounds[p.id], sizeof(ZlSound), hipMemcpyHostToDevice);
+        rollback();
+        return ZLHIP_ERR_HIP;
+    }
+    e->outstanding = false;
+    rs_tables_settled(e);
+    // the swap on the host: the converted extent is the slot's original from now on, the old one goes back to the arena
+    for (const ZlRsPublish &p : pub) {
+        zlhip_engine::SoundSlot &slot = e->soundSlots[(size_t)p.id];
+        const size_t oldOff = (size_t)slot.orig.offset, oldFloats = slot.floats;
+        ZlSound s = p.s;
+        if (verdicts[(size_t)p.verdict] == 0u) s.flags |= ZL_SOUND_FINITE;
+        int32_t i = 0;
+        while (ids[i] != p.id) ++i;
+        slot.orig = s; slot.floats = newFloats[(size_t)i];
+        slot.renderOffsets.clear();
+        e->hc.sounds[p.id] = s;
+        free_extent(e, oldOff, oldFloats);
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_convert_rate(zlhip_engine *e, int32_t id, double target_rate)
+{
+    return zlhip_sound_convert_rate_batch(e, &id, 1, target_rate);
+}
+
+int zlhip_debug_convert_timings(zlhip_engine *e, float *device_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (device_ms) *device_ms = e->rs.ms;
+    return ZLHIP_OK;
+}
+
+// ---- waveform overviews (zl_overview.h, zl_overview.hip) -----------------------------------------------------------------
+// The data behind the reference's WaveFormItem (lib/WaveFormItem.cpp:130-139): per pixel column the minimum and maximum of the
+// clip's playback data, reduced where the data lives -- after a re-render the clip that plays exists on the device only.  Like every
+// analysis below, the call runs on the engine's stream behind what is queued there and does NOT ask the resident real-time kernel to
+// leave (call_begin: it reads the arena, which only uploads, releases and re-renders change -- and those stop the kernel and wait
+// themselves), and its buffers are allocated by the first call and grow only (reserve).
+int zlhip_sound_overview_batch(zlhip_engine *e, const zlhip_overview_request *reqs, int32_t count, float *out, size_t out_floats)
+{
+    if (!e || count < 0 || (count > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
+    if (count == 0) return ZLHIP_OK;
+    // validate everything before anything is written
+    int64_t columns = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        const zlhip_overview_request &q = reqs[i];
+        auto resolve = [&](const ZlSound &) { return q.columns < 1 || q.columns > ZLHIP_OVERVIEW_MAX_COLUMNS ? "columns outside 1 .. 4096" : nullptr; };
+        { const int rc = check_request(e, "sound_overview", q, resolve); if (rc != ZLHIP_OK) return rc; }
+        columns += q.columns;
+        if (columns > ZL_OV_MAX_CALL_COLUMNS) return fail(e, ZLHIP_ERR_INVALID, "sound_overview_batch: more than 262144 columns in one call");
+    }
+    if (out_floats < (size_t)columns * 4) return fail(e, ZLHIP_ERR_CAPACITY, "sound_overview: out holds fewer than 4 floats per column");
+    { const int rc = call_begin(e, false); if (rc != ZLHIP_OK) return rc; }
+    const size_t nreq = (size_t)count, ncols = (size_t)columns, ccap = std::min<size_t>(std::max<size_t>(ncols * 2, ZL_OV_MAX_COLUMNS), ZL_OV_MAX_CALL_COLUMNS);
+    const int rsv = reserve(e, true, { { ZB_OV_REQ, nreq, sizeof(ZlOvRequest), std::max<size_t>(nreq * 2, 64), true, "sound_overview: no memory for the call's requests" },
+                                      { ZB_OV_COLS, ncols, 4 * sizeof(float), ccap, true, "sound_overview: no memory for the call's columns" } });
+    if (rsv != ZLHIP_OK) return rsv;
+    zlhip_engine::Overview &o = e->ov;
+    ZlOvRequest *const hReq = (ZlOvRequest *)e->scratch[ZB_OV_REQ].h, *const dReq = (ZlOvRequest *)e->scratch[ZB_OV_REQ].d;
+    float *const hCols = (float *)e->scratch[ZB_OV_COLS].h; uint32_t *const dCols = (uint32_t *)e->scratch[ZB_OV_COLS].d;
+    // the request records: where the extent lies (64-bit, per request: a grown arena's segments are far apart), what to cut it into
+    int64_t items = 0; int32_t col = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        const zlhip_overview_request &q = reqs[i];
+        const ZlSound &s = e->hc.sounds[q.id];
+        ZlOvRequest &R = hReq[i];
+        R.src = (uint64_t)(uintptr_t)arena_ptr(e, s.offset);
+        R.item_base = items;
+        R.first = q.first_frame; R.frames = q.num_frames; R.columns = q.columns;
+        R.channels = s.channels;
+        R.col_base = col;
+        R.ppc = zl_ov_pieces_per_column(q.num_frames, q.columns);
+        items += zl_ov_items(q.num_frames, q.columns);
+        col += q.columns;
+    }
+    o.timer.on = e->profiling;
+    ZL_HIP(e, hipMemcpyAsync(dReq, hReq, (size_t)count * sizeof(ZlOvRequest), hipMemcpyHostToDevice, e->stream));
+    ZL_HIP(e, o.timer.mark(0, e->stream));
+    ZL_HIP(e, hipMemsetAsync(dCols, 0, (size_t)columns * 4 * sizeof(float), e->stream));
+    ZL_KERNEL(e, zl_launch_overview_reduce(dReq, count, items, dCols, e->stream));
+    ZL_KERNEL(e, zl_launch_overview_finish(dCols, (int32_t)columns, e->stream));
+    ZL_HIP(e, o.timer.mark(1, e->stream));
+    ZL_HIP(e, hipMemcpyAsync(hCols, dCols, (size_t)columns * 4 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    ZL_HIP(e, o.timer.elapsed(0, 1, &o.ms));
+    std::memcpy(out, hCols, (size_t)columns * 4 * sizeof(float));
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_overview(zlhip_engine *e, int32_t id, int32_t first_frame, int32_t num_frames, int32_t columns, float *out)
+{
+    const zlhip_overview_request q = { id, first_frame, num_frames, columns };
+    return zlhip_sound_overview_batch(e, &q, 1, out, columns > 0 ? (size_t)columns * 4 : 0);
+}
+
+int zlhip_debug_overview_timings(zlhip_engine *e, float *device_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (device_ms) *device_ms = e->ov.ms;
+    return ZLHIP_OK;
+}
+
+// ---- transients (zl_onset.h, zl_onset.hip) ---------------------------------------------------------------------------------
+// Where a sampler slices a loop.  The synchronisation and the buffers are the overviews'.  The counts and the onsets are written by
+// the pick kernel into host memory mapped into the device, so only what was found crosses.
+int zlhip_onset_resolve(double sample_rate, zlhip_onset_request *r)
+{
+    if (!r || r->first_frame < 0 || r->num_frames < 1) return ZLHIP_ERR_INVALID;
+    zlhip_onset_request q = *r;
+    if (zl_on_resolve(sample_rate, &q.hop_frames, &q.gate, &q.threshold, &q.min_gap_hops, &q.max_onsets) != 0) return ZLHIP_ERR_INVALID;
+    if (zl_on_hops(q.num_frames, q.hop_frames) > ZL_ON_MAX_HOPS) return ZLHIP_ERR_INVALID;
+    *r = q;
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_onsets_batch(zlhip_engine *e, const zlhip_onset_request *reqs, int32_t nreq, zlhip_onset *out, size_t capacity, int32_t *counts)
+{
+    if (!e || nreq < 0 || (nreq > 0 && (!reqs || !out || !counts))) return ZLHIP_ERR_INVALID;
+    if (nreq == 0) return ZLHIP_OK;
+    // validate and resolve everything before anything is written and before the first HIP call
+    std::vector<zlhip_onset_request> res((size_t)nreq);
+    int64_t hops = 0; size_t nout = 0;
+    for (int32_t i = 0; i < nreq; ++i) {
+        zlhip_onset_request &q = res[(size_t)i];
+        q = reqs[i];
+        auto resolve = [&](const ZlSound &s) { return zlhip_onset_resolve(s.sample_rate, &q) != ZLHIP_OK ? kOutsideLimits : nullptr; };
+        { const int rc = check_request(e, "sound_onsets", q, resolve); if (rc != ZLHIP_OK) return rc; }
+        hops += zl_on_hops(q.num_frames, q.hop_frames);
+        if (hops > ZL_ON_MAX_CALL_HOPS) return fail(e, ZLHIP_ERR_INVALID, "sound_onsets_batch: more than 4194304 hops in one call");
+        nout += (size_t)q.max_onsets;
+    }
+    if (capacity < nout) return fail(e, ZLHIP_ERR_CAPACITY, "sound_onsets: out holds fewer onsets than the requests' max_onsets");
+    { const int rc = call_begin(e, false); if (rc != ZLHIP_OK) return rc; }
+    zlhip_engine::Onset &o = e->on;
+    const char *what = "sound_onsets: no memory for the call's buffers";
+    const size_t n = (size_t)nreq, h = (size_t)hops, hcap = std::min<size_t>(std::max<size_t>(h * 2, 4096), ZL_ON_MAX_CALL_HOPS);
+    const int rsv = reserve(e, true, { { ZB_ON_REQ, n, sizeof(ZlOnRequest), std::max<size_t>(n * 2, 64), true, what }, { ZB_ON_E, h, sizeof(uint64_t), hcap, false, what },
+                                      { ZB_ON_N, h, sizeof(int32_t), hcap, false, what }, { ZB_ON_PS, h, sizeof(uint32_t), hcap, false, what } },
+                           { mapped_need(o.counts, std::max<size_t>(n, 32)), mapped_need(o.out, std::max<size_t>(nout, 512)) });
+    if (rsv != ZLHIP_OK) return rsv;
+    ZlOnRequest *const hReq = (ZlOnRequest *)e->scratch[ZB_ON_REQ].h, *const dReq = (ZlOnRequest *)e->scratch[ZB_ON_REQ].d;
+    uint64_t *const dE = (uint64_t *)e->scratch[ZB_ON_E].d; int32_t *const dN = (int32_t *)e->scratch[ZB_ON_N].d; uint32_t *const dPs = (uint32_t *)e->scratch[ZB_ON_PS].d;
+    o.last.clear();
+    int32_t hop0 = 0, out0 = 0;
+    for (int32_t i = 0; i < nreq; ++i) {
+        const zlhip_onset_request &q = res[(size_t)i];
+        const ZlSound &s = e->hc.sounds[q.id];
+        ZlOnRequest &R = hReq[i];
+        R.src = (uint64_t)(uintptr_t)arena_ptr(e, s.offset);
+        R.floor_ = zl_on_floor(q.hop_frames, s.channels, q.gate);
+        R.first = q.first_frame; R.frames = q.num_frames; R.hop = q.hop_frames; R.channels = s.channels;
+        R.hops = (int32_t)zl_on_hops(q.num_frames, q.hop_frames);
+        R.hop_base = hop0;
+        R.threshold = q.threshold; R.min_gap = q.min_gap_hops; R.max_onsets = q.max_onsets;
+        R.out_base = out0;
+        o.last.emplace_back(hop0, R.hops);
+        hop0 += R.hops; out0 += q.max_onsets;
+    }
+    o.timer.on = e->profiling;
+    ZL_HIP(e, hipMemcpyAsync(dReq, hReq, (size_t)nreq * sizeof(ZlOnRequest), hipMemcpyHostToDevice, e->stream));
+    ZL_HIP(e, o.timer.mark(0, e->stream));
+    ZL_KERNEL(e, zl_launch_onset_energy(dReq, nreq, hops, dE, e->stream));
+    ZL_HIP(e, o.timer.mark(1, e->stream));
+    ZL_KERNEL(e, zl_launch_onset_pick(dReq, nreq, dE, dN, dPs, o.counts.d, o.out.d, e->stream));
+    ZL_HIP(e, o.timer.mark(2, e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    ZL_HIP(e, o.timer.elapsed(0, 1, &o.energyMs)); ZL_HIP(e, o.timer.elapsed(1, 2, &o.restMs));
+    size_t at = 0;
+    for (int32_t i = 0; i < nreq; ++i) {
+        const int32_t n = o.counts.h[i];
+        std::memcpy(out + at, o.out.h + hReq[i].out_base, (size_t)n * sizeof(zlhip_onset));
+        counts[i] = n;
+        at += (size_t)n;
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_onsets(zlhip_engine *e, const zlhip_onset_request *r, zlhip_onset *out, int32_t capacity, int32_t *count)
+{
+    if (capacity < 0) return ZLHIP_ERR_INVALID;
+    return zlhip_sound_onsets_batch(e, r, 1, out, (size_t)capacity, count);
+}
+
+int zlhip_debug_onset_hops(zlhip_engine *e, int32_t request, uint64_t *energy, int32_t *strength, int32_t capacity, int32_t *hops)
+{
+    if (!e || request < 0 || (size_t)request >= e->on.last.size()) return ZLHIP_ERR_INVALID;
+    const int32_t base = e->on.last[(size_t)request].first, n = e->on.last[(size_t)request].second;
+    if (hops) *hops = n;
+    if (!energy && !strength) return ZLHIP_OK;
+    if (capacity < n) return fail(e, ZLHIP_ERR_CAPACITY, "debug_onset_hops: capacity below the request's hops");
+    ZL_HIP(e, hipSetDevice(e->device));
+    if (energy) ZL_HIP(e, hipMemcpyAsync(energy, (const uint64_t *)e->scratch[ZB_ON_E].d + base, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    if (strength) ZL_HIP(e, hipMemcpyAsync(strength, (const int32_t *)e->scratch[ZB_ON_N].d + base, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    return engine_wait(e);
+}
+
+int zlhip_debug_onset_timings(zlhip_engine *e, float *energy_ms, float *rest_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (energy_ms) *energy_ms = e->on.energyMs;
+    if (rest_ms) *rest_ms = e->on.restMs;
+    return ZLHIP_OK;
+}
+
+// ---- tempo (zl_tempo.h, zl_tempo.hip) --------------------------------------------------------------------------------------
+// How fast a loop is.  The samples are read once, by the transients' energy kernel; the flux, the autocorrelation and the pick are
+// integer arithmetic on one word per hop.  Synchronisation and buffers as for the overviews.  The integer records are written by the
+// pick kernel into host memory mapped into the device; bpm and confidence are derived here (zl_tp_finish).
+int zlhip_tempo_resolve(double sample_rate, zlhip_tempo_request *r)
+{
+    if (!r || r->first_frame < 0 || r->num_frames < 1) return ZLHIP_ERR_INVALID;
+    zlhip_tempo_request q = *r;
+    if (zl_tp_resolve(sample_rate, &q.hop_frames, &q.bpm_min, &q.bpm_max) != 0) return ZLHIP_ERR_INVALID;
+    if (zl_on_hops(q.num_frames, q.hop_frames) > ZL_TP_MAX_HOPS) return ZLHIP_ERR_INVALID;
+    *r = q;
+    return ZLHIP_OK;
+}
+
+static const size_t kTpRecordBytes = sizeof(ZlOnRequest) + sizeof(ZlTpRequest);     // per request: the energy pass's record and the tempo kernels'
+
+int zlhip_sound_tempo_batch(zlhip_engine *e, const zlhip_tempo_request *reqs, int32_t nreq, zlhip_tempo *out)
+{
+    static_assert(sizeof(zlhip_tempo) == sizeof(ZlTpResult), "the device writes zlhip_tempo's layout");
+    if (!e || nreq < 0 || (nreq > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
+    if (nreq == 0) return ZLHIP_OK;
+    // validate and resolve everything before anything is written and before the first HIP call
+    std::vector<zlhip_tempo_request> res((size_t)nreq);
+    std::vector<ZlTpRequest> geo((size_t)nreq);
+    int64_t hops = 0, lags = 0, items = 0;
+    for (int32_t i = 0; i < nreq; ++i) {
+        zlhip_tempo_request &q = res[(size_t)i];
+        q = reqs[i];
+        auto resolve = [&](const ZlSound &s) { return zlhip_tempo_resolve(s.sample_rate, &q) != ZLHIP_OK ? kOutsideLimits : nullptr; };
+        { const int rc = check_request(e, "sound_tempo", q, resolve); if (rc != ZLHIP_OK) return rc; }
+        const ZlSound &s = e->hc.sounds[q.id];
+        ZlTpRequest &T = geo[(size_t)i];
+        double lmin, lmax;
+        zl_tp_lags(s.sample_rate, q.hop_frames, q.bpm_min, q.bpm_max, &lmin, &lmax);
+        zl_tp_geometry(&T, (int32_t)zl_on_hops(q.num_frames, q.hop_frames), lmin, lmax);
+        T.hop_base = (int32_t)hops; T.acf_base = (int32_t)lags; T.item_base = (int32_t)items;
+        hops += T.hops; lags += T.nlags; items += zl_tp_items(T);
+        if (hops > ZL_TP_MAX_CALL_HOPS) return fail(e, ZLHIP_ERR_INVALID, "sound_tempo_batch: more than 4194304 hops in one call");
+    }
+    { const int rc = call_begin(e, false); if (rc != ZLHIP_OK) return rc; }
+    zlhip_engine::Tempo &t = e->tp;
+    const char *what = "sound_tempo: no memory for the call's buffers";
+    const size_t n = (size_t)nreq, h = (size_t)hops, l = (size_t)lags, rcap = std::max<size_t>(n * 2, 64);
+    const size_t hcap = std::min<size_t>(std::max<size_t>(h * 2, 4096), ZL_TP_MAX_CALL_HOPS);
+    const int rsv = reserve(e, true, { { ZB_TP_REQ, n, kTpRecordBytes, rcap, true, what }, { ZB_TP_E, h, sizeof(uint64_t), hcap, false, what },
+                                      { ZB_TP_W, h, sizeof(uint16_t), hcap, false, what }, { ZB_TP_A, l, sizeof(uint64_t), std::max<size_t>(l * 2, 4096), false, what },
+                                      { ZB_TP_STAT, n, sizeof(ZlTpStat), rcap, false, what } }, { mapped_need(t.out, std::max<size_t>(n, 32)) });
+    if (rsv != ZLHIP_OK) return rsv;
+    char *const hRec = (char *)e->scratch[ZB_TP_REQ].h, *const dRec = (char *)e->scratch[ZB_TP_REQ].d;
+    ZlOnRequest *const hOn = (ZlOnRequest *)hRec, *const dOn = (ZlOnRequest *)dRec;
+    ZlTpRequest *const hTp = (ZlTpRequest *)(hRec + (size_t)nreq * sizeof(ZlOnRequest)), *const dTp = (ZlTpRequest *)(dRec + (size_t)nreq * sizeof(ZlOnRequest));
+    uint64_t *const dE = (uint64_t *)e->scratch[ZB_TP_E].d; uint16_t *const dW = (uint16_t *)e->scratch[ZB_TP_W].d;
+    uint64_t *const dA = (uint64_t *)e->scratch[ZB_TP_A].d; ZlTpStat *const dStat = (ZlTpStat *)e->scratch[ZB_TP_STAT].d;
+    t.last.clear();
+    for (int32_t i = 0; i < nreq; ++i) {
+        const zlhip_tempo_request &q = res[(size_t)i];
+        const ZlSound &s = e->hc.sounds[q.id];
+        const ZlTpRequest &T = geo[(size_t)i];
+        ZlOnRequest &R = hOn[i];
+        std::memset(&R, 0, sizeof(R));
+        R.src = (uint64_t)(uintptr_t)arena_ptr(e, s.offset);
+        R.first = q.first_frame; R.frames = q.num_frames; R.hop = q.hop_frames; R.channels = s.channels;
+        R.hops = T.hops; R.hop_base = T.hop_base;
+        hTp[i] = T;
+        t.last.push_back({T.hop_base, T.hops, T.acf_base, T.first_lag, T.nlags});
+    }
+    t.timer.on = e->profiling;
+    ZL_HIP(e, hipMemcpyAsync(dRec, hRec, (size_t)nreq * kTpRecordBytes, hipMemcpyHostToDevice, e->stream));
+    ZL_HIP(e, t.timer.mark(0, e->stream));
+    ZL_KERNEL(e, zl_launch_onset_energy(dOn, nreq, hops, dE, e->stream));
+    ZL_HIP(e, t.timer.mark(1, e->stream));
+    ZL_KERNEL(e, zl_launch_tempo_flux(dTp, nreq, dE, dW, dA, dStat, e->stream));
+    ZL_HIP(e, t.timer.mark(2, e->stream));
+    ZL_KERNEL(e, zl_launch_tempo_acf(dTp, nreq, items, dW, dA, e->stream));
+    ZL_HIP(e, t.timer.mark(3, e->stream));
+    ZL_KERNEL(e, zl_launch_tempo_pick(dTp, nreq, dA, dStat, t.out.d, e->stream));
+    ZL_HIP(e, t.timer.mark(4, e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    if (t.timer.on) {
+        float flux = 0.0f, pick = 0.0f;
+        ZL_HIP(e, t.timer.elapsed(0, 1, &t.energyMs)); ZL_HIP(e, t.timer.elapsed(1, 2, &flux));
+        ZL_HIP(e, t.timer.elapsed(2, 3, &t.acfMs)); ZL_HIP(e, t.timer.elapsed(3, 4, &pick));
+        t.restMs = flux + pick;
+    }
+    for (int32_t i = 0; i < nreq; ++i) {
+        ZlTpResult r = t.out.h[i];
+        zl_tp_finish(e->hc.sounds[res[(size_t)i].id].sample_rate, res[(size_t)i].hop_frames, &r);
+        std::memcpy(&out[i], &r, sizeof(r));
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_tempo(zlhip_engine *e, const zlhip_tempo_request *r, zlhip_tempo *out) { return zlhip_sound_tempo_batch(e, r, 1, out); }
+
+int zlhip_debug_tempo_acf(zlhip_engine *e, int32_t request, uint16_t *flux, uint64_t *acf, int32_t capacity, int32_t *hops, int32_t *first_lag, int32_t *lags)
+{
+    if (!e || request < 0 || (size_t)request >= e->tp.last.size()) return ZLHIP_ERR_INVALID;
+    const zlhip_engine::Tempo::Last &l = e->tp.last[(size_t)request];
+    if (hops) *hops = l.hops;
+    if (first_lag) *first_lag = l.first_lag;
+    if (lags) *lags = l.nlags;
+    if (!flux && !acf) return ZLHIP_OK;
+    if ((flux && capacity < l.hops) || (acf && capacity < l.nlags)) return fail(e, ZLHIP_ERR_CAPACITY, "debug_tempo_acf: capacity below the request's hops or lags");
+    ZL_HIP(e, hipSetDevice(e->device));
+    if (flux) ZL_HIP(e, hipMemcpyAsync(flux, (const uint16_t *)e->scratch[ZB_TP_W].d + l.hop_base, (size_t)l.hops * sizeof(uint16_t), hipMemcpyDeviceToHost, e->stream));
+    if (acf && l.nlags > 0) ZL_HIP(e, hipMemcpyAsync(acf, (const uint64_t *)e->scratch[ZB_TP_A].d + l.acf_base, (size_t)l.nlags * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    return engine_wait(e);
+}
+
+int zlhip_debug_tempo_timings(zlhip_engine *e, float *energy_ms, float *acf_ms, float *rest_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (energy_ms) *energy_ms = e->tp.energyMs;
+    if (acf_ms) *acf_ms = e->tp.acfMs;
+    if (rest_ms) *rest_ms = e->tp.restMs;
+    return ZLHIP_OK;
+}
+
+// ---- pitch (zl_pitch.h, zl_pitch.hip) --------------------------------------------------------------------------------------
+// What note a clip is.  The diff kernel reads the analysed frames' samples and leaves d per frame and lag; the pick and the vote are
+// integer arithmetic on it.  Synchronisation and buffers as for the overviews.  The integer records are written by the vote kernel
+// into host memory mapped into the device; hz, note, root_note, cents and confidence are derived here (zl_pt_finish).
+int zlhip_pitch_resolve(double sample_rate, zlhip_pitch_request *r)
+{
+    if (!r || r->first_frame < 0 || r->num_frames < 1) return ZLHIP_ERR_INVALID;
+    zlhip_pitch_request q = *r;
+    if (zl_pt_resolve(sample_rate, &q.window, &q.max_frames, &q.f_min, &q.f_max, &q.threshold, &q.gate) != 0) return ZLHIP_ERR_INVALID;
+    *r = q;
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_pitch_batch(zlhip_engine *e, const zlhip_pitch_request *reqs, int32_t nreq, zlhip_pitch *out)
+{
+    static_assert(sizeof(zlhip_pitch) == sizeof(ZlPtResult), "the device writes zlhip_pitch's layout");
+    static_assert(sizeof(zlhip_pitch_frame) == sizeof(ZlPtFrame), "the device writes zlhip_pitch_frame's layout");
+    if (!e || nreq < 0 || (nreq > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
+    if (nreq == 0) return ZLHIP_OK;
+    // validate and resolve everything before anything is written and before the first HIP call
+    std::vector<ZlPtRequest> geo((size_t)nreq);
+    std::vector<double> rate((size_t)nreq);
+    int64_t frames = 0, words = 0, items = 0;
+    for (int32_t i = 0; i < nreq; ++i) {
+        zlhip_pitch_request q = reqs[i];
+        auto resolve = [&](const ZlSound &s) { return zlhip_pitch_resolve(s.sample_rate, &q) != ZLHIP_OK ? kOutsideLimits : nullptr; };
+        { const int rc = check_request(e, "sound_pitch", q, resolve); if (rc != ZLHIP_OK) return rc; }
+        const ZlSound &s = e->hc.sounds[q.id];
+        ZlPtRequest &R = geo[(size_t)i];
+        double tmin, tmax;
+        zl_pt_lags(s.sample_rate, q.f_min, q.f_max, &tmin, &tmax);
+        R.src = 0;                                                 // (the address: behind the reserve, with the other HIP-side state)
+        R.floor_ = (uint64_t)q.window * (uint64_t)s.channels * (uint64_t)q.gate * (uint64_t)q.gate;
+        R.first = q.first_frame; R.channels = s.channels;
+        R.window = q.window; R.tmin = (int32_t)tmin; R.tmax = (int32_t)tmax; R.threshold = q.threshold;
+        zl_pt_frames(q.num_frames, R.window, R.tmax, q.max_frames, &R.frames, &R.hop);
+        R.d_base = words; R.frame_base = (int32_t)frames; R.item_base = (int32_t)items;
+        rate[(size_t)i] = s.sample_rate;
+        frames += R.frames; words += (int64_t)R.frames * zl_pt_nd(R); items += zl_pt_items(R);
+        if (frames > ZL_PT_MAX_CALL_FRAMES) return fail(e, ZLHIP_ERR_INVALID, "sound_pitch_batch: more than 65536 analysis frames in one call");
+    }
+    { const int rc = call_begin(e, false); if (rc != ZLHIP_OK) return rc; }
+    zlhip_engine::Pitch &t = e->pt;
+    const char *what = "sound_pitch: no memory for the call's buffers";
+    const size_t n = (size_t)nreq, f = (size_t)frames, w = (size_t)words, fcap = std::min<size_t>(std::max<size_t>(f * 2, 256), ZL_PT_MAX_CALL_FRAMES);
+    const int rsv = reserve(e, true, { { ZB_PT_REQ, n, sizeof(ZlPtRequest), std::max<size_t>(n * 2, 64), true, what },
+                                      { ZB_PT_D, w, sizeof(uint64_t), std::max<size_t>(w + w / 2, 65536), false, what },
+                                      { ZB_PT_STAT, f, sizeof(ZlPtStat), fcap, false, what }, { ZB_PT_FRAME, f, sizeof(ZlPtFrame), fcap, false, what } },
+                           { mapped_need(t.out, std::max<size_t>(n, 32)) });
+    if (rsv != ZLHIP_OK) return rsv;
+    ZlPtRequest *const hReq = (ZlPtRequest *)e->scratch[ZB_PT_REQ].h, *const dReq = (ZlPtRequest *)e->scratch[ZB_PT_REQ].d;
+    uint64_t *const dD = (uint64_t *)e->scratch[ZB_PT_D].d; ZlPtStat *const dStat = (ZlPtStat *)e->scratch[ZB_PT_STAT].d;
+    ZlPtFrame *const dFrame = (ZlPtFrame *)e->scratch[ZB_PT_FRAME].d;
+    t.last.clear();
+    for (int32_t i = 0; i < nreq; ++i) {
+        ZlPtRequest &R = hReq[i];
+        R = geo[(size_t)i];
+        R.src = (uint64_t)(uintptr_t)arena_ptr(e, e->hc.sounds[reqs[i].id].offset);
+        t.last.push_back({R.d_base, R.frame_base, R.frames, zl_pt_nd(R)});
+    }
+    t.timer.on = e->profiling;
+    ZL_HIP(e, hipMemcpyAsync(dReq, hReq, (size_t)nreq * sizeof(ZlPtRequest), hipMemcpyHostToDevice, e->stream));
+    ZL_HIP(e, t.timer.mark(0, e->stream));
+    ZL_KERNEL(e, zl_launch_pitch_diff(dReq, nreq, items, dD, dStat, e->stream));
+    ZL_HIP(e, t.timer.mark(1, e->stream));
+    ZL_KERNEL(e, zl_launch_pitch_pick(dReq, nreq, frames, dD, dStat, dFrame, e->stream));
+    ZL_KERNEL(e, zl_launch_pitch_vote(dReq, nreq, dFrame, t.out.d, e->stream));
+    ZL_HIP(e, t.timer.mark(2, e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    ZL_HIP(e, t.timer.elapsed(0, 1, &t.diffMs)); ZL_HIP(e, t.timer.elapsed(1, 2, &t.restMs));
+    for (int32_t i = 0; i < nreq; ++i) {
+        ZlPtResult r = t.out.h[i];
+        zl_pt_finish(rate[(size_t)i], &r);
+        std::memcpy(&out[i], &r, sizeof(r));
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_pitch(zlhip_engine *e, const zlhip_pitch_request *r, zlhip_pitch *out) { return zlhip_sound_pitch_batch(e, r, 1, out); }
+
+int zlhip_debug_pitch_frames(zlhip_engine *e, int32_t request, zlhip_pitch_frame *records, int32_t capacity, int32_t *frames)
+{
+    if (!e || request < 0 || (size_t)request >= e->pt.last.size()) return ZLHIP_ERR_INVALID;
+    const zlhip_engine::Pitch::Last &l = e->pt.last[(size_t)request];
+    if (frames) *frames = l.frames;
+    if (!records) return ZLHIP_OK;
+    if (capacity < l.frames) return fail(e, ZLHIP_ERR_CAPACITY, "debug_pitch_frames: capacity below the request's frames");
+    if (l.frames == 0) return ZLHIP_OK;
+    ZL_HIP(e, hipSetDevice(e->device));
+    ZL_HIP(e, hipMemcpyAsync(records, (const ZlPtFrame *)e->scratch[ZB_PT_FRAME].d + l.frame_base, (size_t)l.frames * sizeof(ZlPtFrame), hipMemcpyDeviceToHost, e->stream));
+    return engine_wait(e);
+}
+
+int zlhip_debug_pitch_diff(zlhip_engine *e, int32_t request, int32_t frame, uint64_t *d, int32_t capacity, int32_t *lags)
+{
+    if (!e || request < 0 || (size_t)request >= e->pt.last.size()) return ZLHIP_ERR_INVALID;
+    const zlhip_engine::Pitch::Last &l = e->pt.last[(size_t)request];
+    if (lags) *lags = l.nd;
+    if (!d) return ZLHIP_OK;
+    if (frame < 0 || frame >= l.frames) return fail(e, ZLHIP_ERR_INVALID, "debug_pitch_diff: no such frame");
+    if (capacity < l.nd) return fail(e, ZLHIP_ERR_CAPACITY, "debug_pitch_diff: capacity below the request's lags");
+    ZL_HIP(e, hipSetDevice(e->device));
+    ZL_HIP(e, hipMemcpyAsync(d, (const uint64_t *)e->scratch[ZB_PT_D].d + l.d_base + (int64_t)frame * l.nd, (size_t)l.nd * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    return engine_wait(e);
+}
+
+int zlhip_debug_pitch_timings(zlhip_engine *e, float *diff_ms, float *rest_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (diff_ms) *diff_ms = e->pt.diffMs;
+    if (rest_ms) *rest_ms = e->pt.restMs;
+    return ZLHIP_OK;
+}
+
+// ---- loudness (zl_loudness.h, zl_loudness.hip) -----------------------------------------------------------------------------
+// How loud a clip is: BS.1770's integrated loudness and the sample peak.  The kernel filters and sums the sub-blocks, one lane each,
+// and writes their records into host memory mapped into the device; the blocks, the gates and lufs are derived here (zl_ld_finish).
+// Synchronisation and buffers as for the overviews.
+int zlhip_loudness_design(double sample_rate, double *coeffs)
+{
+    if (!coeffs) return ZLHIP_ERR_INVALID;
+    double c[10];
+    if (zl_ld_design(sample_rate, c) != 0) return ZLHIP_ERR_INVALID;
+    std::memcpy(coeffs, c, sizeof(c));
+    return ZLHIP_OK;
+}
+
+int zlhip_loudness_resolve(double sample_rate, zlhip_loudness_request *r)
+{
+    if (!r) return ZLHIP_ERR_INVALID;
+    int32_t sub = r->sub_frames;
+    if (zl_ld_resolve(sample_rate, r->first_frame, r->num_frames, &sub) != 0) return ZLHIP_ERR_INVALID;
+    r->sub_frames = sub;
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_loudness_batch(zlhip_engine *e, const zlhip_loudness_request *reqs, int32_t nreq, zlhip_loudness *out)
+{
+    static_assert(sizeof(zlhip_loudness) == sizeof(ZlLdResult), "zl_ld_finish writes zlhip_loudness's layout");
+    static_assert(sizeof(zlhip_loudness_sub) == sizeof(ZlLdSub) && sizeof(ZlLdSub) == 24, "the device writes zlhip_loudness_sub's layout");
+    if (!e || nreq < 0 || (nreq > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
+    if (nreq == 0) return ZLHIP_OK;
+    // validate and resolve everything before anything is written and before the first HIP call
+    std::vector<ZlLdRequest> geo((size_t)nreq);
+    int64_t items = 0;
+    for (int32_t i = 0; i < nreq; ++i) {
+        zlhip_loudness_request q = reqs[i];
+        ZlLdRequest &R = geo[(size_t)i];
+        auto resolve = [&](const ZlSound &s) { return zlhip_loudness_resolve(s.sample_rate, &q) != ZLHIP_OK || zl_ld_design(s.sample_rate, R.c) != 0 ? kOutsideLimits : nullptr; };
+        { const int rc = check_request(e, "sound_loudness", q, resolve); if (rc != ZLHIP_OK) return rc; }
+        const ZlSound &s = e->hc.sounds[q.id];
+        R.src = 0;                                                 // (the address: behind the reserve, with the other HIP-side state)
+        R.first = q.first_frame; R.frames = q.num_frames; R.sub = q.sub_frames; R.channels = s.channels;
+        R.items = (int32_t)zl_ld_items(q.num_frames, q.sub_frames); R.item_base = (int32_t)items;
+        items += R.items;
+        if (items > ZL_LD_MAX_CALL_ITEMS) return fail(e, ZLHIP_ERR_INVALID, "sound_loudness_batch: more than 1048576 sub-blocks in one call");
+    }
+    { const int rc = call_begin(e, false); if (rc != ZLHIP_OK) return rc; }
+    zlhip_engine::Loudness &t = e->ld;
+    const size_t n = (size_t)nreq;
+    const int rsv = reserve(e, true, { { ZB_LD_REQ, n, sizeof(ZlLdRequest), std::max<size_t>(n * 2, 64), true, "sound_loudness: no memory for the call's buffers" } },
+                           { mapped_need(t.out, std::max<size_t>((size_t)items, 512)) });
+    if (rsv != ZLHIP_OK) return rsv;
+    ZlLdRequest *const hReq = (ZlLdRequest *)e->scratch[ZB_LD_REQ].h, *const dReq = (ZlLdRequest *)e->scratch[ZB_LD_REQ].d;
+    t.last.clear();
+    for (int32_t i = 0; i < nreq; ++i) {
+        ZlLdRequest &R = hReq[i];
+        R = geo[(size_t)i];
+        R.src = (uint64_t)(uintptr_t)arena_ptr(e, e->hc.sounds[reqs[i].id].offset);
+        t.last.push_back({R.item_base, R.items});
+    }
+    t.timer.on = e->profiling;
+    ZL_HIP(e, hipMemcpyAsync(dReq, hReq, (size_t)nreq * sizeof(ZlLdRequest), hipMemcpyHostToDevice, e->stream));
+    ZL_HIP(e, t.timer.mark(0, e->stream));
+    ZL_KERNEL(e, zl_launch_loudness(dReq, nreq, (int32_t)items, t.out.d, e->stream));
+    ZL_HIP(e, t.timer.mark(1, e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    ZL_HIP(e, t.timer.elapsed(0, 1, &t.kernelMs));
+    for (int32_t i = 0; i < nreq; ++i) {
+        const ZlLdRequest &R = geo[(size_t)i];
+        ZlLdResult r;
+        zl_ld_finish(t.out.h + R.item_base, R.frames, R.sub, &r);
+        std::memcpy(&out[i], &r, sizeof(r));
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_loudness(zlhip_engine *e, const zlhip_loudness_request *r, zlhip_loudness *out) { return zlhip_sound_loudness_batch(e, r, 1, out); }
+
+int zlhip_debug_loudness_subs(zlhip_engine *e, int32_t request, zlhip_loudness_sub *records, int32_t capacity, int32_t *count)
+{
+    if (!e || request < 0 || (size_t)request >= e->ld.last.size()) return ZLHIP_ERR_INVALID;
+    const zlhip_engine::Loudness::Last &l = e->ld.last[(size_t)request];
+    if (count) *count = l.items;
+    if (!records) return ZLHIP_OK;
+    if (capacity < l.items) return fail(e, ZLHIP_ERR_CAPACITY, "debug_loudness_subs: capacity below the request's sub-blocks");
+    std::memcpy(records, e->ld.out.h + l.item_base, (size_t)l.items * sizeof(ZlLdSub));      // (the call has waited: the records are in host memory)
+    return ZLHIP_OK;
+}
+
+int zlhip_debug_loudness_timings(zlhip_engine *e, float *kernel_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (kernel_ms) *kernel_ms = e->ld.kernelMs;
+    return ZLHIP_OK;
+}
+
+int zlhip_debug_rerender_timings(zlhip_engine *e, float *seek_ms, float *synth_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (seek_ms) *seek_ms = e->st.seekMs;
+    if (synth_ms) *synth_ms = e->st.synthMs;
+    return ZLHIP_OK;
+}
+
+int zlhip_debug_rerender_offsets(zlhip_engine *e, int32_t id, int32_t *out, int32_t capacity, int32_t *count)
+{
+    if (!e || id < 0 || id >= e->cfg.max_sounds || !e->hc.soundUsed[id]) return ZLHIP_ERR_INVALID;
+    const std::vector<int32_t> &o = e->soundSlots[(size_t)id].renderOffsets;
+    if (count) *count = (int32_t)o.size();
+    if (!out) return ZLHIP_OK;
+    if ((size_t)capacity < o.size()) return fail(e, ZLHIP_ERR_CAPACITY, "debug_rerender_offsets: capacity below the count");
+    if (!o.empty()) std::memcpy(out, o.data(), o.size() * sizeof(int32_t));
+    return ZLHIP_OK;
+}
+
+}  // extern "C"

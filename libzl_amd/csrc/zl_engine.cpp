@@ -4,7 +4,8 @@
 // level buffers), mirrors the control-plane half of the reference's SamplerChannel (voice
 // allocation and command merge, SamplerSynth.cpp:187-230; startNote's one-off math,
 // SamplerSynthVoice.cpp:110-144) and launches the kernels of zl_kernels.hip.  There is no CPU
-// render path in this library: every sample is produced by the HIP kernels.
+// render path in this library: every sample is produced by the HIP kernels.  The engine's state and
+// the helpers shared with the clip services (zl_clip_calls.cpp) are declared in zl_engine_impl.h.
 #include <hip/hip_runtime.h>
 #include <sys/resource.h>
 
@@ -21,23 +22,13 @@
 #include <vector>
 
 #include "../../include/zlhip.h"
-#include "zl_arena.h"
-#include "zl_host.h"
+#include "zl_engine_impl.h"
 #include "zl_kernels.h"
 #include "zl_member.h"
 #include "zl_order.h"
 #include "zl_pair.h"
 #include "zl_plan.h"
-#include "zl_onset.h"
-#include "zl_tempo.h"
-#include "zl_pitch.h"
-#include "zl_loudness.h"
-#include "zl_overview.h"
-#include "zl_resample.h"
-#include "zl_decode.h"
 #include "zl_render.h"
-#include "zl_stretch.h"
-#include "zl_types.h"
 
 // buses at least this wide are split into one voice per workgroup for single real-time blocks (pick_group)
 #define ZL_RT_SPLIT_MIN_VOICES 32
@@ -52,260 +43,9 @@ template <typename T> hipError_t dalloc(T **p, size_t n)
     return hipMalloc((void **)p, bytes);
 }
 
-// host memory mapped into the device, grown by doubling (the buffer must be idle)
-template <typename T> hipError_t grow_mapped(T **host, T **dev, size_t *cap, size_t need)
-{
-    if (need <= *cap) return hipSuccess;
-    if (*host) { hipError_t r = hipHostFree(*host); *host = nullptr; *dev = nullptr; *cap = 0; if (r != hipSuccess) return r; }
-    const size_t n = need * 2;
-    hipError_t r = hipHostMalloc((void **)host, n * sizeof(T));
-    if (r != hipSuccess) return r;
-    r = hipHostGetDevicePointer((void **)dev, *host, 0);
-    if (r == hipSuccess) *cap = n;
-    return r;
-}
-
-// a call's records and staging on the device, allocated by the first call that needs them and grown only (grow_buf); an engine that
-// never re-renders, asks for an overview or loads PCM has none.  h: the page-locked host twin, where there is one; cap in elements
-struct GrowBuf { void *d = nullptr, *h = nullptr; size_t cap = 0; };
-enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a call's jobs, the jobs whose stretch runs, their seek offsets
-       ZB_OV_REQ, ZB_OV_COLS,                                 // overviews: a call's request records and its columns [columns][4], with host twins
-       ZB_PCM_STAGE, ZB_PCM_PIECES, ZB_PCM_PUB, ZB_PCM_VERDICTS,   // PCM: the staging buffer for the raw bytes, a call's piece and publish records, its verdict words
-       ZB_RS_JOBS, ZB_RS_PUB, ZB_RS_VERDICTS,                // rate conversion: a call's job and publish records, its verdict words
-       ZB_ON_REQ, ZB_ON_E, ZB_ON_N, ZB_ON_PS,                // transients: a call's request records (with a host twin), and per hop E, N and the windows' running maxima
-       ZB_TP_REQ, ZB_TP_E, ZB_TP_W, ZB_TP_A, ZB_TP_STAT,      // tempo: a call's request records (the energy pass's and the tempo kernels', one host twin), per hop E and W, per lag A, per request the flux's statistics
-       ZB_PT_REQ, ZB_PT_D, ZB_PT_STAT, ZB_PT_FRAME,           // pitch: a call's request records (with a host twin), per frame and lag d, per frame the diff kernel's statistics and the frame records
-       ZB_LD_REQ,                                             // loudness: a call's request records (with a host twin)
-       ZB_COUNT };
-
 }  // namespace
 
-struct zlhip_engine {
-    zlhip_config cfg{};
-    int V = 0;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    char devname[256] = {0};
-
-    // HBM
-    float *arena = nullptr;
-    // the arena's allocator (zl_arena.h): the free extents of the first arena and of the further segments, allocated when a source does
-    // not fit any more (clips are loaded freely; 288 GB of HBM).  A source in a segment is addressed like any other, by its float offset
-    // from `arena` modulo 2^64, which the kernels' 64-bit address arithmetic wraps back.  A segment's handle is its device pointer.
-    ZlArena arenaAlloc;
-    // per sound slot, next to hc.sounds (what the slot plays) and hc.soundUsed: the original upload -- every re-render
-    // (zlhip_sound_rerender) starts from it, as tracktion renders from the clip's source file -- and the render it plays instead while it has one
-    struct SoundSlot {
-        ZlSound orig{0, 0, 0, 0.0}; size_t floats = 0;   // the original upload, the floats it holds in the arena
-        size_t renderFloats = 0;         // floats of the slot's rendered extent, 0 = it plays its original
-        std::vector<int32_t> renderOffsets;   // the seek offsets of the slot's last render (zlhip_debug_rerender_offsets)
-    };
-    std::vector<SoundSlot> soundSlots;
-    GrowBuf scratch[ZB_COUNT];           // a call's records and staging (grow_buf)
-    hipEvent_t stEv[3] = {nullptr, nullptr, nullptr};     // profiling (zlhip_set_profiling): before the seek, between the launches, after
-    float stSeekMs = 0.0f, stSynthMs = 0.0f;             // ... of the last call (zlhip_debug_rerender_timings)
-    // waveform overviews (zlhip_sound_overview; zl_overview.h)
-    struct Overview {
-        hipEvent_t ev[2] = {nullptr, nullptr}; float ms = 0.0f;                 // profiling: around the call's launches (zlhip_debug_overview_timings)
-    } ov;
-    // transients (zlhip_sound_onsets; zl_onset.h)
-    struct Onset {
-        int32_t *hCounts = nullptr, *dCounts = nullptr; size_t countsCap = 0;   // a call's counts and onsets, in host memory mapped into the device:
-        ZlOnOnset *hOut = nullptr, *dOut = nullptr; size_t outCap = 0;         // the pick kernel writes what it found there and nothing else crosses
-        std::vector<std::pair<int32_t, int32_t>> last;                          // per request of the last call: its first hop, its hops (zlhip_debug_onset_hops)
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; float energyMs = 0.0f, restMs = 0.0f;   // profiling (zlhip_debug_onset_timings)
-    } on;
-    // tempo (zlhip_sound_tempo; zl_tempo.h)
-    struct Tempo {
-        ZlTpResult *hOut = nullptr, *dOut = nullptr; size_t outCap = 0;         // a call's integer records, in host memory mapped into the device
-        struct Last { int32_t hop_base, hops, acf_base, first_lag, nlags; };
-        std::vector<Last> last;                                                 // per request of the last call (zlhip_debug_tempo_acf)
-        hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; float energyMs = 0.0f, acfMs = 0.0f, restMs = 0.0f;   // profiling (zlhip_debug_tempo_timings)
-    } tp;
-    // pitch (zlhip_sound_pitch; zl_pitch.h)
-    struct Pitch {
-        ZlPtResult *hOut = nullptr, *dOut = nullptr; size_t outCap = 0;         // a call's integer records, in host memory mapped into the device
-        struct Last { int64_t d_base; int32_t frame_base, frames, nd; };
-        std::vector<Last> last;                                                 // per request of the last call (zlhip_debug_pitch_frames / _diff)
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; float diffMs = 0.0f, restMs = 0.0f;   // profiling (zlhip_debug_pitch_timings)
-    } pt;
-    // loudness (zlhip_sound_loudness; zl_loudness.h)
-    struct Loudness {
-        ZlLdSub *hOut = nullptr, *dOut = nullptr; size_t outCap = 0;            // a call's sub-block records, in host memory mapped into the device
-        struct Last { int32_t item_base, items; };
-        std::vector<Last> last;                                                 // per request of the last call (zlhip_debug_loudness_subs)
-        hipEvent_t ev[2] = {nullptr, nullptr}; float kernelMs = 0.0f;           // profiling (zlhip_debug_loudness_timings)
-    } ld;
-    // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h)
-    struct Pcm {
-        std::vector<hipEvent_t> ev;                                 // profiling: before every pass's copies and every decode launch, behind the last
-        float copyMs = 0.0f, decodeMs = 0.0f;                       // ... of the last call made with profiling on (zlhip_debug_upload_pcm_timings)
-    } pcm;
-    // clips converted to another rate (zlhip_sound_convert_rate; zl_resample.h): the filter tables on the device, one per (L, M) ever asked for
-    struct Resample {
-        struct Table { int32_t L = 0, M = 0; float *d = nullptr; size_t floats = 0; std::vector<float> pending; };   // pending: the host copy, until the call that made the table has waited
-        std::vector<Table> tables;
-        hipEvent_t ev[2] = {nullptr, nullptr}; float ms = 0.0f;                 // profiling: around the call's launches (zlhip_debug_convert_timings)
-    } rs;
-    ZlSound *dSounds = nullptr; ZlClip *dClips = nullptr;
-    ZlVoiceState *dVoices = nullptr;
-    // K1 -> K2 records, double buffered so that planning window i+1 overlaps rendering window i
-    struct PlanSet {
-        ZlVoiceConst *vconst = nullptr; ZlRunList *runs = nullptr; ZlTSeg *tsegs = nullptr;
-        ZlPlanHdr *hdr = nullptr; ZlPlanSeg0 *seg0 = nullptr; ZlPlanSeg1 *seg1 = nullptr;
-        double *ctlP = nullptr; float *ctlEnv = nullptr;  // the window's pool of per-frame control slots (zl_plan.h, zl_ctl_alloc)
-        unsigned long long *ctlNext = nullptr;            // its bump counter, never reset: a window's slots count from ctlBase
-        unsigned long long ctlBase = 0;                   // host side: past every value the counter can have reached
-        ZlSimConst *simConst = nullptr;
-        float *partials = nullptr;
-        int32_t *order = nullptr; size_t orderInts = 0;  // K2's phase order of the window's blocks (K1o): [z-slots][K] and the run summary behind it (zl_order_ints), allocated on first use
-        hipEvent_t planned = nullptr, rendered = nullptr, k1done = nullptr;
-        hipEvent_t renderedEv = nullptr; // the event that marks the end of the last rendering from this set (rendered, or a profiling event)
-        bool used = false;               // `rendered` has been recorded at least once
-    } ps[2];
-    int windowBlocks = 0;                // plan_window_blocks when given (a fixed number of blocks per plan window)
-    size_t windowFrames = 0;             // else a window is this many frames: 2048 blocks of 256 frames, more blocks when they are shorter
-    int windowCap = 0;                   // blocks the K1 -> K2 record arrays hold
-    size_t ctlPoolFrames = 0;            // frames of per-frame control a record set's pool holds (slots = this / nframes)
-    int ctlSlotsOverride = -1;           // ZL_CTL_POOL_SLOTS (tests of the exhausted pool)
-    hipStream_t planStream = nullptr;    // K0 + K1 (sequential per voice)
-    hipStream_t lastRenderStream = nullptr;                          // the stream the previous call rendered on
-    hipStream_t lastPlanStream = nullptr; hipEvent_t evPlanTail = nullptr;   // where the previous call planned (voice-state order)
-    hipEvent_t lastPlanEvent = nullptr;  // marks the end of that planning: evPlanTail, or the call's `done` event when it planned on its render stream
-    hipStream_t asmStream = nullptr;     // K1c of window w runs here, next to K1 of window w+1
-    std::vector<std::pair<int, int>> wins;
-    // Per-call resources, double buffered so that consecutive zlhip_render_batch calls pipeline: the host prepares
-    // (and the planning stream plans) call i+1 while call i still renders; a slot is reused by call i+2.
-    struct CallSlot {
-        ZlClock *hClocks = nullptr, *hClocksDev = nullptr;   // the call's block clocks, in host memory mapped into the device: K1 reads them in place
-        ZlPassParams *hPass = nullptr, *dPass = nullptr;   // fused fan-out parameters of the call
-        // the call's voice operations, in host memory mapped into the device: K0 reads them in place (no copy command)
-        ZlVoiceOp *hOps = nullptr, *hOpsDev = nullptr; ZlOpRange *hRanges = nullptr, *hRangesDev = nullptr;
-        size_t opsCap = 0, rangesCap = 0;
-        ZlClipEdit *hEdits = nullptr, *hEditsDev = nullptr; size_t editsCap = 0;   // the call's clip-parameter edits, same arrangement
-        ZlReport *hReports = nullptr, *dReports = nullptr;
-        float *hGain = nullptr;
-        ZlBatchStats *hStats = nullptr, *dStats = nullptr;
-        ZlReport *hReportsDev = nullptr; float *hGainDev = nullptr; ZlBatchStats *hStatsDev = nullptr;   // device views of the host buffers
-        hipEvent_t evBegin = nullptr, evEnd = nullptr, done = nullptr;
-        // `done` alternates between two events from one use of the slot to the next, so that the NEXT call (the other slot) can take this
-        // call's completion as the begin of its own profile -- one event-record packet fewer between two calls' render kernels -- and
-        // still find it intact when it is harvested, two calls later
-        hipEvent_t doneEv[2] = {nullptr, nullptr}; unsigned doneGen = 0;
-        hipEvent_t beginEv = nullptr;    // what this call's profile counts from: its own evBegin, or the previous call's `done`
-        std::vector<hipEvent_t> evK2;    // [2 * max windows] start/end of every K2 launch (profiling)
-        int windows = 0;
-        bool inflight = false, profiled = false;
-        bool fusedDone = false;          // the call's last K2 launch published the reports and carries `done` as its stop event (no report kernel)
-    } slots[2];
-    unsigned callIndex = 0, setPhase = 0;
-    CallSlot *latest = nullptr;          // slot of the most recent call
-    zlhip_timings totals{}; int totalCalls = 0;   // sums over harvested calls (zlhip_profile_totals)
-    float *dGain = nullptr;
-    ZlPassCache *dPassCache = nullptr;   // per voice: the recorded pass of its loop (zl_plan.h, replay_cached_pass)
-    float *dBus = nullptr;
-    ZlBlockLevels *dLevels = nullptr; ZlLevelsState *dLevelState = nullptr;
-    int32_t *dTrace = nullptr; ZlPassParams *dPass = nullptr;
-    size_t traceInts = 0;
-    int maxGroups = 1;
-
-    // pinned host staging
-    float *hBus = nullptr, *hBusDev = nullptr;   // one real-time block, host memory mapped into the device
-    // one real-time block's JackPassthrough fan-out [B][6][max_frames] (zlhip_render_fanout), written by the kernels like hBus; the
-    // parameter table the resident kernel reads ([B], mapped host memory) and its version (never 0; moved when an entry changes)
-    float *hFan = nullptr, *hFanDev = nullptr;
-    ZlPassParams *hPassRt = nullptr, *hPassRtDev = nullptr;
-    uint32_t *hNonFinite = nullptr, *hNonFiniteDev = nullptr;   // mapped host word: zl_k_interleave sets it when an uploaded sample is NaN or infinite
-    uint32_t passSeq = 1;
-    // zero-copy delivery of a real-time cycle: when the caller's out_left / out_right (/ fan_out) are page-locked and mapped (zlhip_host_alloc,
-    // hipHostMalloc, hipHostRegister) the kernels write them directly -- no copy on the host behind the cycle (24 KB + 72 KB for 12 buses:
-    // 1.6 + 5 us of reading lines the device has just written).  The device views of the last buffers seen are kept.
-    struct OutViews { const void *hL = nullptr, *hR = nullptr, *hF = nullptr; float *dL = nullptr, *dR = nullptr, *dF = nullptr; bool ok = false; } outViews;
-    bool directOut = true;               // ZL_RT_DIRECT_OUT=0: always through the staging rows
-    ZlLevelsState *hLevelState = nullptr;
-
-    // host mirrors
-    ZlHostControl hc;                    // voices / sounds / clip parameters / pending ops (zl_host.h)
-    std::vector<ZlOpRange> ranges;
-
-    // last batch
-    int lastK = 0, lastN = 0, lastWindows = 0; float *lastBus = nullptr; bool outstanding = false; bool reportsFresh = false;
-    bool trace = false; int traceK = 0, traceN = 0;
-    int forceSlow = 0;
-    size_t deviceBytes = 0;              // HBM the engine allocated at creation (arena included)
-    int staged = 0;                      // K2 variant with LDS-staged source windows (zl_kernels.hip), chosen per mode at creation
-
-    // resident real-time kernel (zl_k_rt_loop): the mailbox in mapped host memory, its stream, what it was launched for
-    struct Rt {
-        bool enabled = false, running = false; int wide = -1;    // wide: 1 always, 0 never, -1 only with one voice per workgroup
-        ZlRtShared *h = nullptr, *d = nullptr;
-        ZlRtDev *dev = nullptr;                            // the kernel's own hand-off words in HBM
-        ZlOpRange *devRanges = nullptr;                    // wide buses: workgroup 0's copy of a block's operation ranges
-        int capacity[2] = {-1, -1};                        // workgroups of the kernel the device holds at once (narrow, wide); -1 = not asked yet
-        int vw = 0;                                        // wide buses: voices per resident workgroup (a divisor of voices_per_bus)
-        double share = 0.0;                                // of the device's resident-workgroup capacity this engine's kernel takes (rt_eligible)
-        std::atomic<bool> inCycle{false};                  // a cycle is being rendered through the resident kernel (its share stays taken even if the kernel has just left)
-        int maxFrames = 4096;                              // longest period the resident kernel takes (ZL_RT_MAX_FRAMES)
-        hipStream_t stream = nullptr;
-        int nframes = 0;
-        unsigned long long seq = 0;
-        unsigned long long starts = 0, cycles = 0;        // launches of the resident kernel, cycles it rendered (zlhip_rt_stats)
-        unsigned long long idleTicks = 20000000ull;       // 200 ms of the 100 MHz counter without a block: the kernel leaves
-        bool stampsOn = false; double stampSum[6] = {0, 0, 0, 0, 0, 0}; unsigned long long stampN = 0;   // ZL_RT_STAMPS=1: stage times (us)
-        // where the last real-time cycle spent its time, seen from the host (zlhip_rt_last_cycle): a worst case has to be attributable
-        bool traceOn = false; double slowUs = 0.0;         // ZL_RT_TRACE=1; ZL_RT_TRACE_SLOW_US=<n>: cycles longer than that are reported on stderr
-        zlhip_rt_cycle_trace last{};
-    } rt;
-
-    // offline bounce (zlhip_bounce): the device bus buffers of two chunks rendered into in turn, their 16-bit versions, the copy stream.
-    // A chunk is ONE zlhip_render_batch call; every plan window of it is delivered as soon as its render kernel has finished
-    // (the sink below, called from the window loop), while the following windows render.
-    struct Bounce {
-        static constexpr int NBUF = 2, NEV = 16;
-        float *bus[NBUF] = {nullptr, nullptr}; int16_t *pcm[NBUF] = {nullptr, nullptr};
-        size_t busFloats = 0, pcmFrames = 0;
-        hipStream_t copyStream = nullptr;
-        hipEvent_t copied[NBUF] = {nullptr, nullptr};      // the last delivery out of a chunk buffer
-        hipEvent_t winEv[NEV] = {};                        // "window rendered (and converted)": waited for by the copy stream
-        unsigned winNext = 0;
-        bool active = false;                 // inside zlhip_bounce: every chunk plans on the planning stream
-        struct Sink {
-            bool on = false, pcm = false;
-            char *hostBase = nullptr;        // the chunk's first frame in the caller's buffer
-            void *hostDev = nullptr;         // direct delivery: the device view of hostBase (page-locked memory only), else nullptr
-            size_t totalFrames = 0;          // frames per row of the caller's buffer (the whole bounce)
-            int16_t *pcmDev = nullptr;       // the chunk's 16-bit staging buffer [B][chunk frames][2]
-        } sink;
-    } bnc;
-
-    bool failed = false;                 // the resident kernel stopped answering in the middle of a cycle: the voice table is undefined (zlhip_render)
-
-    // profiling
-    bool profiling = false; hipEvent_t evJoin = nullptr;
-    hipEvent_t joins[2] = {nullptr, nullptr};   // events on caller streams the host still has to wait for (engine_wait)
-    zlhip_timings timings{};
-};
-
-#define ZL_HIP(e, call)                                                                        \
-    do {                                                                                       \
-        hipError_t st_ = (call);                                                               \
-        if (st_ != hipSuccess) {                                                               \
-            (e)->err = std::string(#call) + ": " + hipGetErrorString(st_);                     \
-            return ZLHIP_ERR_HIP;                                                              \
-        }                                                                                      \
-    } while (0)
-
-#define ZL_KERNEL(e, call)                                                                     \
-    do {                                                                                       \
-        int st_ = (call);                                                                      \
-        if (st_ != 0) {                                                                        \
-            (e)->err = std::string(#call) + ": " + hipGetErrorString((hipError_t)st_);         \
-            return ZLHIP_ERR_HIP;                                                              \
-        }                                                                                      \
-    } while (0)
-
-static int fail(zlhip_engine *e, int code, const char *msg)
+int fail(zlhip_engine *e, int code, const char *msg)
 {
     if (e) e->err = msg;
     return code;
@@ -314,7 +54,7 @@ static int fail(zlhip_engine *e, int code, const char *msg)
 // Host-side wait for everything the engine has queued, on its own stream and on caller-provided streams.  (Work on
 // a caller's stream is joined through events waited for on the host, not by queueing a wait on the engine's stream:
 // an idle HIP stream holds no hardware queue, and the process has few of them.)
-static int engine_wait(zlhip_engine *e)
+int engine_wait(zlhip_engine *e)
 {
     for (hipEvent_t &ev : e->joins) {
         if (ev) { ZL_HIP(e, hipEventSynchronize(ev)); ev = nullptr; }
@@ -345,47 +85,44 @@ void rt_unregister(zlhip_engine *e)
     g_rt.engines.erase(std::remove(g_rt.engines.begin(), g_rt.engines.end(), e), g_rt.engines.end());
 }
 
-struct ZlQuiesce {
-    explicit ZlQuiesce(const zlhip_engine *self)
-    {
-        g_rt.quiescing.fetch_add(1, std::memory_order_acq_rel);
-        // The registry's lock is held in short bursts only -- to post the request and to look at the kernels' states -- never while
-        // waiting: rt_start and rt_unregister take the same lock on a JACK thread (an audio thread whose kernel had just
-        // left could sit behind this wait for up to a second).  The engine list is read afresh under the lock every round, so an
-        // engine destroyed meanwhile is simply no longer there.
-        const auto t0 = std::chrono::steady_clock::now();
-        for (;;) {
-            bool all = true;
-            {
-                std::lock_guard<std::mutex> lk(g_rt.mu);
-                for (zlhip_engine *o : g_rt.engines) {
-                    if (o == self || !o->rt.h) continue;
-                    __atomic_store_n(&o->rt.h->yield, 1u, __ATOMIC_RELEASE);
-                    // (a kernel that was just launched reads the request at its first idle poll)
-                    if (__atomic_load_n(&o->rt.h->state, __ATOMIC_ACQUIRE) != 2u) all = false;
-                }
-            }
-            // (one second: thousands of cycles)
-            if (all || std::chrono::steady_clock::now() - t0 > std::chrono::seconds(1)) break;
-            for (int i = 0; i < 256; ++i) __builtin_ia32_pause();
-        }
-    }
-    ~ZlQuiesce()
-    {
-        std::lock_guard<std::mutex> lk(g_rt.mu);
-        if (g_rt.quiescing.fetch_sub(1, std::memory_order_acq_rel) == 1)
-            for (zlhip_engine *o : g_rt.engines) if (o->rt.h) __atomic_store_n(&o->rt.h->yield, 0u, __ATOMIC_RELEASE);
-    }
-    ZlQuiesce(const ZlQuiesce &) = delete;
-    ZlQuiesce &operator=(const ZlQuiesce &) = delete;
-};
 }  // namespace
+
+ZlQuiesce::ZlQuiesce(const zlhip_engine *self)
+{
+    g_rt.quiescing.fetch_add(1, std::memory_order_acq_rel);
+    // The registry's lock is held in short bursts only -- to post the request and to look at the kernels' states -- never while
+    // waiting: rt_start and rt_unregister take the same lock on a JACK thread (an audio thread whose kernel had just
+    // left could sit behind this wait for up to a second).  The engine list is read afresh under the lock every round, so an
+    // engine destroyed meanwhile is simply no longer there.
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+        bool all = true;
+        {
+            std::lock_guard<std::mutex> lk(g_rt.mu);
+            for (zlhip_engine *o : g_rt.engines) {
+                if (o == self || !o->rt.h) continue;
+                __atomic_store_n(&o->rt.h->yield, 1u, __ATOMIC_RELEASE);
+                // (a kernel that was just launched reads the request at its first idle poll)
+                if (__atomic_load_n(&o->rt.h->state, __ATOMIC_ACQUIRE) != 2u) all = false;
+            }
+        }
+        // (one second: thousands of cycles)
+        if (all || std::chrono::steady_clock::now() - t0 > std::chrono::seconds(1)) break;
+        for (int i = 0; i < 256; ++i) __builtin_ia32_pause();
+    }
+}
+ZlQuiesce::~ZlQuiesce()
+{
+    std::lock_guard<std::mutex> lk(g_rt.mu);
+    if (g_rt.quiescing.fetch_sub(1, std::memory_order_acq_rel) == 1)
+        for (zlhip_engine *o : g_rt.engines) if (o->rt.h) __atomic_store_n(&o->rt.h->yield, 0u, __ATOMIC_RELEASE);
+}
 
 // ---- resident real-time kernel ------------------------------------------------------------------
 // Asks the resident kernel to leave and waits for it.  Called before anything else touches the voice table, the clip / sound
 // tables, the arena or the plan records from outside (batches, uploads, parameter changes, destruction): while the kernel is
 // resident its caches are not refreshed by other engines' writes.
-static int rt_stop(zlhip_engine *e)
+int rt_stop(zlhip_engine *e)
 {
     if (!e->rt.running) return ZLHIP_OK;
     __atomic_store_n(&e->rt.h->stop, 1u, __ATOMIC_RELEASE);
@@ -394,6 +131,79 @@ static int rt_stop(zlhip_engine *e)
     e->rt.running = false;
     rt_unregister(e);
     return ZLHIP_OK;
+}
+
+// The start of a call, behind its validation.  stop: the call writes the sound table or the arena, which change under the resident
+// real-time kernel otherwise; an analysis only reads the arena and leaves the kernel alone.  Queued batches still read the table.
+int call_begin(zlhip_engine *e, bool stop)
+{
+    ZL_HIP(e, hipSetDevice(e->device));
+    if (stop) { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }
+    return e->outstanding ? engine_wait(e) : ZLHIP_OK;
+}
+
+// `need` elements of `elem` bytes in a buffer that only grows: one that is too small is freed and one of `new_cap` elements allocated,
+// with a page-locked host twin where `twin`; a failure leaves it empty and the call failed with `what`.  Besides the arena's segments
+// this is the only place after creation that changes deviceBytes.  hipMalloc, hipFree and hipHostFree wait for the device: stopping
+// this engine's resident kernel and asking the others' to step aside (ZlQuiesce) is the caller's part.
+int grow_buf(zlhip_engine *e, GrowBuf &b, size_t need, size_t elem, size_t new_cap, bool twin, const char *what)
+{
+    if (need <= b.cap) return ZLHIP_OK;
+    if (b.d) { (void)hipFree(b.d); e->deviceBytes -= b.cap * elem; }
+    if (b.h) (void)hipHostFree(b.h);
+    b = GrowBuf();
+    if ((twin && hipHostMalloc(&b.h, new_cap * elem) != hipSuccess) || hipMalloc(&b.d, new_cap * elem) != hipSuccess) {
+        (void)hipGetLastError();
+        if (b.h) (void)hipHostFree(b.h);
+        b = GrowBuf();
+        return fail(e, ZLHIP_ERR_CAPACITY, what);
+    }
+    e->deviceBytes += new_cap * elem;
+    b.cap = new_cap;
+    return ZLHIP_OK;
+}
+
+// an extent of `floats` floats (a multiple of 4) of the arena: first fit over the free extents, else a further arena segment
+// (zl_arena.h decides; the device memory of a segment is allocated here)
+int alloc_extent(zlhip_engine *e, size_t floats, size_t *out_off)
+{
+    ZlArena &a = e->arenaAlloc;
+    if (a.take(floats, out_off)) return ZLHIP_OK;
+    const size_t segFloats = a.segment_floats(floats, e->cfg.sound_arena_max_bytes);
+    if (segFloats == 0) return fail(e, ZLHIP_ERR_CAPACITY, "sound arena full");
+    float *seg = nullptr;
+    if (hipMalloc((void **)&seg, (segFloats + 1024) * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return fail(e, ZLHIP_ERR_CAPACITY, "sound arena full (no memory for another segment)"); }
+    e->deviceBytes += (segFloats + 1024) * sizeof(float);
+    // float offset of the segment from `arena`, modulo 2^64 (exact: both are multiples of 4 bytes)
+    const int64_t diffBytes = (int64_t)((uintptr_t)seg - (uintptr_t)e->arena);
+    a.add_segment(seg, (size_t)(uint64_t)(diffBytes / 4), segFloats);
+    (void)a.take(floats, out_off);                                 // (the segment's first floats)
+    return ZLHIP_OK;
+}
+
+// (integer arithmetic: a segment below the first arena in the address space has an offset that wraps -- no pointer ever leaves its allocation)
+float *arena_ptr(const zlhip_engine *e, uint64_t off)
+{
+    return reinterpret_cast<float *>((uintptr_t)e->arena + (uintptr_t)off * sizeof(float));
+}
+
+// an arena extent goes back to the free list.  A later arena segment whose every float is free again goes back to the device (the first
+// arena stays for the engine's life): the caller has waited for the engine and stopped its resident kernel; the free waits for the
+// device: other engines' kernels step aside.
+void free_extent(zlhip_engine *e, size_t off, size_t n)
+{
+    ZlArena::Segment seg;
+    if (!e->arenaAlloc.give(off, n, &seg)) return;
+    { ZlQuiesce quiet(e); (void)hipFree(seg.handle); }
+    e->deviceBytes -= (seg.floats + 1024) * sizeof(float);
+}
+
+// a free slot takes a new sound, whose upload holds `floats` floats of the arena: it plays that upload
+void adopt_sound(zlhip_engine *e, int id, const ZlSound &s, size_t floats)
+{
+    e->hc.sounds[id] = s;
+    e->hc.soundUsed[id] = 1;
+    e->soundSlots[(size_t)id] = zlhip_engine::SoundSlot{ s, floats, 0, {} };
 }
 
 extern "C" {
@@ -456,7 +266,6 @@ void zlhip_engine_destroy(zlhip_engine *e)
     for (auto &seg : e->arenaAlloc.segments) if (seg.handle) (void)hipFree(seg.handle);
     for (auto &b : e->scratch) { if (b.d) (void)hipFree(b.d); if (b.h) (void)hipHostFree(b.h); }
     for (auto &t : e->rs.tables) if (t.d) (void)hipFree(t.d);
-    for (hipEvent_t ev : e->rs.ev) if (ev) (void)hipEventDestroy(ev);
     void *dev[] = { e->arena, e->dSounds, e->dClips, e->dVoices, e->dGain, e->dBus, e->dLevels, e->dLevelState, e->dTrace, e->dPass, e->dPassCache };
     for (void *p : dev) if (p) (void)hipFree(p);
     for (auto &q : e->ps) {
@@ -486,17 +295,11 @@ void zlhip_engine_destroy(zlhip_engine *e)
     if (e->asmStream) (void)hipStreamDestroy(e->asmStream);
     void *host[] = { e->hBus, e->hLevelState, e->hFan, e->hPassRt, e->hNonFinite };
     for (void *p : host) if (p) (void)hipHostFree(p);
-    for (hipEvent_t ev : e->stEv) if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->ov.ev) if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->on.ev) if (ev) (void)hipEventDestroy(ev);
-    if (e->on.hCounts) (void)hipHostFree(e->on.hCounts);
-    if (e->on.hOut) (void)hipHostFree(e->on.hOut);
-    for (hipEvent_t ev : e->tp.ev) if (ev) (void)hipEventDestroy(ev);
-    if (e->tp.hOut) (void)hipHostFree(e->tp.hOut);
-    for (hipEvent_t ev : e->pt.ev) if (ev) (void)hipEventDestroy(ev);
-    if (e->pt.hOut) (void)hipHostFree(e->pt.hOut);
-    for (hipEvent_t ev : e->ld.ev) if (ev) (void)hipEventDestroy(ev);
-    if (e->ld.hOut) (void)hipHostFree(e->ld.hOut);
+    e->st.timer.release(); e->ov.timer.release(); e->rs.timer.release();
+    e->on.timer.release(); e->on.counts.release(); e->on.out.release();
+    e->tp.timer.release(); e->tp.out.release();
+    e->pt.timer.release(); e->pt.out.release();
+    e->ld.timer.release(); e->ld.out.release();
     for (hipEvent_t ev : e->pcm.ev) if (ev) (void)hipEventDestroy(ev);
     if (e->evJoin) (void)hipEventDestroy(e->evJoin);
     if (e->evPlanTail) (void)hipEventDestroy(e->evPlanTail);
@@ -730,70 +533,6 @@ void zlhip_clip_params_default(zlhip_clip_params *p, float duration_seconds)
     ZlHostControl::default_clip_params(p, duration_seconds);
 }
 
-// `need` elements of `elem` bytes in a buffer that only grows: one that is too small is freed and one of `new_cap` elements allocated,
-// with a page-locked host twin where `twin`; a failure leaves it empty and the call failed with `what`.  Besides the arena's segments
-// this is the only place after creation that changes deviceBytes.  hipMalloc, hipFree and hipHostFree wait for the device: stopping
-// this engine's resident kernel and asking the others' to step aside (ZlQuiesce) is the caller's part.
-static int grow_buf(zlhip_engine *e, GrowBuf &b, size_t need, size_t elem, size_t new_cap, bool twin, const char *what)
-{
-    if (need <= b.cap) return ZLHIP_OK;
-    if (b.d) { (void)hipFree(b.d); e->deviceBytes -= b.cap * elem; }
-    if (b.h) (void)hipHostFree(b.h);
-    b = GrowBuf();
-    if ((twin && hipHostMalloc(&b.h, new_cap * elem) != hipSuccess) || hipMalloc(&b.d, new_cap * elem) != hipSuccess) {
-        (void)hipGetLastError();
-        if (b.h) (void)hipHostFree(b.h);
-        b = GrowBuf();
-        return fail(e, ZLHIP_ERR_CAPACITY, what);
-    }
-    e->deviceBytes += new_cap * elem;
-    b.cap = new_cap;
-    return ZLHIP_OK;
-}
-
-// an extent of `floats` floats (a multiple of 4) of the arena: first fit over the free extents, else a further arena segment
-// (zl_arena.h decides; the device memory of a segment is allocated here)
-static int alloc_extent(zlhip_engine *e, size_t floats, size_t *out_off)
-{
-    ZlArena &a = e->arenaAlloc;
-    if (a.take(floats, out_off)) return ZLHIP_OK;
-    const size_t segFloats = a.segment_floats(floats, e->cfg.sound_arena_max_bytes);
-    if (segFloats == 0) return fail(e, ZLHIP_ERR_CAPACITY, "sound arena full");
-    float *seg = nullptr;
-    if (hipMalloc((void **)&seg, (segFloats + 1024) * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return fail(e, ZLHIP_ERR_CAPACITY, "sound arena full (no memory for another segment)"); }
-    e->deviceBytes += (segFloats + 1024) * sizeof(float);
-    // float offset of the segment from `arena`, modulo 2^64 (exact: both are multiples of 4 bytes)
-    const int64_t diffBytes = (int64_t)((uintptr_t)seg - (uintptr_t)e->arena);
-    a.add_segment(seg, (size_t)(uint64_t)(diffBytes / 4), segFloats);
-    (void)a.take(floats, out_off);                                 // (the segment's first floats)
-    return ZLHIP_OK;
-}
-
-// (integer arithmetic: a segment below the first arena in the address space has an offset that wraps -- no pointer ever leaves its allocation)
-static float *arena_ptr(const zlhip_engine *e, uint64_t off)
-{
-    return reinterpret_cast<float *>((uintptr_t)e->arena + (uintptr_t)off * sizeof(float));
-}
-
-// an arena extent goes back to the free list.  A later arena segment whose every float is free again goes back to the device (the first
-// arena stays for the engine's life): the caller has waited for the engine and stopped its resident kernel; the free waits for the
-// device: other engines' kernels step aside.
-static void free_extent(zlhip_engine *e, size_t off, size_t n)
-{
-    ZlArena::Segment seg;
-    if (!e->arenaAlloc.give(off, n, &seg)) return;
-    { ZlQuiesce quiet(e); (void)hipFree(seg.handle); }
-    e->deviceBytes -= (seg.floats + 1024) * sizeof(float);
-}
-
-// a free slot takes a new sound, whose upload holds `floats` floats of the arena: it plays that upload
-static void adopt_sound(zlhip_engine *e, int id, const ZlSound &s, size_t floats)
-{
-    e->hc.sounds[id] = s;
-    e->hc.soundUsed[id] = 1;
-    e->soundSlots[(size_t)id] = zlhip_engine::SoundSlot{ s, floats, 0, {} };
-}
-
 static int alloc_sound_slot(zlhip_engine *e, int32_t length, int channels, double sample_rate, int32_t *out_id, float **dst)
 {
     if (length < 1 || !(sample_rate > 0.0) || !out_id) return fail(e, ZLHIP_ERR_INVALID, "bad sound arguments");
@@ -870,11 +609,9 @@ static int sound_upload_device(zlhip_engine *e, const float *left_dev, const flo
                                bool have_producer, hipStream_t producer, int32_t *out_id)
 {
     if (!e || !left_dev) return ZLHIP_ERR_INVALID;
-    ZL_HIP(e, hipSetDevice(e->device));
-    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }         // (the resident real-time kernel does not see other engines' writes)
+    // (the resident real-time kernel does not see other engines' writes; queued batches may still gather from an extent that was freed and is handed out again here)
+    { const int rc = call_begin(e, true); if (rc != ZLHIP_OK) return rc; }
     float *dst = nullptr;
-    // queued batches may still gather from an extent that was freed and is handed out again here
-    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
     int rc = alloc_sound_slot(e, length, right_dev ? 2 : 1, sample_rate, out_id, &dst);
     if (rc != ZLHIP_OK) return rc;
     hipError_t st;
@@ -904,11 +641,9 @@ static int sound_upload_device(zlhip_engine *e, const float *left_dev, const flo
 int zlhip_sound_upload(zlhip_engine *e, const float *left, const float *right, int32_t length, double sample_rate, int32_t *out_id)
 {
     if (!e || !left) return ZLHIP_ERR_INVALID;
-    ZL_HIP(e, hipSetDevice(e->device));
-    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }         // (the resident real-time kernel does not see other engines' writes)
+    { const int rc = call_begin(e, true); if (rc != ZLHIP_OK) return rc; }     // see zlhip_sound_upload_device
     float *dst = nullptr;
     const int ch = right ? 2 : 1;
-    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }     // see zlhip_sound_upload_device
     int rc = alloc_sound_slot(e, length, ch, sample_rate, out_id, &dst);
     if (rc != ZLHIP_OK) return rc;
     std::vector<float> tmp(((size_t)length + 8) * ch, 0.0f);
@@ -926,148 +661,6 @@ int zlhip_sound_upload(zlhip_engine *e, const float *left, const float *right, i
     return rc;
 }
 
-// ---- clips from raw PCM (zl_decode.h, zl_decode.hip) ---------------------------------------------------------------------
-// The other side of the file boundary: zlhip_bounce writes 16-bit PCM from the render kernel, this reads the bytes of a WAV `data`
-// chunk.  The raw bytes cross the link (half of fp32 for 16-bit files, no host loop over the samples), one decode launch per staging
-// pass writes the arena's layout, pad included, and the call waits for the device once -- whatever the number of clips.
-// ZL_PCM_STAGE_BYTES: the size of the staging buffer, read per call (tests cut clips inside with a small one)
-static uint32_t zl_pcm_stage_switch() { const char *v = std::getenv("ZL_PCM_STAGE_BYTES"); return zl_dec_stage_bytes(v ? std::atoll(v) : (long long)ZL_DEC_STAGE_DEFAULT); }
-
-// (hipMalloc / hipFree wait for the device: other engines' kernels step aside; this engine's has left)
-static int pcm_reserve(zlhip_engine *e, size_t stageBytes, size_t npieces, size_t nclips)
-{
-    GrowBuf *b = e->scratch;
-    if (stageBytes <= b[ZB_PCM_STAGE].cap && npieces <= b[ZB_PCM_PIECES].cap
-        && nclips <= b[ZB_PCM_PUB].cap && nclips <= b[ZB_PCM_VERDICTS].cap) return ZLHIP_OK;
-    ZlQuiesce quiet(e);
-    const char *what = "sound_upload_pcm: no device memory for the staging buffer or the call's records";
-    // (the piece records are measured by their doubled count: a call that grows anything also grows them once it fills more than half)
-    const size_t np = std::max<size_t>(npieces * 2, 64), nc = std::max<size_t>(nclips * 2, 64);
-    int rc = grow_buf(e, b[ZB_PCM_STAGE], stageBytes, 1, stageBytes, false, what);
-    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_PCM_PIECES], np, sizeof(ZlDecPiece), np, false, what);
-    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_PCM_PUB], nclips, sizeof(ZlDecPublish), nc, false, what);
-    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_PCM_VERDICTS], nclips, sizeof(uint32_t), nc, false, what);
-    return rc;
-}
-
-int zlhip_sound_upload_pcm_batch(zlhip_engine *e, const zlhip_pcm_source *srcs, int32_t count, int32_t *out_ids)
-{
-    if (!e || count < 0 || (count > 0 && (!srcs || !out_ids))) return ZLHIP_ERR_INVALID;
-    if (count == 0) return ZLHIP_OK;
-    for (int32_t i = 0; i < count; ++i) out_ids[i] = -1;
-    // every argument before the first HIP call
-    for (int32_t i = 0; i < count; ++i) {
-        const zlhip_pcm_source &q = srcs[i];
-        if (!q.frames) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: frames is NULL");
-        if (q.format < ZLHIP_PCM_U8 || q.format > ZLHIP_PCM_F64) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: format outside 1 .. 6");
-        if (q.channels < 1 || q.channels > ZLHIP_PCM_MAX_CHANNELS) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: channels outside 1 .. 64");
-        if (q.length < 1) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: length below 1");
-        if (!(q.sample_rate > 0.0)) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: sample rate not above 0");
-        if (q.reserved != 0) return fail(e, ZLHIP_ERR_INVALID, "sound_upload_pcm: reserved is not 0");
-    }
-    // the slots: the first free ones in request order, as consecutive zlhip_sound_upload calls would take them
-    std::vector<int32_t> ids;
-    for (int i = 0; i < e->cfg.max_sounds && (int32_t)ids.size() < count; ++i) if (!e->hc.soundUsed[i]) ids.push_back(i);
-    if ((int32_t)ids.size() < count) return fail(e, ZLHIP_ERR_CAPACITY, "sound_upload_pcm: too few free sound slots for the call");
-    ZL_HIP(e, hipSetDevice(e->device));
-    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }         // (the resident real-time kernel does not see other engines' writes)
-    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }     // see zlhip_sound_upload_device
-    // the extents (all or none: an arena that cannot hold the call keeps nothing; a segment it grew by goes back)
-    std::vector<size_t> off((size_t)count, 0), floats((size_t)count, 0);
-    auto rollback = [&]() { for (int32_t k = count - 1; k >= 0; --k) free_extent(e, off[(size_t)k], floats[(size_t)k]); };   // (0 floats: nothing taken)
-    for (int32_t i = 0; i < count; ++i) {
-        const size_t n = zl_extent_floats(srcs[i].length, zl_dec_out_channels(srcs[i].channels));
-        const int rc = alloc_extent(e, n, &off[(size_t)i]);
-        if (rc != ZLHIP_OK) { rollback(); return rc; }
-        floats[(size_t)i] = n;
-    }
-    // the cut into passes and pieces, the records
-    const uint32_t stageBytes = zl_pcm_stage_switch();
-    std::vector<ZlDecClip> clips((size_t)count);
-    for (int32_t i = 0; i < count; ++i) clips[(size_t)i] = ZlDecClip{ srcs[i].length, srcs[i].channels, srcs[i].format };
-    std::vector<ZlDecPiece> pieces; std::vector<ZlDecPass> passes;
-    zl_dec_plan(clips.data(), count, stageBytes, pieces, passes);
-    for (ZlDecPiece &R : pieces) R.dst = (uint64_t)(uintptr_t)arena_ptr(e, off[(size_t)R.verdict]);
-    std::vector<ZlDecPublish> pub((size_t)count);
-    for (int32_t i = 0; i < count; ++i) {
-        ZlSound s; s.offset = off[(size_t)i]; s.length = srcs[i].length; s.channels = zl_dec_out_channels(srcs[i].channels);
-        s.sample_rate = srcs[i].sample_rate; s.flags = 0; s.pad = 0;
-        pub[(size_t)i] = ZlDecPublish{ s, ids[(size_t)i], zl_dec_is_float(srcs[i].format) ? 1 : 0 };
-    }
-    { const int rc = pcm_reserve(e, stageBytes, pieces.size(), (size_t)count); if (rc != ZLHIP_OK) { rollback(); return rc; } }
-    zlhip_engine::Pcm &P = e->pcm;
-    unsigned char *const stage = (unsigned char *)e->scratch[ZB_PCM_STAGE].d; ZlDecPiece *const dPieces = (ZlDecPiece *)e->scratch[ZB_PCM_PIECES].d;
-    ZlDecPublish *const dPub = (ZlDecPublish *)e->scratch[ZB_PCM_PUB].d; uint32_t *const dVerdicts = (uint32_t *)e->scratch[ZB_PCM_VERDICTS].d;
-    // everything is decided: from here on only a HIP error fails the call
-    std::vector<uint32_t> verdicts((size_t)count, 0u);
-    const bool prof = e->profiling;
-    const size_t nev = prof ? 2 * passes.size() + 1 : 0;
-    int krc = 0;
-    while (krc == 0 && P.ev.size() < nev) { hipEvent_t ev = nullptr; krc = (int)hipEventCreate(&ev); if (krc == 0) P.ev.push_back(ev); }
-    if (krc == 0) krc = (int)hipMemsetAsync(dVerdicts, 0, (size_t)count * sizeof(uint32_t), e->stream);
-    if (krc == 0) krc = (int)hipMemcpyAsync(dPieces, pieces.data(), pieces.size() * sizeof(ZlDecPiece), hipMemcpyHostToDevice, e->stream);
-    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, pub.data(), pub.size() * sizeof(ZlDecPublish), hipMemcpyHostToDevice, e->stream);
-    for (size_t a = 0; krc == 0 && a < passes.size(); ++a) {
-        const ZlDecPass &ps = passes[a];
-        if (prof) krc = (int)hipEventRecord(P.ev[2 * a], e->stream);
-        for (int32_t k = ps.first_piece; krc == 0 && k < ps.first_piece + ps.npieces; ++k) {
-            const ZlDecPiece &R = pieces[(size_t)k];
-            const unsigned char *src = (const unsigned char *)srcs[R.verdict].frames + zl_dec_source_offset(R);
-            krc = (int)hipMemcpyAsync(stage + R.stage_off, src, (size_t)zl_dec_piece_bytes(R), hipMemcpyHostToDevice, e->stream);
-        }
-        if (prof && krc == 0) krc = (int)hipEventRecord(P.ev[2 * a + 1], e->stream);
-        if (krc == 0) krc = zl_launch_pcm_decode(dPieces + ps.first_piece, ps.npieces, ps.items, stage, dVerdicts, e->stream);
-    }
-    if (prof && krc == 0) krc = (int)hipEventRecord(P.ev[2 * passes.size()], e->stream);
-    if (krc == 0) krc = zl_launch_pcm_publish(dPub, count, dVerdicts, e->dSounds, e->stream);
-    if (krc == 0) krc = (int)hipMemcpyAsync(verdicts.data(), dVerdicts, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
-    if (krc == 0) { const int w_ = engine_wait(e); if (w_ != ZLHIP_OK) { rollback(); return w_; } }     // the call's one wait
-    if (krc != 0) {
-        e->err = std::string("sound_upload_pcm: ") + hipGetErrorString((hipError_t)krc);
-        (void)hipStreamSynchronize(e->stream);
-        rollback();
-        return ZLHIP_ERR_HIP;
-    }
-    if (prof) {
-        float copy = 0.0f, dec = 0.0f;
-        for (size_t a = 0; a < passes.size(); ++a) {
-            float x = 0.0f, y = 0.0f;
-            ZL_HIP(e, hipEventElapsedTime(&x, P.ev[2 * a], P.ev[2 * a + 1]));
-            ZL_HIP(e, hipEventElapsedTime(&y, P.ev[2 * a + 1], P.ev[2 * a + 2]));
-            copy += x; dec += y;
-        }
-        P.copyMs = copy; P.decodeMs = dec;
-    }
-    // the host's mirror of what the device has published, and every clip's default parameters (applied at the next render call)
-    for (int32_t i = 0; i < count; ++i) {
-        const int id = ids[(size_t)i];
-        ZlSound s = pub[(size_t)i].s;
-        if (!pub[(size_t)i].check || verdicts[(size_t)i] == 0u) s.flags |= ZL_SOUND_FINITE;
-        adopt_sound(e, id, s, floats[(size_t)i]);
-        zlhip_clip_params p;
-        zlhip_clip_params_default(&p, (float)(s.length / s.sample_rate));
-        e->hc.forget_clip_params(id);                              // (the first edit of a slot carries the whole record)
-        (void)zlhip_clip_set(e, id, &p);
-        out_ids[i] = id;
-    }
-    return ZLHIP_OK;
-}
-
-int zlhip_sound_upload_pcm(zlhip_engine *e, const void *frames, int32_t format, int32_t channels, int32_t length, double sample_rate, int32_t *out_id)
-{
-    if (!e || !out_id) return ZLHIP_ERR_INVALID;
-    const zlhip_pcm_source q = { frames, length, channels, format, 0, sample_rate };
-    return zlhip_sound_upload_pcm_batch(e, &q, 1, out_id);
-}
-
-int zlhip_debug_upload_pcm_timings(zlhip_engine *e, float *copy_ms, float *decode_ms)
-{
-    if (!e) return ZLHIP_ERR_INVALID;
-    if (copy_ms) *copy_ms = e->pcm.copyMs;
-    if (decode_ms) *decode_ms = e->pcm.decodeMs;
-    return ZLHIP_OK;
-}
-
 int zlhip_sound_release(zlhip_engine *e, int32_t id)
 {
     if (!e || id < 0 || id >= e->cfg.max_sounds || !e->hc.soundUsed[id]) return ZLHIP_ERR_INVALID;
@@ -1078,336 +671,6 @@ int zlhip_sound_release(zlhip_engine *e, int32_t id)
     ZL_HIP(e, hipMemcpyAsync(e->dSounds + id, &e->hc.sounds[id], sizeof(ZlSound), hipMemcpyHostToDevice, e->stream));
     { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
     return ZLHIP_OK;
-}
-
-// ---- clip re-render (zl_stretch.h, zl_stretch.hip) ----------------------------------------------------------------------
-// ClipAudioSource::setPitch / setSpeedRatio / setGain re-render the clip's playback file from its source and the sound reloads it
-// (ClipAudioSource.cpp:279-311,404-413, SamplerSynthSound.cpp:28-68).  Here: every clip of the call is rendered from its ORIGINAL
-// upload into a new arena extent (one seek launch, one synthesis launch for the call), then the sound table entries switch -- at a
-// block boundary: the resident kernel has left and every queued batch has finished -- and the extents the clips played before go
-// back to the arena.  The clip id keeps its slot; a voice playing it reads the new data from its next block at its unchanged position,
-// as the reference's voices read the sound's data pointer and length on every block (SamplerSynthVoice.cpp:186-191).
-// (a call's device records, grown when a call needs more: the free waits for the device, other engines' kernels step aside)
-static int st_reserve(zlhip_engine *e, GrowBuf &b, size_t need, size_t elem)
-{
-    const size_t n = std::max<size_t>(need, 64);
-    const char *what = "sound_rerender: no device memory for the call's records";
-    if (need <= b.cap || !b.d) return grow_buf(e, b, need, elem, n, false, what);      // (nothing to free: no wait for the device)
-    ZlQuiesce quiet(e);
-    return grow_buf(e, b, need, elem, n, false, what);
-}
-
-int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_rerender_params *params, int32_t count)
-{
-    if (!e || count < 0 || (count > 0 && (!ids || !params))) return ZLHIP_ERR_INVALID;
-    if (count == 0) return ZLHIP_OK;
-    if (count > 65535) return fail(e, ZLHIP_ERR_INVALID, "sound_rerender_batch: more than 65535 clips in one call");
-    // validate everything before anything changes
-    std::vector<ZlStretchGeom> geo((size_t)count);
-    std::vector<char> ident((size_t)count, 0);
-    {
-        std::vector<char> seen((size_t)e->cfg.max_sounds, 0);
-        for (int32_t i = 0; i < count; ++i) {
-            const int32_t id = ids[i];
-            if (id < 0 || id >= e->cfg.max_sounds || !e->hc.soundUsed[id]) return fail(e, ZLHIP_ERR_INVALID, "sound_rerender: no such sound");
-            if (seen[(size_t)id]) return fail(e, ZLHIP_ERR_INVALID, "sound_rerender_batch: a clip appears twice");
-            seen[(size_t)id] = 1;
-            const zlhip_rerender_params &q = params[i];
-            const ZlSound &o = e->soundSlots[(size_t)id].orig;
-            if (zl_st_geometry(o.sample_rate, o.length, q.gain_db, q.pitch_semitones, q.speed_ratio, &geo[(size_t)i]) != 0)
-                return fail(e, ZLHIP_ERR_INVALID, "sound_rerender: speed outside [0.25, 4], pitch outside [-24, 24], non-finite gain, or a sample rate the stretch cannot take");
-            ident[(size_t)i] = zl_st_identity(q.gain_db, q.pitch_semitones, q.speed_ratio) ? 1 : 0;
-        }
-    }
-    ZL_HIP(e, hipSetDevice(e->device));
-    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }         // the sound table and the arena change under the resident kernel otherwise
-    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }     // queued batches still read the table
-
-    // the new extents (all or none: an arena that cannot hold the call leaves every clip as it was)
-    std::vector<size_t> newOff((size_t)count, 0), newFloats((size_t)count, 0);
-    auto rollback = [&]() { for (int32_t i = 0; i < count; ++i) free_extent(e, newOff[(size_t)i], newFloats[(size_t)i]); };
-    std::vector<ZlStretchJob> jobs;
-    std::vector<int32_t> seekList, jobClip;
-    int64_t maxFrames = 0, offs = 0;
-    for (int32_t i = 0; i < count; ++i) {
-        if (ident[(size_t)i]) continue;
-        const ZlSound &o = e->soundSlots[(size_t)ids[i]].orig;
-        const ZlStretchGeom &g = geo[(size_t)i];
-        const size_t floats = zl_extent_floats(g.N, o.channels);
-        const int rc = alloc_extent(e, floats, &newOff[(size_t)i]);
-        if (rc != ZLHIP_OK) { rollback(); return rc; }
-        newFloats[(size_t)i] = floats;
-        ZlStretchJob J; std::memset(&J, 0, sizeof J);
-        J.geom = g;
-        J.src = (uint64_t)(uintptr_t)arena_ptr(e, o.offset);
-        J.dst = (uint64_t)(uintptr_t)arena_ptr(e, newOff[(size_t)i]);
-        J.channels = o.channels;
-        J.off_base = offs;
-        if (g.stretch && g.nseg > 0) { seekList.push_back((int32_t)jobs.size()); offs += g.nseg; }
-        maxFrames = std::max(maxFrames, g.N);
-        jobs.push_back(J);
-        jobClip.push_back(i);
-    }
-    std::vector<int32_t> hOffs((size_t)offs);
-    if (!jobs.empty()) {
-        int rc = st_reserve(e, e->scratch[ZB_ST_JOBS], jobs.size(), sizeof(ZlStretchJob));
-        if (rc == ZLHIP_OK) rc = st_reserve(e, e->scratch[ZB_ST_LIST], std::max<size_t>(seekList.size(), 1), sizeof(int32_t));
-        if (rc == ZLHIP_OK) rc = st_reserve(e, e->scratch[ZB_ST_OFFS], std::max<size_t>((size_t)offs, 1), sizeof(int32_t));
-        if (rc != ZLHIP_OK) { rollback(); return rc; }
-        ZlStretchJob *const dStJobs = (ZlStretchJob *)e->scratch[ZB_ST_JOBS].d;
-        int32_t *const dStList = (int32_t *)e->scratch[ZB_ST_LIST].d, *const dStOffs = (int32_t *)e->scratch[ZB_ST_OFFS].d;
-        hipError_t st = hipMemcpyAsync(dStJobs, jobs.data(), jobs.size() * sizeof(ZlStretchJob), hipMemcpyHostToDevice, e->stream);
-        if (st == hipSuccess && !seekList.empty())
-            st = hipMemcpyAsync(dStList, seekList.data(), seekList.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-        int krc = (int)st;
-        const bool prof = e->profiling;
-        for (int x = 0; prof && krc == 0 && x < 3; ++x) if (!e->stEv[x]) krc = (int)hipEventCreate(&e->stEv[x]);
-        if (prof && krc == 0) krc = (int)hipEventRecord(e->stEv[0], e->stream);
-        if (krc == 0) krc = zl_launch_stretch_seek(dStJobs, dStList, (int)seekList.size(), dStOffs, e->stream);
-        if (prof && krc == 0) krc = (int)hipEventRecord(e->stEv[1], e->stream);
-        if (krc == 0) krc = zl_launch_stretch_synth(dStJobs, (int)jobs.size(), maxFrames, dStOffs, e->stream);
-        if (prof && krc == 0) krc = (int)hipEventRecord(e->stEv[2], e->stream);
-        if (krc == 0 && offs > 0) krc = (int)hipMemcpyAsync(hOffs.data(), dStOffs, (size_t)offs * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream);
-        if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);
-        if (prof && krc == 0) {
-            krc = (int)hipEventElapsedTime(&e->stSeekMs, e->stEv[0], e->stEv[1]);
-            if (krc == 0) krc = (int)hipEventElapsedTime(&e->stSynthMs, e->stEv[1], e->stEv[2]);
-        }
-        if (krc != 0) {
-            e->err = std::string("sound_rerender: ") + hipGetErrorString((hipError_t)krc);
-            (void)hipStreamSynchronize(e->stream);
-            rollback();
-            return ZLHIP_ERR_HIP;
-        }
-    }
-    // the swap: nothing queued can read the extents the clips played until now any more
-    for (int32_t i = 0; i < count; ++i) {
-        const int32_t id = ids[i];
-        zlhip_engine::SoundSlot &slot = e->soundSlots[(size_t)id];
-        free_extent(e, (size_t)e->hc.sounds[id].offset, slot.renderFloats);
-        ZlSound s = slot.orig;
-        // (a rendered extent has not been looked at: it plays without ZL_SOUND_FINITE; identity parameters play the original, with its own flag)
-        if (!ident[(size_t)i]) { s.offset = newOff[(size_t)i]; s.length = (int32_t)geo[(size_t)i].N; s.flags &= ~(int32_t)ZL_SOUND_FINITE; }
-        e->hc.sounds[id] = s;
-        slot.renderFloats = newFloats[(size_t)i];
-        slot.renderOffsets.clear();
-    }
-    for (size_t j = 0; j < jobs.size(); ++j) {
-        const ZlStretchGeom &g = jobs[j].geom;
-        if (g.stretch && g.nseg > 0)
-            e->soundSlots[(size_t)ids[jobClip[j]]].renderOffsets.assign(hOffs.begin() + jobs[j].off_base, hOffs.begin() + jobs[j].off_base + g.nseg);
-    }
-    for (int32_t i = 0; i < count; ++i)
-        ZL_HIP(e, hipMemcpyAsync(e->dSounds + ids[i], &e->hc.sounds[ids[i]], sizeof(ZlSound), hipMemcpyHostToDevice, e->stream));
-    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
-    return ZLHIP_OK;
-}
-
-int zlhip_sound_rerender(zlhip_engine *e, int32_t id, const zlhip_rerender_params *params)
-{
-    return zlhip_sound_rerender_batch(e, &id, params, 1);
-}
-
-// ---- sample-rate conversion (zl_resample.h, zl_resample.hip) --------------------------------------------------------------
-// A clip whose rate differs from the engine's plays through the pitched voice path; converted once, band-limited, it is a unit-step
-// integer-position source and K2 takes its on-grid form.  Every clip of the call is converted from its original upload into a new
-// arena extent by ONE launch, a second one publishes the sound-table entries (ZL_SOUND_FINITE from the device's verdict), and the
-// call waits once.  Synchronisation is zlhip_sound_rerender's: the resident kernel has left and every queued batch has finished before
-// anything is written.  The converted extent becomes the slot's original: later re-renders start from it.
-int zlhip_resample_design(double source_rate, double target_rate, int32_t *L, int32_t *M, int32_t *taps, int32_t *row_floats, float *table, size_t table_floats)
-{
-    ZlRsGeom g;
-    if (zl_rs_geometry(source_rate, target_rate, &g) != 0) return ZLHIP_ERR_INVALID;
-    if (L) *L = g.L;
-    if (M) *M = g.M;
-    if (taps) *taps = g.taps;
-    if (row_floats) *row_floats = g.row;
-    if (!table) return ZLHIP_OK;
-    if (table_floats < (size_t)g.L * (size_t)g.row) return ZLHIP_ERR_CAPACITY;
-    zl_rs_design(g, table);
-    return ZLHIP_OK;
-}
-
-// the device table of a ratio: made by the first call that asks for the ratio, before the call takes anything from the arena, and cached
-// for the engine's life once that call has succeeded -- a call that fails frees the tables it added (hipMalloc and hipFree wait for the
-// device: other engines' kernels step aside).  The copy is queued on the engine's stream in front of the call's launches and shares
-// the call's one wait: the host copy lives until then.
-static int rs_table(zlhip_engine *e, const ZlRsGeom &g, float **out)
-{
-    for (const auto &t : e->rs.tables) if (t.L == g.L && t.M == g.M) { *out = t.d; return ZLHIP_OK; }
-    e->rs.tables.emplace_back();
-    zlhip_engine::Resample::Table &t = e->rs.tables.back();
-    t.L = g.L; t.M = g.M; t.floats = (size_t)g.L * (size_t)g.row;
-    t.pending.resize(t.floats);
-    zl_rs_design(g, t.pending.data());
-    bool ok;
-    { ZlQuiesce quiet(e); ok = hipMalloc((void **)&t.d, t.floats * sizeof(float)) == hipSuccess; }
-    if (!ok) { (void)hipGetLastError(); e->rs.tables.pop_back(); return fail(e, ZLHIP_ERR_CAPACITY, "sound_convert_rate: no device memory for the filter table"); }
-    if (hipMemcpyAsync(t.d, t.pending.data(), t.floats * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(e->stream);
-        { ZlQuiesce quiet(e); (void)hipFree(t.d); }
-        e->rs.tables.pop_back();
-        return fail(e, ZLHIP_ERR_HIP, "sound_convert_rate: the filter table did not reach the device");
-    }
-    e->deviceBytes += t.floats * sizeof(float);
-    *out = t.d;
-    return ZLHIP_OK;
-}
-// after a wait for the engine's stream: the tables' host copies are no longer read
-static void rs_tables_settled(zlhip_engine *e) { for (auto &t : e->rs.tables) std::vector<float>().swap(t.pending); }
-// a failed call: the engine's stream runs dry, the tables behind the first `keep` go back to the device
-static void rs_tables_undo(zlhip_engine *e, size_t keep)
-{
-    (void)hipStreamSynchronize(e->stream);
-    rs_tables_settled(e);
-    while (e->rs.tables.size() > keep) {
-        { ZlQuiesce quiet(e); (void)hipFree(e->rs.tables.back().d); }
-        e->deviceBytes -= e->rs.tables.back().floats * sizeof(float);
-        e->rs.tables.pop_back();
-    }
-}
-
-static int rs_reserve(zlhip_engine *e, size_t njobs)
-{
-    GrowBuf *b = e->scratch;
-    if (njobs <= b[ZB_RS_JOBS].cap && njobs <= b[ZB_RS_PUB].cap && njobs <= b[ZB_RS_VERDICTS].cap) return ZLHIP_OK;
-    ZlQuiesce quiet(e);
-    const char *what = "sound_convert_rate: no device memory for the call's records";
-    const size_t n = std::max<size_t>(njobs * 2, 64);
-    int rc = grow_buf(e, b[ZB_RS_JOBS], njobs, sizeof(ZlRsJob), n, false, what);
-    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_RS_PUB], njobs, sizeof(ZlRsPublish), n, false, what);
-    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_RS_VERDICTS], njobs, sizeof(uint32_t), n, false, what);
-    return rc;
-}
-
-int zlhip_sound_convert_rate_batch(zlhip_engine *e, const int32_t *ids, int32_t count, double target_rate)
-{
-    if (!e || count < 0 || (count > 0 && !ids)) return ZLHIP_ERR_INVALID;
-    if (count == 0) return ZLHIP_OK;
-    const double ft = target_rate == 0.0 ? e->cfg.playback_sample_rate : target_rate;
-    // validate everything before the first HIP call
-    std::vector<ZlRsGeom> geo((size_t)count);
-    std::vector<int64_t> outN((size_t)count, 0);
-    std::vector<char> skip((size_t)count, 0);
-    {
-        std::vector<char> seen((size_t)e->cfg.max_sounds, 0);
-        int64_t wgs = 0;
-        for (int32_t i = 0; i < count; ++i) {
-            const int32_t id = ids[i];
-            if (id < 0 || id >= e->cfg.max_sounds || !e->hc.soundUsed[id]) return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate: no such sound");
-            if (seen[(size_t)id]) return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate_batch: a clip appears twice");
-            seen[(size_t)id] = 1;
-        }
-        for (int32_t i = 0; i < count; ++i) {
-            const ZlSound &o = e->soundSlots[(size_t)ids[i]].orig;
-            skip[(size_t)i] = o.sample_rate == ft ? 1 : 0;           // (already at the rate, whatever the rate: nothing to check, nothing to do)
-            if (skip[(size_t)i]) continue;
-            if (zl_rs_geometry(o.sample_rate, ft, &geo[(size_t)i]) != 0)
-                return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate: a rate that is no integer in [1000, 768000], or a ratio beyond L <= 2048, M <= 8 L, 262144 table floats");
-            outN[(size_t)i] = zl_rs_out_frames(geo[(size_t)i], o.length);
-            if (outN[(size_t)i] < 1) return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate: the converted clip would exceed 2^31 - 9 frames");
-            wgs += zl_rs_job_wgs((int32_t)outN[(size_t)i]);
-        }
-        if (wgs > (int64_t)INT32_MAX) return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate_batch: more than 2^31 - 1 workgroups in one call");
-        for (int32_t i = 0; i < count; ++i)
-            if (!skip[(size_t)i] && e->soundSlots[(size_t)ids[i]].renderFloats != 0)
-                return fail(e, ZLHIP_ERR_STATE, "sound_convert_rate: the clip plays a re-render (re-render it with gain 0, pitch 0, speed 1 first)");
-    }
-    int32_t njobs = 0;
-    for (int32_t i = 0; i < count; ++i) njobs += skip[(size_t)i] ? 0 : 1;
-    if (njobs == 0) return ZLHIP_OK;                               // every clip is at the target rate already: no launch, no copy
-    ZL_HIP(e, hipSetDevice(e->device));
-    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }         // the sound table and the arena change under the resident kernel otherwise
-    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }     // queued batches still read the table
-
-    // the filter tables of the call's ratios first; a call that fails frees the ones it added
-    const size_t tables0 = e->rs.tables.size();
-    std::vector<float *> tables((size_t)count, nullptr);
-    for (int32_t i = 0; i < count; ++i) {
-        if (skip[(size_t)i]) continue;
-        const int rc = rs_table(e, geo[(size_t)i], &tables[(size_t)i]);
-        if (rc != ZLHIP_OK) { rs_tables_undo(e, tables0); return rc; }
-    }
-    // the new extents (all or none: an arena that cannot hold the call leaves every clip as it was)
-    std::vector<size_t> newOff((size_t)count, 0), newFloats((size_t)count, 0);
-    auto rollback = [&]() {
-        rs_tables_undo(e, tables0);
-        for (int32_t i = count - 1; i >= 0; --i) free_extent(e, newOff[(size_t)i], newFloats[(size_t)i]);
-    };
-    for (int32_t i = 0; i < count; ++i) {
-        if (skip[(size_t)i]) continue;
-        const size_t floats = zl_extent_floats(outN[(size_t)i], e->soundSlots[(size_t)ids[i]].orig.channels);
-        const int rc = alloc_extent(e, floats, &newOff[(size_t)i]);
-        if (rc != ZLHIP_OK) { rollback(); return rc; }
-        newFloats[(size_t)i] = floats;
-    }
-    std::vector<ZlRsJob> jobs; std::vector<ZlRsPublish> pub;
-    int32_t wgs = 0;
-    for (int32_t i = 0; i < count; ++i) {
-        if (skip[(size_t)i]) continue;
-        const ZlSound &o = e->soundSlots[(size_t)ids[i]].orig;
-        const ZlRsGeom &g = geo[(size_t)i];
-        float *const table = tables[(size_t)i];
-        ZlRsJob J; std::memset(&J, 0, sizeof J);
-        J.src = (uint64_t)(uintptr_t)arena_ptr(e, o.offset);
-        J.dst = (uint64_t)(uintptr_t)arena_ptr(e, newOff[(size_t)i]);
-        J.table = (uint64_t)(uintptr_t)table;
-        J.len = o.length; J.N = (int32_t)outN[(size_t)i]; J.channels = o.channels;
-        J.L = g.L; J.M = g.M; J.half = g.half; J.taps = g.taps; J.row = g.row;
-        J.wg_base = wgs; J.verdict = (int32_t)jobs.size();
-        wgs += zl_rs_job_wgs(J.N);
-        ZlSound s = o; s.offset = newOff[(size_t)i]; s.length = J.N; s.sample_rate = ft; s.flags &= ~(int32_t)ZL_SOUND_FINITE;
-        pub.push_back(ZlRsPublish{ s, ids[i], J.verdict });
-        jobs.push_back(J);
-    }
-    { const int rc = rs_reserve(e, jobs.size()); if (rc != ZLHIP_OK) { rollback(); return rc; } }
-    ZlRsJob *const dJobs = (ZlRsJob *)e->scratch[ZB_RS_JOBS].d; ZlRsPublish *const dPub = (ZlRsPublish *)e->scratch[ZB_RS_PUB].d;
-    uint32_t *const dVerdicts = (uint32_t *)e->scratch[ZB_RS_VERDICTS].d;
-    // everything is decided: from here on only a HIP error fails the call
-    std::vector<uint32_t> verdicts(jobs.size(), 0u);
-    const bool prof = e->profiling;
-    int krc = 0;
-    for (int x = 0; prof && krc == 0 && x < 2; ++x) if (!e->rs.ev[x]) krc = (int)hipEventCreate(&e->rs.ev[x]);
-    if (krc == 0) krc = (int)hipMemsetAsync(dVerdicts, 0, jobs.size() * sizeof(uint32_t), e->stream);
-    if (krc == 0) krc = (int)hipMemcpyAsync(dJobs, jobs.data(), jobs.size() * sizeof(ZlRsJob), hipMemcpyHostToDevice, e->stream);
-    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, pub.data(), pub.size() * sizeof(ZlRsPublish), hipMemcpyHostToDevice, e->stream);
-    if (prof && krc == 0) krc = (int)hipEventRecord(e->rs.ev[0], e->stream);
-    if (krc == 0) krc = zl_launch_resample(dJobs, (int32_t)jobs.size(), wgs, dVerdicts, e->stream);
-    if (krc == 0) krc = zl_launch_resample_publish(dPub, (int32_t)pub.size(), dVerdicts, e->dSounds, e->stream);
-    if (prof && krc == 0) krc = (int)hipEventRecord(e->rs.ev[1], e->stream);
-    if (krc == 0) krc = (int)hipMemcpyAsync(verdicts.data(), dVerdicts, jobs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
-    if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);      // the call's one wait
-    if (prof && krc == 0) krc = (int)hipEventElapsedTime(&e->rs.ms, e->rs.ev[0], e->rs.ev[1]);
-    if (krc != 0) {
-        e->err = std::string("sound_convert_rate: ") + hipGetErrorString((hipError_t)krc);
-        (void)hipStreamSynchronize(e->stream);
-        // (the table entries the device may have switched go back to what the host's mirror holds)
-        for (const ZlRsPublish &p : pub) (void)hipMemcpy(e->dSounds + p.id, &e->hc.sounds[p.id], sizeof(ZlSound), hipMemcpyHostToDevice);
-        rollback();
-        return ZLHIP_ERR_HIP;
-    }
-    e->outstanding = false;
-    rs_tables_settled(e);
-    // the swap on the host: the converted extent is the slot's original from now on, the old one goes back to the arena
-    for (const ZlRsPublish &p : pub) {
-        zlhip_engine::SoundSlot &slot = e->soundSlots[(size_t)p.id];
-        const size_t oldOff = (size_t)slot.orig.offset, oldFloats = slot.floats;
-        ZlSound s = p.s;
-        if (verdicts[(size_t)p.verdict] == 0u) s.flags |= ZL_SOUND_FINITE;
-        int32_t i = 0;
-        while (ids[i] != p.id) ++i;
-        slot.orig = s; slot.floats = newFloats[(size_t)i];
-        slot.renderOffsets.clear();
-        e->hc.sounds[p.id] = s;
-        free_extent(e, oldOff, oldFloats);
-    }
-    return ZLHIP_OK;
-}
-
-int zlhip_sound_convert_rate(zlhip_engine *e, int32_t id, double target_rate)
-{
-    return zlhip_sound_convert_rate_batch(e, &id, 1, target_rate);
 }
 
 int zlhip_sound_info_get(zlhip_engine *e, int32_t id, zlhip_sound_info *out)
@@ -1428,17 +691,9 @@ int zlhip_debug_sound_extent(zlhip_engine *e, int32_t id, float *out, size_t cap
     if (floats) *floats = n;
     if (!out) return ZLHIP_OK;
     if (capacity < n) return fail(e, ZLHIP_ERR_CAPACITY, "debug_sound_extent: capacity below the extent's floats");
-    ZL_HIP(e, hipSetDevice(e->device));
-    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    { const int rc = call_begin(e, false); if (rc != ZLHIP_OK) return rc; }
     ZL_HIP(e, hipMemcpyAsync(out, arena_ptr(e, s.offset), n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     return engine_wait(e);
-}
-
-int zlhip_debug_convert_timings(zlhip_engine *e, float *device_ms)
-{
-    if (!e) return ZLHIP_ERR_INVALID;
-    if (device_ms) *device_ms = e->rs.ms;
-    return ZLHIP_OK;
 }
 
 int zlhip_sound_read(zlhip_engine *e, int32_t id, float *left, float *right, int32_t capacity, int32_t *length)
@@ -1448,8 +703,7 @@ int zlhip_sound_read(zlhip_engine *e, int32_t id, float *left, float *right, int
     if (length) *length = s.length;
     if (!left) return s.channels;
     if (capacity < s.length) return fail(e, ZLHIP_ERR_CAPACITY, "sound_read: capacity below the sound's length");
-    ZL_HIP(e, hipSetDevice(e->device));
-    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    { const int rc = call_begin(e, false); if (rc != ZLHIP_OK) return rc; }
     std::vector<float> tmp((size_t)s.length * (size_t)s.channels);
     ZL_HIP(e, hipMemcpyAsync(tmp.data(), arena_ptr(e, s.offset), tmp.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
@@ -1459,606 +713,6 @@ int zlhip_sound_read(zlhip_engine *e, int32_t id, float *left, float *right, int
         std::memcpy(left, tmp.data(), tmp.size() * sizeof(float));
     }
     return s.channels;
-}
-
-// ---- waveform overviews (zl_overview.h, zl_overview.hip) -----------------------------------------------------------------
-// The data behind the reference's WaveFormItem (lib/WaveFormItem.cpp:130-139): per pixel column the minimum and maximum of the
-// clip's playback data, reduced where the data lives -- after a re-render the clip that plays exists on the device only.  The
-// synchronisation is zlhip_sound_read's: the call runs on the engine's stream behind what is queued there and does NOT ask the
-// resident real-time kernel to leave (it reads the arena, which only uploads, releases and re-renders change -- and those stop the
-// kernel and wait themselves).  hipMalloc / hipFree / hipHostFree do wait for resident kernels, so the call's buffers are
-// allocated by the first call (this engine's kernel leaves once, the others' step aside) and grow only: a call that fits them makes
-// no device-synchronising HIP call.
-static int ov_reserve(zlhip_engine *e, size_t nreq, size_t ncols)
-{
-    GrowBuf &req = e->scratch[ZB_OV_REQ], &cols = e->scratch[ZB_OV_COLS];
-    if (nreq <= req.cap && ncols <= cols.cap) return ZLHIP_OK;
-    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }
-    ZlQuiesce quiet(e);
-    const int rc = grow_buf(e, req, nreq, sizeof(ZlOvRequest), std::max<size_t>(nreq * 2, 64), true, "sound_overview: no memory for the call's requests");
-    if (rc != ZLHIP_OK) return rc;
-    return grow_buf(e, cols, ncols, 4 * sizeof(float), std::min<size_t>(std::max<size_t>(ncols * 2, ZL_OV_MAX_COLUMNS), ZL_OV_MAX_CALL_COLUMNS), true,
-                    "sound_overview: no memory for the call's columns");
-}
-
-int zlhip_sound_overview_batch(zlhip_engine *e, const zlhip_overview_request *reqs, int32_t count, float *out, size_t out_floats)
-{
-    if (!e || count < 0 || (count > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
-    if (count == 0) return ZLHIP_OK;
-    // validate everything before anything is written
-    int64_t columns = 0;
-    for (int32_t i = 0; i < count; ++i) {
-        const zlhip_overview_request &q = reqs[i];
-        if (q.id < 0 || q.id >= e->cfg.max_sounds || !e->hc.soundUsed[q.id]) return fail(e, ZLHIP_ERR_INVALID, "sound_overview: no such sound");
-        if (q.columns < 1 || q.columns > ZLHIP_OVERVIEW_MAX_COLUMNS) return fail(e, ZLHIP_ERR_INVALID, "sound_overview: columns outside 1 .. 4096");
-        if (q.first_frame < 0 || q.num_frames < 1 || (int64_t)q.first_frame + q.num_frames > e->hc.sounds[q.id].length)
-            return fail(e, ZLHIP_ERR_INVALID, "sound_overview: the frames do not lie inside the sound's playback data");
-        columns += q.columns;
-        if (columns > ZL_OV_MAX_CALL_COLUMNS) return fail(e, ZLHIP_ERR_INVALID, "sound_overview_batch: more than 262144 columns in one call");
-    }
-    if (out_floats < (size_t)columns * 4) return fail(e, ZLHIP_ERR_CAPACITY, "sound_overview: out holds fewer than 4 floats per column");
-    ZL_HIP(e, hipSetDevice(e->device));
-    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
-    { const int rc = ov_reserve(e, (size_t)count, (size_t)columns); if (rc != ZLHIP_OK) return rc; }
-    zlhip_engine::Overview &o = e->ov;
-    ZlOvRequest *const hReq = (ZlOvRequest *)e->scratch[ZB_OV_REQ].h, *const dReq = (ZlOvRequest *)e->scratch[ZB_OV_REQ].d;
-    float *const hCols = (float *)e->scratch[ZB_OV_COLS].h; uint32_t *const dCols = (uint32_t *)e->scratch[ZB_OV_COLS].d;
-    // the request records: where the extent lies (64-bit, per request: a grown arena's segments are far apart), what to cut it into
-    int64_t items = 0; int32_t col = 0;
-    for (int32_t i = 0; i < count; ++i) {
-        const zlhip_overview_request &q = reqs[i];
-        const ZlSound &s = e->hc.sounds[q.id];
-        ZlOvRequest &R = hReq[i];
-        R.src = (uint64_t)(uintptr_t)arena_ptr(e, s.offset);
-        R.item_base = items;
-        R.first = q.first_frame; R.frames = q.num_frames; R.columns = q.columns;
-        R.channels = s.channels;
-        R.col_base = col;
-        R.ppc = zl_ov_pieces_per_column(q.num_frames, q.columns);
-        items += zl_ov_items(q.num_frames, q.columns);
-        col += q.columns;
-    }
-    const bool prof = e->profiling;
-    for (int x = 0; prof && x < 2; ++x) if (!o.ev[x]) ZL_HIP(e, hipEventCreate(&o.ev[x]));
-    ZL_HIP(e, hipMemcpyAsync(dReq, hReq, (size_t)count * sizeof(ZlOvRequest), hipMemcpyHostToDevice, e->stream));
-    if (prof) ZL_HIP(e, hipEventRecord(o.ev[0], e->stream));
-    ZL_HIP(e, hipMemsetAsync(dCols, 0, (size_t)columns * 4 * sizeof(float), e->stream));
-    ZL_KERNEL(e, zl_launch_overview_reduce(dReq, count, items, dCols, e->stream));
-    ZL_KERNEL(e, zl_launch_overview_finish(dCols, (int32_t)columns, e->stream));
-    if (prof) ZL_HIP(e, hipEventRecord(o.ev[1], e->stream));
-    ZL_HIP(e, hipMemcpyAsync(hCols, dCols, (size_t)columns * 4 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
-    if (prof) ZL_HIP(e, hipEventElapsedTime(&o.ms, o.ev[0], o.ev[1]));
-    std::memcpy(out, hCols, (size_t)columns * 4 * sizeof(float));
-    return ZLHIP_OK;
-}
-
-int zlhip_sound_overview(zlhip_engine *e, int32_t id, int32_t first_frame, int32_t num_frames, int32_t columns, float *out)
-{
-    const zlhip_overview_request q = { id, first_frame, num_frames, columns };
-    return zlhip_sound_overview_batch(e, &q, 1, out, columns > 0 ? (size_t)columns * 4 : 0);
-}
-
-int zlhip_debug_overview_timings(zlhip_engine *e, float *device_ms)
-{
-    if (!e) return ZLHIP_ERR_INVALID;
-    if (device_ms) *device_ms = e->ov.ms;
-    return ZLHIP_OK;
-}
-
-// ---- transients (zl_onset.h, zl_onset.hip) ---------------------------------------------------------------------------------
-// Where a sampler slices a loop.  The synchronisation and the buffers are the overviews': the call runs on the engine's stream behind
-// what is queued there and leaves the resident real-time kernel alone; its buffers are allocated by the first call and grow only.
-// The counts and the onsets are written by the pick kernel into host memory mapped into the device, so only what was found crosses.
-int zlhip_onset_resolve(double sample_rate, zlhip_onset_request *r)
-{
-    if (!r || r->first_frame < 0 || r->num_frames < 1) return ZLHIP_ERR_INVALID;
-    zlhip_onset_request q = *r;
-    if (zl_on_resolve(sample_rate, &q.hop_frames, &q.gate, &q.threshold, &q.min_gap_hops, &q.max_onsets) != 0) return ZLHIP_ERR_INVALID;
-    if (zl_on_hops(q.num_frames, q.hop_frames) > ZL_ON_MAX_HOPS) return ZLHIP_ERR_INVALID;
-    *r = q;
-    return ZLHIP_OK;
-}
-
-static int on_reserve(zlhip_engine *e, size_t nreq, size_t hops, size_t nout)
-{
-    GrowBuf *b = e->scratch; zlhip_engine::Onset &o = e->on;
-    if (nreq <= b[ZB_ON_REQ].cap && hops <= b[ZB_ON_E].cap && hops <= b[ZB_ON_N].cap && hops <= b[ZB_ON_PS].cap && nreq <= o.countsCap && nout <= o.outCap)
-        return ZLHIP_OK;
-    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }
-    ZlQuiesce quiet(e);
-    const char *what = "sound_onsets: no memory for the call's buffers";
-    const size_t hcap = std::min<size_t>(std::max<size_t>(hops * 2, 4096), ZL_ON_MAX_CALL_HOPS);
-    int rc = grow_buf(e, b[ZB_ON_REQ], nreq, sizeof(ZlOnRequest), std::max<size_t>(nreq * 2, 64), true, what);
-    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_ON_E], hops, sizeof(uint64_t), hcap, false, what);
-    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_ON_N], hops, sizeof(int32_t), hcap, false, what);
-    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_ON_PS], hops, sizeof(uint32_t), hcap, false, what);
-    if (rc != ZLHIP_OK) return rc;
-    ZL_HIP(e, grow_mapped(&o.hCounts, &o.dCounts, &o.countsCap, std::max<size_t>(nreq, 32)));
-    ZL_HIP(e, grow_mapped(&o.hOut, &o.dOut, &o.outCap, std::max<size_t>(nout, 512)));
-    return ZLHIP_OK;
-}
-
-int zlhip_sound_onsets_batch(zlhip_engine *e, const zlhip_onset_request *reqs, int32_t nreq, zlhip_onset *out, size_t capacity, int32_t *counts)
-{
-    if (!e || nreq < 0 || (nreq > 0 && (!reqs || !out || !counts))) return ZLHIP_ERR_INVALID;
-    if (nreq == 0) return ZLHIP_OK;
-    // validate and resolve everything before anything is written and before the first HIP call
-    std::vector<zlhip_onset_request> res((size_t)nreq);
-    int64_t hops = 0; size_t nout = 0;
-    for (int32_t i = 0; i < nreq; ++i) {
-        zlhip_onset_request &q = res[(size_t)i];
-        q = reqs[i];
-        if (q.id < 0 || q.id >= e->cfg.max_sounds || !e->hc.soundUsed[q.id]) return fail(e, ZLHIP_ERR_INVALID, "sound_onsets: no such sound");
-        const ZlSound &s = e->hc.sounds[q.id];
-        if (zlhip_onset_resolve(s.sample_rate, &q) != ZLHIP_OK) return fail(e, ZLHIP_ERR_INVALID, "sound_onsets: a field of the request is outside its limits");
-        if ((int64_t)q.first_frame + q.num_frames > s.length) return fail(e, ZLHIP_ERR_INVALID, "sound_onsets: the frames do not lie inside the sound's playback data");
-        hops += zl_on_hops(q.num_frames, q.hop_frames);
-        if (hops > ZL_ON_MAX_CALL_HOPS) return fail(e, ZLHIP_ERR_INVALID, "sound_onsets_batch: more than 4194304 hops in one call");
-        nout += (size_t)q.max_onsets;
-    }
-    if (capacity < nout) return fail(e, ZLHIP_ERR_CAPACITY, "sound_onsets: out holds fewer onsets than the requests' max_onsets");
-    ZL_HIP(e, hipSetDevice(e->device));
-    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
-    { const int rc = on_reserve(e, (size_t)nreq, (size_t)hops, nout); if (rc != ZLHIP_OK) return rc; }
-    zlhip_engine::Onset &o = e->on;
-    ZlOnRequest *const hReq = (ZlOnRequest *)e->scratch[ZB_ON_REQ].h, *const dReq = (ZlOnRequest *)e->scratch[ZB_ON_REQ].d;
-    uint64_t *const dE = (uint64_t *)e->scratch[ZB_ON_E].d; int32_t *const dN = (int32_t *)e->scratch[ZB_ON_N].d; uint32_t *const dPs = (uint32_t *)e->scratch[ZB_ON_PS].d;
-    o.last.clear();
-    int32_t hop0 = 0, out0 = 0;
-    for (int32_t i = 0; i < nreq; ++i) {
-        const zlhip_onset_request &q = res[(size_t)i];
-        const ZlSound &s = e->hc.sounds[q.id];
-        ZlOnRequest &R = hReq[i];
-        R.src = (uint64_t)(uintptr_t)arena_ptr(e, s.offset);
-        R.floor_ = zl_on_floor(q.hop_frames, s.channels, q.gate);
-        R.first = q.first_frame; R.frames = q.num_frames; R.hop = q.hop_frames; R.channels = s.channels;
-        R.hops = (int32_t)zl_on_hops(q.num_frames, q.hop_frames);
-        R.hop_base = hop0;
-        R.threshold = q.threshold; R.min_gap = q.min_gap_hops; R.max_onsets = q.max_onsets;
-        R.out_base = out0;
-        o.last.emplace_back(hop0, R.hops);
-        hop0 += R.hops; out0 += q.max_onsets;
-    }
-    const bool prof = e->profiling;
-    for (int x = 0; prof && x < 3; ++x) if (!o.ev[x]) ZL_HIP(e, hipEventCreate(&o.ev[x]));
-    ZL_HIP(e, hipMemcpyAsync(dReq, hReq, (size_t)nreq * sizeof(ZlOnRequest), hipMemcpyHostToDevice, e->stream));
-    if (prof) ZL_HIP(e, hipEventRecord(o.ev[0], e->stream));
-    ZL_KERNEL(e, zl_launch_onset_energy(dReq, nreq, hops, dE, e->stream));
-    if (prof) ZL_HIP(e, hipEventRecord(o.ev[1], e->stream));
-    ZL_KERNEL(e, zl_launch_onset_pick(dReq, nreq, dE, dN, dPs, o.dCounts, o.dOut, e->stream));
-    if (prof) ZL_HIP(e, hipEventRecord(o.ev[2], e->stream));
-    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
-    if (prof) { ZL_HIP(e, hipEventElapsedTime(&o.energyMs, o.ev[0], o.ev[1])); ZL_HIP(e, hipEventElapsedTime(&o.restMs, o.ev[1], o.ev[2])); }
-    size_t at = 0;
-    for (int32_t i = 0; i < nreq; ++i) {
-        const int32_t n = o.hCounts[i];
-        std::memcpy(out + at, o.hOut + hReq[i].out_base, (size_t)n * sizeof(zlhip_onset));
-        counts[i] = n;
-        at += (size_t)n;
-    }
-    return ZLHIP_OK;
-}
-
-int zlhip_sound_onsets(zlhip_engine *e, const zlhip_onset_request *r, zlhip_onset *out, int32_t capacity, int32_t *count)
-{
-    if (capacity < 0) return ZLHIP_ERR_INVALID;
-    return zlhip_sound_onsets_batch(e, r, 1, out, (size_t)capacity, count);
-}
-
-int zlhip_debug_onset_hops(zlhip_engine *e, int32_t request, uint64_t *energy, int32_t *strength, int32_t capacity, int32_t *hops)
-{
-    if (!e || request < 0 || (size_t)request >= e->on.last.size()) return ZLHIP_ERR_INVALID;
-    const int32_t base = e->on.last[(size_t)request].first, n = e->on.last[(size_t)request].second;
-    if (hops) *hops = n;
-    if (!energy && !strength) return ZLHIP_OK;
-    if (capacity < n) return fail(e, ZLHIP_ERR_CAPACITY, "debug_onset_hops: capacity below the request's hops");
-    ZL_HIP(e, hipSetDevice(e->device));
-    if (energy) ZL_HIP(e, hipMemcpyAsync(energy, (const uint64_t *)e->scratch[ZB_ON_E].d + base, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
-    if (strength) ZL_HIP(e, hipMemcpyAsync(strength, (const int32_t *)e->scratch[ZB_ON_N].d + base, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    return engine_wait(e);
-}
-
-int zlhip_debug_onset_timings(zlhip_engine *e, float *energy_ms, float *rest_ms)
-{
-    if (!e) return ZLHIP_ERR_INVALID;
-    if (energy_ms) *energy_ms = e->on.energyMs;
-    if (rest_ms) *rest_ms = e->on.restMs;
-    return ZLHIP_OK;
-}
-
-// ---- tempo (zl_tempo.h, zl_tempo.hip) --------------------------------------------------------------------------------------
-// How fast a loop is.  The samples are read once, by the transients' energy kernel; the flux, the autocorrelation and the pick are
-// integer arithmetic on one word per hop.  Synchronisation and buffers as for the transients: the call runs on the engine's stream
-// behind what is queued there and leaves the resident real-time kernel alone; its buffers are allocated by the first call and grow
-// only.  The integer records are written by the pick kernel into host memory mapped into the device; bpm and confidence are derived
-// here (zl_tp_finish).
-int zlhip_tempo_resolve(double sample_rate, zlhip_tempo_request *r)
-{
-    if (!r || r->first_frame < 0 || r->num_frames < 1) return ZLHIP_ERR_INVALID;
-    zlhip_tempo_request q = *r;
-    if (zl_tp_resolve(sample_rate, &q.hop_frames, &q.bpm_min, &q.bpm_max) != 0) return ZLHIP_ERR_INVALID;
-    if (zl_on_hops(q.num_frames, q.hop_frames) > ZL_TP_MAX_HOPS) return ZLHIP_ERR_INVALID;
-    *r = q;
-    return ZLHIP_OK;
-}
-
-static const size_t kTpRecordBytes = sizeof(ZlOnRequest) + sizeof(ZlTpRequest);     // per request: the energy pass's record and the tempo kernels'
-
-static int tp_reserve(zlhip_engine *e, size_t nreq, size_t hops, size_t lags)
-{
-    GrowBuf *b = e->scratch; zlhip_engine::Tempo &t = e->tp;
-    if (nreq <= b[ZB_TP_REQ].cap && hops <= b[ZB_TP_E].cap && hops <= b[ZB_TP_W].cap && lags <= b[ZB_TP_A].cap && nreq <= b[ZB_TP_STAT].cap && nreq <= t.outCap)
-        return ZLHIP_OK;
-    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }
-    ZlQuiesce quiet(e);
-    const char *what = "sound_tempo: no memory for the call's buffers";
-    const size_t hcap = std::min<size_t>(std::max<size_t>(hops * 2, 4096), ZL_TP_MAX_CALL_HOPS);
-    const size_t rcap = std::max<size_t>(nreq * 2, 64);
-    int rc = grow_buf(e, b[ZB_TP_REQ], nreq, kTpRecordBytes, rcap, true, what);
-    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_TP_E], hops, sizeof(uint64_t), hcap, false, what);
-    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_TP_W], hops, sizeof(uint16_t), hcap, false, what);
-    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_TP_A], lags, sizeof(uint64_t), std::max<size_t>(lags * 2, 4096), false, what);
-    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_TP_STAT], nreq, sizeof(ZlTpStat), rcap, false, what);
-    if (rc != ZLHIP_OK) return rc;
-    ZL_HIP(e, grow_mapped(&t.hOut, &t.dOut, &t.outCap, std::max<size_t>(nreq, 32)));
-    return ZLHIP_OK;
-}
-
-int zlhip_sound_tempo_batch(zlhip_engine *e, const zlhip_tempo_request *reqs, int32_t nreq, zlhip_tempo *out)
-{
-    static_assert(sizeof(zlhip_tempo) == sizeof(ZlTpResult), "the device writes zlhip_tempo's layout");
-    if (!e || nreq < 0 || (nreq > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
-    if (nreq == 0) return ZLHIP_OK;
-    // validate and resolve everything before anything is written and before the first HIP call
-    std::vector<zlhip_tempo_request> res((size_t)nreq);
-    std::vector<ZlTpRequest> geo((size_t)nreq);
-    int64_t hops = 0, lags = 0, items = 0;
-    for (int32_t i = 0; i < nreq; ++i) {
-        zlhip_tempo_request &q = res[(size_t)i];
-        q = reqs[i];
-        if (q.id < 0 || q.id >= e->cfg.max_sounds || !e->hc.soundUsed[q.id]) return fail(e, ZLHIP_ERR_INVALID, "sound_tempo: no such sound");
-        const ZlSound &s = e->hc.sounds[q.id];
-        if (zlhip_tempo_resolve(s.sample_rate, &q) != ZLHIP_OK) return fail(e, ZLHIP_ERR_INVALID, "sound_tempo: a field of the request is outside its limits");
-        if ((int64_t)q.first_frame + q.num_frames > s.length) return fail(e, ZLHIP_ERR_INVALID, "sound_tempo: the frames do not lie inside the sound's playback data");
-        ZlTpRequest &T = geo[(size_t)i];
-        double lmin, lmax;
-        zl_tp_lags(s.sample_rate, q.hop_frames, q.bpm_min, q.bpm_max, &lmin, &lmax);
-        zl_tp_geometry(&T, (int32_t)zl_on_hops(q.num_frames, q.hop_frames), lmin, lmax);
-        T.hop_base = (int32_t)hops; T.acf_base = (int32_t)lags; T.item_base = (int32_t)items;
-        hops += T.hops; lags += T.nlags; items += zl_tp_items(T);
-        if (hops > ZL_TP_MAX_CALL_HOPS) return fail(e, ZLHIP_ERR_INVALID, "sound_tempo_batch: more than 4194304 hops in one call");
-    }
-    ZL_HIP(e, hipSetDevice(e->device));
-    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
-    { const int rc = tp_reserve(e, (size_t)nreq, (size_t)hops, (size_t)lags); if (rc != ZLHIP_OK) return rc; }
-    zlhip_engine::Tempo &t = e->tp;
-    char *const hRec = (char *)e->scratch[ZB_TP_REQ].h, *const dRec = (char *)e->scratch[ZB_TP_REQ].d;
-    ZlOnRequest *const hOn = (ZlOnRequest *)hRec, *const dOn = (ZlOnRequest *)dRec;
-    ZlTpRequest *const hTp = (ZlTpRequest *)(hRec + (size_t)nreq * sizeof(ZlOnRequest)), *const dTp = (ZlTpRequest *)(dRec + (size_t)nreq * sizeof(ZlOnRequest));
-    uint64_t *const dE = (uint64_t *)e->scratch[ZB_TP_E].d; uint16_t *const dW = (uint16_t *)e->scratch[ZB_TP_W].d;
-    uint64_t *const dA = (uint64_t *)e->scratch[ZB_TP_A].d; ZlTpStat *const dStat = (ZlTpStat *)e->scratch[ZB_TP_STAT].d;
-    t.last.clear();
-    for (int32_t i = 0; i < nreq; ++i) {
-        const zlhip_tempo_request &q = res[(size_t)i];
-        const ZlSound &s = e->hc.sounds[q.id];
-        const ZlTpRequest &T = geo[(size_t)i];
-        ZlOnRequest &R = hOn[i];
-        std::memset(&R, 0, sizeof(R));
-        R.src = (uint64_t)(uintptr_t)arena_ptr(e, s.offset);
-        R.first = q.first_frame; R.frames = q.num_frames; R.hop = q.hop_frames; R.channels = s.channels;
-        R.hops = T.hops; R.hop_base = T.hop_base;
-        hTp[i] = T;
-        t.last.push_back({T.hop_base, T.hops, T.acf_base, T.first_lag, T.nlags});
-    }
-    const bool prof = e->profiling;
-    for (int x = 0; prof && x < 5; ++x) if (!t.ev[x]) ZL_HIP(e, hipEventCreate(&t.ev[x]));
-    ZL_HIP(e, hipMemcpyAsync(dRec, hRec, (size_t)nreq * kTpRecordBytes, hipMemcpyHostToDevice, e->stream));
-    if (prof) ZL_HIP(e, hipEventRecord(t.ev[0], e->stream));
-    ZL_KERNEL(e, zl_launch_onset_energy(dOn, nreq, hops, dE, e->stream));
-    if (prof) ZL_HIP(e, hipEventRecord(t.ev[1], e->stream));
-    ZL_KERNEL(e, zl_launch_tempo_flux(dTp, nreq, dE, dW, dA, dStat, e->stream));
-    if (prof) ZL_HIP(e, hipEventRecord(t.ev[2], e->stream));
-    ZL_KERNEL(e, zl_launch_tempo_acf(dTp, nreq, items, dW, dA, e->stream));
-    if (prof) ZL_HIP(e, hipEventRecord(t.ev[3], e->stream));
-    ZL_KERNEL(e, zl_launch_tempo_pick(dTp, nreq, dA, dStat, t.dOut, e->stream));
-    if (prof) ZL_HIP(e, hipEventRecord(t.ev[4], e->stream));
-    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
-    if (prof) {
-        float flux = 0.0f, pick = 0.0f;
-        ZL_HIP(e, hipEventElapsedTime(&t.energyMs, t.ev[0], t.ev[1])); ZL_HIP(e, hipEventElapsedTime(&flux, t.ev[1], t.ev[2]));
-        ZL_HIP(e, hipEventElapsedTime(&t.acfMs, t.ev[2], t.ev[3])); ZL_HIP(e, hipEventElapsedTime(&pick, t.ev[3], t.ev[4]));
-        t.restMs = flux + pick;
-    }
-    for (int32_t i = 0; i < nreq; ++i) {
-        ZlTpResult r = t.hOut[i];
-        zl_tp_finish(e->hc.sounds[res[(size_t)i].id].sample_rate, res[(size_t)i].hop_frames, &r);
-        std::memcpy(&out[i], &r, sizeof(r));
-    }
-    return ZLHIP_OK;
-}
-
-int zlhip_sound_tempo(zlhip_engine *e, const zlhip_tempo_request *r, zlhip_tempo *out) { return zlhip_sound_tempo_batch(e, r, 1, out); }
-
-int zlhip_debug_tempo_acf(zlhip_engine *e, int32_t request, uint16_t *flux, uint64_t *acf, int32_t capacity, int32_t *hops, int32_t *first_lag, int32_t *lags)
-{
-    if (!e || request < 0 || (size_t)request >= e->tp.last.size()) return ZLHIP_ERR_INVALID;
-    const zlhip_engine::Tempo::Last &l = e->tp.last[(size_t)request];
-    if (hops) *hops = l.hops;
-    if (first_lag) *first_lag = l.first_lag;
-    if (lags) *lags = l.nlags;
-    if (!flux && !acf) return ZLHIP_OK;
-    if ((flux && capacity < l.hops) || (acf && capacity < l.nlags)) return fail(e, ZLHIP_ERR_CAPACITY, "debug_tempo_acf: capacity below the request's hops or lags");
-    ZL_HIP(e, hipSetDevice(e->device));
-    if (flux) ZL_HIP(e, hipMemcpyAsync(flux, (const uint16_t *)e->scratch[ZB_TP_W].d + l.hop_base, (size_t)l.hops * sizeof(uint16_t), hipMemcpyDeviceToHost, e->stream));
-    if (acf && l.nlags > 0) ZL_HIP(e, hipMemcpyAsync(acf, (const uint64_t *)e->scratch[ZB_TP_A].d + l.acf_base, (size_t)l.nlags * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
-    return engine_wait(e);
-}
-
-int zlhip_debug_tempo_timings(zlhip_engine *e, float *energy_ms, float *acf_ms, float *rest_ms)
-{
-    if (!e) return ZLHIP_ERR_INVALID;
-    if (energy_ms) *energy_ms = e->tp.energyMs;
-    if (acf_ms) *acf_ms = e->tp.acfMs;
-    if (rest_ms) *rest_ms = e->tp.restMs;
-    return ZLHIP_OK;
-}
-
-// ---- pitch (zl_pitch.h, zl_pitch.hip) --------------------------------------------------------------------------------------
-// What note a clip is.  The diff kernel reads the analysed frames' samples and leaves d per frame and lag; the pick and the vote are
-// integer arithmetic on it.  Synchronisation and buffers as for the transients and the tempo: the call runs on the engine's stream
-// behind what is queued there and leaves the resident real-time kernel alone; its buffers are allocated by the first call and grow
-// only.  The integer records are written by the vote kernel into host memory mapped into the device; hz, note, root_note, cents and
-// confidence are derived here (zl_pt_finish).
-int zlhip_pitch_resolve(double sample_rate, zlhip_pitch_request *r)
-{
-    if (!r || r->first_frame < 0 || r->num_frames < 1) return ZLHIP_ERR_INVALID;
-    zlhip_pitch_request q = *r;
-    if (zl_pt_resolve(sample_rate, &q.window, &q.max_frames, &q.f_min, &q.f_max, &q.threshold, &q.gate) != 0) return ZLHIP_ERR_INVALID;
-    *r = q;
-    return ZLHIP_OK;
-}
-
-static int pt_reserve(zlhip_engine *e, size_t nreq, size_t frames, size_t words)
-{
-    GrowBuf *b = e->scratch; zlhip_engine::Pitch &t = e->pt;
-    if (nreq <= b[ZB_PT_REQ].cap && words <= b[ZB_PT_D].cap && frames <= b[ZB_PT_STAT].cap && frames <= b[ZB_PT_FRAME].cap && nreq <= t.outCap)
-        return ZLHIP_OK;
-    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }
-    ZlQuiesce quiet(e);
-    const char *what = "sound_pitch: no memory for the call's buffers";
-    const size_t fcap = std::min<size_t>(std::max<size_t>(frames * 2, 256), ZL_PT_MAX_CALL_FRAMES);
-    int rc = grow_buf(e, b[ZB_PT_REQ], nreq, sizeof(ZlPtRequest), std::max<size_t>(nreq * 2, 64), true, what);
-    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_PT_D], words, sizeof(uint64_t), std::max<size_t>(words + words / 2, 65536), false, what);
-    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_PT_STAT], frames, sizeof(ZlPtStat), fcap, false, what);
-    if (rc == ZLHIP_OK) rc = grow_buf(e, b[ZB_PT_FRAME], frames, sizeof(ZlPtFrame), fcap, false, what);
-    if (rc != ZLHIP_OK) return rc;
-    ZL_HIP(e, grow_mapped(&t.hOut, &t.dOut, &t.outCap, std::max<size_t>(nreq, 32)));
-    return ZLHIP_OK;
-}
-
-int zlhip_sound_pitch_batch(zlhip_engine *e, const zlhip_pitch_request *reqs, int32_t nreq, zlhip_pitch *out)
-{
-    static_assert(sizeof(zlhip_pitch) == sizeof(ZlPtResult), "the device writes zlhip_pitch's layout");
-    static_assert(sizeof(zlhip_pitch_frame) == sizeof(ZlPtFrame), "the device writes zlhip_pitch_frame's layout");
-    if (!e || nreq < 0 || (nreq > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
-    if (nreq == 0) return ZLHIP_OK;
-    // validate and resolve everything before anything is written and before the first HIP call
-    std::vector<ZlPtRequest> geo((size_t)nreq);
-    std::vector<double> rate((size_t)nreq);
-    int64_t frames = 0, words = 0, items = 0;
-    for (int32_t i = 0; i < nreq; ++i) {
-        zlhip_pitch_request q = reqs[i];
-        if (q.id < 0 || q.id >= e->cfg.max_sounds || !e->hc.soundUsed[q.id]) return fail(e, ZLHIP_ERR_INVALID, "sound_pitch: no such sound");
-        const ZlSound &s = e->hc.sounds[q.id];
-        if (zlhip_pitch_resolve(s.sample_rate, &q) != ZLHIP_OK) return fail(e, ZLHIP_ERR_INVALID, "sound_pitch: a field of the request is outside its limits");
-        if ((int64_t)q.first_frame + q.num_frames > s.length) return fail(e, ZLHIP_ERR_INVALID, "sound_pitch: the frames do not lie inside the sound's playback data");
-        ZlPtRequest &R = geo[(size_t)i];
-        double tmin, tmax;
-        zl_pt_lags(s.sample_rate, q.f_min, q.f_max, &tmin, &tmax);
-        R.src = 0;                                                 // (the address: behind pt_reserve, with the other HIP-side state)
-        R.floor_ = (uint64_t)q.window * (uint64_t)s.channels * (uint64_t)q.gate * (uint64_t)q.gate;
-        R.first = q.first_frame; R.channels = s.channels;
-        R.window = q.window; R.tmin = (int32_t)tmin; R.tmax = (int32_t)tmax; R.threshold = q.threshold;
-        zl_pt_frames(q.num_frames, R.window, R.tmax, q.max_frames, &R.frames, &R.hop);
-        R.d_base = words; R.frame_base = (int32_t)frames; R.item_base = (int32_t)items;
-        rate[(size_t)i] = s.sample_rate;
-        frames += R.frames; words += (int64_t)R.frames * zl_pt_nd(R); items += zl_pt_items(R);
-        if (frames > ZL_PT_MAX_CALL_FRAMES) return fail(e, ZLHIP_ERR_INVALID, "sound_pitch_batch: more than 65536 analysis frames in one call");
-    }
-    ZL_HIP(e, hipSetDevice(e->device));
-    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
-    { const int rc = pt_reserve(e, (size_t)nreq, (size_t)frames, (size_t)words); if (rc != ZLHIP_OK) return rc; }
-    zlhip_engine::Pitch &t = e->pt;
-    ZlPtRequest *const hReq = (ZlPtRequest *)e->scratch[ZB_PT_REQ].h, *const dReq = (ZlPtRequest *)e->scratch[ZB_PT_REQ].d;
-    uint64_t *const dD = (uint64_t *)e->scratch[ZB_PT_D].d; ZlPtStat *const dStat = (ZlPtStat *)e->scratch[ZB_PT_STAT].d;
-    ZlPtFrame *const dFrame = (ZlPtFrame *)e->scratch[ZB_PT_FRAME].d;
-    t.last.clear();
-    for (int32_t i = 0; i < nreq; ++i) {
-        ZlPtRequest &R = hReq[i];
-        R = geo[(size_t)i];
-        R.src = (uint64_t)(uintptr_t)arena_ptr(e, e->hc.sounds[reqs[i].id].offset);
-        t.last.push_back({R.d_base, R.frame_base, R.frames, zl_pt_nd(R)});
-    }
-    const bool prof = e->profiling;
-    for (int x = 0; prof && x < 3; ++x) if (!t.ev[x]) ZL_HIP(e, hipEventCreate(&t.ev[x]));
-    ZL_HIP(e, hipMemcpyAsync(dReq, hReq, (size_t)nreq * sizeof(ZlPtRequest), hipMemcpyHostToDevice, e->stream));
-    if (prof) ZL_HIP(e, hipEventRecord(t.ev[0], e->stream));
-    ZL_KERNEL(e, zl_launch_pitch_diff(dReq, nreq, items, dD, dStat, e->stream));
-    if (prof) ZL_HIP(e, hipEventRecord(t.ev[1], e->stream));
-    ZL_KERNEL(e, zl_launch_pitch_pick(dReq, nreq, frames, dD, dStat, dFrame, e->stream));
-    ZL_KERNEL(e, zl_launch_pitch_vote(dReq, nreq, dFrame, t.dOut, e->stream));
-    if (prof) ZL_HIP(e, hipEventRecord(t.ev[2], e->stream));
-    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
-    if (prof) { ZL_HIP(e, hipEventElapsedTime(&t.diffMs, t.ev[0], t.ev[1])); ZL_HIP(e, hipEventElapsedTime(&t.restMs, t.ev[1], t.ev[2])); }
-    for (int32_t i = 0; i < nreq; ++i) {
-        ZlPtResult r = t.hOut[i];
-        zl_pt_finish(rate[(size_t)i], &r);
-        std::memcpy(&out[i], &r, sizeof(r));
-    }
-    return ZLHIP_OK;
-}
-
-int zlhip_sound_pitch(zlhip_engine *e, const zlhip_pitch_request *r, zlhip_pitch *out) { return zlhip_sound_pitch_batch(e, r, 1, out); }
-
-int zlhip_debug_pitch_frames(zlhip_engine *e, int32_t request, zlhip_pitch_frame *records, int32_t capacity, int32_t *frames)
-{
-    if (!e || request < 0 || (size_t)request >= e->pt.last.size()) return ZLHIP_ERR_INVALID;
-    const zlhip_engine::Pitch::Last &l = e->pt.last[(size_t)request];
-    if (frames) *frames = l.frames;
-    if (!records) return ZLHIP_OK;
-    if (capacity < l.frames) return fail(e, ZLHIP_ERR_CAPACITY, "debug_pitch_frames: capacity below the request's frames");
-    if (l.frames == 0) return ZLHIP_OK;
-    ZL_HIP(e, hipSetDevice(e->device));
-    ZL_HIP(e, hipMemcpyAsync(records, (const ZlPtFrame *)e->scratch[ZB_PT_FRAME].d + l.frame_base, (size_t)l.frames * sizeof(ZlPtFrame), hipMemcpyDeviceToHost, e->stream));
-    return engine_wait(e);
-}
-
-int zlhip_debug_pitch_diff(zlhip_engine *e, int32_t request, int32_t frame, uint64_t *d, int32_t capacity, int32_t *lags)
-{
-    if (!e || request < 0 || (size_t)request >= e->pt.last.size()) return ZLHIP_ERR_INVALID;
-    const zlhip_engine::Pitch::Last &l = e->pt.last[(size_t)request];
-    if (lags) *lags = l.nd;
-    if (!d) return ZLHIP_OK;
-    if (frame < 0 || frame >= l.frames) return fail(e, ZLHIP_ERR_INVALID, "debug_pitch_diff: no such frame");
-    if (capacity < l.nd) return fail(e, ZLHIP_ERR_CAPACITY, "debug_pitch_diff: capacity below the request's lags");
-    ZL_HIP(e, hipSetDevice(e->device));
-    ZL_HIP(e, hipMemcpyAsync(d, (const uint64_t *)e->scratch[ZB_PT_D].d + l.d_base + (int64_t)frame * l.nd, (size_t)l.nd * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
-    return engine_wait(e);
-}
-
-int zlhip_debug_pitch_timings(zlhip_engine *e, float *diff_ms, float *rest_ms)
-{
-    if (!e) return ZLHIP_ERR_INVALID;
-    if (diff_ms) *diff_ms = e->pt.diffMs;
-    if (rest_ms) *rest_ms = e->pt.restMs;
-    return ZLHIP_OK;
-}
-
-// ---- loudness (zl_loudness.h, zl_loudness.hip) -----------------------------------------------------------------------------
-// How loud a clip is: BS.1770's integrated loudness and the sample peak.  The kernel filters and sums the sub-blocks, one lane each,
-// and writes their records into host memory mapped into the device; the blocks, the gates and lufs are derived here (zl_ld_finish).
-// Synchronisation and buffers as for the transients, the tempo and the pitch: the call runs on the engine's stream behind what is
-// queued there and leaves the resident real-time kernel alone; its buffers are allocated by the first call and grow only.
-int zlhip_loudness_design(double sample_rate, double *coeffs)
-{
-    if (!coeffs) return ZLHIP_ERR_INVALID;
-    double c[10];
-    if (zl_ld_design(sample_rate, c) != 0) return ZLHIP_ERR_INVALID;
-    std::memcpy(coeffs, c, sizeof(c));
-    return ZLHIP_OK;
-}
-
-int zlhip_loudness_resolve(double sample_rate, zlhip_loudness_request *r)
-{
-    if (!r) return ZLHIP_ERR_INVALID;
-    int32_t sub = r->sub_frames;
-    if (zl_ld_resolve(sample_rate, r->first_frame, r->num_frames, &sub) != 0) return ZLHIP_ERR_INVALID;
-    r->sub_frames = sub;
-    return ZLHIP_OK;
-}
-
-static int ld_reserve(zlhip_engine *e, size_t nreq, size_t items)
-{
-    GrowBuf *b = e->scratch; zlhip_engine::Loudness &t = e->ld;
-    if (nreq <= b[ZB_LD_REQ].cap && items <= t.outCap) return ZLHIP_OK;
-    { int r_ = rt_stop(e); if (r_ != ZLHIP_OK) return r_; }
-    ZlQuiesce quiet(e);
-    const int rc = grow_buf(e, b[ZB_LD_REQ], nreq, sizeof(ZlLdRequest), std::max<size_t>(nreq * 2, 64), true, "sound_loudness: no memory for the call's buffers");
-    if (rc != ZLHIP_OK) return rc;
-    ZL_HIP(e, grow_mapped(&t.hOut, &t.dOut, &t.outCap, std::max<size_t>(items, 512)));
-    return ZLHIP_OK;
-}
-
-int zlhip_sound_loudness_batch(zlhip_engine *e, const zlhip_loudness_request *reqs, int32_t nreq, zlhip_loudness *out)
-{
-    static_assert(sizeof(zlhip_loudness) == sizeof(ZlLdResult), "zl_ld_finish writes zlhip_loudness's layout");
-    static_assert(sizeof(zlhip_loudness_sub) == sizeof(ZlLdSub) && sizeof(ZlLdSub) == 24, "the device writes zlhip_loudness_sub's layout");
-    if (!e || nreq < 0 || (nreq > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
-    if (nreq == 0) return ZLHIP_OK;
-    // validate and resolve everything before anything is written and before the first HIP call
-    std::vector<ZlLdRequest> geo((size_t)nreq);
-    int64_t items = 0;
-    for (int32_t i = 0; i < nreq; ++i) {
-        zlhip_loudness_request q = reqs[i];
-        if (q.id < 0 || q.id >= e->cfg.max_sounds || !e->hc.soundUsed[q.id]) return fail(e, ZLHIP_ERR_INVALID, "sound_loudness: no such sound");
-        const ZlSound &s = e->hc.sounds[q.id];
-        ZlLdRequest &R = geo[(size_t)i];
-        if (zlhip_loudness_resolve(s.sample_rate, &q) != ZLHIP_OK || zl_ld_design(s.sample_rate, R.c) != 0)
-            return fail(e, ZLHIP_ERR_INVALID, "sound_loudness: a field of the request is outside its limits");
-        if ((int64_t)q.first_frame + q.num_frames > s.length) return fail(e, ZLHIP_ERR_INVALID, "sound_loudness: the frames do not lie inside the sound's playback data");
-        R.src = 0;                                                 // (the address: behind ld_reserve, with the other HIP-side state)
-        R.first = q.first_frame; R.frames = q.num_frames; R.sub = q.sub_frames; R.channels = s.channels;
-        R.items = (int32_t)zl_ld_items(q.num_frames, q.sub_frames); R.item_base = (int32_t)items;
-        items += R.items;
-        if (items > ZL_LD_MAX_CALL_ITEMS) return fail(e, ZLHIP_ERR_INVALID, "sound_loudness_batch: more than 1048576 sub-blocks in one call");
-    }
-    ZL_HIP(e, hipSetDevice(e->device));
-    if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
-    { const int rc = ld_reserve(e, (size_t)nreq, (size_t)items); if (rc != ZLHIP_OK) return rc; }
-    zlhip_engine::Loudness &t = e->ld;
-    ZlLdRequest *const hReq = (ZlLdRequest *)e->scratch[ZB_LD_REQ].h, *const dReq = (ZlLdRequest *)e->scratch[ZB_LD_REQ].d;
-    t.last.clear();
-    for (int32_t i = 0; i < nreq; ++i) {
-        ZlLdRequest &R = hReq[i];
-        R = geo[(size_t)i];
-        R.src = (uint64_t)(uintptr_t)arena_ptr(e, e->hc.sounds[reqs[i].id].offset);
-        t.last.push_back({R.item_base, R.items});
-    }
-    const bool prof = e->profiling;
-    for (int x = 0; prof && x < 2; ++x) if (!t.ev[x]) ZL_HIP(e, hipEventCreate(&t.ev[x]));
-    ZL_HIP(e, hipMemcpyAsync(dReq, hReq, (size_t)nreq * sizeof(ZlLdRequest), hipMemcpyHostToDevice, e->stream));
-    if (prof) ZL_HIP(e, hipEventRecord(t.ev[0], e->stream));
-    ZL_KERNEL(e, zl_launch_loudness(dReq, nreq, (int32_t)items, t.dOut, e->stream));
-    if (prof) ZL_HIP(e, hipEventRecord(t.ev[1], e->stream));
-    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
-    if (prof) ZL_HIP(e, hipEventElapsedTime(&t.kernelMs, t.ev[0], t.ev[1]));
-    for (int32_t i = 0; i < nreq; ++i) {
-        const ZlLdRequest &R = geo[(size_t)i];
-        ZlLdResult r;
-        zl_ld_finish(t.hOut + R.item_base, R.frames, R.sub, &r);
-        std::memcpy(&out[i], &r, sizeof(r));
-    }
-    return ZLHIP_OK;
-}
-
-int zlhip_sound_loudness(zlhip_engine *e, const zlhip_loudness_request *r, zlhip_loudness *out) { return zlhip_sound_loudness_batch(e, r, 1, out); }
-
-int zlhip_debug_loudness_subs(zlhip_engine *e, int32_t request, zlhip_loudness_sub *records, int32_t capacity, int32_t *count)
-{
-    if (!e || request < 0 || (size_t)request >= e->ld.last.size()) return ZLHIP_ERR_INVALID;
-    const zlhip_engine::Loudness::Last &l = e->ld.last[(size_t)request];
-    if (count) *count = l.items;
-    if (!records) return ZLHIP_OK;
-    if (capacity < l.items) return fail(e, ZLHIP_ERR_CAPACITY, "debug_loudness_subs: capacity below the request's sub-blocks");
-    std::memcpy(records, e->ld.hOut + l.item_base, (size_t)l.items * sizeof(ZlLdSub));      // (the call has waited: the records are in host memory)
-    return ZLHIP_OK;
-}
-
-int zlhip_debug_loudness_timings(zlhip_engine *e, float *kernel_ms)
-{
-    if (!e) return ZLHIP_ERR_INVALID;
-    if (kernel_ms) *kernel_ms = e->ld.kernelMs;
-    return ZLHIP_OK;
-}
-
-int zlhip_debug_rerender_timings(zlhip_engine *e, float *seek_ms, float *synth_ms)
-{
-    if (!e) return ZLHIP_ERR_INVALID;
-    if (seek_ms) *seek_ms = e->stSeekMs;
-    if (synth_ms) *synth_ms = e->stSynthMs;
-    return ZLHIP_OK;
-}
-
-int zlhip_debug_rerender_offsets(zlhip_engine *e, int32_t id, int32_t *out, int32_t capacity, int32_t *count)
-{
-    if (!e || id < 0 || id >= e->cfg.max_sounds || !e->hc.soundUsed[id]) return ZLHIP_ERR_INVALID;
-    const std::vector<int32_t> &o = e->soundSlots[(size_t)id].renderOffsets;
-    if (count) *count = (int32_t)o.size();
-    if (!out) return ZLHIP_OK;
-    if ((size_t)capacity < o.size()) return fail(e, ZLHIP_ERR_CAPACITY, "debug_rerender_offsets: capacity below the count");
-    if (!o.empty()) std::memcpy(out, o.data(), o.size() * sizeof(int32_t));
-    return ZLHIP_OK;
 }
 
 int zlhip_clip_set(zlhip_engine *e, int32_t id, const zlhip_clip_params *p)

@@ -1,0 +1,309 @@
+// zl_engine_impl.h -- the engine's state and the helpers its host files share: zl_engine.cpp (the engine itself, where every helper
+// declared here is defined) and zl_clip_calls.cpp (the clip services).  Private to csrc/: nothing else includes it, and an engine
+// group goes through zl_member.h.  The helpers and their types have hidden visibility: what the library exports does not grow by them.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <atomic>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/zlhip.h"
+#include "zl_arena.h"
+#include "zl_host.h"
+#include "zl_types.h"
+
+struct ZlOnOnset; struct ZlTpResult; struct ZlPtResult; struct ZlLdSub;     // (zl_onset.h, zl_tempo.h, zl_pitch.h, zl_loudness.h)
+
+#pragma GCC visibility push(hidden)
+// host memory mapped into the device, grown by doubling (the buffer must be idle)
+template <typename T> hipError_t grow_mapped(T **host, T **dev, size_t *cap, size_t need)
+{
+    if (need <= *cap) return hipSuccess;
+    if (*host) { hipError_t r = hipHostFree(*host); *host = nullptr; *dev = nullptr; *cap = 0; if (r != hipSuccess) return r; }
+    const size_t n = need * 2;
+    hipError_t r = hipHostMalloc((void **)host, n * sizeof(T));
+    if (r != hipSuccess) return r;
+    r = hipHostGetDevicePointer((void **)dev, *host, 0);
+    if (r == hipSuccess) *cap = n;
+    return r;
+}
+
+// a call's records and staging on the device, allocated by the first call that needs them and grown only (grow_buf); an engine that
+// never re-renders, asks for an overview or loads PCM has none.  h: the page-locked host twin, where there is one; cap in elements
+struct GrowBuf { void *d = nullptr, *h = nullptr; size_t cap = 0; };
+enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a call's jobs, the jobs whose stretch runs, their seek offsets
+       ZB_OV_REQ, ZB_OV_COLS,                                 // overviews: a call's request records and its columns [columns][4], with host twins
+       ZB_PCM_STAGE, ZB_PCM_PIECES, ZB_PCM_PUB, ZB_PCM_VERDICTS,   // PCM: the staging buffer for the raw bytes, a call's piece and publish records, its verdict words
+       ZB_RS_JOBS, ZB_RS_PUB, ZB_RS_VERDICTS,                // rate conversion: a call's job and publish records, its verdict words
+       ZB_ON_REQ, ZB_ON_E, ZB_ON_N, ZB_ON_PS,                // transients: a call's request records (with a host twin), and per hop E, N and the windows' running maxima
+       ZB_TP_REQ, ZB_TP_E, ZB_TP_W, ZB_TP_A, ZB_TP_STAT,      // tempo: a call's request records (the energy pass's and the tempo kernels', one host twin), per hop E and W, per lag A, per request the flux's statistics
+       ZB_PT_REQ, ZB_PT_D, ZB_PT_STAT, ZB_PT_FRAME,           // pitch: a call's request records (with a host twin), per frame and lag d, per frame the diff kernel's statistics and the frame records
+       ZB_LD_REQ,                                             // loudness: a call's request records (with a host twin)
+       ZB_COUNT };
+
+// a call's results in host memory mapped into the device: the kernels write them in place and nothing is copied back
+template <typename T> struct ZlMapped {
+    T *h = nullptr, *d = nullptr; size_t cap = 0;
+    hipError_t grow(size_t need) { return grow_mapped(&h, &d, &cap, need); }
+    void release() { if (h) (void)hipHostFree(h); h = d = nullptr; cap = 0; }
+};
+
+// Stage times of a call (zlhip_set_profiling): events 0 .. N-1 recorded between the call's launches.  `on` is set by every call from the
+// engine's switch; while it is off nothing is created, recorded or read, and the times stay those of the last profiled call.  An event
+// is created by the first mark that needs it.
+template <int N> struct ZlStageTimer {
+    hipEvent_t ev[N] = {}; bool on = false;
+    hipError_t mark(int i, hipStream_t s)
+    {
+        if (!on) return hipSuccess;
+        if (!ev[i]) { const hipError_t r = hipEventCreate(&ev[i]); if (r != hipSuccess) return r; }
+        return hipEventRecord(ev[i], s);
+    }
+    hipError_t elapsed(int a, int b, float *ms) { return on ? hipEventElapsedTime(ms, ev[a], ev[b]) : hipSuccess; }   // after the call's wait
+    void release() { for (hipEvent_t &x : ev) if (x) { (void)hipEventDestroy(x); x = nullptr; } }
+};
+#pragma GCC visibility pop
+
+struct zlhip_engine {
+    zlhip_config cfg{};
+    int V = 0;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    char devname[256] = {0};
+
+    // HBM
+    float *arena = nullptr;
+    // the arena's allocator (zl_arena.h): the free extents of the first arena and of the further segments, allocated when a source does
+    // not fit any more (clips are loaded freely; 288 GB of HBM).  A source in a segment is addressed like any other, by its float offset
+    // from `arena` modulo 2^64, which the kernels' 64-bit address arithmetic wraps back.  A segment's handle is its device pointer.
+    ZlArena arenaAlloc;
+    // per sound slot, next to hc.sounds (what the slot plays) and hc.soundUsed: the original upload -- every re-render
+    // (zlhip_sound_rerender) starts from it, as tracktion renders from the clip's source file -- and the render it plays instead while it has one
+    struct SoundSlot {
+        ZlSound orig{0, 0, 0, 0.0}; size_t floats = 0;   // the original upload, the floats it holds in the arena
+        size_t renderFloats = 0;         // floats of the slot's rendered extent, 0 = it plays its original
+        std::vector<int32_t> renderOffsets;   // the seek offsets of the slot's last render (zlhip_debug_rerender_offsets)
+    };
+    std::vector<SoundSlot> soundSlots;
+    GrowBuf scratch[ZB_COUNT];           // a call's records and staging (grow_buf)
+    // the clip services' state (zl_clip_calls.cpp); each `timer` with the times of the last call made with profiling on (zlhip_debug_*_timings)
+    struct Rerender { ZlStageTimer<3> timer; float seekMs = 0.0f, synthMs = 0.0f; } st;     // marks: before the seek, between the launches, after
+    struct Overview { ZlStageTimer<2> timer; float ms = 0.0f; } ov;                         // marks: around the call's launches
+    // transients (zlhip_sound_onsets; zl_onset.h)
+    struct Onset {
+        ZlMapped<int32_t> counts; ZlMapped<ZlOnOnset> out;          // a call's counts and onsets: the pick kernel writes what it found and nothing else crosses
+        std::vector<std::pair<int32_t, int32_t>> last;              // per request of the last call: its first hop, its hops (zlhip_debug_onset_hops)
+        ZlStageTimer<3> timer; float energyMs = 0.0f, restMs = 0.0f;
+    } on;
+    // tempo (zlhip_sound_tempo; zl_tempo.h)
+    struct Tempo {
+        ZlMapped<ZlTpResult> out;                                   // a call's integer records
+        struct Last { int32_t hop_base, hops, acf_base, first_lag, nlags; };
+        std::vector<Last> last;                                     // per request of the last call (zlhip_debug_tempo_acf)
+        ZlStageTimer<5> timer; float energyMs = 0.0f, acfMs = 0.0f, restMs = 0.0f;
+    } tp;
+    // pitch (zlhip_sound_pitch; zl_pitch.h)
+    struct Pitch {
+        ZlMapped<ZlPtResult> out;                                   // a call's integer records
+        struct Last { int64_t d_base; int32_t frame_base, frames, nd; };
+        std::vector<Last> last;                                     // per request of the last call (zlhip_debug_pitch_frames / _diff)
+        ZlStageTimer<3> timer; float diffMs = 0.0f, restMs = 0.0f;
+    } pt;
+    // loudness (zlhip_sound_loudness; zl_loudness.h)
+    struct Loudness {
+        ZlMapped<ZlLdSub> out;                                      // a call's sub-block records
+        struct Last { int32_t item_base, items; };
+        std::vector<Last> last;                                     // per request of the last call (zlhip_debug_loudness_subs)
+        ZlStageTimer<2> timer; float kernelMs = 0.0f;
+    } ld;
+    // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h)
+    struct Pcm {
+        std::vector<hipEvent_t> ev;                                 // profiling: before every pass's copies and every decode launch, behind the last
+        float copyMs = 0.0f, decodeMs = 0.0f;
+    } pcm;
+    // clips converted to another rate (zlhip_sound_convert_rate; zl_resample.h): the filter tables on the device, one per (L, M) ever asked for
+    struct Resample {
+        struct Table { int32_t L = 0, M = 0; float *d = nullptr; size_t floats = 0; std::vector<float> pending; };   // pending: the host copy, until the call that made the table has waited
+        std::vector<Table> tables;
+        ZlStageTimer<2> timer; float ms = 0.0f;                     // marks: around the call's launches
+    } rs;
+    ZlSound *dSounds = nullptr; ZlClip *dClips = nullptr;
+    ZlVoiceState *dVoices = nullptr;
+    // K1 -> K2 records, double buffered so that planning window i+1 overlaps rendering window i
+    struct PlanSet {
+        ZlVoiceConst *vconst = nullptr; ZlRunList *runs = nullptr; ZlTSeg *tsegs = nullptr;
+        ZlPlanHdr *hdr = nullptr; ZlPlanSeg0 *seg0 = nullptr; ZlPlanSeg1 *seg1 = nullptr;
+        double *ctlP = nullptr; float *ctlEnv = nullptr;  // the window's pool of per-frame control slots (zl_plan.h, zl_ctl_alloc)
+        unsigned long long *ctlNext = nullptr;            // its bump counter, never reset: a window's slots count from ctlBase
+        unsigned long long ctlBase = 0;                   // host side: past every value the counter can have reached
+        ZlSimConst *simConst = nullptr;
+        float *partials = nullptr;
+        int32_t *order = nullptr; size_t orderInts = 0;  // K2's phase order of the window's blocks (K1o): [z-slots][K] and the run summary behind it (zl_order_ints), allocated on first use
+        hipEvent_t planned = nullptr, rendered = nullptr, k1done = nullptr;
+        hipEvent_t renderedEv = nullptr; // the event that marks the end of the last rendering from this set (rendered, or a profiling event)
+        bool used = false;               // `rendered` has been recorded at least once
+    } ps[2];
+    int windowBlocks = 0;                // plan_window_blocks when given (a fixed number of blocks per plan window)
+    size_t windowFrames = 0;             // else a window is this many frames: 2048 blocks of 256 frames, more blocks when they are shorter
+    int windowCap = 0;                   // blocks the K1 -> K2 record arrays hold
+    size_t ctlPoolFrames = 0;            // frames of per-frame control a record set's pool holds (slots = this / nframes)
+    int ctlSlotsOverride = -1;           // ZL_CTL_POOL_SLOTS (tests of the exhausted pool)
+    hipStream_t planStream = nullptr;    // K0 + K1 (sequential per voice)
+    hipStream_t lastRenderStream = nullptr;                          // the stream the previous call rendered on
+    hipStream_t lastPlanStream = nullptr; hipEvent_t evPlanTail = nullptr;   // where the previous call planned (voice-state order)
+    hipEvent_t lastPlanEvent = nullptr;  // marks the end of that planning: evPlanTail, or the call's `done` event when it planned on its render stream
+    hipStream_t asmStream = nullptr;     // K1c of window w runs here, next to K1 of window w+1
+    std::vector<std::pair<int, int>> wins;
+    // Per-call resources, double buffered so that consecutive zlhip_render_batch calls pipeline: the host prepares
+    // (and the planning stream plans) call i+1 while call i still renders; a slot is reused by call i+2.
+    struct CallSlot {
+        ZlClock *hClocks = nullptr, *hClocksDev = nullptr;   // the call's block clocks, in host memory mapped into the device: K1 reads them in place
+        ZlPassParams *hPass = nullptr, *dPass = nullptr;   // fused fan-out parameters of the call
+        // the call's voice operations, in host memory mapped into the device: K0 reads them in place (no copy command)
+        ZlVoiceOp *hOps = nullptr, *hOpsDev = nullptr; ZlOpRange *hRanges = nullptr, *hRangesDev = nullptr;
+        size_t opsCap = 0, rangesCap = 0;
+        ZlClipEdit *hEdits = nullptr, *hEditsDev = nullptr; size_t editsCap = 0;   // the call's clip-parameter edits, same arrangement
+        ZlReport *hReports = nullptr, *dReports = nullptr;
+        float *hGain = nullptr;
+        ZlBatchStats *hStats = nullptr, *dStats = nullptr;
+        ZlReport *hReportsDev = nullptr; float *hGainDev = nullptr; ZlBatchStats *hStatsDev = nullptr;   // device views of the host buffers
+        hipEvent_t evBegin = nullptr, evEnd = nullptr, done = nullptr;
+        // `done` alternates between two events from one use of the slot to the next, so that the NEXT call (the other slot) can take this
+        // call's completion as the begin of its own profile -- one event-record packet fewer between two calls' render kernels -- and
+        // still find it intact when it is harvested, two calls later
+        hipEvent_t doneEv[2] = {nullptr, nullptr}; unsigned doneGen = 0;
+        hipEvent_t beginEv = nullptr;    // what this call's profile counts from: its own evBegin, or the previous call's `done`
+        std::vector<hipEvent_t> evK2;    // [2 * max windows] start/end of every K2 launch (profiling)
+        int windows = 0;
+        bool inflight = false, profiled = false;
+        bool fusedDone = false;          // the call's last K2 launch published the reports and carries `done` as its stop event (no report kernel)
+    } slots[2];
+    unsigned callIndex = 0, setPhase = 0;
+    CallSlot *latest = nullptr;          // slot of the most recent call
+    zlhip_timings totals{}; int totalCalls = 0;   // sums over harvested calls (zlhip_profile_totals)
+    float *dGain = nullptr;
+    ZlPassCache *dPassCache = nullptr;   // per voice: the recorded pass of its loop (zl_plan.h, replay_cached_pass)
+    float *dBus = nullptr;
+    ZlBlockLevels *dLevels = nullptr; ZlLevelsState *dLevelState = nullptr;
+    int32_t *dTrace = nullptr; ZlPassParams *dPass = nullptr;
+    size_t traceInts = 0;
+    int maxGroups = 1;
+
+    // pinned host staging
+    float *hBus = nullptr, *hBusDev = nullptr;   // one real-time block, host memory mapped into the device
+    // one real-time block's JackPassthrough fan-out [B][6][max_frames] (zlhip_render_fanout), written by the kernels like hBus; the
+    // parameter table the resident kernel reads ([B], mapped host memory) and its version (never 0; moved when an entry changes)
+    float *hFan = nullptr, *hFanDev = nullptr;
+    ZlPassParams *hPassRt = nullptr, *hPassRtDev = nullptr;
+    uint32_t *hNonFinite = nullptr, *hNonFiniteDev = nullptr;   // mapped host word: zl_k_interleave sets it when an uploaded sample is NaN or infinite
+    uint32_t passSeq = 1;
+    // zero-copy delivery of a real-time cycle: when the caller's out_left / out_right (/ fan_out) are page-locked and mapped (zlhip_host_alloc,
+    // hipHostMalloc, hipHostRegister) the kernels write them directly -- no copy on the host behind the cycle (24 KB + 72 KB for 12 buses:
+    // 1.6 + 5 us of reading lines the device has just written).  The device views of the last buffers seen are kept.
+    struct OutViews { const void *hL = nullptr, *hR = nullptr, *hF = nullptr; float *dL = nullptr, *dR = nullptr, *dF = nullptr; bool ok = false; } outViews;
+    bool directOut = true;               // ZL_RT_DIRECT_OUT=0: always through the staging rows
+    ZlLevelsState *hLevelState = nullptr;
+
+    // host mirrors
+    ZlHostControl hc;                    // voices / sounds / clip parameters / pending ops (zl_host.h)
+    std::vector<ZlOpRange> ranges;
+
+    // last batch
+    int lastK = 0, lastN = 0, lastWindows = 0; float *lastBus = nullptr; bool outstanding = false; bool reportsFresh = false;
+    bool trace = false; int traceK = 0, traceN = 0;
+    int forceSlow = 0;
+    size_t deviceBytes = 0;              // HBM the engine allocated at creation (arena included)
+    int staged = 0;                      // K2 variant with LDS-staged source windows (zl_kernels.hip), chosen per mode at creation
+
+    // resident real-time kernel (zl_k_rt_loop): the mailbox in mapped host memory, its stream, what it was launched for
+    struct Rt {
+        bool enabled = false, running = false; int wide = -1;    // wide: 1 always, 0 never, -1 only with one voice per workgroup
+        ZlRtShared *h = nullptr, *d = nullptr;
+        ZlRtDev *dev = nullptr;                            // the kernel's own hand-off words in HBM
+        ZlOpRange *devRanges = nullptr;                    // wide buses: workgroup 0's copy of a block's operation ranges
+        int capacity[2] = {-1, -1};                        // workgroups of the kernel the device holds at once (narrow, wide); -1 = not asked yet
+        int vw = 0;                                        // wide buses: voices per resident workgroup (a divisor of voices_per_bus)
+        double share = 0.0;                                // of the device's resident-workgroup capacity this engine's kernel takes (rt_eligible)
+        std::atomic<bool> inCycle{false};                  // a cycle is being rendered through the resident kernel (its share stays taken even if the kernel has just left)
+        int maxFrames = 4096;                              // longest period the resident kernel takes (ZL_RT_MAX_FRAMES)
+        hipStream_t stream = nullptr;
+        int nframes = 0;
+        unsigned long long seq = 0;
+        unsigned long long starts = 0, cycles = 0;        // launches of the resident kernel, cycles it rendered (zlhip_rt_stats)
+        unsigned long long idleTicks = 20000000ull;       // 200 ms of the 100 MHz counter without a block: the kernel leaves
+        bool stampsOn = false; double stampSum[6] = {0, 0, 0, 0, 0, 0}; unsigned long long stampN = 0;   // ZL_RT_STAMPS=1: stage times (us)
+        // where the last real-time cycle spent its time, seen from the host (zlhip_rt_last_cycle): a worst case has to be attributable
+        bool traceOn = false; double slowUs = 0.0;         // ZL_RT_TRACE=1; ZL_RT_TRACE_SLOW_US=<n>: cycles longer than that are reported on stderr
+        zlhip_rt_cycle_trace last{};
+    } rt;
+
+    // offline bounce (zlhip_bounce): the device bus buffers of two chunks rendered into in turn, their 16-bit versions, the copy stream.
+    // A chunk is ONE zlhip_render_batch call; every plan window of it is delivered as soon as its render kernel has finished
+    // (the sink below, called from the window loop), while the following windows render.
+    struct Bounce {
+        static constexpr int NBUF = 2, NEV = 16;
+        float *bus[NBUF] = {nullptr, nullptr}; int16_t *pcm[NBUF] = {nullptr, nullptr};
+        size_t busFloats = 0, pcmFrames = 0;
+        hipStream_t copyStream = nullptr;
+        hipEvent_t copied[NBUF] = {nullptr, nullptr};      // the last delivery out of a chunk buffer
+        hipEvent_t winEv[NEV] = {};                        // "window rendered (and converted)": waited for by the copy stream
+        unsigned winNext = 0;
+        bool active = false;                 // inside zlhip_bounce: every chunk plans on the planning stream
+        struct Sink {
+            bool on = false, pcm = false;
+            char *hostBase = nullptr;        // the chunk's first frame in the caller's buffer
+            void *hostDev = nullptr;         // direct delivery: the device view of hostBase (page-locked memory only), else nullptr
+            size_t totalFrames = 0;          // frames per row of the caller's buffer (the whole bounce)
+            int16_t *pcmDev = nullptr;       // the chunk's 16-bit staging buffer [B][chunk frames][2]
+        } sink;
+    } bnc;
+
+    bool failed = false;                 // the resident kernel stopped answering in the middle of a cycle: the voice table is undefined (zlhip_render)
+
+    // profiling
+    bool profiling = false; hipEvent_t evJoin = nullptr;
+    hipEvent_t joins[2] = {nullptr, nullptr};   // events on caller streams the host still has to wait for (engine_wait)
+    zlhip_timings timings{};
+};
+
+#define ZL_HIP(e, call)                                                                        \
+    do {                                                                                       \
+        hipError_t st_ = (call);                                                               \
+        if (st_ != hipSuccess) {                                                               \
+            (e)->err = std::string(#call) + ": " + hipGetErrorString(st_);                     \
+            return ZLHIP_ERR_HIP;                                                              \
+        }                                                                                      \
+    } while (0)
+
+#define ZL_KERNEL(e, call)                                                                     \
+    do {                                                                                       \
+        int st_ = (call);                                                                      \
+        if (st_ != 0) {                                                                        \
+            (e)->err = std::string(#call) + ": " + hipGetErrorString((hipError_t)st_);         \
+            return ZLHIP_ERR_HIP;                                                              \
+        }                                                                                      \
+    } while (0)
+
+#pragma GCC visibility push(hidden)
+// hipFree, hipHostFree and hipDeviceSynchronize wait for every resident kernel on the device: while one of these lives, the other
+// engines' kernels have stepped aside (zl_engine.cpp, "resident kernels and device-synchronising HIP calls")
+struct ZlQuiesce {
+    explicit ZlQuiesce(const zlhip_engine *self);
+    ~ZlQuiesce();
+    ZlQuiesce(const ZlQuiesce &) = delete;
+    ZlQuiesce &operator=(const ZlQuiesce &) = delete;
+};
+
+int fail(zlhip_engine *e, int code, const char *msg);
+int engine_wait(zlhip_engine *e);
+int rt_stop(zlhip_engine *e);
+int call_begin(zlhip_engine *e, bool stop);
+int grow_buf(zlhip_engine *e, GrowBuf &b, size_t need, size_t elem, size_t new_cap, bool twin, const char *what);
+int alloc_extent(zlhip_engine *e, size_t floats, size_t *out_off);
+void free_extent(zlhip_engine *e, size_t off, size_t n);
+float *arena_ptr(const zlhip_engine *e, uint64_t off);
+void adopt_sound(zlhip_engine *e, int id, const ZlSound &s, size_t floats);
+#pragma GCC visibility pop

@@ -947,6 +947,21 @@ int libzl_hotpath_clip_waveform(ClipAudioSource *c, float start_seconds, float e
     return zlhip_sound_overview(G.engine, c->engineClip, (int32_t)a, (int32_t)(b - a), columns, out);
 }
 
+// The clip's region -- its start and its start + length -- in frames of the data it plays now, cast as SamplerSynthSound::startPosition /
+// stopPosition do (SamplerSynthSound.cpp:96-104) and cut to the data.  What the transients, the tempo, the pitch and the loudness analyse.
+static int clip_region(ClipAudioSource *c, zlhip_sound_info *info, int64_t *start, int64_t *stop)      // call with G.mu held
+{
+    { const int rc = zlhip_sound_info_get(G.engine, c->engineClip, info); if (rc != ZLHIP_OK) return rc; }
+    float startSec, lengthSec;
+    { std::lock_guard<std::mutex> sl(c->setMu); startSec = c->startPositionInSeconds; lengthSec = c->lengthInSeconds; }
+    auto frame = [&](float seconds) -> int64_t {
+        const double f = (double)seconds * info->sample_rate;
+        return !(f > 0.0) ? 0 : (f >= (double)info->length ? (int64_t)info->length : (int64_t)f);
+    };
+    *start = frame(startSec); *stop = frame(startSec + lengthSec);
+    return *stop <= *start ? ZLHIP_ERR_INVALID : ZLHIP_OK;
+}
+
 // A sampler plays a loop from the keyboard slice by slice (sliceForMidiNote, getStartPosition(slice) .. getStopPosition(slice)), and the
 // only table setSlices can make is an even division, which cuts through the hits.  Here: the clip's transients, found on the device in
 // the data it plays now (zlhip_sound_onsets, defaults), become its slice table, as setSlicePositions would set it
@@ -956,17 +971,8 @@ int libzl_hotpath_clip_slice_at_transients(ClipAudioSource *c, int max_slices)
     if (!c || max_slices < 1) return ZLHIP_ERR_INVALID;
     std::lock_guard<std::mutex> lk(G.mu);
     if (!G.engine || c->engineClip < 0) return ZLHIP_ERR_STATE;
-    zlhip_sound_info info;
-    { const int rc = zlhip_sound_info_get(G.engine, c->engineClip, &info); if (rc != ZLHIP_OK) return rc; }
-    float startSec, lengthSec;
-    { std::lock_guard<std::mutex> sl(c->setMu); startSec = c->startPositionInSeconds; lengthSec = c->lengthInSeconds; }
-    // the region in frames, cast as SamplerSynthSound::startPosition / stopPosition do (SamplerSynthSound.cpp:96-104), cut to the data
-    auto frame = [&](float seconds) -> int64_t {
-        const double f = (double)seconds * info.sample_rate;
-        return !(f > 0.0) ? 0 : (f >= (double)info.length ? (int64_t)info.length : (int64_t)f);
-    };
-    const int64_t start = frame(startSec), stop = frame(startSec + lengthSec);
-    if (stop <= start) return ZLHIP_ERR_INVALID;
+    zlhip_sound_info info; int64_t start, stop;
+    { const int rc = clip_region(c, &info, &start, &stop); if (rc != ZLHIP_OK) return rc; }
     const int cap = std::min(max_slices, (int)ZLHIP_MAX_SLICES);
     // with more transients than slices the strongest stay (the select rule of the request)
     zlhip_onset_request q = { c->engineClip, (int32_t)start, (int32_t)(stop - start), 0, 0, 0, 0, cap };
@@ -991,17 +997,8 @@ int libzl_hotpath_clip_slice_at_transients(ClipAudioSource *c, int max_slices)
 static int clip_tempo(ClipAudioSource *c, float bpm_min, float bpm_max, zlhip_tempo *t)      // call with G.mu held
 {
     if (!G.engine || c->engineClip < 0) return ZLHIP_ERR_STATE;
-    zlhip_sound_info info;
-    { const int rc = zlhip_sound_info_get(G.engine, c->engineClip, &info); if (rc != ZLHIP_OK) return rc; }
-    float startSec, lengthSec;
-    { std::lock_guard<std::mutex> sl(c->setMu); startSec = c->startPositionInSeconds; lengthSec = c->lengthInSeconds; }
-    // the region in frames, cast as SamplerSynthSound::startPosition / stopPosition do (SamplerSynthSound.cpp:96-104), cut to the data
-    auto frame = [&](float seconds) -> int64_t {
-        const double f = (double)seconds * info.sample_rate;
-        return !(f > 0.0) ? 0 : (f >= (double)info.length ? (int64_t)info.length : (int64_t)f);
-    };
-    const int64_t start = frame(startSec), stop = frame(startSec + lengthSec);
-    if (stop <= start) return ZLHIP_ERR_INVALID;
+    zlhip_sound_info info; int64_t start, stop;
+    { const int rc = clip_region(c, &info, &start, &stop); if (rc != ZLHIP_OK) return rc; }
     const zlhip_tempo_request q = { c->engineClip, (int32_t)start, (int32_t)(stop - start), 0, bpm_min, bpm_max };
     return zlhip_sound_tempo(G.engine, &q, t);
 }
@@ -1040,17 +1037,8 @@ int libzl_hotpath_clip_match_tempo(ClipAudioSource *c, float target_bpm, float m
 static int clip_pitch(ClipAudioSource *c, float f_min, float f_max, zlhip_pitch *t)      // call with G.mu held
 {
     if (!G.engine || c->engineClip < 0) return ZLHIP_ERR_STATE;
-    zlhip_sound_info info;
-    { const int rc = zlhip_sound_info_get(G.engine, c->engineClip, &info); if (rc != ZLHIP_OK) return rc; }
-    float startSec, lengthSec;
-    { std::lock_guard<std::mutex> sl(c->setMu); startSec = c->startPositionInSeconds; lengthSec = c->lengthInSeconds; }
-    // the region in frames, cast as for libzl_hotpath_clip_tempo
-    auto frame = [&](float seconds) -> int64_t {
-        const double f = (double)seconds * info.sample_rate;
-        return !(f > 0.0) ? 0 : (f >= (double)info.length ? (int64_t)info.length : (int64_t)f);
-    };
-    const int64_t start = frame(startSec), stop = frame(startSec + lengthSec);
-    if (stop <= start) return ZLHIP_ERR_INVALID;
+    zlhip_sound_info info; int64_t start, stop;
+    { const int rc = clip_region(c, &info, &start, &stop); if (rc != ZLHIP_OK) return rc; }
     const zlhip_pitch_request q = { c->engineClip, (int32_t)start, (int32_t)(stop - start), 0, 0, f_min, f_max, 0, 0 };
     return zlhip_sound_pitch(G.engine, &q, t);
 }
@@ -1088,17 +1076,8 @@ int libzl_hotpath_clip_detect_root_note(ClipAudioSource *c, float min_confidence
 static int clip_loudness_request(ClipAudioSource *c, zlhip_loudness_request *q)      // call with G.mu held
 {
     if (!G.engine || c->engineClip < 0) return ZLHIP_ERR_STATE;
-    zlhip_sound_info info;
-    { const int rc = zlhip_sound_info_get(G.engine, c->engineClip, &info); if (rc != ZLHIP_OK) return rc; }
-    float startSec, lengthSec;
-    { std::lock_guard<std::mutex> sl(c->setMu); startSec = c->startPositionInSeconds; lengthSec = c->lengthInSeconds; }
-    // the region in frames, cast as for libzl_hotpath_clip_pitch
-    auto frame = [&](float seconds) -> int64_t {
-        const double f = (double)seconds * info.sample_rate;
-        return !(f > 0.0) ? 0 : (f >= (double)info.length ? (int64_t)info.length : (int64_t)f);
-    };
-    const int64_t start = frame(startSec), stop = frame(startSec + lengthSec);
-    if (stop <= start) return ZLHIP_ERR_INVALID;
+    zlhip_sound_info info; int64_t start, stop;
+    { const int rc = clip_region(c, &info, &start, &stop); if (rc != ZLHIP_OK) return rc; }
     *q = zlhip_loudness_request{ c->engineClip, (int32_t)start, (int32_t)(stop - start), 0 };
     return ZLHIP_OK;
 }
