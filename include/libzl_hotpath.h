@@ -225,6 +225,26 @@ int  libzl_hotpath_clip_normalize(ClipAudioSource *c, float target_lufs, float c
  * for NULL).  Duplicate clips are ZLHIP_ERR_INVALID.  If the re-render fails every clip and every stored gain is as it was.  Returns
  * the number of clips levelled, or a negative status. */
 int  libzl_hotpath_clips_level(ClipAudioSource **clips, int count, float target_lufs, float ceiling_db, float *gains_out);
+/* extension (build-defined: the reference has no loop finder): the seamless loop points of the data the clip plays now, searched on
+ * the device near its start and its start + length (zlhip_sound_loop), in frames as for
+ * libzl_hotpath_clip_pitch.  search_ms: how far around each point to look (0: 10 ms; at most 2047 frames); window: the frames
+ * compared around each point (0: 256).  *start_frame, *stop_frame: the pair whose surroundings match best; *seam_db, *nominal_db:
+ * 10 log10 of the mismatch against the windows' energy at that pair and at the clip's own points (0 where those are no candidate
+ * pair).  A candidate's window lies inside the data, so a clip whose region is the whole file is searched from window / 2 frames in:
+ * the call is meant for sustain loops inside a sound.  Returns 1, or 0 where no pair was found, or a negative zlhip status (nothing
+ * is written then). */
+int  libzl_hotpath_clip_find_loop(ClipAudioSource *c, float search_ms, int window, int *start_frame, int *stop_frame, double *seam_db, double *nominal_db);
+/* Move the clip's loop to its seamless points: finds them as libzl_hotpath_clip_find_loop (window 256) and, where the seam improves on
+ * the clip's own points by at least min_improvement_db, sets startPositionInSeconds and lengthInSeconds to the float seconds from
+ * which a voice derives exactly those frames (zlhip_loop_seconds), under ClipAudioSource_setStartPosition's lock and through its
+ * publish.  lengthInBeats stays; the slices are fractions of the length and move with it.  Returns 1 if applied; 0 where nothing was
+ * found, the improvement is below the bar or the frames are not representable in float seconds -- the clip is untouched then; or a
+ * negative status. */
+int  libzl_hotpath_clip_snap_loop(ClipAudioSource *c, float search_ms, float min_improvement_db, int *start_frame, int *stop_frame);
+/* A bank: ONE zlhip_sound_loop_batch call for all clips.  A clip that is NULL or not in the engine stays as it is; applied_out[i] (may
+ * be NULL) is 1 where clip i's loop was moved.  Duplicate clips are ZLHIP_ERR_INVALID.  Returns the number of clips moved, or a
+ * negative status (nothing has changed then). */
+int  libzl_hotpath_clips_snap_loops(ClipAudioSource **clips, int count, float search_ms, float min_improvement_db, int *applied_out);
 /* A bank of clips in one engine call: every file is read, their `data` chunks go to the engine as raw PCM in ONE
  * zlhip_sound_upload_pcm_batch call (decoded on the device, one wait for the whole bank).  out[i] is the clip of paths[i], or NULL
  * for a file that cannot be opened or decoded -- it does not fail the others.  Returns the number of clips loaded (or a negative

@@ -41,7 +41,8 @@ extern "C" {
  *    another sample rate on the device, band-limited), zlhip_resample_design, zlhip_sound_info_get, zlhip_debug_sound_extent, zlhip_sound_onsets / _batch (a clip's transients, found on
  *    the device), zlhip_onset_resolve, zlhip_sound_tempo / _batch (a clip's tempo, estimated on the device), zlhip_tempo_resolve,
  *    zlhip_sound_pitch / _batch (a clip's pitch, detected on the device), zlhip_pitch_resolve, zlhip_sound_loudness / _batch (a clip's
- *    loudness, measured on the device), zlhip_loudness_resolve, zlhip_loudness_design. */
+ *    loudness, measured on the device), zlhip_loudness_resolve, zlhip_loudness_design, zlhip_sound_loop / _batch (a clip's seamless
+ *    loop points, found on the device), zlhip_loop_resolve, zlhip_loop_seconds. */
 #define ZLHIP_ABI_VERSION 3
 
 /* status codes */
@@ -390,6 +391,53 @@ int zlhip_sound_loudness_batch(zlhip_engine *e, const zlhip_loudness_request *re
 int zlhip_debug_loudness_subs(zlhip_engine *e, int32_t request, zlhip_loudness_sub *records, int32_t capacity, int32_t *count);
 /* measurement: device time of the kernel of the last call made with profiling on */
 int zlhip_debug_loudness_timings(zlhip_engine *e, float *kernel_ms);
+/* Loop points: where a clip's sustain loop wraps without a click (a build-defined extension, the reference has
+ * no loop finder) -- searched on the device in the sound's CURRENT playback data of `length` frames, near the nominal loop
+ * [start_frame s0, stop_frame e0), in integers behind the 16-bit quantisation, so the result does not depend on any order of evaluation:
+ *   W = window, H = W / 2.  Starts s in [max(s0 - Rs, H), min(s0 + Rs, length - H)], ends e in [max(e0 - Re, H), min(e0 + Re,
+ *   length - H)] (Rs = start_search, Re = stop_search; -1: "this point stays", the nominal point alone): the window [p - H, p + H) of
+ *   a candidate lies inside the data.  A pair is admissible if e - s >= min_length.  A loop over the whole file has its points inside
+ *   H of the data's ends, so its candidates begin H frames in: the service is meant for sustain loops inside a sound, not for beat
+ *   loops that trust the file's edges.
+ *   m[f] = the sum over the channels of clamp(rint(4096 v), +-32767) (NaN -> 0); one shift per request,
+ *   sh = max(0, bitlength(max |m| over the two strips [smin - H, smax + H) and [emin - H, emax + H)) - 10), x = m >> sh (arithmetic).
+ *   cost(s, e) = the sum over j in [-H, H) of (x[s + j] - x[e + j])^2 (uint32); E(p) = the sum of x[p + j]^2 over the window;
+ *   den(s, e) = E(s) + E(e) + 1.  Pair a is better than pair b under the first rule that differs: cost_a den_b < cost_b den_a
+ *   (uint64); the smaller |s - s0| + |e - e0|; the smaller s; the smaller e.
+ *   zlhip_loop: found, start_frame, stop_frame (the best admissible pair), shift, starts, ends (the candidates), pairs (the
+ *   admissible pairs), cost, den, nominal_valid (1 when (s0, e0) is itself an admissible candidate pair), nominal_cost, nominal_den.
+ *   The host derives, in double: seam_db = -120 where cost == 0, else max(-120, 10 log10(cost / den)); nominal_db the same way;
+ *   improvement_db = nominal_db - seam_db, or 0 without a nominal.
+ *   An empty range or no admissible pair is not an error: found = 0 and every other field is 0.
+ *   A field given as 0 takes its default (zlhip_loop_resolve with the sound's sample rate): start_search and stop_search
+ *   min(2047, rint(0.010 rate)), window 256, min_length = window.
+ *   Limits: start_search and stop_search in [-1, 2047]; window a multiple of 16 in [16, 1024]; min_length >= 1;
+ *   0 <= start_frame < stop_frame <= the sound's length; at most 65536 work items (tiles of 64 starts x 64 ends) and 4194304 strip
+ *   frames (ns - 1 + W and ne - 1 + W per request, each rounded up to 8) per call; nreq >= 0: anything else is ZLHIP_ERR_INVALID.
+ *   On any error out is not written; one bad request fails the call.
+ *   A call is three kernel launches whatever its size, behind one copy of the request records; it waits once and 80 bytes per request
+ *   come back.  It runs on the engine's stream behind what is queued there and the resident real-time kernel keeps running.
+ *   Not provided: a crossfade baked into the data; loop points for beat loops at the file's edges. */
+typedef struct zlhip_loop_request { int32_t id, start_frame, stop_frame, start_search, stop_search, window, min_length; } zlhip_loop_request;
+typedef struct zlhip_loop { int32_t found, start_frame, stop_frame, shift, starts, ends, nominal_valid, reserved; uint64_t pairs;
+                            uint32_t cost, den, nominal_cost, nominal_den; double seam_db, nominal_db, improvement_db; } zlhip_loop;
+/* a work item's record: its best admissible pair (none: start = stop = -1, cost = den = 0) and how many admissible pairs it holds */
+typedef struct zlhip_loop_item { int32_t start, stop; uint32_t cost, den; uint64_t pairs; } zlhip_loop_item;
+/* host only: fills the fields given as 0 and checks every limit that does not need the sound; a refused request is left as it was */
+int zlhip_loop_resolve(double sample_rate, zlhip_loop_request *r);
+int zlhip_sound_loop(zlhip_engine *e, const zlhip_loop_request *r, zlhip_loop *out);
+int zlhip_sound_loop_batch(zlhip_engine *e, const zlhip_loop_request *reqs, int32_t nreq, zlhip_loop *out);
+/* host only: the float seconds from which a voice derives exactly these frames -- start = (int)(start_seconds * rate),
+ * stop = (int)((float)(start_seconds + length_seconds) * rate).  ZLHIP_ERR_INVALID where no such floats are found within 8 single
+ * steps around the frames' middles (from about 2^23 frames on some pairs are not representable) */
+int zlhip_loop_seconds(double sample_rate, int64_t start_frame, int64_t stop_frame, float *start_seconds, float *length_seconds);
+/* the item records of request `request` of the last call, start tile by start tile (items: [capacity], may be NULL to ask for *count only) */
+int zlhip_debug_loop_items(zlhip_engine *e, int32_t request, zlhip_loop_item *items, int32_t capacity, int32_t *count);
+/* every candidate pair's cost, [starts][ends], of request `request` of the last call (costs: [capacity], may be NULL to ask for the
+ * counts only).  Kept only where the call had at most 1048576 candidate pairs: ZLHIP_ERR_STATE otherwise */
+int zlhip_debug_loop_costs(zlhip_engine *e, int32_t request, uint32_t *costs, int32_t capacity, int32_t *starts, int32_t *ends);
+/* measurement: device time of the pairs kernel and of the rest of the last call made with profiling on */
+int zlhip_debug_loop_timings(zlhip_engine *e, float *pairs_ms, float *rest_ms);
 /* Clips from raw PCM.  `frames` is host memory, pageable or page-locked: `length` frames of `channels`
  *   interleaved little-endian samples, exactly the bytes of a WAV `data` chunk.  They are copied raw into a device staging buffer and
  *   decoded there into the arena's layout; one decode launch serves each staging pass and the call waits for the device once.
@@ -619,6 +667,8 @@ int  zlhip_group_sound_tempo_batch(zlhip_group *g, const zlhip_tempo_request *re
 int  zlhip_group_sound_pitch_batch(zlhip_group *g, const zlhip_pitch_request *reqs, int32_t nreq, zlhip_pitch *out);
 /* zlhip_sound_loudness_batch: member 0 answers */
 int  zlhip_group_sound_loudness_batch(zlhip_group *g, const zlhip_loudness_request *reqs, int32_t nreq, zlhip_loudness *out);
+/* zlhip_sound_loop_batch: member 0 answers */
+int  zlhip_group_sound_loop_batch(zlhip_group *g, const zlhip_loop_request *reqs, int32_t nreq, zlhip_loop *out);
 /* zlhip_handle_commands_voices over the whole synth (taken, voices optional) */
 int  zlhip_group_handle_commands(zlhip_group *g, const zlhip_clip_command *cmds, int32_t count, uint64_t current_tick, int32_t *taken,
                                  int32_t *voices);

@@ -153,6 +153,22 @@ class LoudnessSub(C.Structure):
     _fields_ = [("sum", C.c_double * 2), ("peak", C.c_float * 2)]
 
 
+class LoopRequest(C.Structure):
+    _fields_ = [("id", C.c_int32), ("start_frame", C.c_int32), ("stop_frame", C.c_int32), ("start_search", C.c_int32), ("stop_search", C.c_int32),
+                ("window", C.c_int32), ("min_length", C.c_int32)]
+
+
+class Loop(C.Structure):
+    _fields_ = [("found", C.c_int32), ("start_frame", C.c_int32), ("stop_frame", C.c_int32), ("shift", C.c_int32), ("starts", C.c_int32),
+                ("ends", C.c_int32), ("nominal_valid", C.c_int32), ("reserved", C.c_int32), ("pairs", C.c_uint64), ("cost", C.c_uint32),
+                ("den", C.c_uint32), ("nominal_cost", C.c_uint32), ("nominal_den", C.c_uint32), ("seam_db", C.c_double), ("nominal_db", C.c_double),
+                ("improvement_db", C.c_double)]
+
+
+class LoopItem(C.Structure):
+    _fields_ = [("start", C.c_int32), ("stop", C.c_int32), ("cost", C.c_uint32), ("den", C.c_uint32), ("pairs", C.c_uint64)]
+
+
 class Tempo(C.Structure):
     _fields_ = [("bpm", C.c_float), ("confidence", C.c_float), ("lag_coarse", C.c_int32), ("lag_fine", C.c_int32), ("doublings", C.c_int32),
                 ("shift", C.c_int32), ("hops", C.c_int32), ("reserved", C.c_int32), ("acf_lo", C.c_uint64), ("acf_mid", C.c_uint64),
@@ -233,6 +249,13 @@ SIGNATURES = {
     "zlhip_sound_loudness_batch": (C.c_int, [_E, C.POINTER(LoudnessRequest), C.c_int32, C.POINTER(Loudness)]),
     "zlhip_debug_loudness_subs": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_debug_loudness_timings": (C.c_int, [_E, C.POINTER(C.c_float)]),
+    "zlhip_loop_resolve": (C.c_int, [C.c_double, C.POINTER(LoopRequest)]),
+    "zlhip_loop_seconds": (C.c_int, [C.c_double, C.c_int64, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "zlhip_sound_loop": (C.c_int, [_E, C.POINTER(LoopRequest), C.POINTER(Loop)]),
+    "zlhip_sound_loop_batch": (C.c_int, [_E, C.POINTER(LoopRequest), C.c_int32, C.POINTER(Loop)]),
+    "zlhip_debug_loop_items": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zlhip_debug_loop_costs": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "zlhip_debug_loop_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "zlhip_sound_upload_pcm": (C.c_int, [_E, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_int32)]),
     "zlhip_sound_upload_pcm_batch": (C.c_int, [_E, C.POINTER(PcmSource), C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_debug_upload_pcm_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -299,6 +322,7 @@ SIGNATURES = {
     "zlhip_group_sound_onsets_batch": (C.c_int, [_E, C.POINTER(OnsetRequest), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "zlhip_group_sound_tempo_batch": (C.c_int, [_E, C.POINTER(TempoRequest), C.c_int32, C.POINTER(Tempo)]),
     "zlhip_group_sound_pitch_batch": (C.c_int, [_E, C.POINTER(PitchRequest), C.c_int32, C.POINTER(Pitch)]),
+    "zlhip_group_sound_loop_batch": (C.c_int, [_E, C.POINTER(LoopRequest), C.c_int32, C.POINTER(Loop)]),
     "zlhip_group_sound_loudness_batch": (C.c_int, [_E, C.POINTER(LoudnessRequest), C.c_int32, C.POINTER(Loudness)]),
     "zlhip_group_handle_commands": (C.c_int, [_E, C.POINTER(ClipCommand), C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "zlhip_group_start_voice": (C.c_int, [_E, C.c_int32, C.c_int32, C.POINTER(ClipCommand), C.c_uint64]),

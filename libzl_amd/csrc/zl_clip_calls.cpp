@@ -1,5 +1,5 @@
-// zl_clip_calls.cpp -- the clip services of include/zlhip.h: loading from raw PCM, re-render, rate conversion, and the five analyses
-// (waveform overviews, transients, tempo, pitch, loudness).  Every one is a call on a loaded clip that validates everything before its
+// zl_clip_calls.cpp -- the clip services of include/zlhip.h: loading from raw PCM, re-render, rate conversion, and the six analyses
+// (waveform overviews, transients, tempo, pitch, loudness, loop points).  Every one is a call on a loaded clip that validates everything before its
 // first HIP call, reserves buffers that only grow, queues its launches on the engine's stream and waits once.  What they share is
 // written once, below; the engine itself -- arena, sound slots, rendering, the resident kernel -- is zl_engine.cpp.
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 
 #include "zl_engine_impl.h"
 #include "zl_decode.h"
+#include "zl_loop.h"
 #include "zl_loudness.h"
 #include "zl_onset.h"
 #include "zl_overview.h"
@@ -1008,6 +1009,144 @@ int zlhip_debug_loudness_timings(zlhip_engine *e, float *kernel_ms)
 {
     if (!e) return ZLHIP_ERR_INVALID;
     if (kernel_ms) *kernel_ms = e->ld.kernelMs;
+    return ZLHIP_OK;
+}
+
+// ---- loop finder (zl_loop.h, zl_loop.hip) ----------------------------------------------------------------------------------
+// Where a clip's sustain loop wraps without a click.  The prep kernel reads the two strips around the nominal points and leaves them
+// as int16 with E per candidate; the pairs kernel costs every pair, tile by tile; the pick reduces the tiles and writes the integer
+// record into host memory mapped into the device; the three dB values are derived here (zl_lp_finish).  Synchronisation and buffers
+// as for the overviews.
+
+int zlhip_loop_resolve(double sample_rate, zlhip_loop_request *r)
+{
+    if (!r || r->start_frame < 0 || r->stop_frame <= r->start_frame) return ZLHIP_ERR_INVALID;
+    zlhip_loop_request q = *r;
+    if (zl_lp_resolve(sample_rate, &q.start_search, &q.stop_search, &q.window, &q.min_length) != 0) return ZLHIP_ERR_INVALID;
+    *r = q;
+    return ZLHIP_OK;
+}
+
+int zlhip_loop_seconds(double sample_rate, int64_t start_frame, int64_t stop_frame, float *start_seconds, float *length_seconds)
+{
+    if (!start_seconds || !length_seconds) return ZLHIP_ERR_INVALID;
+    float a, l;
+    if (zl_lp_seconds(sample_rate, start_frame, stop_frame, &a, &l) != 0) return ZLHIP_ERR_INVALID;
+    *start_seconds = a; *length_seconds = l;
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_loop_batch(zlhip_engine *e, const zlhip_loop_request *reqs, int32_t nreq, zlhip_loop *out)
+{
+    static_assert(sizeof(zlhip_loop) == sizeof(ZlLpResult), "the device writes zlhip_loop's layout");
+    static_assert(sizeof(zlhip_loop_item) == sizeof(ZlLpItem), "the device writes zlhip_loop_item's layout");
+    if (!e || nreq < 0 || (nreq > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
+    if (nreq == 0) return ZLHIP_OK;
+    // validate and resolve everything before anything is written and before the first HIP call
+    std::vector<ZlLpRequest> geo((size_t)nreq);
+    int64_t items = 0, strip = 0, cands = 0, cpairs = 0;
+    for (int32_t i = 0; i < nreq; ++i) {
+        zlhip_loop_request q = reqs[i];
+        { const int rc = check_sound(e, "sound_loop", q.id); if (rc != ZLHIP_OK) return rc; }
+        const ZlSound &s = e->hc.sounds[q.id];
+        if (zlhip_loop_resolve(s.sample_rate, &q) != ZLHIP_OK) return fail_in(e, ZLHIP_ERR_INVALID, "sound_loop", kOutsideLimits);
+        if (q.stop_frame > s.length) return fail_in(e, ZLHIP_ERR_INVALID, "sound_loop", "the nominal loop does not lie inside the sound's playback data");
+        ZlLpRequest &R = geo[(size_t)i];
+        std::memset(&R, 0, sizeof R);
+        R.s0 = q.start_frame; R.e0 = q.stop_frame; R.window = q.window; R.min_length = q.min_length; R.channels = s.channels;
+        zl_lp_range(q.start_frame, q.start_search, q.window >> 1, s.length, &R.smin, &R.ns);
+        zl_lp_range(q.stop_frame, q.stop_search, q.window >> 1, s.length, &R.emin, &R.ne);
+        if (R.ns == 0 || R.ne == 0) { R.ns = 0; R.ne = 0; }       // an empty range: no candidates at all
+        R.cost_base = cpairs; R.item_base = (int32_t)items;
+        R.xs_base = (int32_t)strip; R.xe_base = R.xs_base + zl_lp_strip_room(R.ns, R.window);
+        R.es_base = (int32_t)cands; R.ee_base = R.es_base + R.ns;
+        items += zl_lp_items(R); strip += zl_lp_strip_room(R.ns, R.window) + zl_lp_strip_room(R.ne, R.window);
+        cands += R.ns + R.ne; cpairs += (int64_t)R.ns * R.ne;
+        if (items > ZL_LP_MAX_CALL_ITEMS) return fail(e, ZLHIP_ERR_INVALID, "sound_loop_batch: more than 65536 work items in one call");
+        if (strip > ZL_LP_MAX_CALL_STRIP) return fail(e, ZLHIP_ERR_INVALID, "sound_loop_batch: more than 4194304 strip frames in one call");
+    }
+    { const int rc = call_begin(e, false); if (rc != ZLHIP_OK) return rc; }
+    zlhip_engine::Loop &t = e->lp;
+    const char *what = "sound_loop: no memory for the call's buffers";
+    const bool keep = cpairs <= ZL_LP_MAX_COST_PAIRS;
+    const size_t n = (size_t)nreq, ni = (size_t)items, nx = (size_t)strip, nc = (size_t)cands, np = keep ? (size_t)cpairs : 0;
+    const int rsv = reserve(e, true, { { ZB_LP_REQ, n, sizeof(ZlLpRequest), std::max<size_t>(n * 2, 64), true, what },
+                                      { ZB_LP_X, nx, sizeof(int16_t), std::min<size_t>(std::max<size_t>(nx * 2, 65536), ZL_LP_MAX_CALL_STRIP), false, what },
+                                      { ZB_LP_E, nc, sizeof(uint32_t), std::max<size_t>(nc * 2, 8192), false, what },
+                                      { ZB_LP_SHIFT, n, sizeof(int32_t), std::max<size_t>(n * 2, 64), false, what },
+                                      { ZB_LP_ITEM, ni, sizeof(ZlLpItem), std::min<size_t>(std::max<size_t>(ni * 2, 1024), ZL_LP_MAX_CALL_ITEMS), false, what },
+                                      { ZB_LP_COST, np, sizeof(uint32_t), np > 0 ? (size_t)ZL_LP_MAX_COST_PAIRS : 0, false, what } },
+                           { mapped_need(t.out, std::max<size_t>(n, 32)) });
+    if (rsv != ZLHIP_OK) return rsv;
+    ZlLpRequest *const hReq = (ZlLpRequest *)e->scratch[ZB_LP_REQ].h, *const dReq = (ZlLpRequest *)e->scratch[ZB_LP_REQ].d;
+    int16_t *const dX = (int16_t *)e->scratch[ZB_LP_X].d; uint32_t *const dE = (uint32_t *)e->scratch[ZB_LP_E].d;
+    int32_t *const dShift = (int32_t *)e->scratch[ZB_LP_SHIFT].d; ZlLpItem *const dItem = (ZlLpItem *)e->scratch[ZB_LP_ITEM].d;
+    uint32_t *const dCost = keep && np > 0 ? (uint32_t *)e->scratch[ZB_LP_COST].d : nullptr;
+    t.last.clear();
+    t.costs = keep;
+    for (int32_t i = 0; i < nreq; ++i) {
+        ZlLpRequest &R = hReq[i];
+        R = geo[(size_t)i];
+        R.src = (uint64_t)(uintptr_t)arena_ptr(e, e->hc.sounds[reqs[i].id].offset);
+        t.last.push_back({R.cost_base, R.item_base, zl_lp_items(R), R.ns, R.ne});
+    }
+    t.timer.on = e->profiling;
+    ZL_HIP(e, hipMemcpyAsync(dReq, hReq, (size_t)nreq * sizeof(ZlLpRequest), hipMemcpyHostToDevice, e->stream));
+    ZL_HIP(e, t.timer.mark(0, e->stream));
+    ZL_KERNEL(e, zl_launch_loop_prep(dReq, nreq, dX, dE, dShift, e->stream));
+    ZL_HIP(e, t.timer.mark(1, e->stream));
+    ZL_KERNEL(e, zl_launch_loop_pairs(dReq, nreq, items, dX, dE, dItem, dCost, e->stream));
+    ZL_HIP(e, t.timer.mark(2, e->stream));
+    ZL_KERNEL(e, zl_launch_loop_pick(dReq, nreq, dX, dE, dShift, dItem, t.out.d, e->stream));
+    ZL_HIP(e, t.timer.mark(3, e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    float prepMs = 0.0f, pickMs = 0.0f;
+    ZL_HIP(e, t.timer.elapsed(0, 1, &prepMs)); ZL_HIP(e, t.timer.elapsed(1, 2, &t.pairsMs)); ZL_HIP(e, t.timer.elapsed(2, 3, &pickMs));
+    if (t.timer.on) t.restMs = prepMs + pickMs;
+    for (int32_t i = 0; i < nreq; ++i) {
+        ZlLpResult r = t.out.h[i];
+        zl_lp_finish(&r);
+        std::memcpy(&out[i], &r, sizeof(r));
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_loop(zlhip_engine *e, const zlhip_loop_request *r, zlhip_loop *out) { return zlhip_sound_loop_batch(e, r, 1, out); }
+
+int zlhip_debug_loop_items(zlhip_engine *e, int32_t request, zlhip_loop_item *items, int32_t capacity, int32_t *count)
+{
+    if (!e || request < 0 || (size_t)request >= e->lp.last.size()) return ZLHIP_ERR_INVALID;
+    const zlhip_engine::Loop::Last &l = e->lp.last[(size_t)request];
+    if (count) *count = l.items;
+    if (!items) return ZLHIP_OK;
+    if (capacity < l.items) return fail(e, ZLHIP_ERR_CAPACITY, "debug_loop_items: capacity below the request's items");
+    if (l.items == 0) return ZLHIP_OK;
+    ZL_HIP(e, hipSetDevice(e->device));
+    ZL_HIP(e, hipMemcpyAsync(items, (const ZlLpItem *)e->scratch[ZB_LP_ITEM].d + l.item_base, (size_t)l.items * sizeof(ZlLpItem), hipMemcpyDeviceToHost, e->stream));
+    return engine_wait(e);
+}
+
+int zlhip_debug_loop_costs(zlhip_engine *e, int32_t request, uint32_t *costs, int32_t capacity, int32_t *starts, int32_t *ends)
+{
+    if (!e || request < 0 || (size_t)request >= e->lp.last.size()) return ZLHIP_ERR_INVALID;
+    if (!e->lp.costs) return fail(e, ZLHIP_ERR_STATE, "debug_loop_costs: the last call had more than 1048576 candidate pairs and stored no costs");
+    const zlhip_engine::Loop::Last &l = e->lp.last[(size_t)request];
+    if (starts) *starts = l.ns;
+    if (ends) *ends = l.ne;
+    if (!costs) return ZLHIP_OK;
+    const int64_t n = (int64_t)l.ns * l.ne;
+    if ((int64_t)capacity < n) return fail(e, ZLHIP_ERR_CAPACITY, "debug_loop_costs: capacity below starts * ends");
+    if (n == 0) return ZLHIP_OK;
+    ZL_HIP(e, hipSetDevice(e->device));
+    ZL_HIP(e, hipMemcpyAsync(costs, (const uint32_t *)e->scratch[ZB_LP_COST].d + l.cost_base, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    return engine_wait(e);
+}
+
+int zlhip_debug_loop_timings(zlhip_engine *e, float *pairs_ms, float *rest_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (pairs_ms) *pairs_ms = e->lp.pairsMs;
+    if (rest_ms) *rest_ms = e->lp.restMs;
     return ZLHIP_OK;
 }
 

@@ -14,7 +14,7 @@
 #include "zl_host.h"
 #include "zl_types.h"
 
-struct ZlOnOnset; struct ZlTpResult; struct ZlPtResult; struct ZlLdSub;     // (zl_onset.h, zl_tempo.h, zl_pitch.h, zl_loudness.h)
+struct ZlOnOnset; struct ZlTpResult; struct ZlPtResult; struct ZlLdSub; struct ZlLpResult;     // (zl_onset.h, zl_tempo.h, zl_pitch.h, zl_loudness.h, zl_loop.h)
 
 #pragma GCC visibility push(hidden)
 // host memory mapped into the device, grown by doubling (the buffer must be idle)
@@ -41,6 +41,7 @@ enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a ca
        ZB_TP_REQ, ZB_TP_E, ZB_TP_W, ZB_TP_A, ZB_TP_STAT,      // tempo: a call's request records (the energy pass's and the tempo kernels', one host twin), per hop E and W, per lag A, per request the flux's statistics
        ZB_PT_REQ, ZB_PT_D, ZB_PT_STAT, ZB_PT_FRAME,           // pitch: a call's request records (with a host twin), per frame and lag d, per frame the diff kernel's statistics and the frame records
        ZB_LD_REQ,                                             // loudness: a call's request records (with a host twin)
+       ZB_LP_REQ, ZB_LP_X, ZB_LP_E, ZB_LP_SHIFT, ZB_LP_ITEM, ZB_LP_COST,   // loop finder: a call's request records (with a host twin), the int16 strips, per candidate E, per request the shift, the item records, the cost matrix (small calls)
        ZB_COUNT };
 
 // a call's results in host memory mapped into the device: the kernels write them in place and nothing is copied back
@@ -119,6 +120,14 @@ struct zlhip_engine {
         std::vector<Last> last;                                     // per request of the last call (zlhip_debug_loudness_subs)
         ZlStageTimer<2> timer; float kernelMs = 0.0f;
     } ld;
+    // loop finder (zlhip_sound_loop; zl_loop.h)
+    struct Loop {
+        ZlMapped<ZlLpResult> out;                                   // a call's integer records
+        struct Last { int64_t cost_base; int32_t item_base, items, ns, ne; };
+        std::vector<Last> last;                                     // per request of the last call (zlhip_debug_loop_items / _costs)
+        bool costs = false;                                         // the last call stored its cost matrix
+        ZlStageTimer<4> timer; float pairsMs = 0.0f, restMs = 0.0f; // marks: before the prep, around the pairs kernel, behind the pick
+    } lp;
     // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h)
     struct Pcm {
         std::vector<hipEvent_t> ev;                                 // profiling: before every pass's copies and every decode launch, behind the last

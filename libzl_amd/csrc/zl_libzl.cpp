@@ -1163,6 +1163,92 @@ int libzl_hotpath_clips_level(ClipAudioSource **clips, int count, float target_l
     return (int)changed.size();
 }
 
+// A sampler sustains a note by looping the clip from its stop to its start (ClipCommand.looping, SamplerSynthVoice.cpp:243), and the
+// only way to place that loop is setStartPosition / setLength with seconds and beats the caller must already know; a loop placed by
+// hand clicks on every lap.  Here: the pair of points near the clip's start and its start + length whose surroundings match best,
+// searched on the device in the data the clip plays now (zlhip_sound_loop).  Build-defined: the reference has
+// no loop finder.
+static int clip_loop_request(ClipAudioSource *c, float search_ms, int window, zlhip_loop_request *q, double *rate)      // call with G.mu held
+{
+    if (!G.engine || c->engineClip < 0) return ZLHIP_ERR_STATE;
+    zlhip_sound_info info; int64_t start, stop;
+    { const int rc = clip_region(c, &info, &start, &stop); if (rc != ZLHIP_OK) return rc; }
+    const double r = std::rint((double)search_ms * info.sample_rate / 1000.0);
+    if (!(r >= 0.0 && r <= 1e6) || (search_ms > 0.0f && r < 1.0)) return ZLHIP_ERR_INVALID;       // (a NaN fails here)
+    *q = zlhip_loop_request{ c->engineClip, (int32_t)start, (int32_t)stop, (int32_t)r, (int32_t)r, window, 0 };
+    if (zlhip_loop_resolve(info.sample_rate, q) != ZLHIP_OK) return ZLHIP_ERR_INVALID;             // (a search beyond 2047 frames, a window outside its limits)
+    *rate = info.sample_rate;
+    return ZLHIP_OK;
+}
+
+// set the clip's start and length from a found loop; call with G.mu held.  1 = applied, 0 = not (below the bar or not representable)
+static int clip_apply_loop(ClipAudioSource *c, const zlhip_loop &l, double rate, float min_improvement_db)
+{
+    if (!l.found || !(l.improvement_db >= (double)min_improvement_db)) return 0;
+    float startSec, lengthSec;
+    if (zlhip_loop_seconds(rate, l.start_frame, l.stop_frame, &startSec, &lengthSec) != ZLHIP_OK) return 0;
+    std::lock_guard<std::mutex> sl(c->setMu);
+    c->startPositionInSeconds = startSec;
+    c->lengthInSeconds = lengthSec;
+    publish_params(c);
+    return 1;
+}
+
+int libzl_hotpath_clip_find_loop(ClipAudioSource *c, float search_ms, int window, int *start_frame, int *stop_frame, double *seam_db, double *nominal_db)
+{
+    if (!c) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    zlhip_loop_request q; zlhip_loop l; double rate;
+    { const int rc = clip_loop_request(c, search_ms, window, &q, &rate); if (rc != ZLHIP_OK) return rc; }
+    { const int rc = zlhip_sound_loop(G.engine, &q, &l); if (rc != ZLHIP_OK) return rc; }
+    if (start_frame) *start_frame = l.start_frame;
+    if (stop_frame) *stop_frame = l.stop_frame;
+    if (seam_db) *seam_db = l.seam_db;
+    if (nominal_db) *nominal_db = l.nominal_db;
+    return l.found ? 1 : 0;
+}
+
+int libzl_hotpath_clip_snap_loop(ClipAudioSource *c, float search_ms, float min_improvement_db, int *start_frame, int *stop_frame)
+{
+    if (!c || min_improvement_db != min_improvement_db) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    zlhip_loop_request q; zlhip_loop l; double rate;
+    { const int rc = clip_loop_request(c, search_ms, 0, &q, &rate); if (rc != ZLHIP_OK) return rc; }
+    { const int rc = zlhip_sound_loop(G.engine, &q, &l); if (rc != ZLHIP_OK) return rc; }
+    if (!clip_apply_loop(c, l, rate, min_improvement_db)) return 0;
+    if (start_frame) *start_frame = l.start_frame;
+    if (stop_frame) *stop_frame = l.stop_frame;
+    return 1;
+}
+
+// A whole bank: ONE zlhip_sound_loop_batch.
+int libzl_hotpath_clips_snap_loops(ClipAudioSource **clips, int count, float search_ms, float min_improvement_db, int *applied_out)
+{
+    if (count < 0 || (count > 0 && !clips) || min_improvement_db != min_improvement_db || !(search_ms >= 0.0f)) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    if (!G.engine) return ZLHIP_ERR_STATE;
+    for (int i = 0; i < count; ++i)
+        for (int j = 0; clips[i] && j < i; ++j) if (clips[j] == clips[i]) return ZLHIP_ERR_INVALID;
+    std::vector<int> who; std::vector<zlhip_loop_request> reqs; std::vector<double> rates;
+    for (int i = 0; i < count; ++i) {
+        zlhip_loop_request q; double rate;
+        if (!clips[i]) continue;
+        const int rc = clip_loop_request(clips[i], search_ms, 0, &q, &rate);
+        if (rc != ZLHIP_OK) continue;                              // not in the engine, an empty region, a search beyond 2047 of its frames: stays as it is
+        who.push_back(i); reqs.push_back(q); rates.push_back(rate);
+    }
+    std::vector<zlhip_loop> res(reqs.size());
+    if (!reqs.empty()) { const int rc = zlhip_sound_loop_batch(G.engine, reqs.data(), (int32_t)reqs.size(), res.data()); if (rc != ZLHIP_OK) return rc; }
+    if (applied_out) for (int i = 0; i < count; ++i) applied_out[i] = 0;
+    int applied = 0;
+    for (size_t n = 0; n < who.size(); ++n) {
+        const int a = clip_apply_loop(clips[who[n]], res[n], rates[n], min_improvement_db);
+        if (applied_out) applied_out[who[n]] = a;
+        applied += a;
+    }
+    return applied;
+}
+
 void ClipAudioSource_setVolume(ClipAudioSource *c, float vol)      // ClipAudioSource.cpp:313-326
 {
     std::lock_guard<std::mutex> sl(c->setMu);

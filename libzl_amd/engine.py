@@ -180,6 +180,26 @@ def _loudness_call(fn, handle, requests, length_of):
     return rc, [{k: (tuple(out[i].peak) if k == "peak" else getattr(out[i], k)) for k in LOUDNESS_FIELDS} for i in range(len(requests))]
 
 
+LOOP_FIELDS = tuple(name for name, _ in _abi.Loop._fields_ if name != "reserved")
+LOOP_ITEM_FIELDS = tuple(name for name, _ in _abi.LoopItem._fields_)
+_LOOP_KEYS = ("start_frame", "stop_frame", "start_search", "stop_search", "window", "min_length")
+
+
+def _loop_call(fn, handle, requests):
+    """one zlhip_sound_loop_batch-shaped call over (clip, start_frame, stop_frame[, start_search[, stop_search[, window[, min_length]]]]) tuples,
+    or dicts with "clip", "start_frame", "stop_frame" and any of the other keys (0 / missing = the default, a search of -1 = the point
+    stays) -> (status, one dict of zlhip_loop's fields per request)"""
+    reqs = (_abi.LoopRequest * max(1, len(requests)))()
+    for i, r in enumerate(requests):
+        if isinstance(r, dict):
+            r = (r["clip"],) + tuple(r.get(k, 0) for k in _LOOP_KEYS)
+        r = tuple(r) + (0, 0, 0, 0)[len(r) - 3:]
+        reqs[i] = _abi.LoopRequest(*(int(v) for v in r))
+    out = (_abi.Loop * max(1, len(requests)))()
+    rc = fn(handle, reqs, len(requests), out)
+    return rc, [{k: getattr(out[i], k) for k in LOOP_FIELDS} for i in range(len(requests))]
+
+
 TEMPO_FIELDS = tuple(name for name, _ in _abi.Tempo._fields_ if name != "reserved")
 
 
@@ -542,6 +562,43 @@ class SamplerSynth:
         a = C.c_float(0.0)
         self._ck(self._lib.zlhip_debug_loudness_timings(self._e, C.byref(a)), "debug_loudness_timings")
         return a.value
+
+    def clip_loop(self, clip: int, start_frame: int, stop_frame: int, start_search: int = 0, stop_search: int = 0, window: int = 0, min_length: int = 0) -> dict:
+        """The seamless loop points of the clip's current playback data near the nominal loop [start_frame, stop_frame), searched on the
+        device (zlhip_sound_loop): a dict of zlhip_loop's fields -- found, start_frame, stop_frame, seam_db,
+        nominal_db, improvement_db and the integers they derive from.  found == 0 means "no admissible pair".  A field given as 0 takes
+        its default (zlhip_loop_resolve: 10 ms of search around each point, a window of 256 frames); a search of -1 keeps the point."""
+        return self.clip_loop_batch([(clip, start_frame, stop_frame, start_search, stop_search, window, min_length)])[0]
+
+    def clip_loop_batch(self, requests: Sequence):
+        """Several requests in one call (zlhip_sound_loop_batch: three launches whatever the count).  requests: tuples
+        (clip, start_frame, stop_frame[, start_search[, stop_search[, window[, min_length]]]]) or dicts; one dict each."""
+        rc, res = _loop_call(self._lib.zlhip_sound_loop_batch, self._e, requests)
+        self._ck(rc, "sound_loop_batch")
+        return res
+
+    def loop_items(self, request: int = 0):
+        """debug: the work items' records (dicts of zlhip_loop_item's fields) of request `request` of the last loop call"""
+        n = C.c_int32(0)
+        self._ck(self._lib.zlhip_debug_loop_items(self._e, request, None, 0, C.byref(n)), "debug_loop_items")
+        recs = (_abi.LoopItem * max(1, n.value))()
+        self._ck(self._lib.zlhip_debug_loop_items(self._e, request, C.addressof(recs), n.value, C.byref(n)), "debug_loop_items")
+        return [{k: getattr(recs[i], k) for k in LOOP_ITEM_FIELDS} for i in range(n.value)]
+
+    def loop_costs(self, request: int = 0):
+        """debug: every candidate pair's cost, uint32 [starts, ends], of request `request` of the last loop call; a call with more than
+        2^20 candidate pairs keeps none (ZlHipError, ZLHIP_ERR_STATE)"""
+        ns, ne = C.c_int32(0), C.c_int32(0)
+        self._ck(self._lib.zlhip_debug_loop_costs(self._e, request, None, 0, C.byref(ns), C.byref(ne)), "debug_loop_costs")
+        d = np.zeros((ns.value, ne.value), np.uint32)
+        self._ck(self._lib.zlhip_debug_loop_costs(self._e, request, d.ctypes.data, d.size, C.byref(ns), C.byref(ne)), "debug_loop_costs")
+        return d
+
+    def loop_timings(self):
+        """device ms of the pairs kernel and of the rest of the last loop call made with profiling on"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        self._ck(self._lib.zlhip_debug_loop_timings(self._e, C.byref(a), C.byref(b)), "debug_loop_timings")
+        return a.value, b.value
 
     def overview_timings(self) -> float:
         """device ms of the last overview call made with profiling on (set_profiling)"""
@@ -953,6 +1010,15 @@ class SamplerSynthGroup:
     def clip_pitch_batch(self, requests: Sequence):
         rc, res = _pitch_call(self._lib.zlhip_group_sound_pitch_batch, self._g, requests, self.clip_length)
         self._ck(rc, "group_sound_pitch_batch")
+        return res
+
+    def clip_loop(self, clip: int, start_frame: int, stop_frame: int, start_search: int = 0, stop_search: int = 0, window: int = 0, min_length: int = 0) -> dict:
+        """SamplerSynth.clip_loop: every member holds every clip, member 0 answers (zlhip_group_sound_loop_batch)"""
+        return self.clip_loop_batch([(clip, start_frame, stop_frame, start_search, stop_search, window, min_length)])[0]
+
+    def clip_loop_batch(self, requests: Sequence):
+        rc, res = _loop_call(self._lib.zlhip_group_sound_loop_batch, self._g, requests)
+        self._ck(rc, "group_sound_loop_batch")
         return res
 
     def clip_loudness(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, sub_frames: int = 0) -> dict:
