@@ -245,6 +245,20 @@ int  libzl_hotpath_clip_snap_loop(ClipAudioSource *c, float search_ms, float min
  * be NULL) is 1 where clip i's loop was moved.  Duplicate clips are ZLHIP_ERR_INVALID.  Returns the number of clips moved, or a
  * negative status (nothing has changed then). */
 int  libzl_hotpath_clips_snap_loops(ClipAudioSource **clips, int count, float search_ms, float min_improvement_db, int *applied_out);
+/* extension (build-defined: the reference has no key detection): the musical key of the data the clip plays now between its start and
+ * its start + length, detected on the device (zlhip_sound_key with the defaults).  *tonic: 0 = C .. 11 = B, or
+ * -1 for "no key" (silence, a region shorter than one analysis frame, a flat chroma), which is not an error; *mode: 0 major, 1 minor;
+ * *confidence: Pearson's r of the chroma with the key's Krumhansl-Kessler profile.  Returns ZLHIP_OK or a negative status. */
+int  libzl_hotpath_clip_key(ClipAudioSource *c, int *tonic, int *mode, double *confidence);
+/* A bank: ONE zlhip_sound_key_batch call for all clips.  A clip that is NULL or not in the engine reads "no key".  The out arrays may
+ * be NULL.  Returns the number of clips with a key, or a negative status. */
+int  libzl_hotpath_clips_keys(ClipAudioSource **clips, int count, int *tonics, int *modes, double *confidences);
+/* Transpose the clip into the session's key (tonic 0 .. 11, mode 0 major / 1 minor), the counterpart of libzl_hotpath_clip_match_tempo:
+ * detects the clip's key and adds shift = ((target - clip_tonic + 6) mod 12) - 6 semitones, -6 .. +5, to its current pitch change, as
+ * ClipAudioSource_setPitch would (same locks, same clamp, one re-render).  Where the modes differ the clip is compared through its
+ * relative key (major: tonic + 9, minor: tonic + 3).  *semitones_out (may be NULL): the shift.  Returns 1, or 0 for "no key" (the clip
+ * is untouched and *semitones_out is 0), or a negative status. */
+int  libzl_hotpath_clip_match_key(ClipAudioSource *c, int tonic, int mode, int *semitones_out);
 /* A bank of clips in one engine call: every file is read, their `data` chunks go to the engine as raw PCM in ONE
  * zlhip_sound_upload_pcm_batch call (decoded on the device, one wait for the whole bank).  out[i] is the clip of paths[i], or NULL
  * for a file that cannot be opened or decoded -- it does not fail the others.  Returns the number of clips loaded (or a negative

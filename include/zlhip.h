@@ -42,7 +42,8 @@ extern "C" {
  *    the device), zlhip_onset_resolve, zlhip_sound_tempo / _batch (a clip's tempo, estimated on the device), zlhip_tempo_resolve,
  *    zlhip_sound_pitch / _batch (a clip's pitch, detected on the device), zlhip_pitch_resolve, zlhip_sound_loudness / _batch (a clip's
  *    loudness, measured on the device), zlhip_loudness_resolve, zlhip_loudness_design, zlhip_sound_loop / _batch (a clip's seamless
- *    loop points, found on the device), zlhip_loop_resolve, zlhip_loop_seconds. */
+ *    loop points, found on the device), zlhip_loop_resolve, zlhip_loop_seconds, zlhip_sound_key / _batch (a clip's musical
+ *    key, detected on the device), zlhip_key_resolve, zlhip_key_design. */
 #define ZLHIP_ABI_VERSION 3
 
 /* status codes */
@@ -438,6 +439,45 @@ int zlhip_debug_loop_items(zlhip_engine *e, int32_t request, zlhip_loop_item *it
 int zlhip_debug_loop_costs(zlhip_engine *e, int32_t request, uint32_t *costs, int32_t capacity, int32_t *starts, int32_t *ends);
 /* measurement: device time of the pairs kernel and of the rest of the last call made with profiling on */
 int zlhip_debug_loop_timings(zlhip_engine *e, float *pairs_ms, float *rest_ms);
+/* Key: what key a loop is in (a build-defined extension, the reference has no key detection) -- detected on the
+ * device in the sound's CURRENT playback data.  Pitch detection answers "no pitch" on a chord loop by design; this is the answer for
+ * those.  Behind section 8's 16-bit quantisation everything the device does is integer arithmetic (libzl_amd/csrc/zl_key.h):
+ *   a bank of correlators, one bin per semitone from note_lo to note_hi (MIDI): f = a4_hz 2^((note - 69) / 12), a Hann window of
+ *   N = q rate / f samples (even, at most 32768), phases j step mod 2^32 with step = rint(f / rate 2^32) into ONE cosine table of 4096
+ *   int16 entries (zlhip_key_design gives the bins and the table).  L = the largest N.  Frames of L samples every `hop` frames, at most
+ *   max_frames of them spread over the region; num_frames < L gives none.  A frame whose energy lies under L channels gate^2 is silent.
+ *   Per frame and bin re = the sum of v c, im = the sum of v s (int64), e = ((re / N) >> 8)^2 + ((im / N) >> 8)^2, which counts where
+ *   e L reaches the frame's energy (-33 dB of a tone of the frame's power; below it is leakage and rounding); the per-bin totals
+ *   over the sounding frames fold into the twelve chroma words; tonic (0 = C .. 11 = B), mode (0 major, 1 minor) and confidence are
+ *   the best of Pearson's r with the 24 rotations of the Krumhansl-Kessler profiles, second_* the runner-up (a relative or parallel key
+ *   close behind is information, not an error).
+ *   No key -- no frames, no sounding frame or a constant chroma -- is not an error: tonic = -1 and every other field 0 except frames.
+ *   A field given as 0 takes its default (zlhip_key_resolve with the sound's sample rate): a4_hz = 440, note_lo = 36, note_hi = 95,
+ *   q = 34, hop = 8192, max_frames = 256, gate = 8.  Limits: a4_hz in [220, 880], 1 <= note_lo <= note_hi <= 127, at most 96 bins,
+ *   the top bin below rate / 2 and at least 32 samples long, q <= 256, hop <= 2^24, max_frames <= 256, gate <= 32767; at most 65536
+ *   frames in one call.  Anything else is ZLHIP_ERR_INVALID and nothing has been launched.
+ *   A call is three launches, whatever the number of requests, and 136 bytes per request to the host. */
+typedef struct zlhip_key_request { int32_t id, first_frame, num_frames, hop, max_frames; float a4_hz; int32_t note_lo, note_hi, q, gate; } zlhip_key_request;
+typedef struct zlhip_key { int32_t tonic, mode, second_tonic, second_mode, frames, sounding; double confidence, second_confidence;
+                           uint64_t chroma[12]; } zlhip_key;
+typedef struct zlhip_key_bin { int32_t note, n; uint32_t step, wstep; } zlhip_key_bin;
+#define ZLHIP_KEY_TABLE 4096
+/* fills the defaults into r and checks the limits that need no sound */
+int zlhip_key_resolve(double sample_rate, zlhip_key_request *r);
+/* the table of a request at a rate: *nbins bins into bins [capacity] and the cosine table into table [4096] (each may be NULL) */
+int zlhip_key_design(double sample_rate, const zlhip_key_request *r, zlhip_key_bin *bins, int32_t capacity, int32_t *nbins, int16_t *table);
+/* how many semitones, -6 .. +5, move a clip in (clip_tonic, clip_mode) into (tonic, mode): ((tonic - from + 6) mod 12) - 6, where from
+ * is clip_tonic, or the clip's relative key where the modes differ (major: clip_tonic + 9, minor: clip_tonic + 3).  Tonics 0 .. 11,
+ * modes 0 / 1; anything else gives 0 */
+int zlhip_key_match_shift(int32_t clip_tonic, int32_t clip_mode, int32_t tonic, int32_t mode);
+int zlhip_sound_key(zlhip_engine *e, const zlhip_key_request *r, zlhip_key *out);
+int zlhip_sound_key_batch(zlhip_engine *e, const zlhip_key_request *reqs, int32_t nreq, zlhip_key *out);
+/* the per-bin totals of request `request` of the last call (totals: [capacity], may be NULL to ask for the count only) */
+int zlhip_debug_key_bins(zlhip_engine *e, int32_t request, uint64_t *totals, int32_t capacity, int32_t *bins);
+/* re and im of every bin of frame `frame` of request `request` of the last call (a silent frame's are 0); *frames: the request's frames */
+int zlhip_debug_key_frame(zlhip_engine *e, int32_t request, int32_t frame, int64_t *re, int64_t *im, int32_t capacity, int32_t *bins, int32_t *frames);
+/* measurement: device time of the three launches of the last call made with profiling on */
+int zlhip_debug_key_timings(zlhip_engine *e, float *gate_ms, float *correlate_ms, float *fold_ms);
 /* Clips from raw PCM.  `frames` is host memory, pageable or page-locked: `length` frames of `channels`
  *   interleaved little-endian samples, exactly the bytes of a WAV `data` chunk.  They are copied raw into a device staging buffer and
  *   decoded there into the arena's layout; one decode launch serves each staging pass and the call waits for the device once.
@@ -669,6 +709,8 @@ int  zlhip_group_sound_pitch_batch(zlhip_group *g, const zlhip_pitch_request *re
 int  zlhip_group_sound_loudness_batch(zlhip_group *g, const zlhip_loudness_request *reqs, int32_t nreq, zlhip_loudness *out);
 /* zlhip_sound_loop_batch: member 0 answers */
 int  zlhip_group_sound_loop_batch(zlhip_group *g, const zlhip_loop_request *reqs, int32_t nreq, zlhip_loop *out);
+/* zlhip_sound_key_batch: member 0 answers */
+int  zlhip_group_sound_key_batch(zlhip_group *g, const zlhip_key_request *reqs, int32_t nreq, zlhip_key *out);
 /* zlhip_handle_commands_voices over the whole synth (taken, voices optional) */
 int  zlhip_group_handle_commands(zlhip_group *g, const zlhip_clip_command *cmds, int32_t count, uint64_t current_tick, int32_t *taken,
                                  int32_t *voices);

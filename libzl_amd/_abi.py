@@ -169,6 +169,20 @@ class LoopItem(C.Structure):
     _fields_ = [("start", C.c_int32), ("stop", C.c_int32), ("cost", C.c_uint32), ("den", C.c_uint32), ("pairs", C.c_uint64)]
 
 
+class KeyRequest(C.Structure):
+    _fields_ = [("id", C.c_int32), ("first_frame", C.c_int32), ("num_frames", C.c_int32), ("hop", C.c_int32), ("max_frames", C.c_int32),
+                ("a4_hz", C.c_float), ("note_lo", C.c_int32), ("note_hi", C.c_int32), ("q", C.c_int32), ("gate", C.c_int32)]
+
+
+class Key(C.Structure):
+    _fields_ = [("tonic", C.c_int32), ("mode", C.c_int32), ("second_tonic", C.c_int32), ("second_mode", C.c_int32), ("frames", C.c_int32),
+                ("sounding", C.c_int32), ("confidence", C.c_double), ("second_confidence", C.c_double), ("chroma", C.c_uint64 * 12)]
+
+
+class KeyBin(C.Structure):
+    _fields_ = [("note", C.c_int32), ("n", C.c_int32), ("step", C.c_uint32), ("wstep", C.c_uint32)]
+
+
 class Tempo(C.Structure):
     _fields_ = [("bpm", C.c_float), ("confidence", C.c_float), ("lag_coarse", C.c_int32), ("lag_fine", C.c_int32), ("doublings", C.c_int32),
                 ("shift", C.c_int32), ("hops", C.c_int32), ("reserved", C.c_int32), ("acf_lo", C.c_uint64), ("acf_mid", C.c_uint64),
@@ -256,6 +270,14 @@ SIGNATURES = {
     "zlhip_debug_loop_items": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_debug_loop_costs": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "zlhip_debug_loop_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "zlhip_key_resolve": (C.c_int, [C.c_double, C.POINTER(KeyRequest)]),
+    "zlhip_key_design": (C.c_int, [C.c_double, C.POINTER(KeyRequest), C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p]),
+    "zlhip_key_match_shift": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "zlhip_sound_key": (C.c_int, [_E, C.POINTER(KeyRequest), C.POINTER(Key)]),
+    "zlhip_sound_key_batch": (C.c_int, [_E, C.POINTER(KeyRequest), C.c_int32, C.POINTER(Key)]),
+    "zlhip_debug_key_bins": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zlhip_debug_key_frame": (C.c_int, [_E, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "zlhip_debug_key_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "zlhip_sound_upload_pcm": (C.c_int, [_E, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_int32)]),
     "zlhip_sound_upload_pcm_batch": (C.c_int, [_E, C.POINTER(PcmSource), C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_debug_upload_pcm_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -323,6 +345,7 @@ SIGNATURES = {
     "zlhip_group_sound_tempo_batch": (C.c_int, [_E, C.POINTER(TempoRequest), C.c_int32, C.POINTER(Tempo)]),
     "zlhip_group_sound_pitch_batch": (C.c_int, [_E, C.POINTER(PitchRequest), C.c_int32, C.POINTER(Pitch)]),
     "zlhip_group_sound_loop_batch": (C.c_int, [_E, C.POINTER(LoopRequest), C.c_int32, C.POINTER(Loop)]),
+    "zlhip_group_sound_key_batch": (C.c_int, [_E, C.POINTER(KeyRequest), C.c_int32, C.POINTER(Key)]),
     "zlhip_group_sound_loudness_batch": (C.c_int, [_E, C.POINTER(LoudnessRequest), C.c_int32, C.POINTER(Loudness)]),
     "zlhip_group_handle_commands": (C.c_int, [_E, C.POINTER(ClipCommand), C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "zlhip_group_start_voice": (C.c_int, [_E, C.c_int32, C.c_int32, C.POINTER(ClipCommand), C.c_uint64]),

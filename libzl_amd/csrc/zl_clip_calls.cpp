@@ -1,5 +1,5 @@
-// zl_clip_calls.cpp -- the clip services of include/zlhip.h: loading from raw PCM, re-render, rate conversion, and the six analyses
-// (waveform overviews, transients, tempo, pitch, loudness, loop points).  Every one is a call on a loaded clip that validates everything before its
+// zl_clip_calls.cpp -- the clip services of include/zlhip.h: loading from raw PCM, re-render, rate conversion, and the seven analyses
+// (waveform overviews, transients, tempo, pitch, loudness, loop points, key).  Every one is a call on a loaded clip that validates everything before its
 // first HIP call, reserves buffers that only grow, queues its launches on the engine's stream and waits once.  What they share is
 // written once, below; the engine itself -- arena, sound slots, rendering, the resident kernel -- is zl_engine.cpp.
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 
 #include "zl_engine_impl.h"
 #include "zl_decode.h"
+#include "zl_key.h"
 #include "zl_loop.h"
 #include "zl_loudness.h"
 #include "zl_onset.h"
@@ -1147,6 +1148,157 @@ int zlhip_debug_loop_timings(zlhip_engine *e, float *pairs_ms, float *rest_ms)
     if (!e) return ZLHIP_ERR_INVALID;
     if (pairs_ms) *pairs_ms = e->lp.pairsMs;
     if (rest_ms) *rest_ms = e->lp.restMs;
+    return ZLHIP_OK;
+}
+
+// ---- key (zl_key.h, zl_key.hip) --------------------------------------------------------------------------------------------
+// What key a loop is in.  The gate kernel leaves every frame's energy verdict, the correlate kernel re and im per frame and bin, the
+// fold the per-bin totals and the integer record in host memory mapped into the device; tonic, mode and the two confidences are
+// derived here (zl_ky_finish).  The bin tables are made here, in double, and handed to the kernels: the device computes no
+// frequency.  Synchronisation and buffers as for the overviews.
+int zlhip_key_resolve(double sample_rate, zlhip_key_request *r)
+{
+    if (!r || r->first_frame < 0 || r->num_frames < 1) return ZLHIP_ERR_INVALID;
+    zlhip_key_request q = *r;
+    if (zl_ky_resolve(sample_rate, &q.hop, &q.max_frames, &q.a4_hz, &q.note_lo, &q.note_hi, &q.q, &q.gate) != 0) return ZLHIP_ERR_INVALID;
+    *r = q;
+    return ZLHIP_OK;
+}
+
+int zlhip_key_design(double sample_rate, const zlhip_key_request *r, zlhip_key_bin *bins, int32_t capacity, int32_t *nbins, int16_t *table)
+{
+    static_assert(sizeof(zlhip_key_bin) == sizeof(ZlKyBin), "zl_ky_design writes zlhip_key_bin's layout");
+    if (!r) return ZLHIP_ERR_INVALID;
+    zlhip_key_request q = *r;
+    if (zlhip_key_resolve(sample_rate, &q) != ZLHIP_OK) return ZLHIP_ERR_INVALID;
+    const int32_t n = q.note_hi - q.note_lo + 1;
+    if (nbins) *nbins = n;
+    if (bins && capacity < n) return ZLHIP_ERR_CAPACITY;
+    zl_ky_design(sample_rate, q.a4_hz, q.note_lo, q.note_hi, q.q, (ZlKyBin *)bins, table);
+    return ZLHIP_OK;
+}
+
+int zlhip_key_match_shift(int32_t clip_tonic, int32_t clip_mode, int32_t tonic, int32_t mode)
+{
+    if (clip_tonic < 0 || clip_tonic > 11 || tonic < 0 || tonic > 11 || clip_mode < 0 || clip_mode > 1 || mode < 0 || mode > 1) return 0;
+    return zl_ky_match_shift(clip_tonic, clip_mode, tonic, mode);
+}
+
+int zlhip_sound_key_batch(zlhip_engine *e, const zlhip_key_request *reqs, int32_t nreq, zlhip_key *out)
+{
+    static_assert(sizeof(zlhip_key) == sizeof(ZlKyResult) && sizeof(ZlKyResult) == 136, "the device writes zlhip_key's layout");
+    if (!e || nreq < 0 || (nreq > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
+    if (nreq == 0) return ZLHIP_OK;
+    // validate and resolve everything before anything is written and before the first HIP call
+    std::vector<ZlKyRequest> geo((size_t)nreq);
+    std::vector<ZlKyBin> table;
+    int64_t frames = 0, pairs = 0, items = 0;
+    for (int32_t i = 0; i < nreq; ++i) {
+        zlhip_key_request q = reqs[i];
+        auto resolve = [&](const ZlSound &s) { return zlhip_key_resolve(s.sample_rate, &q) != ZLHIP_OK ? kOutsideLimits : nullptr; };
+        { const int rc = check_request(e, "sound_key", q, resolve); if (rc != ZLHIP_OK) return rc; }
+        const ZlSound &s = e->hc.sounds[q.id];
+        ZlKyRequest &R = geo[(size_t)i];
+        R.nbins = q.note_hi - q.note_lo + 1; R.bin_base = (int32_t)table.size();
+        table.resize(table.size() + (size_t)R.nbins);
+        zl_ky_design(s.sample_rate, q.a4_hz, q.note_lo, q.note_hi, q.q, table.data() + R.bin_base, nullptr);
+        R.src = 0;                                                 // (the address: behind the reserve, with the other HIP-side state)
+        R.span = table[(size_t)R.bin_base].n;
+        R.floor_ = (uint64_t)R.span * (uint64_t)s.channels * (uint64_t)q.gate * (uint64_t)q.gate;
+        R.first = q.first_frame; R.channels = s.channels; R.reserved = 0;
+        zl_ky_frames(q.num_frames, R.span, q.hop, q.max_frames, &R.frames, &R.hop);
+        R.acc_base = pairs; R.frame_base = (int32_t)frames; R.item_base = (int32_t)items;
+        frames += R.frames; pairs += (int64_t)R.frames * R.nbins; items += zl_ky_items(R);
+        if (frames > ZL_KY_MAX_CALL_FRAMES) return fail(e, ZLHIP_ERR_INVALID, "sound_key_batch: more than 65536 analysis frames in one call");
+    }
+    { const int rc = call_begin(e, false); if (rc != ZLHIP_OK) return rc; }
+    zlhip_engine::Key &t = e->ky;
+    const char *what = "sound_key: no memory for the call's buffers";
+    const size_t n = (size_t)nreq, f = (size_t)frames, p = (size_t)pairs, nb = table.size(), fcap = std::min<size_t>(std::max<size_t>(f * 2, 256), ZL_KY_MAX_CALL_FRAMES);
+    const int rsv = reserve(e, true, { { ZB_KY_REQ, n, sizeof(ZlKyRequest), std::max<size_t>(n * 2, 64), true, what },
+                                      { ZB_KY_BINS, nb, sizeof(ZlKyBin), std::max<size_t>(nb * 2, 4096), true, what },
+                                      { ZB_KY_TABLE, ZL_KY_TABLE, sizeof(uint32_t), ZL_KY_TABLE, true, what },
+                                      { ZB_KY_STAT, f, sizeof(ZlKyStat), fcap, false, what },
+                                      { ZB_KY_ACC, p, sizeof(ZlKyAcc), std::max<size_t>(p + p / 2, 16384), false, what },
+                                      { ZB_KY_TOTAL, nb, sizeof(uint64_t), std::max<size_t>(nb * 2, 4096), false, what } },
+                           { mapped_need(t.out, std::max<size_t>(n, 32)) });
+    if (rsv != ZLHIP_OK) return rsv;
+    ZlKyRequest *const hReq = (ZlKyRequest *)e->scratch[ZB_KY_REQ].h, *const dReq = (ZlKyRequest *)e->scratch[ZB_KY_REQ].d;
+    ZlKyBin *const hBins = (ZlKyBin *)e->scratch[ZB_KY_BINS].h, *const dBins = (ZlKyBin *)e->scratch[ZB_KY_BINS].d;
+    uint32_t *const hP = (uint32_t *)e->scratch[ZB_KY_TABLE].h, *const dP = (uint32_t *)e->scratch[ZB_KY_TABLE].d;
+    ZlKyStat *const dStat = (ZlKyStat *)e->scratch[ZB_KY_STAT].d; ZlKyAcc *const dAcc = (ZlKyAcc *)e->scratch[ZB_KY_ACC].d;
+    uint64_t *const dTotal = (uint64_t *)e->scratch[ZB_KY_TOTAL].d;
+    t.last.clear();
+    for (int32_t i = 0; i < nreq; ++i) {
+        ZlKyRequest &R = hReq[i];
+        R = geo[(size_t)i];
+        R.src = (uint64_t)(uintptr_t)arena_ptr(e, e->hc.sounds[reqs[i].id].offset);
+        t.last.push_back({R.acc_base, R.bin_base, R.nbins, R.frames});
+    }
+    std::memcpy(hBins, table.data(), nb * sizeof(ZlKyBin));
+    {                                                              // (the cosine table depends on nothing; the kernel takes it paired)
+        int16_t T[ZL_KY_TABLE];
+        zl_ky_design(1.0, 0.0f, 1, 0, 0, nullptr, T);
+        for (int32_t i = 0; i < ZL_KY_TABLE; ++i) hP[i] = zl_ky_pair(T, i);
+    }
+    t.timer.on = e->profiling;
+    ZL_HIP(e, hipMemcpyAsync(dReq, hReq, (size_t)nreq * sizeof(ZlKyRequest), hipMemcpyHostToDevice, e->stream));
+    ZL_HIP(e, hipMemcpyAsync(dBins, hBins, nb * sizeof(ZlKyBin), hipMemcpyHostToDevice, e->stream));
+    ZL_HIP(e, hipMemcpyAsync(dP, hP, ZL_KY_TABLE * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    ZL_HIP(e, t.timer.mark(0, e->stream));
+    ZL_KERNEL(e, zl_launch_key_gate(dReq, nreq, frames, dStat, e->stream));
+    ZL_HIP(e, t.timer.mark(1, e->stream));
+    ZL_KERNEL(e, zl_launch_key_correlate(dReq, nreq, items, dBins, dP, dStat, dAcc, e->stream));
+    ZL_HIP(e, t.timer.mark(2, e->stream));
+    ZL_KERNEL(e, zl_launch_key_fold(dReq, nreq, dBins, dStat, dAcc, dTotal, t.out.d, e->stream));
+    ZL_HIP(e, t.timer.mark(3, e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    ZL_HIP(e, t.timer.elapsed(0, 1, &t.gateMs)); ZL_HIP(e, t.timer.elapsed(1, 2, &t.correlateMs)); ZL_HIP(e, t.timer.elapsed(2, 3, &t.foldMs));
+    for (int32_t i = 0; i < nreq; ++i) {
+        ZlKyResult r = t.out.h[i];
+        zl_ky_finish(&r);
+        std::memcpy(&out[i], &r, sizeof(r));
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_key(zlhip_engine *e, const zlhip_key_request *r, zlhip_key *out) { return zlhip_sound_key_batch(e, r, 1, out); }
+
+int zlhip_debug_key_bins(zlhip_engine *e, int32_t request, uint64_t *totals, int32_t capacity, int32_t *bins)
+{
+    if (!e || request < 0 || (size_t)request >= e->ky.last.size()) return ZLHIP_ERR_INVALID;
+    const zlhip_engine::Key::Last &l = e->ky.last[(size_t)request];
+    if (bins) *bins = l.nbins;
+    if (!totals) return ZLHIP_OK;
+    if (capacity < l.nbins) return fail(e, ZLHIP_ERR_CAPACITY, "debug_key_bins: capacity below the request's bins");
+    ZL_HIP(e, hipSetDevice(e->device));
+    ZL_HIP(e, hipMemcpyAsync(totals, (const uint64_t *)e->scratch[ZB_KY_TOTAL].d + l.bin_base, (size_t)l.nbins * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    return engine_wait(e);
+}
+
+int zlhip_debug_key_frame(zlhip_engine *e, int32_t request, int32_t frame, int64_t *re, int64_t *im, int32_t capacity, int32_t *bins, int32_t *frames)
+{
+    if (!e || request < 0 || (size_t)request >= e->ky.last.size()) return ZLHIP_ERR_INVALID;
+    const zlhip_engine::Key::Last &l = e->ky.last[(size_t)request];
+    if (bins) *bins = l.nbins;
+    if (frames) *frames = l.frames;
+    if (!re && !im) return ZLHIP_OK;
+    if (frame < 0 || frame >= l.frames) return fail(e, ZLHIP_ERR_INVALID, "debug_key_frame: no such frame");
+    if (capacity < l.nbins) return fail(e, ZLHIP_ERR_CAPACITY, "debug_key_frame: capacity below the request's bins");
+    std::vector<ZlKyAcc> a((size_t)l.nbins);
+    ZL_HIP(e, hipSetDevice(e->device));
+    ZL_HIP(e, hipMemcpyAsync(a.data(), (const ZlKyAcc *)e->scratch[ZB_KY_ACC].d + l.acc_base + (int64_t)frame * l.nbins, a.size() * sizeof(ZlKyAcc), hipMemcpyDeviceToHost, e->stream));
+    { const int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    for (int32_t b = 0; b < l.nbins; ++b) { if (re) re[b] = a[(size_t)b].re; if (im) im[b] = a[(size_t)b].im; }
+    return ZLHIP_OK;
+}
+
+int zlhip_debug_key_timings(zlhip_engine *e, float *gate_ms, float *correlate_ms, float *fold_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (gate_ms) *gate_ms = e->ky.gateMs;
+    if (correlate_ms) *correlate_ms = e->ky.correlateMs;
+    if (fold_ms) *fold_ms = e->ky.foldMs;
     return ZLHIP_OK;
 }
 

@@ -301,6 +301,7 @@ void zlhip_engine_destroy(zlhip_engine *e)
     e->pt.timer.release(); e->pt.out.release();
     e->ld.timer.release(); e->ld.out.release();
     e->lp.timer.release(); e->lp.out.release();
+    e->ky.timer.release(); e->ky.out.release();
     for (hipEvent_t ev : e->pcm.ev) if (ev) (void)hipEventDestroy(ev);
     if (e->evJoin) (void)hipEventDestroy(e->evJoin);
     if (e->evPlanTail) (void)hipEventDestroy(e->evPlanTail);

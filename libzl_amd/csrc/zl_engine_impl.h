@@ -14,7 +14,7 @@
 #include "zl_host.h"
 #include "zl_types.h"
 
-struct ZlOnOnset; struct ZlTpResult; struct ZlPtResult; struct ZlLdSub; struct ZlLpResult;     // (zl_onset.h, zl_tempo.h, zl_pitch.h, zl_loudness.h, zl_loop.h)
+struct ZlOnOnset; struct ZlTpResult; struct ZlPtResult; struct ZlLdSub; struct ZlLpResult; struct ZlKyResult;     // (zl_onset.h, zl_tempo.h, zl_pitch.h, zl_loudness.h, zl_loop.h, zl_key.h)
 
 #pragma GCC visibility push(hidden)
 // host memory mapped into the device, grown by doubling (the buffer must be idle)
@@ -42,6 +42,7 @@ enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a ca
        ZB_PT_REQ, ZB_PT_D, ZB_PT_STAT, ZB_PT_FRAME,           // pitch: a call's request records (with a host twin), per frame and lag d, per frame the diff kernel's statistics and the frame records
        ZB_LD_REQ,                                             // loudness: a call's request records (with a host twin)
        ZB_LP_REQ, ZB_LP_X, ZB_LP_E, ZB_LP_SHIFT, ZB_LP_ITEM, ZB_LP_COST,   // loop finder: a call's request records (with a host twin), the int16 strips, per candidate E, per request the shift, the item records, the cost matrix (small calls)
+       ZB_KY_REQ, ZB_KY_BINS, ZB_KY_TABLE, ZB_KY_STAT, ZB_KY_ACC, ZB_KY_TOTAL,   // key: a call's request records, its bin tables and the paired cosine table (each with a host twin), per frame the gate's verdict, per frame and bin re and im, per bin the totals
        ZB_COUNT };
 
 // a call's results in host memory mapped into the device: the kernels write them in place and nothing is copied back
@@ -128,6 +129,13 @@ struct zlhip_engine {
         bool costs = false;                                         // the last call stored its cost matrix
         ZlStageTimer<4> timer; float pairsMs = 0.0f, restMs = 0.0f; // marks: before the prep, around the pairs kernel, behind the pick
     } lp;
+    // key (zlhip_sound_key; zl_key.h)
+    struct Key {
+        ZlMapped<ZlKyResult> out;                                   // a call's integer records
+        struct Last { int64_t acc_base; int32_t bin_base, nbins, frames; };
+        std::vector<Last> last;                                     // per request of the last call (zlhip_debug_key_bins / _frame)
+        ZlStageTimer<4> timer; float gateMs = 0.0f, correlateMs = 0.0f, foldMs = 0.0f;   // marks: around each of the three launches
+    } ky;
     // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h)
     struct Pcm {
         std::vector<hipEvent_t> ev;                                 // profiling: before every pass's copies and every decode launch, behind the last

@@ -339,6 +339,13 @@ int zlhip_group_sound_loop_batch(zlhip_group *g, const zlhip_loop_request *reqs,
     return rc != ZLHIP_OK ? member_fail(g, 0, rc) : ZLHIP_OK;
 }
 
+int zlhip_group_sound_key_batch(zlhip_group *g, const zlhip_key_request *reqs, int32_t nreq, zlhip_key *out)
+{
+    if (!g) return ZLHIP_ERR_INVALID;
+    const int rc = zlhip_sound_key_batch(g->m[0], reqs, nreq, out);
+    return rc != ZLHIP_OK ? member_fail(g, 0, rc) : ZLHIP_OK;
+}
+
 // ---- commands (global buses, slots, voices and midi channels) ------------------------------------------------------------
 int zlhip_group_handle_commands(zlhip_group *g, const zlhip_clip_command *cmds, int32_t count, uint64_t current_tick, int32_t *taken,
                                 int32_t *voices)

@@ -1069,6 +1069,78 @@ int libzl_hotpath_clip_detect_root_note(ClipAudioSource *c, float min_confidence
     return 1;
 }
 
+// A loop browser shows a sample's key next to its bpm, and a loop only sits in a session once it is in the session's key.  Here: the key
+// of the data the clip plays now between its start and its start + length, detected on the device (zlhip_sound_key, DESIGN.md section
+// 17).  Build-defined: the reference has no key detection.
+static int clip_key_request(ClipAudioSource *c, zlhip_key_request *q)      // call with G.mu held
+{
+    if (!G.engine || c->engineClip < 0) return ZLHIP_ERR_STATE;
+    zlhip_sound_info info; int64_t start, stop;
+    { const int rc = clip_region(c, &info, &start, &stop); if (rc != ZLHIP_OK) return rc; }
+    *q = zlhip_key_request{ c->engineClip, (int32_t)start, (int32_t)(stop - start), 0, 0, 0.0f, 0, 0, 0, 0 };
+    return ZLHIP_OK;
+}
+
+int libzl_hotpath_clip_key(ClipAudioSource *c, int *tonic, int *mode, double *confidence)
+{
+    if (!c) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    zlhip_key_request q; zlhip_key k;
+    { const int rc = clip_key_request(c, &q); if (rc != ZLHIP_OK) return rc; }
+    { const int rc = zlhip_sound_key(G.engine, &q, &k); if (rc != ZLHIP_OK) return rc; }
+    if (tonic) *tonic = k.tonic;
+    if (mode) *mode = k.mode;
+    if (confidence) *confidence = k.confidence;
+    return ZLHIP_OK;
+}
+
+// A whole bank: ONE zlhip_sound_key_batch.
+int libzl_hotpath_clips_keys(ClipAudioSource **clips, int count, int *tonics, int *modes, double *confidences)
+{
+    if (count < 0 || (count > 0 && !clips)) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    if (!G.engine) return ZLHIP_ERR_STATE;
+    std::vector<int> who; std::vector<zlhip_key_request> reqs;
+    for (int i = 0; i < count; ++i) {
+        if (tonics) tonics[i] = -1;
+        if (modes) modes[i] = 0;
+        if (confidences) confidences[i] = 0.0;
+        zlhip_key_request q;
+        if (!clips[i] || clip_key_request(clips[i], &q) != ZLHIP_OK) continue;         // NULL, not in the engine, an empty region: "no key"
+        who.push_back(i); reqs.push_back(q);
+    }
+    std::vector<zlhip_key> res(reqs.size());
+    if (!reqs.empty()) { const int rc = zlhip_sound_key_batch(G.engine, reqs.data(), (int32_t)reqs.size(), res.data()); if (rc != ZLHIP_OK) return rc; }
+    int found = 0;
+    for (size_t n = 0; n < who.size(); ++n) {
+        if (tonics) tonics[who[n]] = res[n].tonic;
+        if (modes) modes[who[n]] = res[n].mode;
+        if (confidences) confidences[who[n]] = res[n].confidence;
+        found += res[n].tonic >= 0 ? 1 : 0;
+    }
+    return found;
+}
+
+// Fit the clip to the session's key: detect over the data it plays now, then re-render with the pitch change moved by the shortest way
+// there (zlhip_key_match_shift: through the clip's relative key where the modes differ; -6 .. +5 semitones).  A re-render starts from the
+// original upload, so the shift is added to the clip's current pitch change, under ClipAudioSource_setPitch's locks and its clamp.
+int libzl_hotpath_clip_match_key(ClipAudioSource *c, int tonic, int mode, int *semitones_out)
+{
+    if (!c || tonic < 0 || tonic > 11 || mode < 0 || mode > 1) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    zlhip_key_request q; zlhip_key k;
+    { const int rc = clip_key_request(c, &q); if (rc != ZLHIP_OK) return rc; }
+    { const int rc = zlhip_sound_key(G.engine, &q, &k); if (rc != ZLHIP_OK) return rc; }
+    if (semitones_out) *semitones_out = 0;
+    if (k.tonic < 0) return 0;
+    const int32_t shift = zlhip_key_match_shift(k.tonic, k.mode, tonic, mode);
+    if (semitones_out) *semitones_out = shift;
+    if (shift == 0) return 1;
+    { std::lock_guard<std::mutex> sl(c->setMu); c->pitchChange = std::min(std::max(ZL_ST_PITCH_MIN, c->pitchChange + (float)shift), ZL_ST_PITCH_MAX); }
+    clip_rerender(c);
+    return 1;
+}
+
 // A freshly loaded bank is unusable until its clips sit at one level: ClipAudioSource_setGain takes a dB value the caller must already
 // know, and the sample peak is not loudness.  Here: the integrated loudness (BS.1770 / EBU R 128) and the sample peak of the data the
 // clip plays now between its start and its start + length, measured on the device (zlhip_sound_loudness).

@@ -200,6 +200,27 @@ def _loop_call(fn, handle, requests):
     return rc, [{k: getattr(out[i], k) for k in LOOP_FIELDS} for i in range(len(requests))]
 
 
+KEY_FIELDS = tuple(name for name, _ in _abi.Key._fields_)
+_KEY_KEYS = ("first_frame", "num_frames", "hop", "max_frames", "a4_hz", "note_lo", "note_hi", "q", "gate")
+
+
+def _key_call(fn, handle, requests, length_of):
+    """one zlhip_sound_key_batch-shaped call over (clip[, first_frame[, num_frames[, hop[, max_frames[, a4_hz[, note_lo[, note_hi[, q[, gate]]]]]]]]])
+    tuples, or dicts with "clip" and any of those keys (num_frames None / missing = to the end of the clip, every other field 0 / missing =
+    its default) -> (status, one dict of zlhip_key's fields per request; chroma a tuple of twelve integers)"""
+    reqs = (_abi.KeyRequest * max(1, len(requests)))()
+    for i, r in enumerate(requests):
+        if isinstance(r, dict):
+            r = (r["clip"],) + tuple(r.get(k, None if k == "num_frames" else 0) for k in _KEY_KEYS)
+        r = tuple(r) if isinstance(r, (tuple, list)) else (r,)
+        r = r + (0, None, 0, 0, 0.0, 0, 0, 0, 0)[len(r) - 1:]
+        clip, first = int(r[0]), int(r[1])
+        reqs[i] = _abi.KeyRequest(clip, first, int(length_of(clip) - first if r[2] is None else r[2]), int(r[3]), int(r[4]), float(r[5]), int(r[6]), int(r[7]), int(r[8]), int(r[9]))
+    out = (_abi.Key * max(1, len(requests)))()
+    rc = fn(handle, reqs, len(requests), out)
+    return rc, [{k: (tuple(int(v) for v in out[i].chroma) if k == "chroma" else getattr(out[i], k)) for k in KEY_FIELDS} for i in range(len(requests))]
+
+
 TEMPO_FIELDS = tuple(name for name, _ in _abi.Tempo._fields_ if name != "reserved")
 
 
@@ -599,6 +620,49 @@ class SamplerSynth:
         a, b = C.c_float(0.0), C.c_float(0.0)
         self._ck(self._lib.zlhip_debug_loop_timings(self._e, C.byref(a), C.byref(b)), "debug_loop_timings")
         return a.value, b.value
+
+    def clip_key(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, hop: int = 0, max_frames: int = 0, a4_hz: float = 0.0,
+                 note_lo: int = 0, note_hi: int = 0, q: int = 0, gate: int = 0) -> dict:
+        """The musical key of the clip's current playback data over [first_frame, first_frame + num_frames) (None: to the end), detected on
+        the device (zlhip_sound_key): a dict of zlhip_key's fields -- tonic (0 = C .. 11 = B), mode (0 major, 1 minor),
+        confidence, the runner-up second_*, frames, sounding and the twelve chroma integers.  tonic == -1 means "no key" (silence, or shorter
+        than one analysis frame).  A field given as 0 takes its default (zlhip_key_resolve: a4 = 440, notes 36 .. 95, q = 34, hop 8192)."""
+        return self.clip_key_batch([(clip, first_frame, num_frames, hop, max_frames, a4_hz, note_lo, note_hi, q, gate)])[0]
+
+    def clip_key_batch(self, requests: Sequence):
+        """Several requests in one call (zlhip_sound_key_batch: three launches whatever the count).  requests: tuples
+        (clip[, first_frame[, num_frames[, hop[, max_frames[, a4_hz[, note_lo[, note_hi[, q[, gate]]]]]]]]]) or dicts; one dict each."""
+        rc, res = _key_call(self._lib.zlhip_sound_key_batch, self._e, requests, self.clip_length)
+        self._ck(rc, "sound_key_batch")
+        return res
+
+    def key_bins(self, request: int = 0):
+        """debug: the per-bin totals (uint64 [bins]) of request `request` of the last key call"""
+        n = C.c_int32(0)
+        self._ck(self._lib.zlhip_debug_key_bins(self._e, request, None, 0, C.byref(n)), "debug_key_bins")
+        d = np.zeros(n.value, np.uint64)
+        self._ck(self._lib.zlhip_debug_key_bins(self._e, request, d.ctypes.data, n.value, C.byref(n)), "debug_key_bins")
+        return d
+
+    def key_frame(self, request: int = 0, frame: int = 0):
+        """debug: (re, im), int64 [bins] each, of frame `frame` of request `request` of the last key call (a silent frame's are 0)"""
+        n, k = C.c_int32(0), C.c_int32(0)
+        self._ck(self._lib.zlhip_debug_key_frame(self._e, request, frame, None, None, 0, C.byref(n), C.byref(k)), "debug_key_frame")
+        re, im = np.zeros(n.value, np.int64), np.zeros(n.value, np.int64)
+        self._ck(self._lib.zlhip_debug_key_frame(self._e, request, frame, re.ctypes.data, im.ctypes.data, n.value, C.byref(n), C.byref(k)), "debug_key_frame")
+        return re, im
+
+    def key_frames(self, request: int = 0) -> int:
+        """debug: the analysis frames of request `request` of the last key call"""
+        n, k = C.c_int32(0), C.c_int32(0)
+        self._ck(self._lib.zlhip_debug_key_frame(self._e, request, 0, None, None, 0, C.byref(n), C.byref(k)), "debug_key_frame")
+        return k.value
+
+    def key_timings(self):
+        """device ms of the gate, the correlate and the fold launch of the last key call made with profiling on"""
+        a, b, c = C.c_float(0.0), C.c_float(0.0), C.c_float(0.0)
+        self._ck(self._lib.zlhip_debug_key_timings(self._e, C.byref(a), C.byref(b), C.byref(c)), "debug_key_timings")
+        return a.value, b.value, c.value
 
     def overview_timings(self) -> float:
         """device ms of the last overview call made with profiling on (set_profiling)"""
@@ -1019,6 +1083,16 @@ class SamplerSynthGroup:
     def clip_loop_batch(self, requests: Sequence):
         rc, res = _loop_call(self._lib.zlhip_group_sound_loop_batch, self._g, requests)
         self._ck(rc, "group_sound_loop_batch")
+        return res
+
+    def clip_key(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, hop: int = 0, max_frames: int = 0, a4_hz: float = 0.0,
+                 note_lo: int = 0, note_hi: int = 0, q: int = 0, gate: int = 0) -> dict:
+        """SamplerSynth.clip_key: every member holds every clip, member 0 answers (zlhip_group_sound_key_batch)"""
+        return self.clip_key_batch([(clip, first_frame, num_frames, hop, max_frames, a4_hz, note_lo, note_hi, q, gate)])[0]
+
+    def clip_key_batch(self, requests: Sequence):
+        rc, res = _key_call(self._lib.zlhip_group_sound_key_batch, self._g, requests, self.clip_length)
+        self._ck(rc, "group_sound_key_batch")
         return res
 
     def clip_loudness(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, sub_frames: int = 0) -> dict:
