@@ -226,3 +226,105 @@ def grid():
         cases.append((f"special ch{ch}", s, dict(start_frame=701, stop_frame=2203, start_search=33, stop_search=33, window=256)))
         cases.append((f"special tone ch{ch}", s, dict(start_frame=3501, stop_frame=5503, start_search=40, stop_search=64, window=64)))
     return cases
+
+
+# ---- exact ties: the order's later rules, for both tiers -------------------------------------------------------------------------------
+def tie_nominals(period):
+    """the four nominal loops of the CPU tier's tie test: a whole number of periods, half a period too long, 3 too long, 5 too short"""
+    return ((4000, 4000 + 50 * period), (4003, 4003 + 50 * period + period // 2), (4001, 4001 + 30 * period + 3), (4002, 4002 + 30 * period - 5))
+
+
+def ties():
+    """[(what, x float32 [channels][frames], request dict)] in grid()'s form: clips of 12000 frames, W = 64, in which the cost ratio
+    decides nothing among hundreds of pairs, so that the result hangs on the order's later rules and on every step of the reduction
+    (lane tile, wave, workgroup, items) applying them.  Integer-valued signals of exact period 16 and 100 (every pair a whole number of
+    periods long costs 0), mono at shift 0 and stereo at level 11000 (shift 5); digital silence (every cost 0, den 1: the distance alone
+    decides everywhere) and a constant 0.1 (cost 0 under a large den); a nominal too short for min_length (the winner is not the
+    nominal); unequal radii, a start range clipped at the data's first frame and an end range clipped at its last one, which move the
+    winner off the centre item.
+
+    What the restatement gives (tests/test_loop_cpu.py asserts the conditions): zero = admissible pairs of cost 0, in = the items that
+    hold one / the request's items, item and wave = where the winner lies (wave = ((stop_frame - emin) mod 64) // 16, the end tile's
+    quarter a wave of the pairs workgroup owns), rule = the first rule that tells the winner from the runner-up
+
+        case                        zero   in    item wave  rule
+        square 16 n0 r70            1245   9/9     4    0   distance
+        square 16 n1 r70            1242   9/9     1    0   start
+        square 16 n2 r70            1242   9/9     4    0   start
+        square 16 n3 r70            1242   9/9     4    0   start
+        square 16 r100,104          2626  16/16    5    2   start
+        square 16 r33,120           1010   8/8     1    3   start
+        square 16 r140,84           2965  15/15    7    1   distance
+        square 16 first frame       2475  15/15    2    0   end
+        square 100 n0 r70            223   7/9     4    0   distance
+        square 100 n1 r70            182   6/9     1    0   start
+        square 100 n2 r70            220   8/9     4    0   start
+        square 100 n3 r70            218   8/9     4    0   start
+        square 100 r100,104          420  13/16    1    2   start
+        square 100 r33,120           142   7/8     2    0   start
+        square 100 r140,84           469  14/15    7    1   distance
+        square 100 first frame       394  13/15    1    1   end
+        square 16 stereo shift 5    1488   9/9     1    1   start
+        silence                    19881   9/9     4    0   distance
+        silence r140,84            47489  15/15    7    1   distance
+        silence too short          11421   6/12    1    2   start
+        silence last frame         23829   9/9     5    2   distance
+        constant 0.1               28341  12/12    5    2   distance"""
+    cases = []
+    for period in (16, 100):
+        x = square(period, 12000)
+        for k, (s0, e0) in enumerate(tie_nominals(period)):
+            cases.append((f"square {period} n{k} r70", x, dict(start_frame=s0, stop_frame=e0, start_search=70, stop_search=70, window=64)))
+        s0, e0 = tie_nominals(period)[1]
+        # unequal radii: the nominal pair lies in other tiles and other waves of them
+        cases.append((f"square {period} r100,104", x, dict(start_frame=s0, stop_frame=e0, start_search=100, stop_search=104, window=64)))
+        cases.append((f"square {period} r33,120", x, dict(start_frame=s0 + 1, stop_frame=e0 + 1, start_search=33, stop_search=120, window=64)))
+        cases.append((f"square {period} r140,84", x, dict(start_frame=s0, stop_frame=e0 - period // 2, start_search=140, stop_search=84, window=64)))
+        # the start range clipped at the data's first frame, the nominal half a period too long: the start cannot move down, and the
+        # same start with the end half a period down or up is a draw down to the last rule
+        cases.append((f"square {period} first frame", x, dict(start_frame=32, stop_frame=32 + 50 * period + period // 2, start_search=140, stop_search=140, window=64)))
+    x = square(16, 12000, channels=2, level=11000)
+    cases.append(("square 16 stereo shift 5", x, dict(start_frame=4003, stop_frame=4003 + 50 * 16 + 8, start_search=70, stop_search=84, window=64)))
+    z = np.zeros((2, 12000), np.float32)
+    cases.append(("silence", z, dict(start_frame=5000, stop_frame=9000, start_search=70, stop_search=70, window=64)))
+    cases.append(("silence r140,84", z, dict(start_frame=5000, stop_frame=9000, start_search=140, stop_search=84, window=64)))
+    cases.append(("silence too short", z, dict(start_frame=5000, stop_frame=5100, start_search=70, stop_search=110, window=64, min_length=130)))
+    cases.append(("silence last frame", z, dict(start_frame=5000, stop_frame=12000, start_search=70, stop_search=200, window=64)))
+    cases.append(("constant 0.1", np.full((1, 12000), 0.1, np.float32), dict(start_frame=5001, stop_frame=9003, start_search=70, stop_search=100, window=64)))
+    return cases
+
+
+def first_rule(a, b, s0, e0):
+    """the first rule of the order that tells pair a from pair b ((s, e, cost, den) each): "cost", "distance", "start" or "end" """
+    if a[2] * b[3] != b[2] * a[3]:
+        return "cost"
+    if abs(a[0] - s0) + abs(a[1] - e0) != abs(b[0] - s0) + abs(b[1] - e0):
+        return "distance"
+    return "start" if a[0] != b[0] else "end"
+
+
+def tie_facts(x, rate, q):
+    """what ties()'s docstring tabulates about one case, from the definition over the request's whole matrix: zero (admissible pairs of
+    cost 0), zero_items (the items that hold one), items, winner and runner_up as (s, e, cost, den) -- the best admissible pair and the
+    best but that one, both by better() --, item and wave (where the winner lies) and rule (what tells the two apart)"""
+    x = np.atleast_2d(np.asarray(x, np.float32))
+    length = x.shape[1]
+    s0, e0 = q["start_frame"], q["stop_frame"]
+    f = resolve(rate, *(q.get(k, 0) for k in KEYS[2:]), s0, e0)
+    W, H = f["window"], f["window"] // 2
+    smin, ns = candidates(s0, f["start_search"], H, length)
+    emin, ne = candidates(e0, f["stop_search"], H, length)
+    ms, me = quantise(x[:, smin - H:smin + ns - 1 + H]), quantise(x[:, emin - H:emin + ne - 1 + H])
+    shift = max(0, int(max(np.abs(ms).max(), np.abs(me).max())).bit_length() - 10)
+    cost, Es, Ee = cost_matrix(ms >> shift, me >> shift, W)
+    den = Es[:, None] + Ee[None, :] + 1
+    svals, evals = smin + np.arange(ns), emin + np.arange(ne)
+    adm = (evals[None, :] - svals[:, None]) >= f["min_length"]
+    tiles = -(-ne // TILE)
+    zero = np.argwhere(adm & (cost == 0))
+    win, _ = best_of(cost, den, adm, svals, evals, s0, e0)
+    rest = adm.copy()
+    rest[win[0] - smin, win[1] - emin] = False
+    second, _ = best_of(cost, den, rest, svals, evals, s0, e0)
+    return dict(zero=len(zero), zero_items=len({(i // TILE) * tiles + k // TILE for i, k in zero}), items=-(-ns // TILE) * tiles, winner=win, runner_up=second,
+                item=((win[0] - smin) // TILE) * tiles + (win[1] - emin) // TILE, wave=((win[1] - emin) % TILE) // 16, rule=first_rule(win, second, s0, e0))

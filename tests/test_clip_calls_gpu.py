@@ -1,15 +1,18 @@
-"""The five clip analyses -- overviews, transients, tempo, pitch, loudness -- through ONE engine and against each other: they share one
+"""The seven clip analyses -- overviews, transients, tempo, pitch, loudness, loop points, key -- through ONE engine and against each other: they share one
 call scaffold in libzl_amd/csrc/zl_clip_calls.cpp (check, reserve, stage timer), which can go wrong only where a neighbour is present:
 a mixed-up buffer index, a timer shared by mistake, a read-back table overwritten by another service.  Expected values are the
-restatements' (tests/overview_ref.py, onset_ref.py, tempo_ref.py, pitch_ref.py, loudness_ref.py), compared as the per-service tests
-compare them: every integer and every debug array bit for bit, bpm, hz and confidence with ==, note and cents within 1e-9, lufs
-within 1e-9 (tests/test_pitch_gpu.py, tests/test_loudness_gpu.py)."""
+restatements' (tests/overview_ref.py, onset_ref.py, tempo_ref.py, pitch_ref.py, loudness_ref.py, loop_ref.py, key_ref.py), compared as the
+per-service tests compare them: every integer and every debug array bit for bit, bpm, hz and confidence with ==, note and cents within
+1e-9, lufs within 1e-9, the loop's three dB fields within 1e-9, the key's two confidences with == (tests/test_pitch_gpu.py,
+tests/test_loudness_gpu.py, tests/test_loop_gpu.py, tests/test_key_gpu.py)."""
 import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
+import key_ref as kr
+import loop_checks as lc
 import loudness_ref as lr
 import onset_ref as onr
 import overview_ref as ov
@@ -23,7 +26,10 @@ SR = 48000.0
 LENGTH = 50000
 COLUMNS = 100
 TEMPO_INTS = ("lag_coarse", "lag_fine", "doublings", "shift", "hops", "acf_lo", "acf_mid", "acf_hi", "acf_zero", "sum")
-SERVICES = ("overview", "onsets", "tempo", "pitch", "loudness")
+SERVICES = ("overview", "onsets", "tempo", "pitch", "loudness", "loop", "key")
+# the loop finder's default request: 10 ms either way at 48 kHz, 961 x 961 candidate pairs -- one request keeps its cost matrix, a batch of 70 does not
+LOOP = dict(start_frame=12000, stop_frame=36011)
+KEY_INTS = kr.RESULT_INTS
 
 
 def _clip(ch, seed):
@@ -45,12 +51,14 @@ def _coeffs(rate):
 @pytest.fixture(scope="module")
 def wants(built):
     """per clip (mono, stereo): the planar source and every analysis' default request restated, computed once"""
+    from libzl_amd import _abi
     coeffs = _coeffs(SR)
     table = []
     for ch, seed in ((1, 0), (2, 1)):
         src = _clip(ch, seed)
         table.append(dict(src=src, overview=ov.overview(src, COLUMNS), onsets=onr.onsets(src, **onr.resolve(SR)), tempo=tr.tempo(src, SR),
-                          pitch=pr.pitch(src, SR, want_d=True), loudness=lr.measure(src, SR, coeffs=coeffs)))
+                          pitch=pr.pitch(src, SR, want_d=True), loudness=lr.measure(src, SR, coeffs=coeffs), loop=lc.want(src, SR, LOOP),
+                          key=kr.key(src, SR, *kr.library_table(_abi.load(), SR))))
     return table
 
 
@@ -98,6 +106,31 @@ def _loudness_subs_match(syn, i, want):
             and peaks.shape == want[2].shape and np.array_equal(peaks.view(np.uint32), want[2].view(np.uint32)))
 
 
+def _key_matches(got, want):
+    return (all(int(got[k]) == int(want[k]) for k in KEY_INTS) and tuple(got["chroma"]) == want["chroma"] and got["confidence"] == want["confidence"]
+            and got["second_confidence"] == want["second_confidence"])
+
+
+def _loop_costs_match(syn, i, want, kept):
+    """a single request keeps its cost matrix; the batch of 70 has more than 2^20 candidate pairs and keeps none (ZLHIP_ERR_STATE)"""
+    from libzl_amd import ZlHipError
+    if kept:
+        c = syn.loop_costs(i)
+        return c.dtype == np.uint32 and c.shape == want[2].shape == (961, 961) and np.array_equal(c.astype(np.int64), want[2])
+    with pytest.raises(ZlHipError, match=r"\(-5\)"):
+        syn.loop_costs(i)
+    return True
+
+
+def _key_read_backs_match(syn, i, want):
+    totals, frames = syn.key_bins(i), syn.key_frames(i)
+    ok = totals.dtype == np.uint64 and [int(v) for v in totals] == want[1] and frames == len(want[2]) and frames >= 2
+    for k in (0, frames - 1):
+        re, im = syn.key_frame(i, k)
+        ok = ok and re.dtype == np.int64 and [int(v) for v in re] == want[2][k]["re"] and [int(v) for v in im] == want[2][k]["im"]
+    return ok
+
+
 def _run(syn, service, ids, which, wants):
     """one call of `service` with the default request of clips which[0], which[1], ...; every result and, for the requests in `probe`,
     every read-back against the restatement.  Returns the results as comparable bytes / values (round 3 against round 1)."""
@@ -122,6 +155,17 @@ def _run(syn, service, ids, which, wants):
         assert all(_pitch_matches(o, wants[w]["pitch"][0]) for o, w in zip(outs, which)), service
         assert all(_pitch_frames_match(syn, i, wants[which[i]]["pitch"]) for i in probe), service
         return outs
+    if service == "loop":
+        outs = syn.clip_loop_batch([dict(LOOP, clip=c) for c in clips])
+        assert all(lc.same(o, wants[w]["loop"][0]) for o, w in zip(outs, which)), service
+        assert all(syn.loop_items(i) == wants[which[i]]["loop"][1] for i in probe), service
+        assert all(_loop_costs_match(syn, i, wants[which[i]]["loop"], len(which) == 1) for i in probe), service
+        return outs
+    if service == "key":
+        outs = syn.clip_key_batch([dict(clip=c) for c in clips])
+        assert all(_key_matches(o, wants[w]["key"][0]) for o, w in zip(outs, which)), service
+        assert all(_key_read_backs_match(syn, i, wants[which[i]]["key"]) for i in probe), service
+        return outs
     outs = syn.clip_loudness_batch([(c,) for c in clips])
     assert all(lr.same(o, wants[w]["loudness"][0]) for o, w in zip(outs, which)), service
     assert all(_loudness_subs_match(syn, i, wants[which[i]]["loudness"]) for i in probe), service
@@ -129,7 +173,8 @@ def _run(syn, service, ids, which, wants):
 
 
 def _timings(syn):
-    return (syn.overview_timings(),) + tuple(syn.onset_timings()) + tuple(syn.tempo_timings()) + tuple(syn.pitch_timings()) + (syn.loudness_timings(),)
+    return ((syn.overview_timings(),) + tuple(syn.onset_timings()) + tuple(syn.tempo_timings()) + tuple(syn.pitch_timings()) + (syn.loudness_timings(),)
+            + tuple(syn.loop_timings()) + tuple(syn.key_timings()))
 
 
 def test_every_call_on_one_engine_growing(wants):
@@ -151,7 +196,7 @@ def test_every_call_on_one_engine_growing(wants):
         assert syn.memory_bytes()[0] > total1                      # the buffers grew
         times = _timings(syn)
         print("stage times of the batches of 70 (ms):", times)
-        assert len(times) == 9 and all(math.isfinite(t) and t >= 0.0 for t in times), times
+        assert len(times) == 14 and all(math.isfinite(t) and t >= 0.0 for t in times), times
         syn.set_profiling(False)
         for service in SERVICES:
             assert [_run(syn, service, ids, [k], wants) for k in (0, 1)] == first[service], service

@@ -3,11 +3,13 @@ fed with the library's table): re and im of every frame and bin, the per-bin tot
 for bit, the two confidences with == (both sides run the same serial double arithmetic).  The shapes are the smallest at which the
 kernels can still go wrong: 8 kHz clips and narrowed note ranges, so a span is some hundred samples, unless a test says otherwise."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
 
 import key_ref as kr
+import rt_between_cycles as rtc
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -236,6 +238,129 @@ def test_key_follows_the_rerender(syn):
     syn.rerender_clip(cid)                                         # identity: the original upload plays again
     assert syn.clip_key(cid) == before
     syn.unregister_clip(cid)
+
+
+def test_key_follows_the_rate_conversion(syn):
+    """the bin table is built from the sound's rate: after convert_clips to 48 kHz the spans, the totals, re and im and the result are
+    those of the converted data at 48 kHz"""
+    src = _tone(2, 11025, (57, 61, 64), 51, sr=44100.0)
+    cid = _upload(syn, src, 44100.0)
+    r = dict(NARROW, clip=cid, hop=2000)
+    assert _table(44100.0, NARROW)[0][0][1] == 3408 and _table(48000.0, NARROW)[0][0][1] == 3710
+    bad, outs = _check_batch(syn, [r], {cid: src}, {cid: 44100.0})
+    assert not bad, bad
+    assert outs[0]["frames"] == 4 and (outs[0]["tonic"], outs[0]["mode"]) == (9, 0)
+    syn.convert_clips([cid], 48000.0)
+    L, R = syn.read_clip(cid)
+    played = np.stack([L, R])
+    assert syn.clip_info(cid)["sample_rate"] == 48000.0 and abs(played.shape[1] - 12000) <= 2
+    bad, outs = _check_batch(syn, [r, dict(r, first_frame=3, num_frames=played.shape[1] - 7, hop=700)], {cid: played}, {cid: 48000.0})
+    assert not bad, bad
+    assert outs[0]["frames"] == 5 and all((o["tonic"], o["mode"]) == (9, 0) and o["sounding"] == o["frames"] for o in outs)      # the same sound: A major
+    syn.unregister_clip(cid)
+
+
+@pytest.mark.parametrize("ch", [1, 2], ids=["mono", "stereo"])
+def test_a_neighbour_does_not_leak(built, ch):
+    """a quiet clip between two full-scale ones in a small arena that held noise, analysed from its first frame and to its last, whose
+    16-byte group lies partly behind the data: a neighbour's sample in a head or tail group would change re and im (a full-scale sample
+    is 2000 times a quiet one).  The quiet tone sounds under the default gate (amplitude 16 of 4096, mean square 134 per channel against
+    64); a gated frame would read 0 and hide a leak"""
+    from libzl_amd import SamplerSynth
+    with SamplerSynth(num_buses=1, voices_per_bus=1, max_sounds=8, sound_arena_bytes=2 << 20) as s:
+        rng = np.random.default_rng(9)
+        fill = [_upload(s, rng.uniform(-7.9, 7.9, (ch, 60000)).astype(f32)) for _ in range(3)]
+        for cid in fill:
+            s.unregister_clip(cid)
+        L = _table(SR, NARROW)[0][0][1]
+        for n in (6001, 3333):
+            loud = [rng.choice([-7.9, 7.9], (ch, m)).astype(f32) for m in (3001, 3003)]
+            t = np.arange(n)
+            quiet = np.stack([0.004 * np.sin(2 * np.pi * kr.hz_of(64) * t / SR + 0.4 * c) for c in range(ch)]).astype(f32)
+            ids = [_upload(s, x) for x in (loud[0], quiet, loud[1])]
+            srcs = dict(zip(ids, (loud[0], quiet, loud[1])))
+            # two frames each: the first begins at the request's first frame, the last ends at its last one
+            reqs = [dict(NARROW, clip=ids[1], hop=n - L), dict(NARROW, clip=ids[1], first_frame=1, num_frames=n - 1, hop=n - 1 - L),
+                    dict(NARROW, clip=ids[0], hop=3001 - L), dict(NARROW, clip=ids[2], hop=3003 - L)]
+            bad, outs = _check_batch(s, reqs, srcs)
+            assert not bad, bad
+            assert all(o["sounding"] == o["frames"] == 2 for o in outs), outs
+            assert 0 < max(int(np.abs(v).max()) for k in (0, 1) for v in s.key_frame(1, k)) < 1 << 28       # (a full-scale frame reaches 2^34)
+            for cid in ids:
+                s.unregister_clip(cid)
+
+
+def test_a_clip_in_a_grown_arena(built):
+    from libzl_amd import SamplerSynth
+    arena = 1 << 20
+    with SamplerSynth(num_buses=1, voices_per_bus=1, max_sounds=16, sound_arena_bytes=arena) as s:
+        notes = ((57, 61, 64), (62, 66, 69))
+        srcs = [_tone(1 + i % 2, 60000 + 1001 * i, notes[i % 2], 40 + i) for i in range(8)]
+        ids = [_upload(s, x) for x in srcs]
+        assert s.memory_bytes()[1] >= 3 * arena                    # the arena grew
+        bad, outs = _check_batch(s, [dict(NARROW, clip=cid, first_frame=1, num_frames=x.shape[1] - 3, hop=20000) for cid, x in zip(ids, srcs)], dict(zip(ids, srcs)))
+        assert not bad, bad
+        assert [(o["tonic"], o["frames"]) for o in outs] == [((9, 2)[i % 2], 3 + (i >= 1)) for i in range(8)]
+
+
+def test_an_engine_that_never_asks_allocates_nothing(built):
+    from libzl_amd import SamplerSynth
+    with SamplerSynth(num_buses=1, voices_per_bus=1, max_sounds=4, sound_arena_bytes=1 << 20) as s:
+        cid = _upload(s, _tone(2, 20000, (57, 61, 64), 2))
+        total0, _ = s.memory_bytes()
+        s.clip_loop(cid, 5000, 15000)
+        total1, _ = s.memory_bytes()
+        s.clip_key(cid, hop=500, **NARROW)
+        total2, _ = s.memory_bytes()
+        assert total2 > total1 > total0
+        s.clip_key(cid, hop=500, **NARROW); s.clip_key(cid, 3, 15000, hop=1000, **TINY); s.clip_loop(cid, 5000, 15000)       # fit the first call's buffers
+        assert s.memory_bytes()[0] == total2
+
+
+@pytest.fixture()
+def rt_env():
+    old = os.environ.get("ZL_RT_PERSISTENT")
+    os.environ["ZL_RT_PERSISTENT"] = "1"
+    yield
+    if old is None:
+        os.environ.pop("ZL_RT_PERSISTENT", None)
+    else:
+        os.environ["ZL_RT_PERSISTENT"] = old
+
+
+def test_the_resident_kernel_stays(built, rt_env):
+    """After one warm-up call (it allocates the call's buffers) key calls between real-time cycles leave the resident kernel where it
+    is: one launch of it for the whole scene, the cycles' audio bit-exact against the oracle, the results right.  The scene's clips are
+    1500 to 6000 frames at 22.05, 44.1 and 48 kHz: twelve notes from A4 up with q of 3 to 5 keep a span under 550 frames."""
+    sc = rtc.scene()
+    tone = _tone(2, 6000, (69, 73, 76), 5, sr=48000.0)             # one more clip, which no voice plays
+
+    def request(cid, k, planar):
+        n, first = planar[cid].shape[1], k % 5
+        return dict(clip=cid, note_lo=69, note_hi=80, q=(3, 5, 4)[k % 3], hop=(300, 500)[k % 2], first_frame=first, num_frames=min(n - first, 3000))
+
+    def warm_up(syn, planar, rates):
+        # more requests, bins, analysis frames and (frame, bin) pairs than any call below
+        outs = syn.clip_key_batch([dict(clip=i, note_lo=69, note_hi=80, q=3, hop=100) for i in range(len(planar))] + [dict(clip=len(planar) - 1, note_lo=69, note_hi=80, q=3, hop=100)] * 4)
+        assert len(outs) == 25 and sum(o["frames"] for o in outs) > 500
+
+    def between(syn, k, playing, planar, rates):
+        # the keys of clips that play, a single call and a batch in turn
+        reqs = [request(cid, k, planar) for cid in playing[:2]] + [request(len(planar) - 1, k, planar)]
+        gots = [syn.clip_key_batch([r])[0] for r in reqs] if k % 2 else syn.clip_key_batch(reqs)
+        return zip(reqs, gots)
+
+    out, ref_bus, stats, todo, planar, rates = rtc.run(sc, [(tone, 48000.0)], warm_up, between)
+    assert stats[0] == 1 and stats[1:] == (1, sc.nblocks)
+    expect = {}
+    for r, got in todo:
+        key = tuple(sorted(r.items()))
+        if key not in expect:
+            expect[key] = _want(planar[r["clip"]], rates[r["clip"]], r)[0]
+        assert _same(got, expect[key]), (r, got, expect[key])
+    assert max(g["frames"] for _, g in todo) <= 11
+    assert len(todo) >= 2 * sc.nblocks and sum(g["tonic"] >= 0 for _, g in todo) >= sc.nblocks
+    assert np.array_equal(out.view(np.int32), ref_bus.view(np.int32)), f"max diff {np.abs(out - ref_bus).max()}"
 
 
 def test_group_key_equals_the_single_engine(syn):

@@ -79,13 +79,25 @@ def test_tones_loop_on_a_whole_number_of_periods(period, channels):
 
 
 # ---- (b) exact ties -----------------------------------------------------------------------------------------------------------------
+def nearest_zero(period, s0, e0):
+    """where the order sends a nominal loop on a signal of exact period with both ranges reaching a period either way: the nearest
+    zero -- shorten by off or lengthen by period - off, whichever is less; among the ways to spread that over the two points the smallest
+    s wins: the start moves down as far as the distance lets it, or the stop moves down while the start stays"""
+    off = (e0 - s0) % period                                       # the nominal loop is `off` frames longer than a whole number of periods
+    down, up = off, period - off
+    if off == 0:
+        return (s0, e0)
+    if down < up:
+        return (s0, e0 - down)                                     # s stays (moving it up would be a larger s), e comes down
+    return (s0 - up, e0)                                           # lengthen (or a draw between the two): the smallest s is s0 - up with e at e0
+
+
 @pytest.mark.parametrize("period", [16, 100])
 def test_exact_ties_go_to_the_nearest_pair_then_the_smaller_start_then_the_smaller_end(period):
     """An integer-valued signal of exact period: every pair whose length is a whole number of periods costs 0, so the order's later rules
     decide -- the smallest |s - s0| + |e - e0|, then the smallest s, then the smallest e"""
     x = lr.square(period, 12000)
-    for s0, e0, R in ((4000, 4000 + 50 * period, 70), (4003, 4003 + 50 * period + period // 2, 70), (4001, 4001 + 30 * period + 3, 70), (4002, 4002 + 30 * period - 5, 70),
-                      (4000, 4000 + 50 * period + 1, -1)):
+    for s0, e0, R in [(s0, e0, 70) for s0, e0 in lr.tie_nominals(period)] + [(4000, 4000 + 50 * period + 1, -1)]:
         r, items, cost = lr.loop(x, SR, s0, e0, R, R, 64, want=True)
         off = (e0 - s0) % period                                   # the nominal loop is `off` frames longer than a whole number of periods
         assert r["found"] == 1 and r["shift"] == 0
@@ -93,15 +105,7 @@ def test_exact_ties_go_to_the_nearest_pair_then_the_smaller_start_then_the_small
             assert (r["start_frame"], r["stop_frame"]) == (s0, e0) and (r["cost"] == 0) == (off == 0)
             continue
         assert r["cost"] == 0 and r["seam_db"] == -120.0 and (r["stop_frame"] - r["start_frame"]) % period == 0
-        # the nearest zero: shorten by off or lengthen by period - off, whichever is less; among the ways to spread that over the two points the
-        # smallest s wins: the start moves down as far as the distance lets it, or the stop moves down while the start stays
-        down, up = off, period - off
-        if off == 0:
-            want = (s0, e0)
-        elif down < up:
-            want = (s0, e0 - down)                                 # s stays (moving it up would be a larger s), e comes down
-        else:
-            want = (s0 - up, e0)                                   # lengthen (or a draw between the two): the smallest s is s0 - up with e at e0
+        want = nearest_zero(period, s0, e0)
         assert (r["start_frame"], r["stop_frame"]) == want, (period, s0, e0, r)
         zeros = int((cost == 0).sum())
         assert zeros >= (2 * R + 1) ** 2 // period - 2 * R - 1     # (ties everywhere: a rule that looked at the cost alone would not get here)
@@ -203,6 +207,44 @@ def test_the_grid_equals_the_restatement(form):
     assert 0 < d["pairs"] < d["starts"] * d["ends"] and d["stop_frame"] - d["start_frame"] >= 40       # min_length cuts the tiles
     assert by["both kept"][0]["pairs"] == 1 and by["both kept"][0]["improvement_db"] == 0.0
     assert all(res["nominal_valid"] == 1 for what, (res, _) in by.items() if what.startswith("W"))
+
+
+def test_the_tie_cases_tie_where_they_are_meant_to():
+    """lr.ties() from the restatement alone, before anything runs on a device: every square and silence case has at least 100
+    admissible pairs of cost 0 in at least 6 of its items; over the list the winner lies in at least 4 different item indices and in
+    all four waves of the pairs workgroup; each later rule -- distance, smaller start, smaller end -- decides at least one result"""
+    cases = lr.ties()
+    facts = {what: lr.tie_facts(x, SR, q) for what, x, q in cases}
+    assert len(facts) == len(cases)
+    for what, x, q in cases:
+        f = facts[what]
+        print(f"{what:26s} zero {f['zero']:5d} in {f['zero_items']:2d}/{f['items']:<2d} item {f['item']:2d} wave {f['wave']} rule {f['rule']}")
+        assert x.shape[1] <= 12000 and q["window"] == 64
+        res = lr.loop(x, SR, *(q.get(k, 0) for k in lr.KEYS))
+        assert (res["start_frame"], res["stop_frame"], res["cost"], res["den"]) == f["winner"] and res["cost"] == 0
+        assert lr.better(f["winner"], f["runner_up"], q["start_frame"], q["stop_frame"]) and f["runner_up"][2] == 0 and f["rule"] != "cost"
+        if what.startswith(("square", "silence")):
+            assert f["zero"] >= 100 and f["zero_items"] >= 6, (what, f)
+    assert len({f["item"] for f in facts.values()}) >= 4, sorted({f["item"] for f in facts.values()})
+    assert {f["wave"] for f in facts.values()} == {0, 1, 2, 3}
+    assert {f["rule"] for f in facts.values()} == {"distance", "start", "end"}
+    assert facts["silence too short"]["winner"][:2] != (5000, 5100) and facts["square 16 stereo shift 5"]["winner"][3] < facts["square 16 n1 r70"]["winner"][3]
+
+
+@pytest.mark.parametrize("form", sorted(FORMS))
+def test_the_ties_equal_the_restatement(form):
+    """lr.ties() through the harness walk in one call: every cost, every item record and every result, as for the grid; the four
+    symmetric nominals of either period land where the closed form says"""
+    cases = lr.ties()
+    out = call([(x, SR, q) for _, x, q in cases], FORMS[form])
+    by = {what: res for (what, _, _), (res, _, _) in zip(cases, out)}
+    for period in (16, 100):
+        for k, (s0, e0) in enumerate(lr.tie_nominals(period)):
+            res = by[f"square {period} n{k} r70"]
+            assert (res["start_frame"], res["stop_frame"]) == nearest_zero(period, s0, e0) and res["pairs"] == 141 * 141 and res["shift"] == 0
+    assert by["square 16 stereo shift 5"]["shift"] == 5 and by["silence"]["den"] == 1 and by["constant 0.1"]["den"] > 1 << 20
+    assert all(res["found"] == 1 and res["cost"] == 0 and res["seam_db"] == -120.0 for res in by.values())
+    assert by["silence too short"]["nominal_valid"] == 0 and by["silence last frame"]["nominal_valid"] == 0
 
 
 def test_a_call_with_empty_requests_between_the_others():

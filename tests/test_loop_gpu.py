@@ -7,40 +7,11 @@ import numpy as np
 import pytest
 
 import loop_ref as lr
+from loop_checks import SR, check_batch as _check_batch, same as _same, upload as _upload
 from scenario import Scene, play_cmd, run_backend, run_oracle
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-SR = 48000.0
-
-
-def _upload(syn, src, sr=SR):
-    return syn.register_clip(src[0], src[1] if src.shape[0] == 2 else None, sr)
-
-
-def _want(src, rate, r):
-    return lr.loop(src, rate, *(r.get(k, 0) for k in lr.KEYS), want=True)
-
-
-def _same(got, want):
-    return all(int(got[k]) == int(want[k]) for k in lr.RESULT_INTS) and all(abs(float(got[k]) - float(want[k])) <= 1e-9 for k in lr.RESULT_DBS)
-
-
-def _check_batch(syn, reqs, srcs, costs=True):
-    """reqs: dicts with "clip" and zlhip_loop_request's fields; srcs: {clip: planar}.  The costs, the item records and the result of every
-    request against the restatement; returns the mismatches and the results"""
-    bad = []
-    outs = syn.clip_loop_batch(reqs)
-    for i, (r, got) in enumerate(zip(reqs, outs)):
-        res, items, cost = _want(srcs[r["clip"]], SR, r)
-        okI = syn.loop_items(i) == items
-        okC = True
-        if costs:
-            c = syn.loop_costs(i)
-            okC = c.dtype == np.uint32 and c.shape == cost.shape and np.array_equal(c.astype(np.int64), cost)
-        if not (okI and okC and _same(got, res)):
-            bad.append((srcs[r["clip"]].shape, r, "items" if not okI else "costs" if not okC else ("result", got, res)))
-    return bad, outs
 
 
 @pytest.fixture(scope="module")

@@ -154,6 +154,47 @@ def test_special_values(syn):
             syn.unregister_clip(cid)
 
 
+@pytest.mark.parametrize("ch", [1, 2], ids=["mono", "stereo"])
+def test_a_neighbour_does_not_leak(built, ch):
+    """a quiet clip between two full-scale ones in a small arena that held noise, measured from its first frame and to its last, whose
+    16-byte group lies partly behind the data: a neighbour's sample in a head or tail group would show in a sum and in a peak (a
+    full-scale sample is 2000 times a quiet one)"""
+    from libzl_amd import SamplerSynth
+    with SamplerSynth(num_buses=1, voices_per_bus=1, max_sounds=8, sound_arena_bytes=2 << 20) as s:
+        rng = np.random.default_rng(9)
+        fill = [_upload(s, rng.uniform(-7.9, 7.9, (ch, 60000)).astype(f32)) for _ in range(3)]
+        for cid in fill:
+            s.unregister_clip(cid)
+        for n in (6001, 3333):
+            loud = [rng.choice([-7.9, 7.9], (ch, m)).astype(f32) for m in (3001, 3003)]
+            quiet = _clip(ch, n, n, level=0.004)
+            ids = [_upload(s, x) for x in (loud[0], quiet, loud[1])]
+            srcs = dict(zip(ids, (loud[0], quiet, loud[1])))
+            assert n % 64 and (n - 1) % 64
+            reqs = [dict(clip=ids[0]), dict(clip=ids[1]), dict(clip=ids[2]),                             # the whole clips: the last group's tail is masked
+                    dict(clip=ids[1], sub_frames=64), dict(clip=ids[1], first_frame=1, num_frames=n - 1, sub_frames=64),
+                    dict(clip=ids[0], first_frame=3, num_frames=2998, sub_frames=100)]
+            bad, outs = _check_batch(s, reqs, srcs)
+            assert not bad, bad
+            assert all(0.0 < max(outs[i]["peak"]) < 0.01 for i in (1, 3, 4)) and all(max(outs[i]["peak"]) == float(f32(7.9)) for i in (0, 2, 5))
+            assert outs[3]["lufs"] < -40.0 < 0.0 < outs[0]["lufs"]
+            for cid in ids:
+                s.unregister_clip(cid)
+
+
+def test_a_clip_in_a_grown_arena(built):
+    from libzl_amd import SamplerSynth
+    arena = 1 << 20
+    with SamplerSynth(num_buses=1, voices_per_bus=1, max_sounds=16, sound_arena_bytes=arena) as s:
+        srcs = [_clip(1 + i % 2, 60000 + 1001 * i, 40 + i, level=0.05 * (i + 1)) for i in range(8)]
+        ids = [_upload(s, x) for x in srcs]
+        assert s.memory_bytes()[1] >= 3 * arena                    # the arena grew
+        bad, outs = _check_batch(s, [dict(clip=cid, first_frame=1, num_frames=x.shape[1] - 3, sub_frames=1000) for cid, x in zip(ids, srcs)], dict(zip(ids, srcs)))
+        assert not bad, bad
+        assert [o["sub_blocks"] for o in outs] == [(x.shape[1] - 3) // 1000 for x in srcs] and all(-30.0 < o["lufs"] < -5.0 for o in outs)
+        assert all(a["lufs"] < b["lufs"] for a, b in zip(outs, outs[2:]))                  # (each louder than the last one with its channel count)
+
+
 def test_loudness_follows_the_rendered_data(syn):
     """after a re-render (gain and pitch) and after a rate conversion the rendered extent is what gets measured"""
     from libzl_amd import ZlHipError
