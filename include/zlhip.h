@@ -43,7 +43,7 @@ extern "C" {
  *    zlhip_sound_pitch / _batch (a clip's pitch, detected on the device), zlhip_pitch_resolve, zlhip_sound_loudness / _batch (a clip's
  *    loudness, measured on the device), zlhip_loudness_resolve, zlhip_loudness_design, zlhip_sound_loop / _batch (a clip's seamless
  *    loop points, found on the device), zlhip_loop_resolve, zlhip_loop_seconds, zlhip_sound_key / _batch (a clip's musical
- *    key, detected on the device), zlhip_key_resolve, zlhip_key_design. */
+ *    key, detected on the device), zlhip_key_resolve, zlhip_key_design, zlhip_debug_live_resources. */
 #define ZLHIP_ABI_VERSION 3
 
 /* status codes */
@@ -608,6 +608,11 @@ int zlhip_voice_reports(zlhip_engine *e, zlhip_voice_report *out, int32_t count)
  * kept on device and read back with zlhip_debug_read_trace: out [nblocks][voices][nframes] int32 */
 int zlhip_debug_enable_trace(zlhip_engine *e, int enable);   /* bit 0: trace; bits 1, 2: planner test hooks */
 int zlhip_debug_read_trace(zlhip_engine *e, int32_t *out, size_t out_ints);
+/* debug: the HIP resources the process's engines hold at this moment -- counts[0..3] = device buffers, page-locked host buffers,
+ * events, streams.  Process-wide, no engine: whatever an engine took while it lived, its destruction gives back (a host asserting
+ * a clean shutdown reads the same four numbers before its first engine and after its last).  Not counted: the arena's later
+ * segments, memory from zlhip_host_alloc, an engine group's own events. */
+int zlhip_debug_live_resources(int32_t counts[4]);
 
 /* ---- levels -------------------------------------------------------------------------------- */
 /* One AudioLevels timer tick for every bus over block `block_index` of the last batch

@@ -307,6 +307,7 @@ SIGNATURES = {
     "zlhip_voice_reports": (C.c_int, [_E, C.POINTER(VoiceReport), C.c_int32]),
     "zlhip_debug_enable_trace": (C.c_int, [_E, C.c_int]),
     "zlhip_debug_read_trace": (C.c_int, [_E, C.c_void_p, C.c_size_t]),
+    "zlhip_debug_live_resources": (C.c_int, [C.POINTER(C.c_int32)]),
     "zlhip_levels_tick": (C.c_int, [_E, C.c_int32, C.c_int32, C.POINTER(Levels)]),
     "zlhip_block_peaks": (C.c_int, [_E, C.c_void_p, C.c_size_t]),
     "zlhip_levels_scan_device": (C.c_int, [_E, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),

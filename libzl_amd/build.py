@@ -20,7 +20,7 @@ LIBDIR = os.path.join(ROOT, "libzl_amd", "lib")
 LIB = os.path.join(LIBDIR, "libzlhip.so")
 
 HIP_SOURCES = ["zl_kernels.hip", "zl_stretch.hip", "zl_overview.hip", "zl_onset.hip", "zl_tempo.hip", "zl_pitch.hip", "zl_loudness.hip", "zl_loop.hip", "zl_key.hip", "zl_decode.hip", "zl_resample.hip", "zl_engine.cpp", "zl_clip_calls.cpp", "zl_libzl.cpp", "zl_group.cpp"]
-HEADERS = ["zl_types.h", "zl_arena.h", "zl_plan.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_render.h", "zl_kernels.h", "zl_host.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", "zl_overview.h", "zl_onset.h", "zl_tempo.h", "zl_pitch.h", "zl_loudness.h", "zl_loop.h", "zl_key.h", "zl_decode.h", "zl_resample.h", "zl_group.h", "zl_member.h", "zl_engine_impl.h",
+HEADERS = ["zl_types.h", "zl_arena.h", "zl_plan.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_render.h", "zl_kernels.h", "zl_host.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", "zl_overview.h", "zl_onset.h", "zl_tempo.h", "zl_pitch.h", "zl_loudness.h", "zl_loop.h", "zl_key.h", "zl_decode.h", "zl_resample.h", "zl_group.h", "zl_member.h", "zl_owned.h", "zl_engine_impl.h",
            os.path.join("..", "..", "include", "zlhip.h"), os.path.join("..", "..", "include", "libzl_hotpath.h")]
 
 
@@ -78,9 +78,9 @@ SOURCE_DEPS = {
     "zl_decode.hip": ["zl_types.h", "zl_decode.h"],
     "zl_resample.hip": ["zl_types.h", "zl_resample.h"],
     # (zl_stretch.h: through zl_arena.h)
-    "zl_engine.cpp": ["zl_types.h", "zl_arena.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_engine_impl.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h")],
+    "zl_engine.cpp": ["zl_types.h", "zl_arena.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_owned.h", "zl_engine_impl.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h")],
     # the clip services: the engine's state and the services' own headers, none of the render kernels'
-    "zl_clip_calls.cpp": ["zl_types.h", "zl_arena.h", "zl_plan.h", "zl_host.h", "zl_engine_impl.h", "zl_stretch.h", "zl_overview.h", "zl_onset.h", "zl_tempo.h", "zl_pitch.h", "zl_loudness.h", "zl_loop.h", "zl_key.h", "zl_decode.h", "zl_resample.h", os.path.join(_INC, "zlhip.h")],
+    "zl_clip_calls.cpp": ["zl_types.h", "zl_arena.h", "zl_plan.h", "zl_host.h", "zl_owned.h", "zl_engine_impl.h", "zl_stretch.h", "zl_overview.h", "zl_onset.h", "zl_tempo.h", "zl_pitch.h", "zl_loudness.h", "zl_loop.h", "zl_key.h", "zl_decode.h", "zl_resample.h", os.path.join(_INC, "zlhip.h")],
     "zl_group.cpp": ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_group.h", os.path.join(_INC, "zlhip.h")],
     "zl_libzl.cpp": ["zl_render.h", "zl_types.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h"), os.path.join(_INC, "libzl_hotpath.h")],
 }

@@ -131,7 +131,7 @@ int zlhip_sound_upload_pcm_batch(zlhip_engine *e, const zlhip_pcm_source *srcs, 
     const bool prof = e->profiling;
     const size_t nev = prof ? 2 * passes.size() + 1 : 0;
     int krc = 0;
-    while (krc == 0 && P.ev.size() < nev) { hipEvent_t ev = nullptr; krc = (int)hipEventCreate(&ev); if (krc == 0) P.ev.push_back(ev); }
+    while (krc == 0 && P.ev.size() < nev) { ZlEvent ev; krc = (int)ev.create(); if (krc == 0) P.ev.push_back(std::move(ev)); }
     if (krc == 0) krc = (int)hipMemsetAsync(dVerdicts, 0, (size_t)count * sizeof(uint32_t), e->stream);
     if (krc == 0) krc = (int)hipMemcpyAsync(dPieces, pieces.data(), pieces.size() * sizeof(ZlDecPiece), hipMemcpyHostToDevice, e->stream);
     if (krc == 0) krc = (int)hipMemcpyAsync(dPub, pub.data(), pub.size() * sizeof(ZlDecPublish), hipMemcpyHostToDevice, e->stream);
@@ -353,12 +353,12 @@ static int rs_table(zlhip_engine *e, const ZlRsGeom &g, float **out)
     t.pending.resize(t.floats);
     zl_rs_design(g, t.pending.data());
     bool ok;
-    { ZlQuiesce quiet(e); ok = hipMalloc((void **)&t.d, t.floats * sizeof(float)) == hipSuccess; }
+    { ZlQuiesce quiet(e); ok = t.d.alloc(t.floats) == hipSuccess; }
     if (!ok) { (void)hipGetLastError(); e->rs.tables.pop_back(); return fail(e, ZLHIP_ERR_CAPACITY, "sound_convert_rate: no device memory for the filter table"); }
     if (hipMemcpyAsync(t.d, t.pending.data(), t.floats * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess) {
         (void)hipGetLastError();
         (void)hipStreamSynchronize(e->stream);
-        { ZlQuiesce quiet(e); (void)hipFree(t.d); }
+        { ZlQuiesce quiet(e); t.d.reset(); }
         e->rs.tables.pop_back();
         return fail(e, ZLHIP_ERR_HIP, "sound_convert_rate: the filter table did not reach the device");
     }
@@ -374,7 +374,7 @@ static void rs_tables_undo(zlhip_engine *e, size_t keep)
     (void)hipStreamSynchronize(e->stream);
     rs_tables_settled(e);
     while (e->rs.tables.size() > keep) {
-        { ZlQuiesce quiet(e); (void)hipFree(e->rs.tables.back().d); }
+        { ZlQuiesce quiet(e); e->rs.tables.back().d.reset(); }
         e->deviceBytes -= e->rs.tables.back().floats * sizeof(float);
         e->rs.tables.pop_back();
     }

@@ -33,18 +33,6 @@
 // buses at least this wide are split into one voice per workgroup for single real-time blocks (pick_group)
 #define ZL_RT_SPLIT_MIN_VOICES 32
 
-namespace {
-
-size_t g_alloc_bytes = 0;          // device bytes allocated by the engine being created (zlhip_engine_create is not re-entrant)
-template <typename T> hipError_t dalloc(T **p, size_t n)
-{
-    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-    g_alloc_bytes += bytes;
-    return hipMalloc((void **)p, bytes);
-}
-
-}  // namespace
-
 int fail(zlhip_engine *e, int code, const char *msg)
 {
     if (e) e->err = msg;
@@ -100,10 +88,10 @@ ZlQuiesce::ZlQuiesce(const zlhip_engine *self)
         {
             std::lock_guard<std::mutex> lk(g_rt.mu);
             for (zlhip_engine *o : g_rt.engines) {
-                if (o == self || !o->rt.h) continue;
-                __atomic_store_n(&o->rt.h->yield, 1u, __ATOMIC_RELEASE);
+                if (o == self || !o->rt.mail.h) continue;
+                __atomic_store_n(&o->rt.mail.h->yield, 1u, __ATOMIC_RELEASE);
                 // (a kernel that was just launched reads the request at its first idle poll)
-                if (__atomic_load_n(&o->rt.h->state, __ATOMIC_ACQUIRE) != 2u) all = false;
+                if (__atomic_load_n(&o->rt.mail.h->state, __ATOMIC_ACQUIRE) != 2u) all = false;
             }
         }
         // (one second: thousands of cycles)
@@ -115,7 +103,7 @@ ZlQuiesce::~ZlQuiesce()
 {
     std::lock_guard<std::mutex> lk(g_rt.mu);
     if (g_rt.quiescing.fetch_sub(1, std::memory_order_acq_rel) == 1)
-        for (zlhip_engine *o : g_rt.engines) if (o->rt.h) __atomic_store_n(&o->rt.h->yield, 0u, __ATOMIC_RELEASE);
+        for (zlhip_engine *o : g_rt.engines) if (o->rt.mail.h) __atomic_store_n(&o->rt.mail.h->yield, 0u, __ATOMIC_RELEASE);
 }
 
 // ---- resident real-time kernel ------------------------------------------------------------------
@@ -125,9 +113,9 @@ ZlQuiesce::~ZlQuiesce()
 int rt_stop(zlhip_engine *e)
 {
     if (!e->rt.running) return ZLHIP_OK;
-    __atomic_store_n(&e->rt.h->stop, 1u, __ATOMIC_RELEASE);
+    __atomic_store_n(&e->rt.mail.h->stop, 1u, __ATOMIC_RELEASE);
     ZL_HIP(e, hipStreamSynchronize(e->rt.stream));
-    __atomic_store_n(&e->rt.h->stop, 0u, __ATOMIC_RELEASE);
+    __atomic_store_n(&e->rt.mail.h->stop, 0u, __ATOMIC_RELEASE);
     e->rt.running = false;
     rt_unregister(e);
     return ZLHIP_OK;
@@ -149,17 +137,9 @@ int call_begin(zlhip_engine *e, bool stop)
 int grow_buf(zlhip_engine *e, GrowBuf &b, size_t need, size_t elem, size_t new_cap, bool twin, const char *what)
 {
     if (need <= b.cap) return ZLHIP_OK;
-    if (b.d) { (void)hipFree(b.d); e->deviceBytes -= b.cap * elem; }
-    if (b.h) (void)hipHostFree(b.h);
-    b = GrowBuf();
-    if ((twin && hipHostMalloc(&b.h, new_cap * elem) != hipSuccess) || hipMalloc(&b.d, new_cap * elem) != hipSuccess) {
-        (void)hipGetLastError();
-        if (b.h) (void)hipHostFree(b.h);
-        b = GrowBuf();
-        return fail(e, ZLHIP_ERR_CAPACITY, what);
-    }
+    if (b.d) e->deviceBytes -= b.cap * elem;
+    if (b.grow(need, new_cap, new_cap * elem, twin) != hipSuccess) { (void)hipGetLastError(); return fail(e, ZLHIP_ERR_CAPACITY, what); }
     e->deviceBytes += new_cap * elem;
-    b.cap = new_cap;
     return ZLHIP_OK;
 }
 
@@ -175,7 +155,7 @@ int alloc_extent(zlhip_engine *e, size_t floats, size_t *out_off)
     if (hipMalloc((void **)&seg, (segFloats + 1024) * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return fail(e, ZLHIP_ERR_CAPACITY, "sound arena full (no memory for another segment)"); }
     e->deviceBytes += (segFloats + 1024) * sizeof(float);
     // float offset of the segment from `arena`, modulo 2^64 (exact: both are multiples of 4 bytes)
-    const int64_t diffBytes = (int64_t)((uintptr_t)seg - (uintptr_t)e->arena);
+    const int64_t diffBytes = (int64_t)((uintptr_t)seg - (uintptr_t)e->arena.p);
     a.add_segment(seg, (size_t)(uint64_t)(diffBytes / 4), segFloats);
     (void)a.take(floats, out_off);                                 // (the segment's first floats)
     return ZLHIP_OK;
@@ -184,7 +164,7 @@ int alloc_extent(zlhip_engine *e, size_t floats, size_t *out_off)
 // (integer arithmetic: a segment below the first arena in the address space has an offset that wraps -- no pointer ever leaves its allocation)
 float *arena_ptr(const zlhip_engine *e, uint64_t off)
 {
-    return reinterpret_cast<float *>((uintptr_t)e->arena + (uintptr_t)off * sizeof(float));
+    return reinterpret_cast<float *>((uintptr_t)e->arena.p + (uintptr_t)off * sizeof(float));
 }
 
 // an arena extent goes back to the free list.  A later arena segment whose every float is free again goes back to the device (the first
@@ -249,63 +229,16 @@ void zlhip_engine_destroy(zlhip_engine *e)
     (void)hipSetDevice(e->device);
     (void)rt_stop(e);
     rt_unregister(e);
-    ZlQuiesce quiet(e);                 // the frees below wait for the device: no other engine's resident kernel may be on it
+    ZlQuiesce quiet(e);                 // the frees below, `delete e` included, wait for the device: no other engine's resident kernel may be on it
     if (e->rt.stampsOn && e->rt.stampN)
         std::fprintf(stderr, "zlhip resident kernel (workgroup 0), mean us per block over %llu blocks: K0 %.2f  K1 %.2f  K1c %.2f  K2 %.2f  reports + release %.2f\n", e->rt.stampN,
                      e->rt.stampSum[0] / e->rt.stampN, e->rt.stampSum[1] / e->rt.stampN, e->rt.stampSum[2] / e->rt.stampN, e->rt.stampSum[3] / e->rt.stampN,
                      e->rt.stampSum[4] / e->rt.stampN);
-    if (e->rt.stream) (void)hipStreamDestroy(e->rt.stream);
-    if (e->rt.h) (void)hipHostFree(e->rt.h);
-    if (e->rt.dev) (void)hipFree(e->rt.dev);
-    if (e->rt.devRanges) (void)hipFree(e->rt.devRanges);
     for (auto &c : e->slots) if (c.inflight && c.done) (void)hipEventSynchronize(c.done);   // calls queued on a caller's stream
     for (hipEvent_t ev : e->joins) if (ev) (void)hipEventSynchronize(ev);
-    if (e->stream) (void)hipStreamSynchronize(e->stream);
-    if (e->planStream) (void)hipStreamSynchronize(e->planStream);
-    if (e->asmStream) (void)hipStreamSynchronize(e->asmStream);
+    for (const ZlStream *x : { &e->stream, &e->planStream, &e->asmStream, &e->bnc.copyStream, &e->rt.stream }) if (*x) (void)hipStreamSynchronize(*x);
+    // every wait lies above, every free below: the arena's later segments here, everything else in the members' destructors (zl_owned.h)
     for (auto &seg : e->arenaAlloc.segments) if (seg.handle) (void)hipFree(seg.handle);
-    for (auto &b : e->scratch) { if (b.d) (void)hipFree(b.d); if (b.h) (void)hipHostFree(b.h); }
-    for (auto &t : e->rs.tables) if (t.d) (void)hipFree(t.d);
-    void *dev[] = { e->arena, e->dSounds, e->dClips, e->dVoices, e->dGain, e->dBus, e->dLevels, e->dLevelState, e->dTrace, e->dPass, e->dPassCache };
-    for (void *p : dev) if (p) (void)hipFree(p);
-    for (auto &q : e->ps) {
-        void *pd[] = { q.vconst, q.runs, q.tsegs, q.hdr, q.seg0, q.seg1, q.ctlP, q.ctlEnv, q.partials, q.ctlNext, q.simConst, q.order };
-        for (void *p : pd) if (p) (void)hipFree(p);
-        if (q.planned) (void)hipEventDestroy(q.planned);
-        if (q.rendered) (void)hipEventDestroy(q.rendered);
-        if (q.k1done) (void)hipEventDestroy(q.k1done);
-    }
-    for (auto &c : e->slots) {
-        void *cd[] = { c.dReports, c.dStats, c.dPass };
-        for (void *p : cd) if (p) (void)hipFree(p);
-        void *ch[] = { c.hClocks, c.hReports, c.hGain, c.hStats, c.hPass, c.hOps, c.hRanges, c.hEdits };
-        for (void *p : ch) if (p) (void)hipHostFree(p);
-        for (auto &x : c.evK2) if (x) (void)hipEventDestroy(x);
-        hipEvent_t evs[] = { c.evBegin, c.evEnd, c.doneEv[0], c.doneEv[1] };
-        for (hipEvent_t x : evs) if (x) (void)hipEventDestroy(x);
-    }
-    if (e->bnc.copyStream) { (void)hipStreamSynchronize(e->bnc.copyStream); (void)hipStreamDestroy(e->bnc.copyStream); }
-    for (int i = 0; i < zlhip_engine::Bounce::NBUF; ++i) {
-        if (e->bnc.bus[i]) (void)hipFree(e->bnc.bus[i]);
-        if (e->bnc.pcm[i]) (void)hipFree(e->bnc.pcm[i]);
-        if (e->bnc.copied[i]) (void)hipEventDestroy(e->bnc.copied[i]);
-    }
-    for (hipEvent_t ev : e->bnc.winEv) if (ev) (void)hipEventDestroy(ev);
-    if (e->planStream) (void)hipStreamDestroy(e->planStream);
-    if (e->asmStream) (void)hipStreamDestroy(e->asmStream);
-    void *host[] = { e->hBus, e->hLevelState, e->hFan, e->hPassRt, e->hNonFinite };
-    for (void *p : host) if (p) (void)hipHostFree(p);
-    e->st.timer.release(); e->ov.timer.release(); e->rs.timer.release();
-    e->on.timer.release(); e->on.counts.release(); e->on.out.release();
-    e->tp.timer.release(); e->tp.out.release();
-    e->pt.timer.release(); e->pt.out.release();
-    e->ld.timer.release(); e->ld.out.release();
-    e->lp.timer.release(); e->lp.out.release();
-    e->ky.timer.release(); e->ky.out.release();
-    for (hipEvent_t ev : e->pcm.ev) if (ev) (void)hipEventDestroy(ev);
-    if (e->evJoin) (void)hipEventDestroy(e->evJoin);
-    if (e->evPlanTail) (void)hipEventDestroy(e->evPlanTail);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
 
@@ -335,7 +268,6 @@ int zlhip_engine_create(const zlhip_config *cfg_in, zlhip_engine **out)
     if (hipSetDevice(cfg->device) != hipSuccess) return ZLHIP_ERR_NO_DEVICE;
 
     zlhip_engine *e = new zlhip_engine();
-    g_alloc_bytes = 0;
     e->cfg = *cfg;
     e->device = cfg->device;
     e->V = cfg->num_buses * cfg->voices_per_bus;
@@ -350,11 +282,14 @@ int zlhip_engine_create(const zlhip_config *cfg_in, zlhip_engine **out)
     auto chk = [&](hipError_t st, const char *what) {
         if (st != hipSuccess && rc == ZLHIP_OK) { e->err = std::string(what) + ": " + hipGetErrorString(st); rc = ZLHIP_ERR_HIP; }
     };
-    chk(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking), "hipStreamCreate");
-    chk(dalloc(&e->arena, e->arenaAlloc.arenaFloats + 1024), "arena");     // + 4 KB: wide loads at the end of the last source stay inside
-    chk(dalloc(&e->dSounds, (size_t)cfg->max_sounds), "sounds");
-    chk(dalloc(&e->dClips, (size_t)cfg->max_sounds), "clips");
-    chk(dalloc(&e->dVoices, V), "voices");
+    // n elements on the device (at least one), counted into deviceBytes.  After creation scratch[], the rate-conversion tables and the
+    // arena's segments are counted; the position trace, K2's order tables, the resident kernel's words and the bounce buffers are not
+    auto dev = [&](auto &buf, size_t n, const char *what) { n = std::max<size_t>(n, 1); e->deviceBytes += n * sizeof(*buf.p); chk(buf.alloc(n), what); };
+    chk(e->stream.create(), "hipStreamCreate");
+    dev(e->arena, e->arenaAlloc.arenaFloats + 1024, "arena");     // + 4 KB: wide loads at the end of the last source stay inside
+    dev(e->dSounds, (size_t)cfg->max_sounds, "sounds");
+    dev(e->dClips, (size_t)cfg->max_sounds, "clips");
+    dev(e->dVoices, V, "voices");
     {
         // plan window: a call is cut into windows of ~512 Ki frames (2048 blocks of 256 frames; K2 launches of that
         // size reach the kernel's steady-state bandwidth) or of plan_window_blocks blocks when that is given; the
@@ -373,11 +308,11 @@ int zlhip_engine_create(const zlhip_config *cfg_in, zlhip_engine **out)
             // planning is a small latency-bound kernel that rendering waits for: give its stream the highest priority
             int lo = 0, hi = 0;
             (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-            chk(hipStreamCreateWithPriority(&e->planStream, hipStreamNonBlocking, hi), "plan stream");
+            chk(e->planStream.create(&hi), "plan stream");
             // a second planning stream pays only when it gets a hardware queue of its own (the runtime's default is 4
             // per process: two streams sharing one serialise behind each other's kernels)
             const char *hwq = std::getenv("GPU_MAX_HW_QUEUES");
-            if (hwq && std::atoi(hwq) >= 6) chk(hipStreamCreateWithPriority(&e->asmStream, hipStreamNonBlocking, hi), "assemble stream");
+            if (hwq && std::atoi(hwq) >= 6) chk(e->asmStream.create(&hi), "assemble stream");
         }
         const size_t minWindow = e->windowBlocks > 0 ? (size_t)e->windowBlocks : std::max<size_t>(1, e->windowFrames / N);
         // two record sets: windows of one call, and consecutive calls, are planned while the previous one renders
@@ -385,16 +320,14 @@ int zlhip_engine_create(const zlhip_config *cfg_in, zlhip_engine **out)
         const int nsets = (K > minWindow || K * N >= 65536) ? 2 : 1;
         for (int i = 0; i < 2; ++i) {
             zlhip_engine::PlanSet &q = e->ps[i];
-            chk(hipEventCreateWithFlags(&q.planned, hipEventDisableTiming), "event");
-            chk(hipEventCreateWithFlags(&q.rendered, hipEventDisableTiming), "event");
-            chk(hipEventCreateWithFlags(&q.k1done, hipEventDisableTiming), "event");
+            for (ZlEvent *x : { &q.planned, &q.rendered, &q.k1done }) chk(x->create(hipEventDisableTiming), "event");
             if (i >= nsets) continue;
-            chk(dalloc(&q.vconst, V), "vconst");
-            chk(dalloc(&q.runs, V), "run lists");
-            chk(dalloc(&q.tsegs, V * (size_t)ZL_MAXTSEG), "segment streams");
-            chk(dalloc(&q.hdr, W * V), "plan headers");
-            chk(dalloc(&q.seg0, W * V), "plan segment 0");
-            chk(dalloc(&q.seg1, W * V), "plan segment 1");
+            dev(q.vconst, V, "vconst");
+            dev(q.runs, V, "run lists");
+            dev(q.tsegs, V * (size_t)ZL_MAXTSEG, "segment streams");
+            dev(q.hdr, W * V, "plan headers");
+            dev(q.seg0, W * V, "plan segment 0");
+            dev(q.seg1, W * V, "plan segment 1");
             // per-frame control of the window's slow (block, voice)s: a pool of block-sized slots.  One slot for every (block, voice)
             // of a window would be 12 bytes per voice-frame (6.4 GB per set for 1024 voices); slow blocks are sparse (release tails of
             // one-shots, the block behind a loop restart), so the pool is capped -- ZL_CTL_POOL_MB per set, default 256 -- and a
@@ -406,69 +339,54 @@ int zlhip_engine_create(const zlhip_config *cfg_in, zlhip_engine **out)
                 const char *so = std::getenv("ZL_CTL_POOL_SLOTS");
                 if (so) e->ctlSlotsOverride = std::max(0, std::atoi(so));
             }
-            chk(dalloc(&q.ctlP, e->ctlPoolFrames), "ctlP");
-            chk(dalloc(&q.ctlEnv, e->ctlPoolFrames), "ctlEnv");
-            chk(dalloc(&q.ctlNext, 1), "ctlNext");
-            chk(dalloc(&q.simConst, V), "simConst");
+            dev(q.ctlP, e->ctlPoolFrames, "ctlP");
+            dev(q.ctlEnv, e->ctlPoolFrames, "ctlEnv");
+            dev(q.ctlNext, 1, "ctlNext");
+            dev(q.simConst, V, "simConst");
             if (rc == ZLHIP_OK) chk(hipMemsetAsync(q.ctlNext, 0, sizeof(unsigned long long), e->stream), "memset ctlNext");
             {
                 // mix-group partials of a window; or, for the per-voice split of single real-time blocks, of one block
                 size_t pf = e->maxGroups > 1 ? ctlFrames * B * (size_t)e->maxGroups * 2 : 1;
                 if (cfg->voices_per_task <= 0 && cfg->voices_per_bus >= ZL_RT_SPLIT_MIN_VOICES) pf = std::max(pf, N * V * 2);
-                chk(dalloc(&q.partials, pf), "partials");
+                dev(q.partials, pf, "partials");
             }
         }
         const size_t nwin = (K + minWindow - 1) / minWindow + 16; // + the doubling windows at the start of a call
         e->wins.reserve(nwin);
         for (auto &c : e->slots) {
-            c.evK2.assign(2 * nwin, nullptr);
-            for (auto &x : c.evK2) chk(hipEventCreate(&x), "hipEventCreate");
-            chk(hipEventCreate(&c.evBegin), "hipEventCreate");
-            chk(hipEventCreate(&c.evEnd), "hipEventCreate");
-            chk(hipEventCreate(&c.doneEv[0]), "hipEventCreate");   // (they can ride on a kernel dispatch as its stop event)
-            chk(hipEventCreate(&c.doneEv[1]), "hipEventCreate");
+            c.evK2.resize(2 * nwin);
+            for (auto &x : c.evK2) chk(x.create(), "hipEventCreate");
+            for (ZlEvent *x : { &c.evBegin, &c.evEnd, &c.doneEv[0], &c.doneEv[1] }) chk(x->create(), "hipEventCreate");   // (timing events: doneEv can ride on a kernel dispatch as its stop event)
             c.done = c.doneEv[0];
 
-            chk(dalloc(&c.dReports, V), "reports");
-            chk(dalloc(&c.dStats, 1), "stats");
-            chk(hipHostMalloc((void **)&c.hClocks, K * sizeof(ZlClock)), "hClocks");
-            if (rc == ZLHIP_OK) chk(hipHostGetDevicePointer((void **)&c.hClocksDev, c.hClocks, 0), "hClocks device view");
-            chk(dalloc(&c.dPass, B), "fan-out params");
-            chk(hipHostMalloc((void **)&c.hPass, std::max<size_t>(B, 1) * sizeof(ZlPassParams)), "hPass");
-            chk(hipHostMalloc((void **)&c.hReports, V * sizeof(ZlReport)), "hReports");
-            chk(hipHostMalloc((void **)&c.hGain, V * sizeof(float)), "hGain");
-            chk(hipHostMalloc((void **)&c.hStats, sizeof(ZlBatchStats)), "hStats");
+            dev(c.dReports, V, "reports");
+            dev(c.dStats, 1, "stats");
+            chk(c.clocks.alloc(K), "hClocks");
+            dev(c.dPass, B, "fan-out params");
+            chk(c.pass.alloc(std::max<size_t>(B, 1)), "hPass");
+            chk(c.reports.alloc(V), "hReports");
+            chk(c.gain.alloc(V), "hGain");
+            chk(c.stats.alloc(1), "hStats");
             // room for a cycle's clip-parameter edits without ever growing (growing frees pinned memory, which waits for the device)
-            c.editsCap = (size_t)std::min(cfg->max_sounds, 64);
-            chk(hipHostMalloc((void **)&c.hEdits, c.editsCap * sizeof(ZlClipEdit)), "hEdits");
-            if (rc == ZLHIP_OK) chk(hipHostGetDevicePointer((void **)&c.hEditsDev, c.hEdits, 0), "map hEdits");
+            chk(c.edits.alloc((size_t)std::min(cfg->max_sounds, 64)), "hEdits");
             // ... and for its voice operations: two per voice (a stop and a start of every voice in one cycle) before anything grows
-            if (rc == ZLHIP_OK) chk(grow_mapped(&c.hOps, &c.hOpsDev, &c.opsCap, V + 32), "hOps");
-            if (rc == ZLHIP_OK) chk(grow_mapped(&c.hRanges, &c.hRangesDev, &c.rangesCap, V + 32), "hRanges");
-            if (rc == ZLHIP_OK) {
-                chk(hipHostGetDevicePointer((void **)&c.hReportsDev, c.hReports, 0), "map hReports");
-                chk(hipHostGetDevicePointer((void **)&c.hGainDev, c.hGain, 0), "map hGain");
-                chk(hipHostGetDevicePointer((void **)&c.hStatsDev, c.hStats, 0), "map hStats");
-            }
+            chk(c.ops.grow(V + 32), "hOps");
+            chk(c.ranges.grow(V + 32), "hRanges");
         }
     }
-    chk(dalloc(&e->dGain, V), "gain");
-    chk(dalloc(&e->dPassCache, V), "pass cache");
-    chk(dalloc(&e->dBus, B * 2 * K * N), "bus");
-    chk(dalloc(&e->dLevels, K * B), "levels");
-    chk(dalloc(&e->dLevelState, B), "levelState");
-    chk(dalloc(&e->dPass, B), "passthrough params");
-    chk(hipHostMalloc((void **)&e->hBus, B * 2 * N * sizeof(float)), "hBus");
-    if (rc == ZLHIP_OK) chk(hipHostGetDevicePointer((void **)&e->hBusDev, e->hBus, 0), "map hBus");
-    chk(hipHostMalloc((void **)&e->hFan, B * 6 * N * sizeof(float)), "hFan");
-    if (rc == ZLHIP_OK) chk(hipHostGetDevicePointer((void **)&e->hFanDev, e->hFan, 0), "map hFan");
-    chk(hipHostMalloc((void **)&e->hPassRt, B * sizeof(ZlPassParams)), "hPassRt");
-    if (rc == ZLHIP_OK) { chk(hipHostGetDevicePointer((void **)&e->hPassRtDev, e->hPassRt, 0), "map hPassRt"); std::memset(e->hPassRt, 0xff, B * sizeof(ZlPassParams)); }
-    chk(hipHostMalloc((void **)&e->hLevelState, B * sizeof(ZlLevelsState)), "hLevelState");
-    chk(hipHostMalloc((void **)&e->hNonFinite, sizeof(uint32_t)), "hNonFinite");
-    if (rc == ZLHIP_OK) { chk(hipHostGetDevicePointer((void **)&e->hNonFiniteDev, e->hNonFinite, 0), "map hNonFinite"); *e->hNonFinite = 1u; }
-    chk(hipEventCreateWithFlags(&e->evJoin, hipEventDisableTiming), "hipEventCreate");
-    chk(hipEventCreateWithFlags(&e->evPlanTail, hipEventDisableTiming), "hipEventCreate");
+    dev(e->dGain, V, "gain");
+    dev(e->dPassCache, V, "pass cache");
+    dev(e->dBus, B * 2 * K * N, "bus");
+    dev(e->dLevels, K * B, "levels");
+    dev(e->dLevelState, B, "levelState");
+    dev(e->dPass, B, "passthrough params");
+    chk(e->hBus.alloc(B * 2 * N), "hBus");
+    chk(e->hFan.alloc(B * 6 * N), "hFan");
+    chk(e->hPassRt.alloc(B), "hPassRt");
+    chk(e->hLevelState.alloc(B), "hLevelState");
+    chk(e->hNonFinite.alloc(1), "hNonFinite");
+    if (rc == ZLHIP_OK) { std::memset(e->hPassRt.h, 0xff, B * sizeof(ZlPassParams)); *e->hNonFinite.h = 1u; }
+    for (ZlEvent *x : { &e->evJoin, &e->evPlanTail }) chk(x->create(hipEventDisableTiming), "hipEventCreate");
     if (rc == ZLHIP_OK) {
         chk(hipMemsetAsync(e->dSounds, 0, (size_t)cfg->max_sounds * sizeof(ZlSound), e->stream), "memset sounds");
         chk(hipMemsetAsync(e->dClips, 0, (size_t)cfg->max_sounds * sizeof(ZlClip), e->stream), "memset clips");
@@ -515,9 +433,8 @@ int zlhip_engine_create(const zlhip_config *cfg_in, zlhip_engine **out)
     }
     e->hc.init(cfg->num_buses, cfg->voices_per_bus, cfg->max_sounds, cfg->playback_sample_rate);
     e->soundSlots.assign((size_t)cfg->max_sounds, zlhip_engine::SoundSlot());
-    for (auto &c : e->slots) { std::memset(c.hReports, 0, V * sizeof(ZlReport)); std::memset(c.hStats, 0, sizeof(ZlBatchStats)); }
+    for (auto &c : e->slots) { std::memset(c.reports.h, 0, V * sizeof(ZlReport)); std::memset(c.stats.h, 0, sizeof(ZlBatchStats)); }
     e->latest = &e->slots[0];
-    e->deviceBytes = g_alloc_bytes;
     *out = e;
     return ZLHIP_OK;
 }
@@ -563,7 +480,7 @@ static void free_sound_slot(zlhip_engine *e, int id)
     free_extent(e, played, slot.renderFloats);
 }
 
-// dev_checked: the extent was written by zl_k_interleave, which leaves its verdict on the samples in *hNonFinite -- read after the wait
+// dev_checked: the extent was written by zl_k_interleave, which leaves its verdict on the samples in *hNonFinite.h -- read after the wait
 // that is here anyway; a finite source then gets ZL_SOUND_FINITE (the table entry goes to the device once more, in stream order)
 // ZL_K2_ONGRID: 0 = K2 never takes the one-tap form of on-grid unit-step chunks, 1 = wherever its condition holds (default); read per call
 // (A/B runs of one build, tests that compare both forms).  Results do not depend on it.
@@ -583,7 +500,7 @@ static int publish_sound(zlhip_engine *e, int id, bool dev_checked = false)
     zlhip_clip_params p;
     zlhip_clip_params_default(&p, (float)(e->hc.sounds[id].length / e->hc.sounds[id].sample_rate));
     { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
-    if (dev_checked && __atomic_load_n(e->hNonFinite, __ATOMIC_ACQUIRE) == 0u) {
+    if (dev_checked && __atomic_load_n(e->hNonFinite.h, __ATOMIC_ACQUIRE) == 0u) {
         e->hc.sounds[id].flags |= ZL_SOUND_FINITE;
         e->soundSlots[(size_t)id].orig.flags |= ZL_SOUND_FINITE;
         ZL_HIP(e, hipMemcpyAsync(e->dSounds + id, &e->hc.sounds[id], sizeof(ZlSound), hipMemcpyHostToDevice, e->stream));
@@ -628,8 +545,8 @@ static int sound_upload_device(zlhip_engine *e, const float *left_dev, const flo
         ZlQuiesce quiet(e);
         st = hipDeviceSynchronize();
     }
-    __atomic_store_n(e->hNonFinite, 0u, __ATOMIC_RELEASE);         // (nothing of this engine's is in flight that writes it: see the waits above)
-    int krc = st == hipSuccess ? zl_launch_interleave(left_dev, right_dev, dst, length, 8, e->hNonFiniteDev, e->stream) : (int)st;
+    __atomic_store_n(e->hNonFinite.h, 0u, __ATOMIC_RELEASE);         // (nothing of this engine's is in flight that writes it: see the waits above)
+    int krc = st == hipSuccess ? zl_launch_interleave(left_dev, right_dev, dst, length, 8, e->hNonFinite.d, e->stream) : (int)st;
     if (krc != 0) {
         free_sound_slot(e, *out_id); *out_id = -1;
         e->err = std::string("sound_upload_device: ") + hipGetErrorString((hipError_t)krc);
@@ -744,7 +661,7 @@ static int refresh_host_voices(zlhip_engine *e)
         if (rc != ZLHIP_OK) return rc;
     }
     if (e->reportsFresh) {
-        e->hc.absorb_reports(e->latest->hReports);
+        e->hc.absorb_reports(e->latest->reports.h);
         e->reportsFresh = false;
     }
     return ZLHIP_OK;
@@ -842,22 +759,22 @@ static int upload_ops(zlhip_engine *e, zlhip_engine::CallSlot &c, ZlBatch &A)
     A.n_op_ranges = 0; A.ops = nullptr; A.op_ranges = nullptr; A.n_clip_edits = 0; A.clip_edits = nullptr;
     const size_t ne = e->hc.pendingClipEdits.size();
     if (ne > 0) {
-        if (ne > c.editsCap) { ZlQuiesce quiet(e); ZL_HIP(e, grow_mapped(&c.hEdits, &c.hEditsDev, &c.editsCap, ne)); }
-        std::memcpy(c.hEdits, e->hc.pendingClipEdits.data(), ne * sizeof(ZlClipEdit));
+        if (ne > c.edits.cap) { ZlQuiesce quiet(e); ZL_HIP(e, c.edits.grow(ne)); }
+        std::memcpy(c.edits.h, e->hc.pendingClipEdits.data(), ne * sizeof(ZlClipEdit));
         e->hc.pendingClipEdits.clear();
-        A.n_clip_edits = (int)ne; A.clip_edits = c.hEditsDev;
+        A.n_clip_edits = (int)ne; A.clip_edits = c.edits.d;
     }
     const size_t n = e->hc.pendingOps.size();
     if (n == 0) return ZLHIP_OK;
-    if (n > c.opsCap || n > c.rangesCap) {
+    if (n > c.ops.cap || n > c.ranges.cap) {
         ZlQuiesce quiet(e);                                        // growing frees pinned memory, which waits for the device
-        ZL_HIP(e, grow_mapped(&c.hOps, &c.hOpsDev, &c.opsCap, n));
-        ZL_HIP(e, grow_mapped(&c.hRanges, &c.hRangesDev, &c.rangesCap, n));
+        ZL_HIP(e, c.ops.grow(n));
+        ZL_HIP(e, c.ranges.grow(n));
     }
-    e->hc.drain_ops_to(c.hOps, e->ranges);
-    ZL_HIP(e, grow_mapped(&c.hRanges, &c.hRangesDev, &c.rangesCap, e->ranges.size()));
-    std::memcpy(c.hRanges, e->ranges.data(), e->ranges.size() * sizeof(ZlOpRange));
-    A.n_op_ranges = (int)e->ranges.size(); A.ops = c.hOpsDev; A.op_ranges = c.hRangesDev;
+    e->hc.drain_ops_to(c.ops.h, e->ranges);
+    ZL_HIP(e, c.ranges.grow(e->ranges.size()));
+    std::memcpy(c.ranges.h, e->ranges.data(), e->ranges.size() * sizeof(ZlOpRange));
+    A.n_op_ranges = (int)e->ranges.size(); A.ops = c.ops.d; A.op_ranges = c.ranges.d;
     return ZLHIP_OK;
 }
 
@@ -882,7 +799,7 @@ static int harvest_slot(zlhip_engine *e, zlhip_engine::CallSlot &c)
     t.plan_ms = first;                                             // planning that is NOT hidden behind rendering
     t.finalize_ms = t.total_ms - k2 - first;                       // K3 + reports + gaps between launches
     t.render_launches = c.windows;
-    t.source_bytes = c.hStats->source_bytes; t.slow_blocks = c.hStats->slow_blocks; t.active_voice_frames = c.hStats->active_frames;
+    t.source_bytes = c.stats.h->source_bytes; t.slow_blocks = c.stats.h->slow_blocks; t.active_voice_frames = c.stats.h->active_frames;
     e->timings = t;
     e->totals.plan_ms += t.plan_ms; e->totals.render_ms += t.render_ms; e->totals.finalize_ms += t.finalize_ms; e->totals.total_ms += t.total_ms;
     e->totals.render_launches += t.render_launches; e->totals.source_bytes += t.source_bytes; e->totals.slow_blocks += t.slow_blocks;
@@ -960,9 +877,9 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
     const auto tSlot = std::chrono::steady_clock::now();
     bool regular = true;                                           // monotone time, one period: lets K1 bisect for loop restarts
     for (int k = 0; k < nblocks; ++k) {
-        ZlHostControl::fill_clock(c.hClocks[k], clocks[k], nframes);
-        if (c.hClocks[k].usecs_per_frame >= (1ull << 21) || c.hClocks[k].usecs_per_frame != c.hClocks[0].usecs_per_frame
-            || (k > 0 && c.hClocks[k].current_usecs < c.hClocks[k - 1].current_usecs)) regular = false;
+        ZlHostControl::fill_clock(c.clocks.h[k], clocks[k], nframes);
+        if (c.clocks.h[k].usecs_per_frame >= (1ull << 21) || c.clocks.h[k].usecs_per_frame != c.clocks.h[0].usecs_per_frame
+            || (k > 0 && c.clocks.h[k].current_usecs < c.clocks.h[k - 1].current_usecs)) regular = false;
     }
 
     ZlBatch A; std::memset(&A, 0, sizeof A);
@@ -984,8 +901,8 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
         const size_t need = (size_t)nblocks * e->V * nframes;
         if (need > e->traceInts) {
             ZlQuiesce quiet(e);
-            if (e->dTrace) ZL_HIP(e, hipFree(e->dTrace));
-            ZL_HIP(e, dalloc(&e->dTrace, need));
+            e->traceInts = 0;
+            ZL_HIP(e, e->dTrace.alloc(need));
             e->traceInts = need;
         }
         ZL_HIP(e, hipMemsetAsync(e->dTrace, 0xff, need * sizeof(int32_t), s));
@@ -1054,9 +971,8 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
             ZlQuiesce quiet(e);                                    // (as for the trace buffer: hipFree waits for the whole device)
             for (auto &q : e->ps) {
                 if (need <= q.orderInts || q.hdr == nullptr) continue;
-                if (q.order) ZL_HIP(e, hipFree(q.order));
-                q.order = nullptr; q.orderInts = 0;
-                ZL_HIP(e, dalloc(&q.order, need));
+                q.orderInts = 0;
+                ZL_HIP(e, q.order.alloc(need));
                 q.orderInts = need;
             }
         }
@@ -1073,10 +989,10 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
     // The block clocks stay where fill_clock wrote them, in host memory mapped into the device (like the voice operations): the planner
     // reads them at a voice's first block, in simulated blocks, and stage by stage for beat-locked loops.  (A copy command here blocked
     // the host for 6-7 ms every now and then -- hipMemcpyAsync on the planning stream, seen at the fifth call of a run.)
-    if (nblocks == 1) { A.inline_clock = 1; A.clock0 = c.hClocks[0]; A.fuse_assemble = 1; }   // a real-time block: the clock travels with the kernel arguments
+    if (nblocks == 1) { A.inline_clock = 1; A.clock0 = c.clocks.h[0]; A.fuse_assemble = 1; }   // a real-time block: the clock travels with the kernel arguments
     if (fan_out_dev) {                                             // the rendering stream is ordered behind ps by the window events
-        for (int b = 0; b < A.B; ++b) c.hPass[b] = pass_params(fan_params[b]);
-        ZL_HIP(e, hipMemcpyAsync(c.dPass, c.hPass, (size_t)A.B * sizeof(ZlPassParams), hipMemcpyHostToDevice, ps));
+        for (int b = 0; b < A.B; ++b) c.pass.h[b] = pass_params(fan_params[b]);
+        ZL_HIP(e, hipMemcpyAsync(c.dPass, c.pass.h, (size_t)A.B * sizeof(ZlPassParams), hipMemcpyHostToDevice, ps));
         A.pass = c.dPass; A.fan = fan_out_dev;
     }
     int rc = upload_ops(e, c, A);
@@ -1103,7 +1019,7 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
         ZlBatch Aw = A;
         Aw.k0 = wins[(size_t)w].first;
         Aw.K = wins[(size_t)w].second;
-        Aw.clocks = c.hClocksDev + Aw.k0;
+        Aw.clocks = c.clocks.d + Aw.k0;
         Aw.levels = e->dLevels + (size_t)Aw.k0 * A.B;
         Aw.pos_trace = traceBase ? traceBase + (size_t)Aw.k0 * e->V * nframes : nullptr;
         Aw.vconst = q.vconst; Aw.runs = q.runs; Aw.tsegs = q.tsegs; Aw.plan_hdr = q.hdr; Aw.plan_seg0 = q.seg0; Aw.plan_seg1 = q.seg1;
@@ -1140,7 +1056,7 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
         if (direct) { Aw.host_out = e->bnc.sink.hostDev; Aw.host_fmt = e->bnc.sink.pcm ? 1 : 0; Aw.host_total = (long long)e->bnc.sink.totalFrames; Aw.host_k0 = 0; }
         // profiling: the K2 dispatch carries its own start / stop events (hipExtLaunchKernel); the call's last launch carries `done`
         const bool closes = fusedReports && w == nwin - 1;
-        if (fusedReports) { Aw.fused_reports = 1; Aw.rep_gain = e->dGain; Aw.rep_host = c.hReportsDev; Aw.rep_host_gain = c.hGainDev; Aw.rep_host_stats = c.hStatsDev; }
+        if (fusedReports) { Aw.fused_reports = 1; Aw.rep_gain = e->dGain; Aw.rep_host = c.reports.d; Aw.rep_host_gain = c.gain.d; Aw.rep_host_stats = c.stats.d; }
         Aw.pair = (L.kernel == ZL_K2_PAIR_RENDER || L.kernel == ZL_K2_PAIR_PHASE_RENDER) ? 1 : 0;
         hipEvent_t k2stop = closes ? c.done : (e->profiling ? c.evK2[2 * (size_t)w + 1] : nullptr);
         ZL_KERNEL(e, zl_launch_render(Aw, L, s, e->profiling ? c.evK2[2 * (size_t)w] : nullptr, k2stop));
@@ -1168,7 +1084,7 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
     if (fusedReports) {
         if (e->profiling) c.profiled = true;                      // (total = evBegin .. done, the last K2 launch's stop event)
     } else {
-        ZL_KERNEL(e, zl_launch_reports(c.dReports, e->V, e->dGain, c.hReportsDev, c.hGainDev, c.dStats, c.hStatsDev, s, e->profiling ? nullptr : c.done));
+        ZL_KERNEL(e, zl_launch_reports(c.dReports, e->V, e->dGain, c.reports.d, c.gain.d, c.dStats, c.stats.d, s, e->profiling ? nullptr : c.done));
         if (e->profiling) { ZL_HIP(e, hipEventRecord(c.evEnd, s)); c.profiled = true; ZL_HIP(e, hipEventRecord(c.done, s)); }
     }
     c.inflight = true;
@@ -1250,10 +1166,10 @@ int zlhip_bounce(zlhip_engine *e, int64_t nblocks, int32_t nframes, const zlhip_
     chunk = std::min<int64_t>(std::min<int64_t>(chunk, e->cfg.max_batch_blocks), nblocks);
     const bool pcm = format == ZLHIP_BOUNCE_PCM16_STEREO;
     zlhip_engine::Bounce &q = e->bnc;
-    if (!q.copyStream) {
-        ZL_HIP(e, hipStreamCreateWithFlags(&q.copyStream, hipStreamNonBlocking));
-        for (int i = 0; i < NBUF; ++i) ZL_HIP(e, hipEventCreateWithFlags(&q.copied[i], hipEventDisableTiming));
-        for (hipEvent_t &ev : q.winEv) ZL_HIP(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    if (!q.copyStream) {                                           // (the stream last: where it exists, so do the events)
+        for (ZlEvent &ev : q.copied) ZL_HIP(e, ev.create(hipEventDisableTiming));
+        for (ZlEvent &ev : q.winEv) ZL_HIP(e, ev.create(hipEventDisableTiming));
+        ZL_HIP(e, q.copyStream.create());
     }
     const int nbuf = nblocks > chunk ? NBUF : 1;
     const size_t needFloats = (size_t)B * 2 * (size_t)chunk * (size_t)nframes, needFrames = (size_t)B * (size_t)chunk * (size_t)nframes;
@@ -1263,21 +1179,17 @@ int zlhip_bounce(zlhip_engine *e, int64_t nblocks, int32_t nframes, const zlhip_
         ZL_HIP(e, hipStreamSynchronize(q.copyStream));
         ZlQuiesce quiet(e);                                        // hipFree waits for the device
         const size_t nf = std::max(q.busFloats, needFloats), np = pcm ? std::max(q.pcmFrames, needFrames) : q.pcmFrames;
-        for (int i = 0; i < nbuf; ++i) {
-            if (!q.bus[i] || q.busFloats < nf) {
-                if (q.bus[i]) { ZL_HIP(e, hipFree(q.bus[i])); q.bus[i] = nullptr; }
-                ZL_HIP(e, hipMalloc((void **)&q.bus[i], nf * sizeof(float)));
-            }
-            if (pcm && (!q.pcm[i] || q.pcmFrames < np)) {
-                if (q.pcm[i]) { ZL_HIP(e, hipFree(q.pcm[i])); q.pcm[i] = nullptr; }
-                ZL_HIP(e, hipMalloc((void **)&q.pcm[i], np * 2 * sizeof(int16_t)));
-            }
+        // every buffer that exists holds busFloats / pcmFrames: too small ones go first -- also a second buffer this bounce does not
+        // need, which is allocated again when one needs it -- and a failure leaves none
+        hipError_t chunkBuffers = hipSuccess;
+        for (int i = 0; i < NBUF; ++i) {
+            if (q.busFloats < nf) q.bus[i].reset();
+            if (q.pcmFrames < np) q.pcm[i].reset();
+            if (i < nbuf && chunkBuffers == hipSuccess && !q.bus[i]) chunkBuffers = q.bus[i].alloc(nf);
+            if (i < nbuf && chunkBuffers == hipSuccess && pcm && !q.pcm[i]) chunkBuffers = q.pcm[i].alloc(np * 2);
         }
-        // (a second buffer allocated earlier at a smaller size is dropped: it is allocated again when a bounce needs it)
-        for (int i = nbuf; i < NBUF; ++i) {
-            if (q.bus[i] && q.busFloats < nf) { ZL_HIP(e, hipFree(q.bus[i])); q.bus[i] = nullptr; }
-            if (q.pcm[i] && q.pcmFrames < np) { ZL_HIP(e, hipFree(q.pcm[i])); q.pcm[i] = nullptr; }
-        }
+        if (chunkBuffers != hipSuccess) { q.busFloats = q.pcmFrames = 0; for (int i = 0; i < NBUF; ++i) { q.bus[i].reset(); q.pcm[i].reset(); } }
+        ZL_HIP(e, chunkBuffers);
         q.busFloats = nf; q.pcmFrames = np;
     }
     q.active = true;
@@ -1344,8 +1256,8 @@ static bool rt_fits(const zlhip_engine *e)
 {
     double used = 0.0;
     for (const zlhip_engine *o : g_rt.engines) {
-        if (o == e || o->device != e->device || !o->rt.h) continue;
-        if (__atomic_load_n(&o->rt.h->state, __ATOMIC_ACQUIRE) != 2u || o->rt.inCycle.load(std::memory_order_acquire)) used += o->rt.share;
+        if (o == e || o->device != e->device || !o->rt.mail.h) continue;
+        if (__atomic_load_n(&o->rt.mail.h->state, __ATOMIC_ACQUIRE) != 2u || o->rt.inCycle.load(std::memory_order_acquire)) used += o->rt.share;
     }
     return used + e->rt.share <= 0.75;
 }
@@ -1357,13 +1269,18 @@ static int rt_start(zlhip_engine *e, int nframes)
     { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
     for (auto &c : e->slots) if (c.inflight) { ZL_HIP(e, hipEventSynchronize(c.done)); c.inflight = false; int h_ = harvest_slot(e, c); if (h_ != ZLHIP_OK) return h_; }
     if (e->planStream) ZL_HIP(e, hipStreamSynchronize(e->planStream));
-    if (!e->rt.h) {
-        ZL_HIP(e, hipHostMalloc((void **)&e->rt.h, sizeof(ZlRtShared)));
-        ZL_HIP(e, hipHostGetDevicePointer((void **)&e->rt.d, e->rt.h, 0));
-        std::memset(e->rt.h, 0, sizeof(ZlRtShared));
-        ZL_HIP(e, hipStreamCreateWithFlags(&e->rt.stream, hipStreamNonBlocking));
-        ZL_HIP(e, hipMalloc((void **)&e->rt.dev, sizeof(ZlRtDev)));
-        ZL_HIP(e, hipMalloc((void **)&e->rt.devRanges, (size_t)std::max(e->V, 1) * sizeof(ZlOpRange)));   // at most one range per voice
+    if (!e->rt.mail.h) {
+        // all four or none: the engine takes them only when every one exists (the mailbox last: it is what says they do)
+        ZlMapped<ZlRtShared> mail; ZlStream stream; ZlDev<ZlRtDev> dev; ZlDev<ZlOpRange> devRanges;
+        if (mail.alloc(1) != hipSuccess || stream.create() != hipSuccess || dev.alloc(1) != hipSuccess
+            || devRanges.alloc((size_t)std::max(e->V, 1)) != hipSuccess) {                           // (at most one range per voice)
+            (void)hipGetLastError();
+            ZlQuiesce quiet(e);                                    // (the frees wait for the device)
+            mail.reset(); dev.reset(); devRanges.reset();
+            return fail(e, ZLHIP_ERR_HIP, "no memory for the resident kernel's mailbox, stream and hand-off words");
+        }
+        std::memset(mail.h, 0, sizeof(ZlRtShared));
+        e->rt.stream = std::move(stream); e->rt.dev = std::move(dev); e->rt.devRanges = std::move(devRanges); e->rt.mail = std::move(mail);
     }
     // the hand-off words start from the last block the previous residency finished
     {
@@ -1383,8 +1300,8 @@ static int rt_start(zlhip_engine *e, int nframes)
     A.mode = e->cfg.mode;
     A.ongrid = zl_ongrid_switch();                                 // (the resident kernel keeps the value it was started with)
     A.sounds = e->dSounds; A.clips = e->dClips; A.arena = e->arena; A.voices = e->dVoices; A.reports = c.dReports; A.pass_cache = e->dPassCache;
-    A.bus = e->hBusDev; A.stats = nullptr; A.levels = e->dLevels;
-    A.fan = e->hFanDev; A.pass = e->hPassRtDev;                     // a cycle says whether it wants the fan-out (ZlRtShared::fan_seq)
+    A.bus = e->hBus.d; A.stats = nullptr; A.levels = e->dLevels;
+    A.fan = e->hFan.d; A.pass = e->hPassRt.d;                     // a cycle says whether it wants the fan-out (ZlRtShared::fan_seq)
     A.vconst = q.vconst; A.runs = q.runs; A.tsegs = q.tsegs; A.plan_hdr = q.hdr; A.plan_seg0 = q.seg0; A.plan_seg1 = q.seg1;
     A.ctl_P = q.ctlP; A.ctl_env = q.ctlEnv; A.partials = q.partials; A.ctl_next = q.ctlNext; A.sim_const = q.simConst;
     A.ctl_slots = e->ctlSlotsOverride >= 0 ? std::min<int>(e->ctlSlotsOverride, (int)(e->ctlPoolFrames / (size_t)nframes)) : (int)std::min<size_t>(e->ctlPoolFrames / (size_t)nframes, 0x7fffffff);
@@ -1394,10 +1311,10 @@ static int rt_start(zlhip_engine *e, int nframes)
     std::lock_guard<std::mutex> lk(g_rt.mu);
     if (g_rt.quiescing.load(std::memory_order_acquire) > 0) return ZL_RT_BUSY;
     if (!rt_fits(e)) return ZL_RT_NOFIT;
-    __atomic_store_n(&e->rt.h->state, 0u, __ATOMIC_RELEASE);
-    __atomic_store_n(&e->rt.h->yield, 0u, __ATOMIC_RELEASE);
-    for (uint32_t &d : e->rt.h->wg_done) __atomic_store_n(&d, (uint32_t)e->rt.seq, __ATOMIC_RELAXED);   // (no workgroup has finished the cycle to come)
-    ZL_KERNEL(e, zl_launch_rt_loop(A, e->rt.d, e->rt.dev, e->rt.seq, e->rt.idleTicks, e->dGain, c.hReportsDev, c.hGainDev, e->rt.devRanges, std::max(e->rt.vw, 1), zl_whole_waves(nframes), e->rt.stream));
+    __atomic_store_n(&e->rt.mail.h->state, 0u, __ATOMIC_RELEASE);
+    __atomic_store_n(&e->rt.mail.h->yield, 0u, __ATOMIC_RELEASE);
+    for (uint32_t &d : e->rt.mail.h->wg_done) __atomic_store_n(&d, (uint32_t)e->rt.seq, __ATOMIC_RELAXED);   // (no workgroup has finished the cycle to come)
+    ZL_KERNEL(e, zl_launch_rt_loop(A, e->rt.mail.d, e->rt.dev, e->rt.seq, e->rt.idleTicks, e->dGain, c.reports.d, c.gain.d, e->rt.devRanges, std::max(e->rt.vw, 1), zl_whole_waves(nframes), e->rt.stream));
     e->rt.running = true; e->rt.nframes = nframes; e->rt.starts += 1;
     if (std::find(g_rt.engines.begin(), g_rt.engines.end(), e) == g_rt.engines.end()) g_rt.engines.push_back(e);
     return ZLHIP_OK;
@@ -1448,25 +1365,25 @@ static int rt_render(zlhip_engine *e, int32_t nframes, const zlhip_clock *clock,
     const bool tr = e->rt.traceOn;
     const auto tEnter = tr ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
     const long sw0 = tr ? thread_nivcsw() : 0;
-    if (e->rt.running && (e->rt.nframes != nframes || __atomic_load_n(&e->rt.h->state, __ATOMIC_ACQUIRE) == 2u)) {
+    if (e->rt.running && (e->rt.nframes != nframes || __atomic_load_n(&e->rt.mail.h->state, __ATOMIC_ACQUIRE) == 2u)) {
         int rc = rt_stop(e);                                       // another block size, or the kernel left after an idle spell
         if (rc != ZLHIP_OK) return rc;
     }
     ZlBatch A; std::memset(&A, 0, sizeof A);
     // the block's voice operations and clip edits: mapped host memory, read in place by the kernel.  (Growing the buffers frees
     // pinned memory, which waits for the device: stop the kernel first, and grow them before it is started again.)
-    if (e->hc.pendingOps.size() > c.opsCap || e->hc.pendingOps.size() > c.rangesCap || e->hc.pendingClipEdits.size() > c.editsCap) {
+    if (e->hc.pendingOps.size() > c.ops.cap || e->hc.pendingOps.size() > c.ranges.cap || e->hc.pendingClipEdits.size() > c.edits.cap) {
         int rc = rt_stop(e);
         if (rc != ZLHIP_OK) return rc;
         ZlQuiesce quiet(e);
-        ZL_HIP(e, grow_mapped(&c.hOps, &c.hOpsDev, &c.opsCap, e->hc.pendingOps.size()));
-        ZL_HIP(e, grow_mapped(&c.hRanges, &c.hRangesDev, &c.rangesCap, e->hc.pendingOps.size()));
-        ZL_HIP(e, grow_mapped(&c.hEdits, &c.hEditsDev, &c.editsCap, e->hc.pendingClipEdits.size()));
+        ZL_HIP(e, c.ops.grow(e->hc.pendingOps.size()));
+        ZL_HIP(e, c.ranges.grow(e->hc.pendingOps.size()));
+        ZL_HIP(e, c.edits.grow(e->hc.pendingClipEdits.size()));
     }
     // (started before the operations are taken out of the host's pending list: when the start is refused, the cycle goes through
     // the launched path with everything still pending)
     if (!e->rt.running) { int rc = rt_start(e, nframes); if (rc != ZLHIP_OK) return rc; }
-    ZlRtShared *sh = e->rt.h;
+    ZlRtShared *sh = e->rt.mail.h;
     unsigned long long *w = sh->cmd;                                // the cycle's command words (zl_types.h, ZlRtShared)
     {
         // knob edits (no slice table) ride in the mailbox itself, the first ZL_RT_INLINE_EDITS of them; the rest go through the edit buffer
@@ -1496,7 +1413,7 @@ static int rt_render(zlhip_engine *e, int32_t nframes, const zlhip_clock *clock,
         w[12] = (unsigned long long)(uintptr_t)e->outViews.dL; w[13] = (unsigned long long)(uintptr_t)e->outViews.dF;
         w[14] = (unsigned long long)(long long)nframes; w[15] = (unsigned long long)(long long)(e->outViews.dR - e->outViews.dL);
     } else {
-        w[12] = (unsigned long long)(uintptr_t)e->hBusDev; w[13] = (unsigned long long)(uintptr_t)e->hFanDev;
+        w[12] = (unsigned long long)(uintptr_t)e->hBus.d; w[13] = (unsigned long long)(uintptr_t)e->hFan.d;
         w[14] = (unsigned long long)(2ll * nframes); w[15] = (unsigned long long)(long long)nframes;
     }
     uint32_t fanSeq = 0u;
@@ -1506,7 +1423,7 @@ static int rt_render(zlhip_engine *e, int32_t nframes, const zlhip_clock *clock,
         bool moved = false;
         for (int b = 0; b < e->cfg.num_buses; ++b) {
             const ZlPassParams pp = pass_params(fan_params[b]);
-            if (std::memcmp(&pp, &e->hPassRt[b], sizeof pp) != 0) { e->hPassRt[b] = pp; moved = true; }
+            if (std::memcmp(&pp, &e->hPassRt.h[b], sizeof pp) != 0) { e->hPassRt.h[b] = pp; moved = true; }
         }
         if (moved && ++e->passSeq == 0u) e->passSeq = 1u;
         fanSeq = e->passSeq;
@@ -1560,10 +1477,10 @@ static int rt_render(zlhip_engine *e, int32_t nframes, const zlhip_clock *clock,
     if (tr) { const double g = us_between(tPoll, tDone); if (g > maxGap) maxGap = g; }   // (the thread may be taken off between the post and its first poll)
     if (!direct) {
         for (size_t b = 0; b < B; ++b) {
-            std::memcpy(out_left + b * N, e->hBus + (b * 2) * N, N * sizeof(float));
-            std::memcpy(out_right + b * N, e->hBus + (b * 2 + 1) * N, N * sizeof(float));
+            std::memcpy(out_left + b * N, e->hBus.h + (b * 2) * N, N * sizeof(float));
+            std::memcpy(out_right + b * N, e->hBus.h + (b * 2 + 1) * N, N * sizeof(float));
         }
-        if (fan_out) std::memcpy(fan_out, e->hFan, B * 6 * N * sizeof(float));
+        if (fan_out) std::memcpy(fan_out, e->hFan.h, B * 6 * N * sizeof(float));
     }
     double devUs = 0.0;
     if (e->rt.stampsOn) {                                          // (workgroup 0's last stamp may still be in flight when another workgroup finishes the block)
@@ -1579,7 +1496,7 @@ static int rt_render(zlhip_engine *e, int32_t nframes, const zlhip_clock *clock,
         rt_trace_report(e, t);
     }
     e->latest = &c;
-    e->lastK = 1; e->lastN = nframes; e->lastBus = direct ? nullptr : e->hBusDev; e->lastWindows = 1;   // (delivered straight to the caller: nothing to read back)
+    e->lastK = 1; e->lastN = nframes; e->lastBus = direct ? nullptr : e->hBus.d; e->lastWindows = 1;   // (delivered straight to the caller: nothing to read back)
     e->outstanding = false; e->reportsFresh = true;
     e->rt.cycles += 1;
     return ZLHIP_OK;
@@ -1610,7 +1527,7 @@ int zlhip_render_fanout(zlhip_engine *e, int32_t nframes, const zlhip_clock *clo
     const bool direct = rt_out_views(e, out_left, out_right, fan_out);
     int rc = direct ? render_batch_impl(e, 1, nframes, clock, e->outViews.dL, (long long)nframes, (long long)(e->outViews.dR - e->outViews.dL), fan_params,
                                         fan_out ? e->outViews.dF : nullptr, nullptr)
-                    : render_batch_impl(e, 1, nframes, clock, e->hBusDev, 0, 0, fan_params, fan_out ? e->hFanDev : nullptr, nullptr);
+                    : render_batch_impl(e, 1, nframes, clock, e->hBus.d, 0, 0, fan_params, fan_out ? e->hFan.d : nullptr, nullptr);
     if (rc != ZLHIP_OK) return rc;
     const size_t B = (size_t)e->cfg.num_buses, N = (size_t)nframes;
     const auto tPost = tr ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
@@ -1619,10 +1536,10 @@ int zlhip_render_fanout(zlhip_engine *e, int32_t nframes, const zlhip_clock *clo
     e->outstanding = false;
     if (!direct) {
         for (size_t b = 0; b < B; ++b) {
-            std::memcpy(out_left + b * N, e->hBus + (b * 2) * N, N * sizeof(float));
-            std::memcpy(out_right + b * N, e->hBus + (b * 2 + 1) * N, N * sizeof(float));
+            std::memcpy(out_left + b * N, e->hBus.h + (b * 2) * N, N * sizeof(float));
+            std::memcpy(out_right + b * N, e->hBus.h + (b * 2 + 1) * N, N * sizeof(float));
         }
-        if (fan_out) std::memcpy(fan_out, e->hFan, B * 6 * N * sizeof(float));
+        if (fan_out) std::memcpy(fan_out, e->hFan.h, B * 6 * N * sizeof(float));
     }
     if (tr) {
         const auto tExit = std::chrono::steady_clock::now();
@@ -1652,7 +1569,7 @@ int zlhip_read_bus(zlhip_engine *e, float *out, size_t out_floats)
     ZL_HIP(e, hipSetDevice(e->device));
     { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
     e->outstanding = false;
-    if (e->lastBus == e->hBusDev) { std::memcpy(out, e->hBus, need * sizeof(float)); return ZLHIP_OK; }   // a real-time block
+    if (e->lastBus == e->hBus.d) { std::memcpy(out, e->hBus.h, need * sizeof(float)); return ZLHIP_OK; }   // a real-time block
     ZL_HIP(e, hipMemcpyAsync(out, e->lastBus, need * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
     return ZLHIP_OK;
@@ -1664,10 +1581,10 @@ int zlhip_voice_reports(zlhip_engine *e, zlhip_voice_report *out, int32_t count)
     ZL_HIP(e, hipSetDevice(e->device));
     if (e->outstanding) { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
     for (int v = 0; v < e->V; ++v) {
-        const ZlReport &r = e->latest->hReports[v];
+        const ZlReport &r = e->latest->reports.h[v];
         zlhip_voice_report &o = out[v];
         // (playing is 2 inside the engine for a voice on a disabled bus)
-        o.playing = r.playing ? 1 : 0; o.valid = r.valid; o.gain = r.valid ? e->latest->hGain[v] : 0.0f; o.progress = r.progress;
+        o.playing = r.playing ? 1 : 0; o.valid = r.valid; o.gain = r.valid ? e->latest->gain.h[v] : 0.0f; o.progress = r.progress;
         o.clip = r.clip; o.reserved = 0; o.source_sample_position = r.P;
     }
     return ZLHIP_OK;
@@ -1680,6 +1597,13 @@ int zlhip_debug_enable_trace(zlhip_engine *e, int enable)
     // test hooks: bit 1 routes every block through the per-frame control path, bit 2 plans periodic loops pass by pass
     e->forceSlow = ((enable & 2) ? 1 : 0) | ((enable & 4) ? 2 : 0);
     return ZLHIP_OK;
+}
+
+int zlhip_debug_live_resources(int32_t counts[4])
+{
+    static_assert(ZL_LIVE_COUNT == 4, "ABI: counts[4]");
+    for (int i = 0; counts && i < ZL_LIVE_COUNT; ++i) counts[i] = zl_live[i].load(std::memory_order_relaxed);
+    return counts ? ZLHIP_OK : ZLHIP_ERR_INVALID;
 }
 
 int zlhip_debug_read_trace(zlhip_engine *e, int32_t *out, size_t out_ints)
@@ -1728,12 +1652,12 @@ int zlhip_levels_tick(zlhip_engine *e, int32_t block_index, int32_t with_hold_bu
     // stream != NULL): the engine's stream is non-blocking and nothing else orders it behind that work
     { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
     ZL_KERNEL(e, zl_launch_levels_tick(e->dLevelState, lv, B, e->lastN, with_hold_bus, e->stream));
-    ZL_HIP(e, hipMemcpyAsync(e->hLevelState, e->dLevelState, (size_t)B * sizeof(ZlLevelsState), hipMemcpyDeviceToHost, e->stream));
+    ZL_HIP(e, hipMemcpyAsync(e->hLevelState.h, e->dLevelState, (size_t)B * sizeof(ZlLevelsState), hipMemcpyDeviceToHost, e->stream));
     { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
     e->outstanding = false;
     static const float intToFloatMultiplier = 0.00000152587f;     // AudioLevels.cpp:349
     for (int b = 0; b < B; ++b) {
-        const ZlLevelsState &s = e->hLevelState[b];
+        const ZlLevelsState &s = e->hLevelState.h[b];
         zlhip_levels &o = out[b];
         o.peak_a = s.peak_a; o.peak_b = s.peak_b;
         o.peak_a_hold_signal = s.hold_a; o.peak_b_hold_signal = s.hold_b;
@@ -1849,9 +1773,9 @@ int zlhip_last_timings(zlhip_engine *e, zlhip_timings *out)
     }
     *out = e->timings;
     out->render_launches = e->lastWindows;
-    out->source_bytes = e->latest->hStats->source_bytes;
-    out->slow_blocks = e->latest->hStats->slow_blocks;
-    out->active_voice_frames = e->latest->hStats->active_frames;
+    out->source_bytes = e->latest->stats.h->source_bytes;
+    out->slow_blocks = e->latest->stats.h->slow_blocks;
+    out->active_voice_frames = e->latest->stats.h->active_frames;
     return ZLHIP_OK;
 }
 
@@ -1880,7 +1804,7 @@ int zlhip_rt_stats(zlhip_engine *e, uint64_t *kernel_starts, uint64_t *cycles_re
 int zlhip_rt_residency(zlhip_engine *e, int32_t *resident, double *share)
 {
     if (!e) return ZLHIP_ERR_INVALID;
-    if (resident) *resident = (e->rt.running && e->rt.h && __atomic_load_n(&e->rt.h->state, __ATOMIC_ACQUIRE) != 2u) ? 1 : 0;
+    if (resident) *resident = (e->rt.running && e->rt.mail.h && __atomic_load_n(&e->rt.mail.h->state, __ATOMIC_ACQUIRE) != 2u) ? 1 : 0;
     if (share) *share = e->rt.share;
     return ZLHIP_OK;
 }

@@ -1,6 +1,8 @@
 // zl_engine_impl.h -- the engine's state and the helpers its host files share: zl_engine.cpp (the engine itself, where every helper
 // declared here is defined) and zl_clip_calls.cpp (the clip services).  Private to csrc/: nothing else includes it, and an engine
 // group goes through zl_member.h.  The helpers and their types have hidden visibility: what the library exports does not grow by them.
+// Every HIP resource the engine owns is a member of an owning type (zl_owned.h) and goes back in its destructor, at `delete e`; a plain
+// hipEvent_t / hipStream_t member only names one that another member owns ("alias").  The exception: the arena's later segments (zl_arena.h).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -12,27 +14,13 @@
 #include "../../include/zlhip.h"
 #include "zl_arena.h"
 #include "zl_host.h"
+#include "zl_owned.h"
 #include "zl_types.h"
 
 struct ZlOnOnset; struct ZlTpResult; struct ZlPtResult; struct ZlLdSub; struct ZlLpResult; struct ZlKyResult;     // (zl_onset.h, zl_tempo.h, zl_pitch.h, zl_loudness.h, zl_loop.h, zl_key.h)
 
 #pragma GCC visibility push(hidden)
-// host memory mapped into the device, grown by doubling (the buffer must be idle)
-template <typename T> hipError_t grow_mapped(T **host, T **dev, size_t *cap, size_t need)
-{
-    if (need <= *cap) return hipSuccess;
-    if (*host) { hipError_t r = hipHostFree(*host); *host = nullptr; *dev = nullptr; *cap = 0; if (r != hipSuccess) return r; }
-    const size_t n = need * 2;
-    hipError_t r = hipHostMalloc((void **)host, n * sizeof(T));
-    if (r != hipSuccess) return r;
-    r = hipHostGetDevicePointer((void **)dev, *host, 0);
-    if (r == hipSuccess) *cap = n;
-    return r;
-}
-
-// a call's records and staging on the device, allocated by the first call that needs them and grown only (grow_buf); an engine that
-// never re-renders, asks for an overview or loads PCM has none.  h: the page-locked host twin, where there is one; cap in elements
-struct GrowBuf { void *d = nullptr, *h = nullptr; size_t cap = 0; };
+// scratch[]: a call's records and staging (GrowBuf; grow_buf); an engine that never re-renders, asks for an overview or loads PCM has none
 enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a call's jobs, the jobs whose stretch runs, their seek offsets
        ZB_OV_REQ, ZB_OV_COLS,                                 // overviews: a call's request records and its columns [columns][4], with host twins
        ZB_PCM_STAGE, ZB_PCM_PIECES, ZB_PCM_PUB, ZB_PCM_VERDICTS,   // PCM: the staging buffer for the raw bytes, a call's piece and publish records, its verdict words
@@ -45,26 +33,18 @@ enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a ca
        ZB_KY_REQ, ZB_KY_BINS, ZB_KY_TABLE, ZB_KY_STAT, ZB_KY_ACC, ZB_KY_TOTAL,   // key: a call's request records, its bin tables and the paired cosine table (each with a host twin), per frame the gate's verdict, per frame and bin re and im, per bin the totals
        ZB_COUNT };
 
-// a call's results in host memory mapped into the device: the kernels write them in place and nothing is copied back
-template <typename T> struct ZlMapped {
-    T *h = nullptr, *d = nullptr; size_t cap = 0;
-    hipError_t grow(size_t need) { return grow_mapped(&h, &d, &cap, need); }
-    void release() { if (h) (void)hipHostFree(h); h = d = nullptr; cap = 0; }
-};
-
 // Stage times of a call (zlhip_set_profiling): events 0 .. N-1 recorded between the call's launches.  `on` is set by every call from the
 // engine's switch; while it is off nothing is created, recorded or read, and the times stay those of the last profiled call.  An event
 // is created by the first mark that needs it.
 template <int N> struct ZlStageTimer {
-    hipEvent_t ev[N] = {}; bool on = false;
+    ZlEvent ev[N]; bool on = false;
     hipError_t mark(int i, hipStream_t s)
     {
         if (!on) return hipSuccess;
-        if (!ev[i]) { const hipError_t r = hipEventCreate(&ev[i]); if (r != hipSuccess) return r; }
+        if (!ev[i]) { const hipError_t r = ev[i].create(); if (r != hipSuccess) return r; }
         return hipEventRecord(ev[i], s);
     }
     hipError_t elapsed(int a, int b, float *ms) { return on ? hipEventElapsedTime(ms, ev[a], ev[b]) : hipSuccess; }   // after the call's wait
-    void release() { for (hipEvent_t &x : ev) if (x) { (void)hipEventDestroy(x); x = nullptr; } }
 };
 #pragma GCC visibility pop
 
@@ -72,12 +52,12 @@ struct zlhip_engine {
     zlhip_config cfg{};
     int V = 0;
     int device = 0;
-    hipStream_t stream = nullptr;
+    ZlStream stream;
     std::string err;
     char devname[256] = {0};
 
     // HBM
-    float *arena = nullptr;
+    ZlDev<float> arena;
     // the arena's allocator (zl_arena.h): the free extents of the first arena and of the further segments, allocated when a source does
     // not fit any more (clips are loaded freely; 288 GB of HBM).  A source in a segment is addressed like any other, by its float offset
     // from `arena` modulo 2^64, which the kernels' 64-bit address arithmetic wraps back.  A segment's handle is its device pointer.
@@ -138,29 +118,29 @@ struct zlhip_engine {
     } ky;
     // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h)
     struct Pcm {
-        std::vector<hipEvent_t> ev;                                 // profiling: before every pass's copies and every decode launch, behind the last
+        std::vector<ZlEvent> ev;                                    // profiling: before every pass's copies and every decode launch, behind the last
         float copyMs = 0.0f, decodeMs = 0.0f;
     } pcm;
     // clips converted to another rate (zlhip_sound_convert_rate; zl_resample.h): the filter tables on the device, one per (L, M) ever asked for
     struct Resample {
-        struct Table { int32_t L = 0, M = 0; float *d = nullptr; size_t floats = 0; std::vector<float> pending; };   // pending: the host copy, until the call that made the table has waited
+        struct Table { int32_t L = 0, M = 0; ZlDev<float> d; size_t floats = 0; std::vector<float> pending; };   // pending: the host copy, until the call that made the table has waited
         std::vector<Table> tables;
         ZlStageTimer<2> timer; float ms = 0.0f;                     // marks: around the call's launches
     } rs;
-    ZlSound *dSounds = nullptr; ZlClip *dClips = nullptr;
-    ZlVoiceState *dVoices = nullptr;
+    ZlDev<ZlSound> dSounds; ZlDev<ZlClip> dClips;
+    ZlDev<ZlVoiceState> dVoices;
     // K1 -> K2 records, double buffered so that planning window i+1 overlaps rendering window i
     struct PlanSet {
-        ZlVoiceConst *vconst = nullptr; ZlRunList *runs = nullptr; ZlTSeg *tsegs = nullptr;
-        ZlPlanHdr *hdr = nullptr; ZlPlanSeg0 *seg0 = nullptr; ZlPlanSeg1 *seg1 = nullptr;
-        double *ctlP = nullptr; float *ctlEnv = nullptr;  // the window's pool of per-frame control slots (zl_plan.h, zl_ctl_alloc)
-        unsigned long long *ctlNext = nullptr;            // its bump counter, never reset: a window's slots count from ctlBase
+        ZlDev<ZlVoiceConst> vconst; ZlDev<ZlRunList> runs; ZlDev<ZlTSeg> tsegs;
+        ZlDev<ZlPlanHdr> hdr; ZlDev<ZlPlanSeg0> seg0; ZlDev<ZlPlanSeg1> seg1;
+        ZlDev<double> ctlP; ZlDev<float> ctlEnv;          // the window's pool of per-frame control slots (zl_plan.h, zl_ctl_alloc)
+        ZlDev<unsigned long long> ctlNext;                // its bump counter, never reset: a window's slots count from ctlBase
         unsigned long long ctlBase = 0;                   // host side: past every value the counter can have reached
-        ZlSimConst *simConst = nullptr;
-        float *partials = nullptr;
-        int32_t *order = nullptr; size_t orderInts = 0;  // K2's phase order of the window's blocks (K1o): [z-slots][K] and the run summary behind it (zl_order_ints), allocated on first use
-        hipEvent_t planned = nullptr, rendered = nullptr, k1done = nullptr;
-        hipEvent_t renderedEv = nullptr; // the event that marks the end of the last rendering from this set (rendered, or a profiling event)
+        ZlDev<ZlSimConst> simConst;
+        ZlDev<float> partials;
+        ZlDev<int32_t> order; size_t orderInts = 0;       // K2's phase order of the window's blocks (K1o): [z-slots][K] and the run summary behind it (zl_order_ints), allocated on first use
+        ZlEvent planned, rendered, k1done;
+        hipEvent_t renderedEv = nullptr; // alias: the event that marks the end of the last rendering from this set (rendered, or a profiling event)
         bool used = false;               // `rendered` has been recorded at least once
     } ps[2];
     int windowBlocks = 0;                // plan_window_blocks when given (a fixed number of blocks per plan window)
@@ -168,32 +148,32 @@ struct zlhip_engine {
     int windowCap = 0;                   // blocks the K1 -> K2 record arrays hold
     size_t ctlPoolFrames = 0;            // frames of per-frame control a record set's pool holds (slots = this / nframes)
     int ctlSlotsOverride = -1;           // ZL_CTL_POOL_SLOTS (tests of the exhausted pool)
-    hipStream_t planStream = nullptr;    // K0 + K1 (sequential per voice)
-    hipStream_t lastRenderStream = nullptr;                          // the stream the previous call rendered on
-    hipStream_t lastPlanStream = nullptr; hipEvent_t evPlanTail = nullptr;   // where the previous call planned (voice-state order)
-    hipEvent_t lastPlanEvent = nullptr;  // marks the end of that planning: evPlanTail, or the call's `done` event when it planned on its render stream
-    hipStream_t asmStream = nullptr;     // K1c of window w runs here, next to K1 of window w+1
+    ZlStream planStream;                 // K0 + K1 (sequential per voice)
+    hipStream_t lastRenderStream = nullptr;                          // alias: the stream the previous call rendered on
+    hipStream_t lastPlanStream = nullptr;                            // alias: where the previous call planned (voice-state order)
+    ZlEvent evPlanTail;                  // the end of that planning, where it ran on the planning stream
+    hipEvent_t lastPlanEvent = nullptr;  // alias: marks the end of that planning: evPlanTail, or the call's `done` event when it planned on its render stream
+    ZlStream asmStream;                  // K1c of window w runs here, next to K1 of window w+1
     std::vector<std::pair<int, int>> wins;
     // Per-call resources, double buffered so that consecutive zlhip_render_batch calls pipeline: the host prepares
     // (and the planning stream plans) call i+1 while call i still renders; a slot is reused by call i+2.
     struct CallSlot {
-        ZlClock *hClocks = nullptr, *hClocksDev = nullptr;   // the call's block clocks, in host memory mapped into the device: K1 reads them in place
-        ZlPassParams *hPass = nullptr, *dPass = nullptr;   // fused fan-out parameters of the call
+        ZlMapped<ZlClock> clocks;        // the call's block clocks, in host memory mapped into the device: K1 reads them in place
+        ZlMapped<ZlPassParams> pass; ZlDev<ZlPassParams> dPass;   // fused fan-out parameters of the call
         // the call's voice operations, in host memory mapped into the device: K0 reads them in place (no copy command)
-        ZlVoiceOp *hOps = nullptr, *hOpsDev = nullptr; ZlOpRange *hRanges = nullptr, *hRangesDev = nullptr;
-        size_t opsCap = 0, rangesCap = 0;
-        ZlClipEdit *hEdits = nullptr, *hEditsDev = nullptr; size_t editsCap = 0;   // the call's clip-parameter edits, same arrangement
-        ZlReport *hReports = nullptr, *dReports = nullptr;
-        float *hGain = nullptr;
-        ZlBatchStats *hStats = nullptr, *dStats = nullptr;
-        ZlReport *hReportsDev = nullptr; float *hGainDev = nullptr; ZlBatchStats *hStatsDev = nullptr;   // device views of the host buffers
-        hipEvent_t evBegin = nullptr, evEnd = nullptr, done = nullptr;
+        ZlMapped<ZlVoiceOp> ops; ZlMapped<ZlOpRange> ranges;
+        ZlMapped<ZlClipEdit> edits;      // the call's clip-parameter edits, same arrangement
+        ZlMapped<ZlReport> reports; ZlDev<ZlReport> dReports;
+        ZlMapped<float> gain;
+        ZlMapped<ZlBatchStats> stats; ZlDev<ZlBatchStats> dStats;
+        ZlEvent evBegin, evEnd;
+        hipEvent_t done = nullptr;       // alias: doneEv[doneGen]
         // `done` alternates between two events from one use of the slot to the next, so that the NEXT call (the other slot) can take this
         // call's completion as the begin of its own profile -- one event-record packet fewer between two calls' render kernels -- and
         // still find it intact when it is harvested, two calls later
-        hipEvent_t doneEv[2] = {nullptr, nullptr}; unsigned doneGen = 0;
-        hipEvent_t beginEv = nullptr;    // what this call's profile counts from: its own evBegin, or the previous call's `done`
-        std::vector<hipEvent_t> evK2;    // [2 * max windows] start/end of every K2 launch (profiling)
+        ZlEvent doneEv[2]; unsigned doneGen = 0;
+        hipEvent_t beginEv = nullptr;    // alias: what this call's profile counts from: its own evBegin, or the previous call's `done`
+        std::vector<ZlEvent> evK2;       // [2 * max windows] start/end of every K2 launch (profiling)
         int windows = 0;
         bool inflight = false, profiled = false;
         bool fusedDone = false;          // the call's last K2 launch published the reports and carries `done` as its stop event (no report kernel)
@@ -201,28 +181,28 @@ struct zlhip_engine {
     unsigned callIndex = 0, setPhase = 0;
     CallSlot *latest = nullptr;          // slot of the most recent call
     zlhip_timings totals{}; int totalCalls = 0;   // sums over harvested calls (zlhip_profile_totals)
-    float *dGain = nullptr;
-    ZlPassCache *dPassCache = nullptr;   // per voice: the recorded pass of its loop (zl_plan.h, replay_cached_pass)
-    float *dBus = nullptr;
-    ZlBlockLevels *dLevels = nullptr; ZlLevelsState *dLevelState = nullptr;
-    int32_t *dTrace = nullptr; ZlPassParams *dPass = nullptr;
+    ZlDev<float> dGain;
+    ZlDev<ZlPassCache> dPassCache;       // per voice: the recorded pass of its loop (zl_plan.h, replay_cached_pass)
+    ZlDev<float> dBus;
+    ZlDev<ZlBlockLevels> dLevels; ZlDev<ZlLevelsState> dLevelState;
+    ZlDev<int32_t> dTrace; ZlDev<ZlPassParams> dPass;
     size_t traceInts = 0;
     int maxGroups = 1;
 
     // pinned host staging
-    float *hBus = nullptr, *hBusDev = nullptr;   // one real-time block, host memory mapped into the device
+    ZlMapped<float> hBus;                // one real-time block, host memory mapped into the device
     // one real-time block's JackPassthrough fan-out [B][6][max_frames] (zlhip_render_fanout), written by the kernels like hBus; the
     // parameter table the resident kernel reads ([B], mapped host memory) and its version (never 0; moved when an entry changes)
-    float *hFan = nullptr, *hFanDev = nullptr;
-    ZlPassParams *hPassRt = nullptr, *hPassRtDev = nullptr;
-    uint32_t *hNonFinite = nullptr, *hNonFiniteDev = nullptr;   // mapped host word: zl_k_interleave sets it when an uploaded sample is NaN or infinite
+    ZlMapped<float> hFan;
+    ZlMapped<ZlPassParams> hPassRt;
+    ZlMapped<uint32_t> hNonFinite;       // mapped host word: zl_k_interleave sets it when an uploaded sample is NaN or infinite
     uint32_t passSeq = 1;
     // zero-copy delivery of a real-time cycle: when the caller's out_left / out_right (/ fan_out) are page-locked and mapped (zlhip_host_alloc,
     // hipHostMalloc, hipHostRegister) the kernels write them directly -- no copy on the host behind the cycle (24 KB + 72 KB for 12 buses:
     // 1.6 + 5 us of reading lines the device has just written).  The device views of the last buffers seen are kept.
     struct OutViews { const void *hL = nullptr, *hR = nullptr, *hF = nullptr; float *dL = nullptr, *dR = nullptr, *dF = nullptr; bool ok = false; } outViews;
     bool directOut = true;               // ZL_RT_DIRECT_OUT=0: always through the staging rows
-    ZlLevelsState *hLevelState = nullptr;
+    ZlMapped<ZlLevelsState> hLevelState;
 
     // host mirrors
     ZlHostControl hc;                    // voices / sounds / clip parameters / pending ops (zl_host.h)
@@ -232,21 +212,21 @@ struct zlhip_engine {
     int lastK = 0, lastN = 0, lastWindows = 0; float *lastBus = nullptr; bool outstanding = false; bool reportsFresh = false;
     bool trace = false; int traceK = 0, traceN = 0;
     int forceSlow = 0;
-    size_t deviceBytes = 0;              // HBM the engine allocated at creation (arena included)
+    size_t deviceBytes = 0;              // HBM the engine allocated at creation (arena included), and since then in scratch[], rate-conversion tables and arena segments
     int staged = 0;                      // K2 variant with LDS-staged source windows (zl_kernels.hip), chosen per mode at creation
 
     // resident real-time kernel (zl_k_rt_loop): the mailbox in mapped host memory, its stream, what it was launched for
     struct Rt {
         bool enabled = false, running = false; int wide = -1;    // wide: 1 always, 0 never, -1 only with one voice per workgroup
-        ZlRtShared *h = nullptr, *d = nullptr;
-        ZlRtDev *dev = nullptr;                            // the kernel's own hand-off words in HBM
-        ZlOpRange *devRanges = nullptr;                    // wide buses: workgroup 0's copy of a block's operation ranges
+        ZlMapped<ZlRtShared> mail;                         // the mailbox; with dev, devRanges and stream made by the first start, all or none (rt_start)
+        ZlDev<ZlRtDev> dev;                                // the kernel's own hand-off words in HBM
+        ZlDev<ZlOpRange> devRanges;                        // wide buses: workgroup 0's copy of a block's operation ranges
         int capacity[2] = {-1, -1};                        // workgroups of the kernel the device holds at once (narrow, wide); -1 = not asked yet
         int vw = 0;                                        // wide buses: voices per resident workgroup (a divisor of voices_per_bus)
         double share = 0.0;                                // of the device's resident-workgroup capacity this engine's kernel takes (rt_eligible)
         std::atomic<bool> inCycle{false};                  // a cycle is being rendered through the resident kernel (its share stays taken even if the kernel has just left)
         int maxFrames = 4096;                              // longest period the resident kernel takes (ZL_RT_MAX_FRAMES)
-        hipStream_t stream = nullptr;
+        ZlStream stream;
         int nframes = 0;
         unsigned long long seq = 0;
         unsigned long long starts = 0, cycles = 0;        // launches of the resident kernel, cycles it rendered (zlhip_rt_stats)
@@ -262,11 +242,11 @@ struct zlhip_engine {
     // (the sink below, called from the window loop), while the following windows render.
     struct Bounce {
         static constexpr int NBUF = 2, NEV = 16;
-        float *bus[NBUF] = {nullptr, nullptr}; int16_t *pcm[NBUF] = {nullptr, nullptr};
-        size_t busFloats = 0, pcmFrames = 0;
-        hipStream_t copyStream = nullptr;
-        hipEvent_t copied[NBUF] = {nullptr, nullptr};      // the last delivery out of a chunk buffer
-        hipEvent_t winEv[NEV] = {};                        // "window rendered (and converted)": waited for by the copy stream
+        ZlDev<float> bus[NBUF]; ZlDev<int16_t> pcm[NBUF];
+        size_t busFloats = 0, pcmFrames = 0;               // what every buffer that exists holds
+        ZlStream copyStream;
+        ZlEvent copied[NBUF];                              // the last delivery out of a chunk buffer
+        ZlEvent winEv[NEV];                                // "window rendered (and converted)": waited for by the copy stream
         unsigned winNext = 0;
         bool active = false;                 // inside zlhip_bounce: every chunk plans on the planning stream
         struct Sink {
@@ -281,8 +261,8 @@ struct zlhip_engine {
     bool failed = false;                 // the resident kernel stopped answering in the middle of a cycle: the voice table is undefined (zlhip_render)
 
     // profiling
-    bool profiling = false; hipEvent_t evJoin = nullptr;
-    hipEvent_t joins[2] = {nullptr, nullptr};   // events on caller streams the host still has to wait for (engine_wait)
+    bool profiling = false; ZlEvent evJoin;
+    hipEvent_t joins[2] = {nullptr, nullptr};   // alias: events on caller streams the host still has to wait for (engine_wait)
     zlhip_timings timings{};
 };
 

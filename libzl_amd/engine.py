@@ -18,7 +18,7 @@ from ._abi import (Clock, ClipCommand, ClipParams, Config, Levels, PassthroughPa
                    MODE_FAITHFUL, MODE_FIX_DELAY, MODE_FIX_GAIN, MODE_HERMITE, ZlHipError)
 
 __all__ = ["SamplerSynth", "SamplerSynthGroup", "Clock", "ClipCommand", "ClipParams", "Levels", "PassthroughParams", "VoiceReport",
-           "MODE_FAITHFUL", "MODE_FIX_GAIN", "MODE_FIX_DELAY", "MODE_HERMITE", "ZlHipError", "clip_command", "synthetic_clocks", "running_playhead"]
+           "MODE_FAITHFUL", "MODE_FIX_GAIN", "MODE_FIX_DELAY", "MODE_HERMITE", "ZlHipError", "clip_command", "synthetic_clocks", "running_playhead", "live_resources"]
 
 
 def clip_command(lib=None, **fields) -> ClipCommand:
@@ -87,6 +87,14 @@ def pinned_array(lib, shape, dtype) -> np.ndarray:
     buf = (C.c_char * max(nbytes, 1)).from_address(p.value)
     weakref.finalize(buf, lib.zlhip_host_free, p.value)
     return np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape))).reshape(shape)
+
+
+def live_resources(lib=None) -> tuple:
+    """debug: (device buffers, page-locked host buffers, events, streams) the process's engines hold now (zlhip_debug_live_resources)"""
+    counts = (C.c_int32 * 4)()
+    if (lib or _abi.load()).zlhip_debug_live_resources(counts) != 0:
+        raise ZlHipError("zlhip_debug_live_resources failed")
+    return tuple(counts)
 
 
 def _overview_requests(requests, length_of):

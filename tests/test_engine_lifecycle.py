@@ -1,6 +1,7 @@
 """GPU tier: engine life-cycle behaviour behind the C-ABI that the audio parity tests do not reach -- the source arena
-under load / release cycles (SamplerSynth::registerClip / unregisterClip, reference lib/SamplerSynth.cpp:285-312) and the
-ordering of engine-stream work behind batches queued on a caller's stream."""
+under load / release cycles (SamplerSynth::registerClip / unregisterClip, reference lib/SamplerSynth.cpp:285-312), the
+ordering of engine-stream work behind batches queued on a caller's stream, and the balance of an engine's life: the HIP
+resources it holds (zlhip_debug_live_resources) go back when it is closed, and a steady state allocates none."""
 import ctypes as C
 
 import numpy as np
@@ -453,3 +454,134 @@ def test_the_clip_store_through_a_mixed_life(Engine):
     assert run(21)[0] == peak_floats                               # the same sequence
     assert syn.memory_bytes() == mem
     syn.close()
+
+
+# ---- a balanced life: what an engine takes, it gives back (zlhip_debug_live_resources) ---------------------------------------------
+# The smallest engines that still reach every allocation site: 2 buses x 2 voices, blocks of 64 frames, 8 sounds, a 1 MB arena; four
+# blocks per call in ONE record set, or in windows of two blocks, which takes the second set.
+LIFE = dict(max_frames=64, max_batch_blocks=4, max_sounds=8, sound_arena_bytes=1 << 20)
+LIFE_FRAMES = 4096
+
+
+def _counts():
+    """(device buffers, host buffers, events, streams) of the process, with no engine of an earlier test waiting to be collected"""
+    import gc
+    from libzl_amd.engine import live_resources
+    gc.collect()
+    return live_resources()
+
+
+def _life_clips(syn, rng):
+    """one float clip and one 16-bit PCM clip (a batch of one) of 4096 frames each; the first one plays on both buses"""
+    import decode_ref as dr
+    from libzl_amd import clip_command
+    L, R = rand_source(rng, LIFE_FRAMES, stereo=True)
+    a = syn.register_clip(L, R, 48000.0)
+    raw = dr.random_raw(rng, dr.S16, 2, LIFE_FRAMES)
+    (b,) = syn.register_clips_pcm([(raw.view(np.int16), dr.S16, 2, 48000.0)])
+    for ch in (-2, -1):
+        assert syn.handle_clip_command(clip_command(clip=a, midi_note=60, midi_channel=ch, start_playback=1, looping=1, change_volume=1, volume=0.7), 0) >= 1
+    return a, b
+
+
+def _analyses(syn, clip):
+    """each of the seven analyses once, at one size"""
+    syn.clip_overview(clip, 16)
+    syn.clip_onsets(clip)
+    syn.clip_tempo(clip)
+    syn.clip_pitch(clip)
+    syn.clip_loudness(clip)
+    syn.clip_loop(clip, 1000, 3000, 30, 30)
+    syn.clip_key(clip)
+
+
+@pytest.mark.parametrize("window,sets", [(0, 1), (2, 2)])
+def test_an_engine_gives_back_what_it_took(Engine, monkeypatch, window, sets):
+    """With profiling on, one of everything that allocates: both kinds of upload, a batch with the position trace, a batch in K2's
+    phase order, real-time cycles through the resident kernel with the fan-out, a 16-bit bounce in two chunks, a re-render, a rate
+    conversion, the seven analyses.  While the engine lives every count lies above where it started; the same calls again at the same
+    sizes allocate nothing; a larger overview call replaces its buffers, it does not add any; close() gives everything back.
+    (K2's phase order: the launch shape refuses it for blocks of 64 and 128 frames, zl_order_shape, so that batch has blocks of 32.)"""
+    from libzl_amd import PassthroughParams
+    from libzl_amd.engine import synthetic_clocks
+    start = _counts()
+    syn = Engine(2, 2, plan_window_blocks=window, **LIFE)
+    created = _counts()
+    assert all(c > s for c, s in zip(created, start))
+    syn.set_profiling(True)
+    a, b = _life_clips(syn, np.random.default_rng(31))
+    fan = [PassthroughParams(1.0, 0.5, 0.25, 0.0, 0)] * 2
+    block = [0]
+
+    def clocks(n, frames=64):
+        block[0] += n
+        return synthetic_clocks(n, frames, 48000.0, start_block=block[0] - n)
+
+    def batches():
+        syn.enable_trace(True)
+        syn.render_batch(4, 64, clocks(4))
+        assert syn.read_trace().size == 4 * 4 * 64
+        syn.enable_trace(False)
+        monkeypatch.setenv("ZL_K2_PHASE_ORDER", "2")
+        syn.render_batch(4, 32, clocks(4, 32))
+        syn.synchronize()
+        monkeypatch.delenv("ZL_K2_PHASE_ORDER")
+
+    def cycles(n):
+        for _ in range(n):
+            syn.process_fanout(64, clocks(1)[0], fan)
+
+    before = _counts()
+    batches()
+    # the trace buffer, and one order table per record set
+    assert _counts() == (before[0] + 1 + sets, before[1], before[2], before[3])
+    cycles(3)
+    assert syn.rt_stats() == (1, 3)                                # through the resident kernel: its mailbox, its two device buffers, its stream
+    assert _counts() == (before[0] + 3 + sets, before[1] + 1, before[2], before[3] + 1)
+    out = syn.bounce(4, 64, clocks(4), "pcm16", sub_blocks=2)
+    assert out.shape == (2, 256, 2)
+    syn.convert_clips([b], 44100.0)                                # (in this order: a clip that plays a re-render is not converted)
+    syn.rerender_clip(b, gain_db=-6.0)
+    _analyses(syn, a)
+    alive = _counts()
+    assert all(c > s for c, s in zip(alive, created))
+    assert alive[3] - start[3] >= 4                                # the engine's, the planning, the resident kernel's and the bounce's copy stream
+    # a steady state allocates nothing
+    mem = syn.memory_bytes()
+    batches()
+    cycles(1)
+    _analyses(syn, a)
+    assert _counts() == alive and syn.memory_bytes() == mem
+    # a call that outgrows its buffers replaces them
+    syn.clip_overviews([(a, 4096), (a, 4096)])
+    grown = _counts()
+    assert grown[:2] == alive[:2] and grown[3] == alive[3]
+    assert syn.memory_bytes()[0] > mem[0]
+    syn.close()
+    assert _counts() == start
+
+
+def test_a_group_gives_back_what_it_took(built):
+    """two members on one device with a spanning bus: uploads, a batch, a re-render, a rate conversion and the analyses go to the
+    members' engines, which give everything back when the group is destroyed"""
+    from libzl_amd import SamplerSynthGroup
+    from libzl_amd.engine import synthetic_clocks
+    start = _counts()
+    g = SamplerSynthGroup([0, 0], 2, 2, partition="span", **LIFE)
+    assert all(m["partition"] == "span" for m in g.layout())
+    created = _counts()
+    assert all(c >= s + 2 for c, s in zip(created, start))
+    a, b = _life_clips(g, np.random.default_rng(32))
+    g.render_batch(4, 64, synthetic_clocks(4, 64, 48000.0))
+    assert np.abs(g.read_bus()).max() > 0.0
+    g.convert_clips([b], 44100.0)
+    g.rerender_clip(b, gain_db=-6.0)
+    _analyses(g, a)
+    alive = _counts()
+    assert alive[0] > created[0] and alive[1] > created[1] and alive[2:] >= created[2:]
+    g.render_batch(4, 64, synthetic_clocks(4, 64, 48000.0, start_block=4))
+    g.synchronize()
+    _analyses(g, a)
+    assert _counts() == alive
+    g.close()
+    assert _counts() == start
