@@ -245,6 +245,20 @@ int  libzl_hotpath_clip_snap_loop(ClipAudioSource *c, float search_ms, float min
  * be NULL) is 1 where clip i's loop was moved.  Duplicate clips are ZLHIP_ERR_INVALID.  Returns the number of clips moved, or a
  * negative status (nothing has changed then). */
 int  libzl_hotpath_clips_snap_loops(ClipAudioSource **clips, int count, float search_ms, float min_improvement_db, int *applied_out);
+/* extension (build-defined: the reference has no loop crossfade): bakes a crossfade into the clip's data on the device, so that its
+ * sustain loop wraps without a jump (zlhip_sound_loop_crossfade).  The loop is the clip's start .. start + length
+ * in the frames a voice derives from them; fade_ms: the length of the fade (0: 20 ms), cut to what the lead-in in front of the start
+ * and the loop itself hold, at most 65536 frames; curve: ZLHIP_XFADE_AUTO (from the measured correlation of the two regions),
+ * ZLHIP_XFADE_LINEAR or ZLHIP_XFADE_EQUAL_POWER.  *fade_frames, *correlation (may be NULL): what was faded and measured.  The clip keeps
+ * its id and its parameters; a voice playing it reads the new data from its next block.  The fade cannot be taken back: reload the
+ * clip.  A clip that plays a re-render (a gain, pitch or speed other than the identity) is refused with ZLHIP_ERR_STATE: crossfade
+ * first, level afterwards -- a later gain keeps the seam, a pitch or speed render moves the frames.  Returns 1 if applied, 0 where there
+ * is nothing to fade (a loop from frame 0 has no lead-in), or a negative status (nothing has changed then). */
+int  libzl_hotpath_clip_crossfade_loop(ClipAudioSource *c, float fade_ms, int curve, int *fade_frames, double *correlation);
+/* A bank: ONE zlhip_sound_loop_batch with libzl_hotpath_clips_snap_loops' logic, then ONE zlhip_sound_loop_crossfade_batch.  results[i]
+ * (may be NULL): bit 0 = clip i's loop was moved, bit 1 = its loop was crossfaded.  A clip that is NULL, not in the engine or playing a
+ * re-render stays as it is.  Duplicate clips are ZLHIP_ERR_INVALID.  Returns the number of clips crossfaded, or a negative status. */
+int  libzl_hotpath_clips_seal_loops(ClipAudioSource **clips, int count, float search_ms, float min_improvement_db, float fade_ms, int curve, int *results);
 /* extension (build-defined: the reference has no key detection): the musical key of the data the clip plays now between its start and
  * its start + length, detected on the device (zlhip_sound_key with the defaults).  *tonic: 0 = C .. 11 = B, or
  * -1 for "no key" (silence, a region shorter than one analysis frame, a flat chroma), which is not an error; *mode: 0 major, 1 minor;

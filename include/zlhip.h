@@ -43,7 +43,8 @@ extern "C" {
  *    zlhip_sound_pitch / _batch (a clip's pitch, detected on the device), zlhip_pitch_resolve, zlhip_sound_loudness / _batch (a clip's
  *    loudness, measured on the device), zlhip_loudness_resolve, zlhip_loudness_design, zlhip_sound_loop / _batch (a clip's seamless
  *    loop points, found on the device), zlhip_loop_resolve, zlhip_loop_seconds, zlhip_sound_key / _batch (a clip's musical
- *    key, detected on the device), zlhip_key_resolve, zlhip_key_design, zlhip_debug_live_resources. */
+ *    key, detected on the device), zlhip_key_resolve, zlhip_key_design, zlhip_debug_live_resources, zlhip_sound_loop_crossfade / _batch (a loop crossfade
+ *    baked into a clip's data on the device), zlhip_xfade_resolve, zlhip_xfade_design. */
 #define ZLHIP_ABI_VERSION 3
 
 /* status codes */
@@ -418,7 +419,7 @@ int zlhip_debug_loudness_timings(zlhip_engine *e, float *kernel_ms);
  *   On any error out is not written; one bad request fails the call.
  *   A call is three kernel launches whatever its size, behind one copy of the request records; it waits once and 80 bytes per request
  *   come back.  It runs on the engine's stream behind what is queued there and the resident real-time kernel keeps running.
- *   Not provided: a crossfade baked into the data; loop points for beat loops at the file's edges. */
+ *   Not provided: loop points for beat loops at the file's edges.  (A crossfade baked into the data: zlhip_sound_loop_crossfade, below.) */
 typedef struct zlhip_loop_request { int32_t id, start_frame, stop_frame, start_search, stop_search, window, min_length; } zlhip_loop_request;
 typedef struct zlhip_loop { int32_t found, start_frame, stop_frame, shift, starts, ends, nominal_valid, reserved; uint64_t pairs;
                             uint32_t cost, den, nominal_cost, nominal_den; double seam_db, nominal_db, improvement_db; } zlhip_loop;
@@ -439,6 +440,49 @@ int zlhip_debug_loop_items(zlhip_engine *e, int32_t request, zlhip_loop_item *it
 int zlhip_debug_loop_costs(zlhip_engine *e, int32_t request, uint32_t *costs, int32_t capacity, int32_t *starts, int32_t *ends);
 /* measurement: device time of the pairs kernel and of the rest of the last call made with profiling on */
 int zlhip_debug_loop_timings(zlhip_engine *e, float *pairs_ms, float *rest_ms);
+/* Loop crossfade: the X frames in front of a loop's stop faded into the X frames in front of its start, baked into the clip's data on
+ * the device (a build-defined extension, the reference has no loop crossfade).  The loop finder only chooses among
+ * points that exist; a decaying pad or a loop placed by ear still jumps from x[stop - 1] to x[start] on every lap.
+ *   A request is (id, start_frame s, stop_frame e, fade_frames X, curve) over the slot's ORIGINAL data of `length` frames,
+ *   0 <= s < e <= length, e exclusive.  fade_frames 0 means min(rint(0.020 rate), s, e - s, 65536); where that is 0 (a loop from frame 0
+ *   has no lead-in) the request answers applied = 0 and every other field 0, which is no error: the clip is left alone.  An explicit
+ *   fade_frames lies in [1, min(s, e - s, 65536)], curve is ZLHIP_XFADE_AUTO, _LINEAR or _EQUAL_POWER: anything else is
+ *   ZLHIP_ERR_INVALID, as are ids not in use or repeated and count < 0 -- all decided before the first HIP call.
+ *   Correlation: m[f] = the sum over the channels of q(v) (section 8's 16-bit quantisation); sab = the sum over i in [0, X) of
+ *   m[e - X + i] m[s - X + i], saa and sbb likewise, exact in int64; correlation = sab / sqrt(saa sbb) (0 where saa or sbb is 0), in
+ *   double on the host.  Always measured and reported.
+ *   Weights: rho = min(1, max(0, correlation)) for AUTO, 1 for LINEAR, 0 for EQUAL_POWER (the result's rho is the one used); for
+ *   i in [0, X): t = (i + 1) / X, u = 1 - t, d = sqrt(((u u) + (t t)) + ((2 rho) (t u))), a[i] = (float)(u / d), b[i] = (float)(t / d), in
+ *   double on the host: a^2 + b^2 + 2 rho a b = 1, the power of material of that correlation stays constant through the fade.
+ *   Output: y[e - X + i] = (a[i] x[e - X + i]) + (b[i] x[s - X + i]) per channel in fp32, two rounded multiplies and a rounded add;
+ *   every other frame is copied bit for bit into a new arena extent.  The loop's last frame becomes the frame in front of the loop's
+ *   start, so the wrap e - 1 -> s is the original's own step s - 1 -> s.  ZL_SOUND_FINITE stays set iff the original had it and every
+ *   written fade sample is finite.
+ *   A clip that currently plays a re-render is ZLHIP_ERR_STATE; an arena that cannot hold the whole call is ZLHIP_ERR_CAPACITY.  All
+ *   or nothing: on any error every clip is as it was and out is not written; one bad request fails the call.
+ *   Synchronisation is zlhip_sound_convert_rate's: the resident kernel leaves, queued batches finish, the table entries switch at a
+ *   block boundary.  A call is one measuring launch, a wait, one render launch and one publishing launch, a second wait -- whatever
+ *   the number of requests; a call whose every request answers applied = 0 launches and copies nothing.
+ *   Consequences.  A baked fade cannot be taken back: reload the clip.  The new extent becomes the clip's ORIGINAL: a later re-render
+ *   starts from the crossfaded data -- a gain keeps the seam, a pitch or speed render moves the frames and the loop must be placed
+ *   again.  A voice playing the clip reads the new data from its next block at its unchanged position.  The fade serves the
+ *   free-running loop branch; a clip whose lengthInBeats is whole restarts by the clock and does not pass the seam.
+ *   Not provided: a guard copy of x[s ...] behind the stop for the interpolation taps of pitched laps (it would change data a
+ *   non-looping command plays); undo; fades for beat-locked restarts; fading under a re-render. */
+enum { ZLHIP_XFADE_AUTO = 0, ZLHIP_XFADE_LINEAR = 1, ZLHIP_XFADE_EQUAL_POWER = 2 };
+typedef struct zlhip_xfade_request { int32_t id, start_frame, stop_frame, fade_frames, curve; } zlhip_xfade_request;
+typedef struct zlhip_xfade { int32_t applied, fade_frames, start_frame, stop_frame, curve, reserved; int64_t sab, saa, sbb;
+                             double correlation, rho; } zlhip_xfade;
+/* host only: checks the request against a sound of `length` frames at `sample_rate` and fills fade_frames where it was given as 0
+ * (it stays 0 where there is nothing to fade); a refused request is left as it was */
+int zlhip_xfade_resolve(double sample_rate, int32_t length, zlhip_xfade_request *r);
+/* host only: the X weight pairs (a[i], b[i]) of a correlation, ab: [2 X]; X outside [1, 65536] or rho outside [0, 1] is
+ * ZLHIP_ERR_INVALID.  The engine builds its tables with this code */
+int zlhip_xfade_design(int32_t fade_frames, double rho, float *ab);
+int zlhip_sound_loop_crossfade(zlhip_engine *e, const zlhip_xfade_request *r, zlhip_xfade *out);
+int zlhip_sound_loop_crossfade_batch(zlhip_engine *e, const zlhip_xfade_request *reqs, int32_t count, zlhip_xfade *out);
+/* measurement: device time of the measuring launch and of the render and publishing launches of the last call made with profiling on */
+int zlhip_debug_xfade_timings(zlhip_engine *e, float *measure_ms, float *render_ms);
 /* Key: what key a loop is in (a build-defined extension, the reference has no key detection) -- detected on the
  * device in the sound's CURRENT playback data.  Pitch detection answers "no pitch" on a chord loop by design; this is the answer for
  * those.  Behind section 8's 16-bit quantisation everything the device does is integer arithmetic (libzl_amd/csrc/zl_key.h):
@@ -714,6 +758,10 @@ int  zlhip_group_sound_pitch_batch(zlhip_group *g, const zlhip_pitch_request *re
 int  zlhip_group_sound_loudness_batch(zlhip_group *g, const zlhip_loudness_request *reqs, int32_t nreq, zlhip_loudness *out);
 /* zlhip_sound_loop_batch: member 0 answers */
 int  zlhip_group_sound_loop_batch(zlhip_group *g, const zlhip_loop_request *reqs, int32_t nreq, zlhip_loop *out);
+/* zlhip_sound_loop_crossfade_batch on every member, in member order, with zlhip_group_sound_convert_rate_batch's semantics: a call
+ * that is invalid, refused or does not fit fails on member 0 and changes nothing.  out receives member 0's results (the members hold
+ * the same data: every member measures the same integers) */
+int  zlhip_group_sound_loop_crossfade_batch(zlhip_group *g, const zlhip_xfade_request *reqs, int32_t count, zlhip_xfade *out);
 /* zlhip_sound_key_batch: member 0 answers */
 int  zlhip_group_sound_key_batch(zlhip_group *g, const zlhip_key_request *reqs, int32_t nreq, zlhip_key *out);
 /* zlhip_handle_commands_voices over the whole synth (taken, voices optional) */

@@ -169,6 +169,18 @@ class LoopItem(C.Structure):
     _fields_ = [("start", C.c_int32), ("stop", C.c_int32), ("cost", C.c_uint32), ("den", C.c_uint32), ("pairs", C.c_uint64)]
 
 
+class XfadeRequest(C.Structure):
+    _fields_ = [("id", C.c_int32), ("start_frame", C.c_int32), ("stop_frame", C.c_int32), ("fade_frames", C.c_int32), ("curve", C.c_int32)]
+
+
+class Xfade(C.Structure):
+    _fields_ = [("applied", C.c_int32), ("fade_frames", C.c_int32), ("start_frame", C.c_int32), ("stop_frame", C.c_int32), ("curve", C.c_int32),
+                ("reserved", C.c_int32), ("sab", C.c_int64), ("saa", C.c_int64), ("sbb", C.c_int64), ("correlation", C.c_double), ("rho", C.c_double)]
+
+
+XFADE_AUTO, XFADE_LINEAR, XFADE_EQUAL_POWER = 0, 1, 2
+
+
 class KeyRequest(C.Structure):
     _fields_ = [("id", C.c_int32), ("first_frame", C.c_int32), ("num_frames", C.c_int32), ("hop", C.c_int32), ("max_frames", C.c_int32),
                 ("a4_hz", C.c_float), ("note_lo", C.c_int32), ("note_hi", C.c_int32), ("q", C.c_int32), ("gate", C.c_int32)]
@@ -270,6 +282,11 @@ SIGNATURES = {
     "zlhip_debug_loop_items": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zlhip_debug_loop_costs": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "zlhip_debug_loop_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "zlhip_xfade_resolve": (C.c_int, [C.c_double, C.c_int32, C.POINTER(XfadeRequest)]),
+    "zlhip_xfade_design": (C.c_int, [C.c_int32, C.c_double, C.c_void_p]),
+    "zlhip_sound_loop_crossfade": (C.c_int, [_E, C.POINTER(XfadeRequest), C.POINTER(Xfade)]),
+    "zlhip_sound_loop_crossfade_batch": (C.c_int, [_E, C.POINTER(XfadeRequest), C.c_int32, C.POINTER(Xfade)]),
+    "zlhip_debug_xfade_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "zlhip_key_resolve": (C.c_int, [C.c_double, C.POINTER(KeyRequest)]),
     "zlhip_key_design": (C.c_int, [C.c_double, C.POINTER(KeyRequest), C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p]),
     "zlhip_key_match_shift": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
@@ -346,6 +363,7 @@ SIGNATURES = {
     "zlhip_group_sound_tempo_batch": (C.c_int, [_E, C.POINTER(TempoRequest), C.c_int32, C.POINTER(Tempo)]),
     "zlhip_group_sound_pitch_batch": (C.c_int, [_E, C.POINTER(PitchRequest), C.c_int32, C.POINTER(Pitch)]),
     "zlhip_group_sound_loop_batch": (C.c_int, [_E, C.POINTER(LoopRequest), C.c_int32, C.POINTER(Loop)]),
+    "zlhip_group_sound_loop_crossfade_batch": (C.c_int, [_E, C.POINTER(XfadeRequest), C.c_int32, C.POINTER(Xfade)]),
     "zlhip_group_sound_key_batch": (C.c_int, [_E, C.POINTER(KeyRequest), C.c_int32, C.POINTER(Key)]),
     "zlhip_group_sound_loudness_batch": (C.c_int, [_E, C.POINTER(LoudnessRequest), C.c_int32, C.POINTER(Loudness)]),
     "zlhip_group_handle_commands": (C.c_int, [_E, C.POINTER(ClipCommand), C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

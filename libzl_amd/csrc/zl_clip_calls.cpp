@@ -1,5 +1,5 @@
 // zl_clip_calls.cpp -- the clip services of include/zlhip.h: loading from raw PCM, re-render, rate conversion, and the seven analyses
-// (waveform overviews, transients, tempo, pitch, loudness, loop points, key).  Every one is a call on a loaded clip that validates everything before its
+// (waveform overviews, transients, tempo, pitch, loudness, loop points, key), and the loop crossfade.  Every one is a call on a loaded clip that validates everything before its
 // first HIP call, reserves buffers that only grow, queues its launches on the engine's stream and waits once.  What they share is
 // written once, below; the engine itself -- arena, sound slots, rendering, the resident kernel -- is zl_engine.cpp.
 #include <hip/hip_runtime.h>
@@ -20,6 +20,7 @@
 #include "zl_resample.h"
 #include "zl_stretch.h"
 #include "zl_tempo.h"
+#include "zl_xfade.h"
 
 // ---- what every service does ---------------------------------------------------------------------------------------------------
 static int fail_in(zlhip_engine *e, int code, const char *svc, const char *msg) { return fail(e, code, (std::string(svc) + ": " + msg).c_str()); }
@@ -1148,6 +1149,174 @@ int zlhip_debug_loop_timings(zlhip_engine *e, float *pairs_ms, float *rest_ms)
     if (!e) return ZLHIP_ERR_INVALID;
     if (pairs_ms) *pairs_ms = e->lp.pairsMs;
     if (rest_ms) *rest_ms = e->lp.restMs;
+    return ZLHIP_OK;
+}
+
+// ---- loop crossfade (zl_xfade.h, zl_xfade.hip) ---------------------------------------------------------------------------------
+// The loop finder chooses among points that exist; this bakes a crossfade into the data, so that the wrap from the loop's last frame to
+// its start is the original's own step.  The scaffold is the rate conversion's: every applied clip gets a new arena extent, one launch
+// measures the correlation of every request's two regions into mapped host memory, the call waits, the weight tables are made here in
+// double from the measured or the fixed rho, one launch copies and fades every clip, zl_k_resample_publish switches the sound-table
+// entries (ZL_SOUND_FINITE from the device's verdict: a clip whose original lacks the flag starts with its word set), and the call waits
+// a second time.  The new extent becomes the slot's original.
+int zlhip_xfade_resolve(double sample_rate, int32_t length, zlhip_xfade_request *r)
+{
+    if (!r) return ZLHIP_ERR_INVALID;
+    int32_t X = r->fade_frames;
+    if (zl_xf_resolve(sample_rate, length, r->start_frame, r->stop_frame, &X, r->curve) != 0) return ZLHIP_ERR_INVALID;
+    r->fade_frames = X;
+    return ZLHIP_OK;
+}
+
+int zlhip_xfade_design(int32_t fade_frames, double rho, float *ab)
+{
+    if (!ab || fade_frames < 1 || fade_frames > ZL_XF_MAX_FADE || !(rho >= 0.0 && rho <= 1.0)) return ZLHIP_ERR_INVALID;
+    zl_xf_design(fade_frames, rho, ab);
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_loop_crossfade_batch(zlhip_engine *e, const zlhip_xfade_request *reqs, int32_t count, zlhip_xfade *out)
+{
+    static_assert(sizeof(zlhip_xfade) == 64, "zlhip_xfade's layout");
+    static_assert(ZLHIP_XFADE_AUTO == ZL_XF_AUTO && ZLHIP_XFADE_LINEAR == ZL_XF_LINEAR && ZLHIP_XFADE_EQUAL_POWER == ZL_XF_EQUAL_POWER, "the curves");
+    if (!e || count < 0 || (count > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
+    if (count == 0) return ZLHIP_OK;
+    // validate and resolve everything before the first HIP call
+    std::vector<zlhip_xfade_request> res((size_t)count);
+    int32_t njobs = 0;
+    {
+        std::vector<char> seen((size_t)e->cfg.max_sounds, 0);
+        int64_t wgs = 0, pairs = 0;
+        for (int32_t i = 0; i < count; ++i) {
+            zlhip_xfade_request &q = res[(size_t)i];
+            q = reqs[i];
+            { const int rc = check_sound(e, "sound_loop_crossfade", q.id); if (rc != ZLHIP_OK) return rc; }
+            if (seen[(size_t)q.id]) return fail(e, ZLHIP_ERR_INVALID, "sound_loop_crossfade_batch: a clip appears twice");
+            seen[(size_t)q.id] = 1;
+            const ZlSound &o = e->soundSlots[(size_t)q.id].orig;
+            if (zlhip_xfade_resolve(o.sample_rate, o.length, &q) != ZLHIP_OK)
+                return fail_in(e, ZLHIP_ERR_INVALID, "sound_loop_crossfade", "the loop does not lie inside the sound's data, fade_frames outside 1 .. min(start, stop - start, 65536), or no such curve");
+            if (q.fade_frames == 0) continue;
+            ZlXfJob J; std::memset(&J, 0, sizeof J);
+            J.length = o.length; J.channels = o.channels;
+            wgs += zl_xf_job_wgs(J); pairs += q.fade_frames; ++njobs;
+        }
+        if (wgs > (int64_t)INT32_MAX || pairs > (int64_t)INT32_MAX) return fail(e, ZLHIP_ERR_INVALID, "sound_loop_crossfade_batch: more than 2^31 - 1 workgroups or fade frames in one call");
+        for (int32_t i = 0; i < count; ++i)
+            if (res[(size_t)i].fade_frames != 0 && e->soundSlots[(size_t)res[(size_t)i].id].renderFloats != 0)
+                return fail(e, ZLHIP_ERR_STATE, "sound_loop_crossfade: the clip plays a re-render (crossfade first, re-render afterwards; re-render it with gain 0, pitch 0, speed 1 first)");
+    }
+    if (njobs == 0) {                                              // nothing to fade anywhere: no launch, no copy
+        std::memset(out, 0, (size_t)count * sizeof(zlhip_xfade));
+        return ZLHIP_OK;
+    }
+    { const int rc = call_begin(e, true); if (rc != ZLHIP_OK) return rc; }
+    // the new extents (all or none: an arena that cannot hold the call leaves every clip as it was)
+    std::vector<size_t> newOff((size_t)count, 0), newFloats((size_t)count, 0);
+    auto rollback = [&]() { for (int32_t i = count - 1; i >= 0; --i) free_extent(e, newOff[(size_t)i], newFloats[(size_t)i]); };
+    for (int32_t i = 0; i < count; ++i) {
+        if (res[(size_t)i].fade_frames == 0) continue;
+        const ZlSound &o = e->soundSlots[(size_t)res[(size_t)i].id].orig;
+        const size_t floats = zl_extent_floats(o.length, o.channels);
+        const int rc = alloc_extent(e, floats, &newOff[(size_t)i]);
+        if (rc != ZLHIP_OK) { rollback(); return rc; }
+        newFloats[(size_t)i] = floats;
+    }
+    std::vector<ZlXfJob> jobs; std::vector<ZlRsPublish> pub; std::vector<int32_t> jobReq; std::vector<uint32_t> verdicts;
+    int32_t wgs = 0, pairs = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        const zlhip_xfade_request &q = res[(size_t)i];
+        if (q.fade_frames == 0) continue;
+        const ZlSound &o = e->soundSlots[(size_t)q.id].orig;
+        ZlXfJob J; std::memset(&J, 0, sizeof J);
+        J.src = (uint64_t)(uintptr_t)arena_ptr(e, o.offset);
+        J.dst = (uint64_t)(uintptr_t)arena_ptr(e, newOff[(size_t)i]);
+        J.length = o.length; J.channels = o.channels;
+        J.s = q.start_frame; J.e = q.stop_frame; J.X = q.fade_frames;
+        J.wg_base = wgs; J.weights = pairs; J.verdict = (int32_t)jobs.size();
+        wgs += zl_xf_job_wgs(J); pairs += J.X;
+        ZlSound s = o; s.offset = newOff[(size_t)i]; s.flags &= ~(int32_t)ZL_SOUND_FINITE;
+        pub.push_back(ZlRsPublish{ s, q.id, J.verdict });
+        verdicts.push_back((o.flags & ZL_SOUND_FINITE) ? 0u : 1u); // (an original without the flag stays without it)
+        jobs.push_back(J);
+        jobReq.push_back(i);
+    }
+    const char *what = "sound_loop_crossfade: no memory for the call's records";
+    const size_t nj = jobs.size(), n = std::max<size_t>(nj * 2, 64), np = (size_t)pairs;
+    zlhip_engine::Xfade &t = e->xf;
+    const int rsv = reserve(e, false, { { ZB_XF_JOBS, nj, sizeof(ZlXfJob), n, false, what }, { ZB_XF_WEIGHTS, np, 2 * sizeof(float), std::max<size_t>(np * 2, 4096), false, what },
+                                       { ZB_XF_PUB, nj, sizeof(ZlRsPublish), n, false, what }, { ZB_XF_VERDICTS, nj, sizeof(uint32_t), n, false, what } },
+                            { mapped_need(t.sums, std::max<size_t>(nj, 32)) });
+    if (rsv != ZLHIP_OK) { rollback(); return rsv; }
+    ZlXfJob *const dJobs = (ZlXfJob *)e->scratch[ZB_XF_JOBS].d; float *const dWeights = (float *)e->scratch[ZB_XF_WEIGHTS].d;
+    ZlRsPublish *const dPub = (ZlRsPublish *)e->scratch[ZB_XF_PUB].d; uint32_t *const dVerdicts = (uint32_t *)e->scratch[ZB_XF_VERDICTS].d;
+    // everything is decided: from here on only a HIP error fails the call
+    auto hip_failed = [&](int krc) {
+        e->err = std::string("sound_loop_crossfade: ") + hipGetErrorString((hipError_t)krc);
+        (void)hipStreamSynchronize(e->stream);
+        // (the table entries the device may have switched go back to what the host's mirror holds)
+        for (const ZlRsPublish &p : pub) (void)hipMemcpy(e->dSounds + p.id, &e->hc.sounds[p.id], sizeof(ZlSound), hipMemcpyHostToDevice);
+        rollback();
+        return ZLHIP_ERR_HIP;
+    };
+    t.timer.on = e->profiling;
+    int krc = (int)hipMemcpyAsync(dJobs, jobs.data(), nj * sizeof(ZlXfJob), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)t.timer.mark(0, e->stream);
+    if (krc == 0) krc = zl_launch_xfade_measure(dJobs, (int32_t)nj, t.sums.d, e->stream);
+    if (krc == 0) krc = (int)t.timer.mark(1, e->stream);
+    if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);      // the call's first wait: the sums are in host memory
+    if (krc != 0) return hip_failed(krc);
+    // the tables, from the measured or the fixed rho
+    std::vector<zlhip_xfade> results((size_t)count);
+    std::memset(results.data(), 0, results.size() * sizeof(zlhip_xfade));
+    std::vector<float> weights(np * 2);
+    for (size_t j = 0; j < nj; ++j) {
+        const zlhip_xfade_request &q = res[(size_t)jobReq[j]];
+        const ZlXfSums m = t.sums.h[j];
+        zlhip_xfade &r = results[(size_t)jobReq[j]];
+        double corr, rho;
+        zl_xf_finish(m.sab, m.saa, m.sbb, &corr, &rho);
+        r.applied = 1; r.fade_frames = q.fade_frames; r.start_frame = q.start_frame; r.stop_frame = q.stop_frame; r.curve = q.curve;
+        r.sab = m.sab; r.saa = m.saa; r.sbb = m.sbb; r.correlation = corr; r.rho = zl_xf_curve_rho(q.curve, rho);
+        zl_xf_design(q.fade_frames, r.rho, weights.data() + 2 * (size_t)jobs[j].weights);
+    }
+    std::vector<uint32_t> verdictsOut(nj, 0u);
+    krc = (int)hipMemcpyAsync(dWeights, weights.data(), weights.size() * sizeof(float), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dVerdicts, verdicts.data(), nj * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, pub.data(), nj * sizeof(ZlRsPublish), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)t.timer.mark(2, e->stream);
+    if (krc == 0) krc = zl_launch_xfade_render(dJobs, (int32_t)nj, wgs, dWeights, dVerdicts, e->stream);
+    if (krc == 0) krc = zl_launch_resample_publish(dPub, (int32_t)nj, dVerdicts, e->dSounds, e->stream);
+    if (krc == 0) krc = (int)t.timer.mark(3, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(verdictsOut.data(), dVerdicts, nj * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
+    if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);      // the call's second wait
+    if (krc == 0) krc = (int)t.timer.elapsed(0, 1, &t.measureMs);
+    if (krc == 0) krc = (int)t.timer.elapsed(2, 3, &t.renderMs);
+    if (krc != 0) return hip_failed(krc);
+    e->outstanding = false;
+    // the swap on the host: the crossfaded extent is the slot's original from now on, the old one goes back to the arena
+    for (size_t j = 0; j < nj; ++j) {
+        const ZlRsPublish &p = pub[j];
+        zlhip_engine::SoundSlot &slot = e->soundSlots[(size_t)p.id];
+        const size_t oldOff = (size_t)slot.orig.offset, oldFloats = slot.floats;
+        ZlSound s = p.s;
+        if (verdictsOut[j] == 0u) s.flags |= ZL_SOUND_FINITE;
+        slot.orig = s; slot.floats = newFloats[(size_t)jobReq[j]];
+        slot.renderOffsets.clear();
+        e->hc.sounds[p.id] = s;
+        free_extent(e, oldOff, oldFloats);
+    }
+    std::memcpy(out, results.data(), results.size() * sizeof(zlhip_xfade));
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_loop_crossfade(zlhip_engine *e, const zlhip_xfade_request *r, zlhip_xfade *out) { return zlhip_sound_loop_crossfade_batch(e, r, 1, out); }
+
+int zlhip_debug_xfade_timings(zlhip_engine *e, float *measure_ms, float *render_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (measure_ms) *measure_ms = e->xf.measureMs;
+    if (render_ms) *render_ms = e->xf.renderMs;
     return ZLHIP_OK;
 }
 

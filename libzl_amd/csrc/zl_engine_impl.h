@@ -17,7 +17,7 @@
 #include "zl_owned.h"
 #include "zl_types.h"
 
-struct ZlOnOnset; struct ZlTpResult; struct ZlPtResult; struct ZlLdSub; struct ZlLpResult; struct ZlKyResult;     // (zl_onset.h, zl_tempo.h, zl_pitch.h, zl_loudness.h, zl_loop.h, zl_key.h)
+struct ZlOnOnset; struct ZlTpResult; struct ZlPtResult; struct ZlLdSub; struct ZlLpResult; struct ZlKyResult; struct ZlXfSums;     // (zl_onset.h, zl_tempo.h, zl_pitch.h, zl_loudness.h, zl_loop.h, zl_key.h, zl_xfade.h)
 
 #pragma GCC visibility push(hidden)
 // scratch[]: a call's records and staging (GrowBuf; grow_buf); an engine that never re-renders, asks for an overview or loads PCM has none
@@ -31,6 +31,7 @@ enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a ca
        ZB_LD_REQ,                                             // loudness: a call's request records (with a host twin)
        ZB_LP_REQ, ZB_LP_X, ZB_LP_E, ZB_LP_SHIFT, ZB_LP_ITEM, ZB_LP_COST,   // loop finder: a call's request records (with a host twin), the int16 strips, per candidate E, per request the shift, the item records, the cost matrix (small calls)
        ZB_KY_REQ, ZB_KY_BINS, ZB_KY_TABLE, ZB_KY_STAT, ZB_KY_ACC, ZB_KY_TOTAL,   // key: a call's request records, its bin tables and the paired cosine table (each with a host twin), per frame the gate's verdict, per frame and bin re and im, per bin the totals
+       ZB_XF_JOBS, ZB_XF_WEIGHTS, ZB_XF_PUB, ZB_XF_VERDICTS,  // loop crossfade: a call's job records, its (a, b) pairs, its publish records, its verdict words
        ZB_COUNT };
 
 // Stage times of a call (zlhip_set_profiling): events 0 .. N-1 recorded between the call's launches.  `on` is set by every call from the
@@ -116,6 +117,11 @@ struct zlhip_engine {
         std::vector<Last> last;                                     // per request of the last call (zlhip_debug_key_bins / _frame)
         ZlStageTimer<4> timer; float gateMs = 0.0f, correlateMs = 0.0f, foldMs = 0.0f;   // marks: around each of the three launches
     } ky;
+    // loop crossfade (zlhip_sound_loop_crossfade; zl_xfade.h)
+    struct Xfade {
+        ZlMapped<ZlXfSums> sums;                                    // a call's measured sums, one record per applied request
+        ZlStageTimer<4> timer; float measureMs = 0.0f, renderMs = 0.0f;   // marks: around the measuring launch, around the render and publish launches
+    } xf;
     // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h)
     struct Pcm {
         std::vector<ZlEvent> ev;                                    // profiling: before every pass's copies and every decode launch, behind the last

@@ -339,6 +339,19 @@ int zlhip_group_sound_loop_batch(zlhip_group *g, const zlhip_loop_request *reqs,
     return rc != ZLHIP_OK ? member_fail(g, 0, rc) : ZLHIP_OK;
 }
 
+int zlhip_group_sound_loop_crossfade_batch(zlhip_group *g, const zlhip_xfade_request *reqs, int32_t count, zlhip_xfade *out)
+{
+    if (!g) return ZLHIP_ERR_INVALID;
+    // (the members hold the same clips in arenas that are alike: a call that is invalid or does not fit fails on member 0 and leaves every
+    // member as it was; every member measures the same integers, member 0's results are the call's)
+    std::vector<zlhip_xfade> rest((size_t)(count > 0 ? count : 0));
+    for (int r = 0; r < g->L.n; ++r) {
+        const int rc = zlhip_sound_loop_crossfade_batch(g->m[(size_t)r], reqs, count, r == 0 ? out : rest.data());
+        if (rc != ZLHIP_OK) return member_fail(g, r, rc);
+    }
+    return ZLHIP_OK;
+}
+
 int zlhip_group_sound_key_batch(zlhip_group *g, const zlhip_key_request *reqs, int32_t nreq, zlhip_key *out)
 {
     if (!g) return ZLHIP_ERR_INVALID;

@@ -1321,6 +1321,70 @@ int libzl_hotpath_clips_snap_loops(ClipAudioSource **clips, int count, float sea
     return applied;
 }
 
+// The loop finder only chooses among points that exist: a decaying pad or a loop placed by ear still jumps on every lap.  Here the
+// frames in front of the clip's stop are crossfaded into the frames in front of its start, baked into the clip's data on the device
+// (zlhip_sound_loop_crossfade).  The frames are the ones a voice derives from the clip's seconds (zl_clip_start /
+// zl_clip_stop and K1's casts, zl_plan.h).  Build-defined: the reference has no loop crossfade.
+static int clip_xfade_request(ClipAudioSource *c, float fade_ms, int curve, zlhip_xfade_request *q)      // call with G.mu held
+{
+    if (!G.engine || c->engineClip < 0) return ZLHIP_ERR_STATE;
+    zlhip_sound_info info;
+    { const int rc = zlhip_sound_info_get(G.engine, c->engineClip, &info); if (rc != ZLHIP_OK) return rc; }
+    if (info.rendered) return ZLHIP_ERR_STATE;                     // crossfade first, level afterwards
+    float startSec, lengthSec;
+    { std::lock_guard<std::mutex> sl(c->setMu); startSec = c->startPositionInSeconds; lengthSec = c->lengthInSeconds; }
+    const float stopSec = startSec + lengthSec;
+    const double a = (double)startSec * info.sample_rate, b = (double)stopSec * info.sample_rate;
+    if (!(a >= 0.0) || !(b > a) || !(fade_ms >= 0.0f)) return ZLHIP_ERR_INVALID;        // (a NaN fails here)
+    const int64_t start = (int64_t)a, stop = b >= (double)info.length ? (int64_t)info.length : (int64_t)b;
+    const double x = std::rint((double)fade_ms * info.sample_rate / 1000.0);
+    if (fade_ms > 0.0f && x < 1.0) return ZLHIP_ERR_INVALID;
+    // (a fade longer than the lead-in, the loop or the limit: what fits; 0 frames: the default, or nothing to fade)
+    const int64_t most = std::min<int64_t>(std::min<int64_t>(start, stop - start), 65536);
+    *q = zlhip_xfade_request{ c->engineClip, (int32_t)start, (int32_t)stop, (int32_t)std::min<double>(x, (double)most), curve };
+    return zlhip_xfade_resolve(info.sample_rate, info.length, q) == ZLHIP_OK ? ZLHIP_OK : ZLHIP_ERR_INVALID;
+}
+
+int libzl_hotpath_clip_crossfade_loop(ClipAudioSource *c, float fade_ms, int curve, int *fade_frames, double *correlation)
+{
+    if (!c) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    zlhip_xfade_request q; zlhip_xfade r;
+    { const int rc = clip_xfade_request(c, fade_ms, curve, &q); if (rc != ZLHIP_OK) return rc; }
+    { const int rc = zlhip_sound_loop_crossfade(G.engine, &q, &r); if (rc != ZLHIP_OK) return rc; }
+    if (fade_frames) *fade_frames = r.fade_frames;
+    if (correlation) *correlation = r.correlation;
+    return r.applied ? 1 : 0;
+}
+
+// A whole bank: ONE zlhip_sound_loop_batch with clips_snap_loops' logic, then ONE zlhip_sound_loop_crossfade_batch.
+int libzl_hotpath_clips_seal_loops(ClipAudioSource **clips, int count, float search_ms, float min_improvement_db, float fade_ms, int curve, int *results)
+{
+    if (count < 0 || (count > 0 && !clips) || min_improvement_db != min_improvement_db || !(search_ms >= 0.0f) || !(fade_ms >= 0.0f)) return ZLHIP_ERR_INVALID;
+    if (curve != ZLHIP_XFADE_AUTO && curve != ZLHIP_XFADE_LINEAR && curve != ZLHIP_XFADE_EQUAL_POWER) return ZLHIP_ERR_INVALID;
+    std::vector<int> snapped((size_t)count, 0);
+    { const int rc = libzl_hotpath_clips_snap_loops(clips, count, search_ms, min_improvement_db, snapped.data()); if (rc < 0) return rc; }
+    std::lock_guard<std::mutex> lk(G.mu);
+    if (!G.engine) return ZLHIP_ERR_STATE;
+    std::vector<int> who; std::vector<zlhip_xfade_request> reqs;
+    for (int i = 0; i < count; ++i) {
+        zlhip_xfade_request q;
+        if (!clips[i]) continue;
+        if (clip_xfade_request(clips[i], fade_ms, curve, &q) != ZLHIP_OK) continue;     // not in the engine, plays a re-render, an empty region: stays as it is
+        who.push_back(i); reqs.push_back(q);
+    }
+    std::vector<zlhip_xfade> res(reqs.size());
+    if (!reqs.empty()) { const int rc = zlhip_sound_loop_crossfade_batch(G.engine, reqs.data(), (int32_t)reqs.size(), res.data()); if (rc != ZLHIP_OK) return rc; }
+    int sealed = 0;
+    std::vector<int> faded((size_t)count, 0);
+    for (size_t n = 0; n < who.size(); ++n) faded[(size_t)who[n]] = res[n].applied ? 1 : 0;
+    for (int i = 0; i < count; ++i) {
+        if (results) results[i] = snapped[(size_t)i] | (faded[(size_t)i] << 1);
+        sealed += faded[(size_t)i];
+    }
+    return sealed;
+}
+
 void ClipAudioSource_setVolume(ClipAudioSource *c, float vol)      // ClipAudioSource.cpp:313-326
 {
     std::lock_guard<std::mutex> sl(c->setMu);

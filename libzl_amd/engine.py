@@ -208,6 +208,25 @@ def _loop_call(fn, handle, requests):
     return rc, [{k: getattr(out[i], k) for k in LOOP_FIELDS} for i in range(len(requests))]
 
 
+XFADE_FIELDS = tuple(name for name, _ in _abi.Xfade._fields_ if name != "reserved")
+_XFADE_KEYS = ("start_frame", "stop_frame", "fade_frames", "curve")
+
+
+def _xfade_call(fn, handle, requests):
+    """one zlhip_sound_loop_crossfade_batch-shaped call over (clip, start_frame, stop_frame[, fade_frames[, curve]]) tuples, or dicts with
+    "clip", "start_frame", "stop_frame" and either of the other keys (fade_frames 0 / missing = 20 ms, curve 0 / missing = from the measured
+    correlation) -> (status, one dict of zlhip_xfade's fields per request)"""
+    reqs = (_abi.XfadeRequest * max(1, len(requests)))()
+    for i, r in enumerate(requests):
+        if isinstance(r, dict):
+            r = (r["clip"],) + tuple(r.get(k, 0) for k in _XFADE_KEYS)
+        r = tuple(r) + (0, 0)[len(r) - 3:]
+        reqs[i] = _abi.XfadeRequest(*(int(v) for v in r))
+    out = (_abi.Xfade * max(1, len(requests)))()
+    rc = fn(handle, reqs, len(requests), out)
+    return rc, [{k: getattr(out[i], k) for k in XFADE_FIELDS} for i in range(len(requests))]
+
+
 KEY_FIELDS = tuple(name for name, _ in _abi.Key._fields_)
 _KEY_KEYS = ("first_frame", "num_frames", "hop", "max_frames", "a4_hz", "note_lo", "note_hi", "q", "gate")
 
@@ -627,6 +646,27 @@ class SamplerSynth:
         """device ms of the pairs kernel and of the rest of the last loop call made with profiling on"""
         a, b = C.c_float(0.0), C.c_float(0.0)
         self._ck(self._lib.zlhip_debug_loop_timings(self._e, C.byref(a), C.byref(b)), "debug_loop_timings")
+        return a.value, b.value
+
+    def clip_loop_crossfade(self, clip: int, start_frame: int, stop_frame: int, fade_frames: int = 0, curve: int = 0) -> dict:
+        """Bake a crossfade into the clip's data on the device, so that the loop [start_frame, stop_frame) wraps without a jump
+        (zlhip_sound_loop_crossfade): the fade_frames frames in front of stop_frame are faded into the ones in
+        front of start_frame.  fade_frames 0: 20 ms, cut to the lead-in and the loop; curve: 0 from the measured correlation, 1 linear,
+        2 equal power.  A dict of zlhip_xfade's fields -- applied (0: nothing to fade, the clip is untouched), fade_frames, the three
+        integer sums, correlation, rho.  The clip keeps its id; the fade cannot be taken back."""
+        return self.clip_loop_crossfade_batch([(clip, start_frame, stop_frame, fade_frames, curve)])[0]
+
+    def clip_loop_crossfade_batch(self, requests: Sequence):
+        """Several clips in one call (zlhip_sound_loop_crossfade_batch: three launches and two waits whatever the count; all or nothing).
+        requests: tuples (clip, start_frame, stop_frame[, fade_frames[, curve]]) or dicts; one dict each."""
+        rc, res = _xfade_call(self._lib.zlhip_sound_loop_crossfade_batch, self._e, requests)
+        self._ck(rc, "sound_loop_crossfade_batch")
+        return res
+
+    def xfade_timings(self):
+        """device ms of the measuring launch and of the render and publishing launches of the last crossfade call made with profiling on"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        self._ck(self._lib.zlhip_debug_xfade_timings(self._e, C.byref(a), C.byref(b)), "debug_xfade_timings")
         return a.value, b.value
 
     def clip_key(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, hop: int = 0, max_frames: int = 0, a4_hz: float = 0.0,
@@ -1091,6 +1131,15 @@ class SamplerSynthGroup:
     def clip_loop_batch(self, requests: Sequence):
         rc, res = _loop_call(self._lib.zlhip_group_sound_loop_batch, self._g, requests)
         self._ck(rc, "group_sound_loop_batch")
+        return res
+
+    def clip_loop_crossfade(self, clip: int, start_frame: int, stop_frame: int, fade_frames: int = 0, curve: int = 0) -> dict:
+        """SamplerSynth.clip_loop_crossfade on every member; member 0's results (zlhip_group_sound_loop_crossfade_batch)"""
+        return self.clip_loop_crossfade_batch([(clip, start_frame, stop_frame, fade_frames, curve)])[0]
+
+    def clip_loop_crossfade_batch(self, requests: Sequence):
+        rc, res = _xfade_call(self._lib.zlhip_group_sound_loop_crossfade_batch, self._g, requests)
+        self._ck(rc, "group_sound_loop_crossfade_batch")
         return res
 
     def clip_key(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, hop: int = 0, max_frames: int = 0, a4_hz: float = 0.0,
