@@ -2,7 +2,9 @@
 alone; the host build of libzl_amd/csrc/zl_pitch.h (tests/cpu_harness/pitch_host.cpp walks a call the way the kernels do, work item by
 work item, with the header's own arithmetic) against the restatement on every integer of d, of every frame record and of the result,
 with == on hz and confidence; the defaults and the limits; the struct layouts; the new kernels' resources; the walk under the
-sanitizers (tests/cpp/pitch_check.cpp).  tests/test_pitch_gpu.py holds the kernels themselves to the restatement on the GPU."""
+sanitizers (tests/cpp/pitch_check.cpp); the edge cases that reach the kernels as clips (tests/pitch_cases.py): every predicate, and the
+list through the walk.  tests/test_pitch_gpu.py and tests/test_pitch_edges_gpu.py hold the kernels themselves to the restatement on
+the GPU."""
 import ctypes as C
 import math
 import os
@@ -11,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import pitch_cases as pc
 import pitch_ref as pr
 from libzl_amd import _abi, build
 
@@ -338,6 +341,39 @@ def test_vote_ties_in_the_median_and_in_the_clarity():
     # 256 frames, a lane each
     res, recs = pick_vote([valley(tmax, 100 + (k % 2)) for k in range(256)], tmin, tmax)
     assert (res["frames"], res["consistent"], res["frame"], res["lag"]) == (256, 256, 0, 100)
+
+
+# ---- the edge cases that reach the device as clips (tests/pitch_cases.py) -------------------------------------------------------------
+def test_every_edge_case_hits_its_edge():
+    """by the restatement alone: a case that stops hitting its edge fails here, without a GPU.  The list holds every kind of case"""
+    cases = pc.cases()
+    for c in cases:
+        pc.holds(c)
+    names = " | ".join(c["name"] for c in cases)
+    for kind in ("threshold at equality", "plateau", "descent ends at t_max", "neighbouring lanes", "neighbouring waves", "one lane", "at t_max + 1", "at t_min - 1", "DC",
+                 "gate at equality, mono", "gate one below, mono", "gate at equality, stereo", "shift 0", "shift 4", "in the lagged tail", "at the last sample", "= -32768",
+                 "even count", "consistent band", "silent frames", "256 frames", "different waves", "neighbouring frames", "bin 7", "bin 8", "bin 511", "bin 512",
+                 "median 31", "median 32", "mono, first frame 2", "mono, first frame 6", "window 256, t_max + 1 = 256", "window 576", "t_max + 1 = 255", "t_max + 1 = 257"):
+        assert kind in names, kind
+    assert len(cases) == 82
+    for c in pc.too_short():
+        res, recs, ds = pc.want(c)
+        assert res["frames"] == 0 and recs == [] and all(int(res[k]) == 0 for k in pr.RESULT_INTS)
+
+
+def test_the_edge_cases_through_the_harness():
+    """the whole list in one call of the host walk, requests without a frame first, last and twice in a row in the middle: d, every
+    frame record and every result equal the restatement's (call), and the named outcomes are the harness's too"""
+    cases, (s0, s1) = pc.cases(), pc.too_short()
+    half = len(cases) // 2
+    order = [s0] + cases[:half] + [s1, s0] + cases[half:] + [s1]
+    out = call([(c["x"], c["rate"], c["req"]) for c in order])
+    assert len(out) == len(cases) + 4
+    for c, (res, recs, g) in zip(order, out):
+        if "pred" in c:
+            pc.literal(c, res, recs)
+        else:
+            assert g["frames"] == 0 and res["frames"] == 0
 
 
 # ---- defaults and limits ------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 kernels do, work item by work item, with the header's own arithmetic) against the numpy / Python-integer restatement
 (tests/tempo_ref.py) on every integer and with == on bpm and confidence; what the definition does to sound, with the restatement
 alone; the defaults and the limits; the new kernels' resources; the walk under the sanitizers (tests/cpp/tempo_check.cpp).
-tests/test_tempo_gpu.py holds the kernels themselves to the restatement on the GPU."""
+The tie cases that reach the kernels as clips (tests/tempo_cases.py): every predicate, and the list through the walk.
+tests/test_tempo_gpu.py and tests/test_tempo_edges_gpu.py hold the kernels themselves to the restatement on the GPU."""
 import ctypes as C
 import math
 import os
@@ -11,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import tempo_cases as tc
 import tempo_ref as tr
 from libzl_amd import _abi, build
 
@@ -185,6 +187,37 @@ def test_the_largest_request():
     recs, geom = call([(E, 48000.0, 64, 43.945, 150.0)])
     assert int(geom[0][1]) == 1024 and int(geom[0][3]) + int(geom[0][4]) - 1 == 8200 and int(geom[0][6]) == 16 * 31
     assert recs[0]["lag_coarse"] == 700 and recs[0]["doublings"] == 3
+
+
+# ---- the tie cases that reach the device as clips (tests/tempo_cases.py) --------------------------------------------------------------
+def test_every_tie_case_hits_its_edge():
+    """by the restatement alone: a case whose lags stop tying where it says fails here, without a GPU"""
+    cases = tc.cases()
+    for c in cases:
+        tc.holds(c)
+    names = " | ".join(c["name"] for c in cases)
+    for kind in ("every lag ties", "neighbouring lanes", "all four waves", "successive passes", "doubling's triple"):
+        assert kind in names, kind
+    assert len(cases) == 5
+    for c in tc.too_short():
+        rec, W, first_lag, A = tc.want(c)
+        assert A == [] and rec["lag_coarse"] == 0 and rec["lag_fine"] == 0 and rec["bpm"] == 0.0
+
+
+def test_the_tie_cases_through_the_harness():
+    """the whole list in one call of the host walk (the energies are the restatement's), requests without a lag first, last and twice
+    in a row in the middle"""
+    import onset_ref as onr
+    cases, (s0, s1) = tc.cases(), tc.too_short()
+    half = len(cases) // 2
+    order = [s0] + cases[:half] + [s1, s0] + cases[half:] + [s1]
+    recs, geom = call([(onr.energy(c["x"], c["req"][0], c["req"][1], c["req"][2]), c["rate"]) + c["req"][2:] for c in order], count_limit=40 << 20)
+    for c, rec, g in zip(order, recs, geom):
+        if "pred" in c:
+            tc.literal(c, rec)
+            assert (int(g[0]), int(g[1]), int(g[2])) == tc.lags_of(c)
+        else:
+            assert int(g[4]) == 0 and rec["lag_fine"] == 0
 
 
 # ---- what the definition does to sound (the restatement alone) ----------------------------------------------------------------------
