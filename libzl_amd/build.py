@@ -284,6 +284,14 @@ def build_pair_wrap_harness(force: bool = False) -> str:
                           _NO_CONTRACT + ["-Wall", "-Wno-unused-function"], force)
 
 
+def build_pair_scalar_harness(force: bool = False) -> str:
+    """The pair kernels' scalar records (zl_render.h: zl_voice_block_class, zl_pair_fast_bits, zl_pair_group_need; zl_pair.h:
+    zl_pair_scalar_window), made the way K1c makes them, with the host planner."""
+    plan_host = os.path.join("..", "..", "tests", "cpu_harness", "plan_host.cpp")        # (included by the harness for its ZlSim)
+    return _build_harness("zl_pair_scalar_host", "pair_scalar_host.cpp", ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_pair.h", "zl_host.h", _ZLHIP_H, plan_host],
+                          _NO_CONTRACT + ["-Wall", "-Wno-unused-function"], force)
+
+
 def build_group_harness(force: bool = False) -> str:
     """The engine group's partition arithmetic and command routing (zl_group.h)."""
     return _build_harness("zl_group_host", "group_host.cpp", ["zl_types.h", "zl_plan.h", "zl_host.h", "zl_group.h", _ZLHIP_H], _NO_CONTRACT + ["-Wall", "-Wno-unused-function"], force)

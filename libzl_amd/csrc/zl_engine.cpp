@@ -328,6 +328,9 @@ int zlhip_engine_create(const zlhip_config *cfg_in, zlhip_engine **out)
             dev(q.hdr, W * V, "plan headers");
             dev(q.seg0, W * V, "plan segment 0");
             dev(q.seg1, W * V, "plan segment 1");
+            // the pair kernels' scalar records (ZL_K2_PAIR_SCALAR): 8 bytes per (block, voice) + 2 per (block, 64 voices) + 8 per voice --
+            // an eighth of the plan records' 64.  Only the faithful linear mode has those kernels (zl_pair_shape)
+            if (cfg->mode == 0u) dev(q.pairTab, zl_pair_tab_words((int)W, (int)V), "pair scalar records");
             // per-frame control of the window's slow (block, voice)s: a pool of block-sized slots.  One slot for every (block, voice)
             // of a window would be 12 bytes per voice-frame (6.4 GB per set for 1024 voices); slow blocks are sparse (release tails of
             // one-shots, the block behind a loop restart), so the pool is capped -- ZL_CTL_POOL_MB per set, default 256 -- and a
@@ -952,6 +955,10 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
     // ---- the pair kernels' staging without the run lists (zl_order.h): ZL_K2_STAGE_NORUN 1 = in the blocks behind the last
     //      inline run of the bus's voices (default), 0 = never (K1o then leaves run_end = INT_MAX); read per call
     const int stageNorun = [] { const char *v = std::getenv("ZL_K2_STAGE_NORUN"); return v ? (std::atoi(v) != 0 ? 1 : 0) : 1; }();
+    // ---- the pair kernels' fast workgroups (zl_render.h, ZL_ONGRID_SCALAR): ZL_K2_PAIR_SCALAR 1 = K1c leaves the scalar records of a
+    //      window that zl_k2_pair_phase_render renders, and that launch's workgroups whose bus is on-grid throughout do not stage (default),
+    //      0 = no records, every workgroup stages; read per call.  Results do not depend on it.
+    const int pairScalar = [] { const char *v = std::getenv("ZL_K2_PAIR_SCALAR"); return v ? (std::atoi(v) != 0 ? 1 : 0) : 1; }();
     // offline bounce, direct delivery: K2 itself also stores the finished bus into the caller's page-locked host buffer
     const bool direct = e->bnc.sink.on && e->bnc.sink.hostDev && A.groups == 1;
     // ---- which kernel a window of K blocks gets, its grid, and what follows from it (zl_launch.h) ----
@@ -1031,6 +1038,11 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
         q.ctlBase += (unsigned long long)Aw.K * (unsigned long long)e->V + 1ull;
         const ZlK2Launch L = k2Launch(Aw.K, q.order != nullptr);
         Aw.order = L.order ? q.order : nullptr;
+        // the pair kernels' scalar records: this window's K1c writes them and its launch reads them (bit 2 of ongrid, seen by those two alone)
+        if (zl_pair_scalar_window(pairScalar, L.kernel == ZL_K2_PAIR_PHASE_RENDER, L.order, q.pairTab != nullptr && Aw.K <= e->windowCap, A.VPB)) {
+            Aw.ongrid |= ZL_ONGRID_SCALAR;
+            zl_batch_set_pair_tab(Aw, q.pairTab);
+        }
         if (w > 0) { Aw.n_op_ranges = 0; Aw.ops = nullptr; Aw.op_ranges = nullptr; Aw.n_clip_edits = 0; Aw.clip_edits = nullptr; }   // commands and parameter edits apply before the first block only
         // planning may not overwrite a record set while an earlier window (of this or the previous call) still renders from it
         if (ps != s && q.used) ZL_HIP(e, hipStreamWaitEvent(ps, q.renderedEv, 0));

@@ -139,6 +139,7 @@ struct zlhip_engine {
     struct PlanSet {
         ZlDev<ZlVoiceConst> vconst; ZlDev<ZlRunList> runs; ZlDev<ZlTSeg> tsegs;
         ZlDev<ZlPlanHdr> hdr; ZlDev<ZlPlanSeg0> seg0; ZlDev<ZlPlanSeg1> seg1;
+        ZlDev<uint64_t> pairTab;                          // the pair kernels' scalar records of a window (zl_render.h, zl_pair_tab_words), engines in mode 0 only
         ZlDev<double> ctlP; ZlDev<float> ctlEnv;          // the window's pool of per-frame control slots (zl_plan.h, zl_ctl_alloc)
         ZlDev<unsigned long long> ctlNext;                // its bump counter, never reset: a window's slots count from ctlBase
         unsigned long long ctlBase = 0;                   // host side: past every value the counter can have reached

@@ -58,10 +58,10 @@ __global__ void zl_k0_apply_ops(const ZlBatch A)
 // ------------------------------------------------------------------------------------------------
 // K1c body for one wave: block k of the wave's 64 voices (one lane each).  Blocks with more than two position
 // segments are expanded into per-frame control by the whole wave, lanes over frames.
-static __device__ __forceinline__ void zl_k1c_block(const ZlBatch &A, ZlAssembler &as, int v, int lane, int k)
+static __device__ __forceinline__ void zl_k1c_block(const ZlBatch &A, ZlAssembler &as, int v, int lane, int k, ZlBlockPlan *rec = nullptr)
 {
     int idx0 = 0, base0 = 0, n_active = 0;
-    const int nseg = as.block(A, k, idx0, base0, n_active);
+    const int nseg = as.block(A, k, idx0, base0, n_active, rec);
     unsigned long long m = __ballot(nseg > 2);
     while (m) {
         const int l = __builtin_ctzll(m);
@@ -159,7 +159,28 @@ __global__ void __launch_bounds__(64) zl_k1c_assemble(const ZlBatch A, int block
     const int kend = kbeg + blocks_per_lane < A.K ? kbeg + blocks_per_lane : A.K;
     ZlAssembler as;
     as.begin(A, mine ? v : 0, kbeg, mine ? kend : kbeg);
-    for (int k = kbeg; k < kend; ++k) zl_k1c_block(A, as, v, lane, k);
+    if (!(A.ongrid & ZL_ONGRID_SCALAR)) {
+        for (int k = kbeg; k < kend; ++k) zl_k1c_block(A, as, v, lane, k);
+        return;
+    }
+    // A window whose launch is zl_k2_pair_phase_render with ZL_K2_PAIR_SCALAR on: the scalar records (zl_render.h).  The lane holds the
+    // voice-block's plan as it stores it; the class is the text the pair kernels' staging reads (zl_voice_block_class, mode 0), so a
+    // chunk's bit is set exactly where staging would class it (cc & 132) == 132.  Every (block, voice) of the window gets its word and
+    // every (block, group) its 16 bits, the blocks without a record of K1c's included: nothing of an earlier window is left to read.
+    const ZlVoiceConst vc = A.vconst[mine ? v : 0];
+    uint64_t *tab = zl_batch_pair_tab(A);
+    uint16_t *bits = reinterpret_cast<uint16_t *>(tab + zl_pair_tab_fast(A.K, A.V));
+    const int G = (A.V + 63) / 64;
+    if (mine && kbeg == 0) tab[zl_pair_tab_pan(A.K, A.V) + (size_t)v] = *reinterpret_cast<const uint64_t *>(&vc.lpan);
+    for (int k = kbeg; k < kend; ++k) {
+        ZlBlockPlan pl;
+        zl_k1c_block(A, as, v, lane, k, &pl);
+        const int cls = zl_voice_block_class(0u, A.ongrid, A.trace, A.N, vc, pl);
+        const bool fast = mine && zl_voice_block_fast(cls);
+        if (mine) tab[(size_t)k * A.V + (size_t)v] = fast ? zl_ongrid_addr0((uint64_t)reinterpret_cast<uintptr_t>(A.arena), vc.src_offset, pl.P0, (cls & 16) != 0) : 0ull;
+        const unsigned long long mf = __ballot(fast), mm = __ballot(fast && (cls & 16));
+        if (lane == 0) bits[(size_t)k * G + blockIdx.x] = (uint16_t)zl_pair_fast_bits(mf, mm);
+    }
 }
 
 // K1o: K2's launch order of the window's blocks, sorted by the loop phase of each z-slot's key voice (zl_order.h).  One
@@ -1254,30 +1275,11 @@ static __device__ __forceinline__ void zl_k2_stage_load(const ZlBatch &A, int kk
 template <uint32_t MODE>
 static __device__ __forceinline__ int zl_k2_stage_class(const ZlBatch &A, const ZlVoiceConst &vc, const ZlBlockPlan &pl)
 {
-    const int N = A.N;
-    int cls = (pl.flags & ZL_PLAN_ACTIVE) ? (1 | ((pl.flags & ZL_PLAN_SLOW) ? 2 : 0)) : 0;
-    // 4 = "simple": whole block, sustain (and no debug trace); 8 = it has a second position segment; 16 = mono source
-    const float gprod = vc.lgain * vc.rgain * vc.clip_volume * pl.env;     // finite iff every factor is (or one is 0 * inf = NaN)
-    // (sources of 4 GiB and more take the general path: the simple paths address a source with 32-bit byte offsets)
-    if (cls == 1 && pl.nseg <= 2 && !(pl.flags & ZL_PLAN_ENV) && pl.n_active == N && (vc.channels == 1 || vc.channels == 2) && !A.trace
-        && (gprod - gprod) == 0.0f && (uint32_t)vc.sample_duration < 0x1ffffff0u)
-    {
-        // 64 = "interior": first and last position of the block (P0 and P0 + (N-1) step, step > 0) leave room for
-        // every tap: pos + 1 <= duration (pos >= 1 and pos + 2 <= duration with 4 taps)
-        constexpr bool HM = (MODE & ZL_MODE_HERMITE) != 0;
-        const double Pmax = fma((double)(N - 1), pl.step, pl.P0);
-        const bool interior = pl.nseg == 1 && pl.P0 >= (HM ? 1.0 : 0.0) && Pmax < (double)(vc.sample_duration - (HM ? 1 : 0));
-        cls |= 4 | (pl.nseg == 2 ? 8 : 0) | (vc.channels == 1 ? 16 : 0) | ((pl.nseg == 1 && pl.step == 1.0 && pl.P0 < 1073741824.0) ? 32 : 0)
-             | (interior ? 64 : 0);
-        // 128 = "on-grid": a unit-step interior block from an integer position of a source known to be finite -- alpha = 0 in
-        // every frame, the second tap only adds a signed zero (zl_render.h): zl_k2_chunk_ongrid mixes it from one tap
-        cls |= zl_voice_ongrid(MODE, A.ongrid, true, (cls & 32) != 0, interior, pl.P0, pl.step, vc.pad[0]) ? 128 : 0;
-        // 256 = "on-grid with one loop restart": two unit-step segments from integer positions, every tap of both inside the source
-        // (zl_render.h, zl_voice_ongrid2): zl_k2_chunk_ongrid_pair_wrap mixes each frame from the first tap of its own segment
-        cls |= zl_voice_ongrid2(MODE, A.ongrid, vc.pad[0], cls & 3, pl.n_active, pl.flags, true, pl.nseg, pl.n1, N, pl.step, pl.step1, pl.P0, pl.P1,
-                                vc.sample_duration) ? 256 : 0;
-    }
-    return cls;
+    // 4 = "simple": whole block, sustain (and no debug trace); 8 = it has a second position segment; 16 = mono source; 32 = unit step;
+    // 64 = "interior"; 128 = "on-grid": zl_k2_chunk_ongrid mixes it from one tap; 256 = "on-grid with one loop restart":
+    // zl_k2_chunk_ongrid_pair_wrap mixes each frame from the first tap of its own segment.  The text is zl_render.h's, which K1c reads too
+    // when it leaves the scalar records of a window (zl_k1c_scalar)
+    return zl_voice_block_class(MODE, A.ongrid, A.trace, A.N, vc, pl);
 }
 
 // ... its ZlUnit: zl_unit_record's, and for a voice-block of class 256, whose record no chunk function reads (a chunk with a two-segment
@@ -1857,6 +1859,83 @@ __global__ void __launch_bounds__(256, (MODE & ZL_MODE_HERMITE) == 0 ? ZL_K2_WAV
 #define ZL_K2_PAIR_WAVES 4
 #endif
 #define ZL_K2_PAIR_LDS 18432   // LDS per workgroup the launch pads to: 8 workgroups and the planner's 12 KB fit a CU's 160 KB, a ninth does not
+
+// THE FAST WORKGROUP (ZL_K2_PAIR_SCALAR; the records: zl_render.h, written by K1c's zl_k1c_assemble).  Everything zl_k2_chunk_ongrid_pair reads of a
+// voice is wave-uniform -- the address of the block's frame 0 and the pan pair -- so a workgroup whose bus is on-grid in every chunk of its
+// block does not stage at all: no per-lane record loads, no class, no LDS records, no barrier, no v_readfirstlane.  Per chunk of 8 voices ONE
+// scalar load brings the eight addresses (16 SGPRs) and one the eight pan pairs; the source loads take the SGPR pair as their scalar base and
+// the packed multiply takes the pan pair from SGPRs.  The addresses of chunk c + 1 are asked for behind the source loads of chunk c, so a miss
+// on the streamed table waits behind them.  The loads, the order of the voices and the mix are zl_k2_chunk_ongrid_pair's: the same bits.
+// Scalar LOADS only; nothing is written through the scalar path.
+typedef uint64_t zl_u64x8 __attribute__((ext_vector_type(8)));
+typedef float zl_f16 __attribute__((ext_vector_type(16)));
+#define ZL_CONST_AS __attribute__((address_space(4)))
+// (lpan m, rpan m) with the pan pair in SGPRs
+static __device__ __forceinline__ zl_f2 zl_pk_pan_s(zl_f2 pan, zl_f2 ms)
+{
+    zl_f2 r; asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(r) : "s"(pan), "v"(ms)); return r;
+}
+// zl_mix_acc_ongrid_pk with that multiply: the same five operations on the same operands
+template <int SEL>
+static __device__ __forceinline__ void zl_mix_acc_ongrid_pk_s(zl_f2 &acc, zl_f2 x, zl_f2 pan)
+{
+    zl_f2 ms = SEL == 0 ? zl_pk_sumdiff(x) : SEL == 1 ? zl_pk_sumdiff_lo(x) : zl_pk_sumdiff_hi(x);
+    ms.x = 0.5f * ms.x;                                           // :208
+    acc = zl_pk_add(acc, zl_pk_side(zl_pk_pan_s(pan, ms), ms));   // :210-211, :218-221 (index shift applied at the store)
+}
+// addr = the addr0 words of the bus's first voice in this block, pan = its pan word; nch chunks of 8 voices, all of one layout
+template <bool MONO>
+static __device__ __forceinline__ void zl_k2_pair_fast(const uint64_t *addr, const uint64_t *pan, int nch, int f0,
+                                                       float &accL0, float &accR0, float &accL1, float &accR1)
+{
+    constexpr int U = 8;
+    const ZL_CONST_AS zl_u64x8 *at = reinterpret_cast<const ZL_CONST_AS zl_u64x8 *>(reinterpret_cast<uintptr_t>(addr));
+    const ZL_CONST_AS zl_f16 *pt = reinterpret_cast<const ZL_CONST_AS zl_f16 *>(reinterpret_cast<uintptr_t>(pan));
+    zl_f2 acc0 = {accL0, accR0}, acc1 = {accL1, accR1};
+    zl_u64x8 a = at[0];
+    for (int c = 0; c < nch; ++c) {
+        zl_f4a8 d4[MONO ? 1 : U];
+        zl_f2   d2[MONO ? U : 1];
+        const uint32_t ob = zl_k2_ongrid_offset((uint32_t)f0 << (MONO ? 2 : 3));   // interior: frames ipos + f0 and ipos + f0 + 1 are inside the source
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (MONO) d2[u] = zl_k2_ongrid_load<zl_f2a4b>(a[u], ob);
+            else      d4[u] = zl_k2_ongrid_load<zl_f4a8>(a[u], ob);
+        }
+        const zl_f16 p = pt[c];
+        a = at[c + 1 < nch ? c + 1 : c];                          // the next chunk's addresses, behind this chunk's source loads
+        __builtin_amdgcn_sched_barrier(0);                        // (all loads in flight before the first mix, as in zl_k2_chunk_ongrid_pair)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const zl_f2 pu = {p[2 * u], p[2 * u + 1]};
+            if (MONO) {
+                zl_mix_acc_ongrid_pk_s<1>(acc0, d2[u], pu);
+                zl_mix_acc_ongrid_pk_s<2>(acc1, d2[u], pu);
+            } else {
+                zl_mix_acc_ongrid_pk_s<0>(acc0, __builtin_shufflevector(d4[u], d4[u], 0, 1), pu);
+                zl_mix_acc_ongrid_pk_s<0>(acc1, __builtin_shufflevector(d4[u], d4[u], 2, 3), pu);
+            }
+        }
+    }
+    accL0 = acc0.x; accR0 = acc0.y; accL1 = acc1.x; accR1 = acc1.y;
+}
+// May the workgroup of (block k, voices [v0, v1)) take it?  Every chunk bit of its voices set, and one layout for the whole bus (a bus of
+// mono and stereo chunks stages: the walk is compiled once per layout).  1 = stereo, 2 = mono, 0 = no.  Scalar loads of 16-bit entries, two to a word.
+static __device__ __forceinline__ int zl_k2_pair_fast_kind(const uint64_t *tab, int K, int V, int k, int v0, int v1)
+{
+    const ZL_CONST_AS uint32_t *bw = reinterpret_cast<const ZL_CONST_AS uint32_t *>(reinterpret_cast<uintptr_t>(tab + zl_pair_tab_fast(K, V)));
+    const int G = (V + 63) / 64;
+    bool all = true, anyMono = false, allMono = true;
+    for (int g = v0 >> 6; g <= (v1 - 1) >> 6; ++g) {
+        const size_t i = (size_t)k * (size_t)G + (size_t)g;
+        const uint32_t w = (bw[i >> 1] >> ((i & 1) * 16)) & 0xffffu;
+        const uint32_t need = zl_pair_group_need(v0, v1, g);
+        all = all && (w & need) == need;
+        anyMono = anyMono || ((w >> 8) & need) != 0u;
+        allMono = allMono && ((w >> 8) & need) == need;
+    }
+    return !all ? 0 : allMono ? 2 : anyMono ? 0 : 1;
+}
 template <bool ORD>
 static __device__ __forceinline__ void zl_k2_pair_body(const ZlBatch &A)
 {
@@ -1889,6 +1968,17 @@ static __device__ __forceinline__ void zl_k2_pair_body(const ZlBatch &A)
     const bool norun = ORD && __builtin_amdgcn_readfirstlane((int)(k >= A.order[zl_order_tail_run_end((int)gridDim.z, A.K, (int)bz)])) != 0;
 
     float accL0 = 0.0f, accR0 = 0.0f, accL1 = 0.0f, accR1 = 0.0f;
+    // the fast workgroup (zl_k2_pair_fast): the window has the scalar records, every record of the block is an explicit one (norun), it is not
+    // the call's last block (the report path reads s_plan) and every chunk of the bus is fast in this block.  Every other workgroup stages.
+    int fastKind = 0;
+    if (ORD && (A.ongrid & ZL_ONGRID_SCALAR) && norun && !wantPeak)
+        fastKind = zl_k2_pair_fast_kind(zl_batch_pair_tab(A), A.K, V, __builtin_amdgcn_readfirstlane(k), v0, v1);
+    if (fastKind != 0) {
+        const uint64_t *addr = zl_batch_pair_tab(A) + (size_t)__builtin_amdgcn_readfirstlane(k) * (size_t)V + (size_t)v0;
+        const uint64_t *pan = zl_batch_pair_tab(A) + zl_pair_tab_pan(A.K, V) + (size_t)v0;
+        if (fastKind == 2) zl_k2_pair_fast<true>(addr, pan, (v1 - v0) >> 3, f0, accL0, accR0, accL1, accR1);
+        else               zl_k2_pair_fast<false>(addr, pan, (v1 - v0) >> 3, f0, accL0, accR0, accL1, accR1);
+    } else
     for (int vb = v0; vb < v1; vb += CH) {
         const int nv = (v1 - vb < CH) ? v1 - vb : CH;
         if (vb != v0) __syncthreads();                            // (nothing to wait for before the first pass)

@@ -23,3 +23,12 @@ inline bool zl_pair_window(int sw, bool shape, bool cheap)
     if (sw == 2) return shape;
     return sw == 1 && shape && cheap;
 }
+
+// does a pair launch read the scalar records K1c leaves (zl_render.h, ZL_ONGRID_SCALAR)?  sw = ZL_K2_PAIR_SCALAR (0 / 1); phase_order: the
+// launch is zl_k2_pair_phase_render -- only it knows the blocks no inline run reaches (run_end, zl_order.h), and only there every record
+// is an explicit one; have_tab: the engine has the buffer (mode 0).  A fast workgroup walks its bus in whole chunks of 8 voices read with
+// one scalar load each: buses whose width is not a multiple of 8 (then some bus's first voice is not one either) never qualify.
+inline bool zl_pair_scalar_window(int sw, bool pair, bool phase_order, bool have_tab, int VPB)
+{
+    return sw != 0 && pair && phase_order && have_tab && VPB > 0 && (VPB % 8) == 0;
+}

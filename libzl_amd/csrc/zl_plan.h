@@ -945,8 +945,11 @@ struct ZlAssembler {
 
     // Returns the number of position segments of block k (0: nothing to write).  A block with more than two is marked
     // ZL_PLAN_SLOW and the caller fills its per-frame control with zl_expand_frame(idx0, base0, ...) for frames < n_active.
-    ZL_HD int block(const ZlBatch &A, int k, int &idx0, int &base0, int &n_active)
+    // rec (K1c's scalar records, zl_render.h): the header and first segment as they were stored, for a block of ONE segment whose record
+    // has no second part -- the only kind a reader of rec asks about; every other block leaves *rec cleared.
+    ZL_HD int block(const ZlBatch &A, int k, int &idx0, int &base0, int &n_active, ZlBlockPlan *rec = nullptr)
     {
+        if (rec) zl_plan_clear(*rec);
         if (k >= kend) return 0;
         const int N = A.N;
         const int T = k * N;
@@ -988,6 +991,8 @@ struct ZlAssembler {
             ZlPlanSeg1 s1; s1.P1 = b.P; s1.step1 = b.step; s1.n1 = nseg == 2 ? bt - T : INT_MAX;
             s1.estep0 = a.estep; s1.E1 = b.E; s1.estep1 = b.estep;
             A.plan_seg1[pidx] = s1;
+        } else if (rec) {
+            rec->flags = h.flags; rec->n_active = h.n_active; rec->nseg = h.nseg; rec->env = h.env; rec->P0 = s0.P0; rec->step = s0.step;
         }
         idx0 = idx; base0 = base;
         return nseg;

@@ -140,6 +140,73 @@ ZL_HD inline ZlWrapLane zl_ongrid2_lane(int ipos, int alt, int n1, int f0)
     return w;
 }
 
+// The class bits of one voice-block as K2's pair kernels stage it (zl_kernels.hip, zl_k2_stage_class) and as K1c reads it when it leaves
+// the scalar records below: 1 = plays this block, 2 = per-frame control, 4 = "simple" (whole block, sustain, finite gains, no debug
+// trace), 8 = it has a second position segment, 16 = mono source, 32 = unit step, 64 = "interior" (every tap of the block inside the
+// source), 128 = on-grid (zl_voice_ongrid), 256 = on-grid with one loop restart (zl_voice_ongrid2).  One text for both readers and for
+// the CPU tier (tests/cpu_harness/pair_scalar_host.cpp).  zl_k2_body's kernels keep their own text (zl_kernels.hip, above zl_k2_stage_load).
+ZL_HD inline int zl_voice_block_class(uint32_t mode, int ongrid, int trace, int N, const ZlVoiceConst &vc, const ZlBlockPlan &pl)
+{
+    int cls = (pl.flags & ZL_PLAN_ACTIVE) ? (1 | ((pl.flags & ZL_PLAN_SLOW) ? 2 : 0)) : 0;
+    const float gprod = vc.lgain * vc.rgain * vc.clip_volume * pl.env;     // finite iff every factor is (or one is 0 * inf = NaN)
+    // (sources of 4 GiB and more take the general path: the simple paths address a source with 32-bit byte offsets)
+    if (cls == 1 && pl.nseg <= 2 && !(pl.flags & ZL_PLAN_ENV) && pl.n_active == N && (vc.channels == 1 || vc.channels == 2) && !trace
+        && (gprod - gprod) == 0.0f && (uint32_t)vc.sample_duration < 0x1ffffff0u)
+    {
+        // first and last position of the block (P0 and P0 + (N-1) step, step > 0) leave room for every tap: pos + 1 <= duration
+        // (pos >= 1 and pos + 2 <= duration with 4 taps)
+        const bool HM = (mode & ZL_MODE_HERMITE) != 0;
+        const double Pmax = fma((double)(N - 1), pl.step, pl.P0);
+        const bool interior = pl.nseg == 1 && pl.P0 >= (HM ? 1.0 : 0.0) && Pmax < (double)(vc.sample_duration - (HM ? 1 : 0));
+        cls |= 4 | (pl.nseg == 2 ? 8 : 0) | (vc.channels == 1 ? 16 : 0) | ((pl.nseg == 1 && pl.step == 1.0 && pl.P0 < 1073741824.0) ? 32 : 0)
+             | (interior ? 64 : 0);
+        cls |= zl_voice_ongrid(mode, ongrid, true, (cls & 32) != 0, interior, pl.P0, pl.step, vc.pad[0]) ? 128 : 0;
+        cls |= zl_voice_ongrid2(mode, ongrid, vc.pad[0], cls & 3, pl.n_active, pl.flags, true, pl.nseg, pl.n1, N, pl.step, pl.step1, pl.P0, pl.P1,
+                                vc.sample_duration) ? 256 : 0;
+    }
+    return cls;
+}
+
+// ---- the pair kernels' scalar records (ZL_K2_PAIR_SCALAR; zl_kernels.hip: K1c writes them, zl_k2_pair_body reads them with scalar loads) --------
+// What an on-grid chunk reads of a voice-block is wave-uniform: the byte address of the block's frame 0 and the pan pair.  K1c holds the
+// block's plan when it stores it and leaves, per window and record set, in ONE buffer of 8-byte words (zl_batch_pair_tab, zl_types.h):
+//   addr0[k V + v]        words [0, K V): the address, as zl_unit_record forms it -- meaningful only where the voice-block is on-grid
+//   pan[v]                words [K V, K V + V): (lpan, rpan) of ZlVoiceConst, dense
+//   fast[k G + g]         behind them, 16 bits per (block, group of 64 voices; G = ceil(V / 64)): bit c = chunk c of the group (voices 8 c .. 8 c + 7)
+//                         is FAST -- every voice on-grid, interior, one segment, all of one source layout, which is the chunk class test
+//                         (cc & 132) == 132 of the staged path; bit 8 + c = the chunk is all mono.  A block that an inline run covers
+//                         or K1 simulated has no record assembled by K1c: its bit is 0.
+#define ZL_ONGRID_SCALAR 4        // ZlBatch::ongrid bit 2 (only with bit 0): this window's K1c writes the records and its pair launch reads them
+ZL_HD inline size_t zl_pair_tab_pan(int K, int V) { return (size_t)K * (size_t)V; }
+ZL_HD inline size_t zl_pair_tab_fast(int K, int V) { return (size_t)K * (size_t)V + (size_t)V; }
+ZL_HD inline size_t zl_pair_tab_words(int K, int V) { return zl_pair_tab_fast(K, V) + ((size_t)K * (size_t)((V + 63) / 64) * 2 + 7) / 8; }
+// a voice-block of this class is one a fast chunk may hold; its layout bit
+ZL_HD inline bool zl_voice_block_fast(int cls) { return (cls & (4 | 64 | 128)) == (4 | 64 | 128); }
+// frame 0 of an on-grid voice-block: arena + 4 src_offset + 8 ipos (4 ipos mono) in 64-bit unsigned arithmetic, which wraps modulo 2^64 for
+// a source in a grown arena segment exactly as zl_unit_record's does
+ZL_HD inline uint64_t zl_ongrid_addr0(uint64_t arena, uint64_t src_offset, double P0, bool mono)
+{
+    return arena + (src_offset << 2) + ((uint64_t)(uint32_t)(int)P0 << (mono ? 2 : 3));
+}
+// the 16 bits of one (block, group): cls[i] = class of voice 64 g + i (0 for a voice the group does not have)
+ZL_HD inline uint32_t zl_pair_fast_bits(unsigned long long fast, unsigned long long mono)
+{
+    uint32_t w = 0;
+    for (int c = 0; c < 8; ++c) {
+        const unsigned f = (unsigned)(fast >> (8 * c)) & 255u, m = (unsigned)(mono >> (8 * c)) & 255u;
+        if (f == 255u && (m == 0u || m == 255u)) w |= 1u << c;
+        if (m == 255u) w |= 256u << c;
+    }
+    return w;
+}
+// the chunks of voices [v0, v1) (both multiples of 8) inside group g as a mask of the group's 8 bits; 0: none
+ZL_HD inline uint32_t zl_pair_group_need(int v0, int v1, int g)
+{
+    const int lo = v0 > 64 * g ? v0 : 64 * g, hi = v1 < 64 * g + 64 ? v1 : 64 * g + 64;
+    if (hi <= lo) return 0u;
+    return ((1u << ((hi - lo) >> 3)) - 1u) << ((lo - 64 * g) >> 3);
+}
+
 // :208-211 on the one tap (x0l, x0r) of an on-grid frame; a mono source passes x0r = x0l (r = l, :205)
 ZL_HD inline void zl_mix_frame_ongrid(float x0l, float x0r, float lpan, float rpan, float &lout, float &rout)
 {

@@ -302,7 +302,9 @@ struct ZlBatch {
     int32_t             ctl_slots;
     ZlSimConst         *sim_const;// [V]
     ZlReport           *reports;  // [V]
-    float              *partials; // [K][B][groups][2][N]  (only when groups > 1)
+    float              *partials; // [K][B][groups][2][N]  (only when groups > 1).  With ongrid bit 2 (a pair launch: groups == 1) the word holds the
+                                  // window's scalar records instead (zl_batch_pair_tab below): the two are never wanted by the same window, and
+                                  // the layout of the kernel argument does not move
     float              *bus;      // [B][2][Ktot*N] -- or, with the strides below, rows wherever the caller wants them
     long long           bus_stride, ch_stride;   // floats from one bus's rows to the next / from a bus's left row to its right row; 0 = the
                                                  // layout above (2 * Ktot * N, Ktot * N).  A real-time cycle delivered straight into the caller's
@@ -314,6 +316,8 @@ struct ZlBatch {
     int32_t             pass_inline;
     int32_t             ongrid;     // ZL_K2_ONGRID: bit 0 = K2 may mix on-grid unit-step chunks from one tap (zl_render.h, zl_voice_ongrid), 0 = never;
                                     // bit 1 (ZL_K2_PAIR_WRAP, only with bit 0) = the pair kernels also take blocks with one loop restart (zl_voice_ongrid2)
+                                    // bit 2 (ZL_K2_PAIR_SCALAR, only with bit 0 and only in a window whose launch is zl_k2_pair_phase_render) = K1c
+                                    // leaves the scalar records in pair_tab and the launch's on-grid workgroups read them instead of staging
     int32_t             tile_accum; // 1 (resident kernel, blocks longer than 256 frames): ONE workgroup walks the frame tiles of its block in
                                     // order (bx = 0, 1, ...), and the fused level scan carries on from tile to tile (same defined order)
     // the call's per-voice reports, published by the K2 workgroups that render its LAST block (fused_reports = 1: every bus of that
@@ -332,3 +336,8 @@ struct ZlBatch {
     const int32_t      *order;    // [z-slots][K] K2's block of each launch slot (K1o, zl_order.h), or null: time order
     ZlBatchStats       *stats;
 };
+
+// the pair kernels' scalar records of a window (zl_render.h, ZL_ONGRID_SCALAR): 8-byte words that travel in the word of `partials`
+// (see there).  Never read as floats by anybody.
+ZL_HD inline uint64_t *zl_batch_pair_tab(const ZlBatch &A) { return reinterpret_cast<uint64_t *>(A.partials); }
+ZL_HD inline void zl_batch_set_pair_tab(ZlBatch &A, uint64_t *tab) { A.partials = reinterpret_cast<float *>(tab); }
