@@ -259,6 +259,17 @@ int  libzl_hotpath_clip_crossfade_loop(ClipAudioSource *c, float fade_ms, int cu
  * (may be NULL): bit 0 = clip i's loop was moved, bit 1 = its loop was crossfaded.  A clip that is NULL, not in the engine or playing a
  * re-render stays as it is.  Duplicate clips are ZLHIP_ERR_INVALID.  Returns the number of clips crossfaded, or a negative status. */
 int  libzl_hotpath_clips_seal_loops(ClipAudioSource **clips, int count, float search_ms, float min_improvement_db, float fade_ms, int curve, int *results);
+/* extension (build-defined: the reference has no warp): fits a loop to the session grid hit by hit, on the device (zlhip_sound_warp,
+ * DESIGN.md section 19) -- what a sampler calls "warp" or "quantise audio".  The clip's transients are found over its whole original
+ * (zlhip_sound_onsets with its defaults); every hit is moved by `strength` (0 .. 1) towards the nearest step of the grid of src_bpm
+ * with steps_per_beat steps (1 .. 64) per beat, counted from the clip's start frame, and the whole is scaled to the session's bpm (the
+ * scheduler's); zlhip_warp_plan makes the anchors, hits that would need a region outside a ratio of 2 are left where the stretch puts
+ * them.  src_bpm 0: detected as libzl_hotpath_clip_tempo(c, 0, 0, ...) does; no tempo returns 0 and changes nothing.  *onsets_moved
+ * (may be NULL): the hits that became anchors; *new_length_frames (may be NULL): the frames of the clip's data now.  The clip keeps its
+ * id and its parameters (seconds of the playback data); the warp cannot be taken back: reload the clip.  A clip that plays a re-render
+ * is refused with ZLHIP_ERR_STATE: warp first, then tune and level.  Returns 1 for warped, 0 for nothing to do, or a negative status
+ * (nothing has changed then). */
+int  libzl_hotpath_clip_warp_to_grid(ClipAudioSource *c, float src_bpm, int steps_per_beat, float strength, int *onsets_moved, int *new_length_frames);
 /* extension (build-defined: the reference has no key detection): the musical key of the data the clip plays now between its start and
  * its start + length, detected on the device (zlhip_sound_key with the defaults).  *tonic: 0 = C .. 11 = B, or
  * -1 for "no key" (silence, a region shorter than one analysis frame, a flat chroma), which is not an error; *mode: 0 major, 1 minor;

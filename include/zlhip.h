@@ -483,6 +483,56 @@ int zlhip_sound_loop_crossfade(zlhip_engine *e, const zlhip_xfade_request *r, zl
 int zlhip_sound_loop_crossfade_batch(zlhip_engine *e, const zlhip_xfade_request *reqs, int32_t count, zlhip_xfade *out);
 /* measurement: device time of the measuring launch and of the render and publishing launches of the last call made with profiling on */
 int zlhip_debug_xfade_timings(zlhip_engine *e, float *measure_ms, float *render_ms);
+/* Warp: a clip fitted to the session grid on the device, a time stretch cut at the clip's hits (a build-defined
+ * extension, the reference has no warp).  A uniform stretch leaves a hit that is early or late early or late; here every region between
+ * two anchors gets its own ratio, starts exactly at its anchor with no seek (the attack is copied 1:1) and is searched by its own
+ * workgroup.
+ *   A request is (id, count, anchors[count]), each anchor (src_frame a, dst_frame d), over the slot's ORIGINAL data of `length` frames:
+ *   2 <= count <= ZLHIP_WARP_MAX_ANCHORS, anchors[0] = (0, 0), anchors[count - 1].src_frame = length, a and d strictly increasing,
+ *   N = d_last with N + 8 <= INT32_MAX.  Region i plays [a_i, a_i+1) in [d_i, d_i+1): A and D frames, A <= 4 D and D <= 4 A.  A region
+ *   with A != D is stretched with section 8's overlap O of the rate and section 8's sequence S and seek window W of tau = A / D:
+ *   L = S - O, nseg = ceil(D / L), room = A - L - (W - 1) >= 0, S > O, W >= 1, W + O <= 4608.  A region with A = D is copied.  Anything
+ *   else is ZLHIP_ERR_INVALID, as are ids not in use or repeated and count < 0 -- all decided before the first HIP call.  A request
+ *   whose every region has A = D is the identity: applied = 0, no error, the clip is left alone.
+ *   Segments and output: libzl_amd/csrc/zl_warp.h.  b_0 = a; b_k = a + min(floor(k tau L), room) + off_k with section 8's seek and tie
+ *   rule, so no frame a region plays comes from the next one (a hit is never heard twice); the first O frames of every segment but the
+ *   clip's first are faded from the continuation of the segment in front of it (zl_st_xfade), across region joins too.
+ *   The result: applied, regions, stretched_regions, segments (one seek offset each, zlhip_debug_warp_offsets), length (= N), overlap.
+ *   ZL_SOUND_FINITE stays set iff the original had it and every written sample is finite.
+ *   A clip that currently plays a re-render is ZLHIP_ERR_STATE; an arena that cannot hold the whole call is ZLHIP_ERR_CAPACITY.  All
+ *   or nothing: on any error every clip is as it was and out is not written.  Synchronisation is zlhip_sound_convert_rate's.  A call is
+ *   one copy of each of its tables, a seek launch, a synthesis launch, a publishing launch and one wait, whatever the number of requests; a
+ *   call whose every request is the identity launches and copies nothing.
+ *   Consequences.  The new extent becomes the clip's ORIGINAL: warp first, then tune and level (a later re-render starts from the
+ *   warped data).  Clip parameters are seconds of the playback data and keep their meaning; zlhip_warp_map carries a frame across.
+ *   Not provided: undo (reload the clip); a variable seek window or anything cleverer than the clamp at a stretched slice's end (far
+ *   below tau = 1 the last segments of a slice repeat its tail); band-limiting; warping under a re-render; moving the clip's own start,
+ *   length and slices; beat-phase or downbeat detection (origin is the caller's); any change to section 8's kernels. */
+#define ZLHIP_WARP_MAX_ANCHORS 4096
+typedef struct zlhip_warp_anchor { int32_t src_frame, dst_frame; } zlhip_warp_anchor;
+typedef struct zlhip_warp_request { int32_t id, count; const zlhip_warp_anchor *anchors; } zlhip_warp_request;
+typedef struct zlhip_warp { int32_t applied, regions, stretched_regions, segments, length, overlap; } zlhip_warp;
+/* host only: checks the anchors against a sound of `length` frames at `sample_rate` and fills the summary (applied = 0: the identity) */
+int zlhip_warp_resolve(double sample_rate, int32_t length, const zlhip_warp_anchor *anchors, int32_t count, zlhip_warp *summary);
+/* host only: from hits to anchors, pure arithmetic in double (zl_warp.h, zl_wp_plan).  scale = src_bpm / dst_bpm,
+ * g = rate 60 / (src_bpm steps_per_beat); every onset t (ascending, inside the clip): q = rint((t - origin) / g), target = origin + q g,
+ * moved = t + strength (target - t), the anchor (t - P, rint(moved scale) - P) with P = preroll_frames (-1: the rate's overlap O), so
+ * that the attack lands on the grid and the join's fade lies in front of it; anchors with src <= 0 are skipped.  Start (0, 0), end
+ * (length, max(1, rint(length scale))).  A candidate is kept iff the region from the last kept anchor to it and the region from it to
+ * the end are acceptable by zlhip_warp_resolve's rules with the tighter ratio A <= 2 D, D <= 2 A: the result always resolves.
+ * *dropped counts the candidates not kept.  strength in [0, 1], steps_per_beat in [1, 64], both bpm > 0 and finite,
+ * 0 <= origin_frame < length, an acceptable region start -> end: else ZLHIP_ERR_INVALID; capacity too small: ZLHIP_ERR_CAPACITY */
+int zlhip_warp_plan(double sample_rate, int32_t length, const int32_t *onset_frames, int32_t n, double src_bpm, double dst_bpm, int32_t steps_per_beat,
+                    double strength, int32_t origin_frame, int32_t preroll_frames, zlhip_warp_anchor *anchors_out, int32_t capacity, int32_t *count, int32_t *dropped);
+/* host only: the piecewise-linear image of a source frame under the anchors (floor, 64-bit integers); frames in front of the clip map
+ * to 0, frames behind it to d_last; -1 for anchors == NULL or count < 2 */
+int64_t zlhip_warp_map(const zlhip_warp_anchor *anchors, int32_t count, int64_t src_frame);
+int zlhip_sound_warp(zlhip_engine *e, const zlhip_warp_request *request, zlhip_warp *out);
+int zlhip_sound_warp_batch(zlhip_engine *e, const zlhip_warp_request *reqs, int32_t count, zlhip_warp *out);
+/* the seek offsets of the clip's last warp, region by region in output order (a copy region has one, 0); out may be NULL to ask for the count */
+int zlhip_debug_warp_offsets(zlhip_engine *e, int32_t id, int32_t *out, int32_t capacity, int32_t *count);
+/* measurement: device time of the seek launch and of the synthesis and publishing launches of the last call made with profiling on */
+int zlhip_debug_warp_timings(zlhip_engine *e, float *seek_ms, float *synth_ms);
 /* Key: what key a loop is in (a build-defined extension, the reference has no key detection) -- detected on the
  * device in the sound's CURRENT playback data.  Pitch detection answers "no pitch" on a chord loop by design; this is the answer for
  * those.  Behind section 8's 16-bit quantisation everything the device does is integer arithmetic (libzl_amd/csrc/zl_key.h):
@@ -762,6 +812,9 @@ int  zlhip_group_sound_loop_batch(zlhip_group *g, const zlhip_loop_request *reqs
  * that is invalid, refused or does not fit fails on member 0 and changes nothing.  out receives member 0's results (the members hold
  * the same data: every member measures the same integers) */
 int  zlhip_group_sound_loop_crossfade_batch(zlhip_group *g, const zlhip_xfade_request *reqs, int32_t count, zlhip_xfade *out);
+/* zlhip_sound_warp_batch on every member, in member order, with zlhip_group_sound_convert_rate_batch's semantics; out receives member
+ * 0's results (the members hold the same data: every member finds the same offsets) */
+int  zlhip_group_sound_warp_batch(zlhip_group *g, const zlhip_warp_request *reqs, int32_t count, zlhip_warp *out);
 /* zlhip_sound_key_batch: member 0 answers */
 int  zlhip_group_sound_key_batch(zlhip_group *g, const zlhip_key_request *reqs, int32_t nreq, zlhip_key *out);
 /* zlhip_handle_commands_voices over the whole synth (taken, voices optional) */

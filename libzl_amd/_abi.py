@@ -181,6 +181,22 @@ class Xfade(C.Structure):
 XFADE_AUTO, XFADE_LINEAR, XFADE_EQUAL_POWER = 0, 1, 2
 
 
+class WarpAnchor(C.Structure):
+    _fields_ = [("src_frame", C.c_int32), ("dst_frame", C.c_int32)]
+
+
+class WarpRequest(C.Structure):
+    _fields_ = [("id", C.c_int32), ("count", C.c_int32), ("anchors", C.POINTER(WarpAnchor))]
+
+
+class Warp(C.Structure):
+    _fields_ = [("applied", C.c_int32), ("regions", C.c_int32), ("stretched_regions", C.c_int32), ("segments", C.c_int32), ("length", C.c_int32),
+                ("overlap", C.c_int32)]
+
+
+WARP_MAX_ANCHORS = 4096
+
+
 class KeyRequest(C.Structure):
     _fields_ = [("id", C.c_int32), ("first_frame", C.c_int32), ("num_frames", C.c_int32), ("hop", C.c_int32), ("max_frames", C.c_int32),
                 ("a4_hz", C.c_float), ("note_lo", C.c_int32), ("note_hi", C.c_int32), ("q", C.c_int32), ("gate", C.c_int32)]
@@ -287,6 +303,14 @@ SIGNATURES = {
     "zlhip_sound_loop_crossfade": (C.c_int, [_E, C.POINTER(XfadeRequest), C.POINTER(Xfade)]),
     "zlhip_sound_loop_crossfade_batch": (C.c_int, [_E, C.POINTER(XfadeRequest), C.c_int32, C.POINTER(Xfade)]),
     "zlhip_debug_xfade_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "zlhip_warp_resolve": (C.c_int, [C.c_double, C.c_int32, C.POINTER(WarpAnchor), C.c_int32, C.POINTER(Warp)]),
+    "zlhip_warp_plan": (C.c_int, [C.c_double, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32,
+                                  C.POINTER(WarpAnchor), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "zlhip_warp_map": (C.c_int64, [C.POINTER(WarpAnchor), C.c_int32, C.c_int64]),
+    "zlhip_sound_warp": (C.c_int, [_E, C.POINTER(WarpRequest), C.POINTER(Warp)]),
+    "zlhip_sound_warp_batch": (C.c_int, [_E, C.POINTER(WarpRequest), C.c_int32, C.POINTER(Warp)]),
+    "zlhip_debug_warp_offsets": (C.c_int, [_E, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zlhip_debug_warp_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "zlhip_key_resolve": (C.c_int, [C.c_double, C.POINTER(KeyRequest)]),
     "zlhip_key_design": (C.c_int, [C.c_double, C.POINTER(KeyRequest), C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p]),
     "zlhip_key_match_shift": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
@@ -364,6 +388,7 @@ SIGNATURES = {
     "zlhip_group_sound_pitch_batch": (C.c_int, [_E, C.POINTER(PitchRequest), C.c_int32, C.POINTER(Pitch)]),
     "zlhip_group_sound_loop_batch": (C.c_int, [_E, C.POINTER(LoopRequest), C.c_int32, C.POINTER(Loop)]),
     "zlhip_group_sound_loop_crossfade_batch": (C.c_int, [_E, C.POINTER(XfadeRequest), C.c_int32, C.POINTER(Xfade)]),
+    "zlhip_group_sound_warp_batch": (C.c_int, [_E, C.POINTER(WarpRequest), C.c_int32, C.POINTER(Warp)]),
     "zlhip_group_sound_key_batch": (C.c_int, [_E, C.POINTER(KeyRequest), C.c_int32, C.POINTER(Key)]),
     "zlhip_group_sound_loudness_batch": (C.c_int, [_E, C.POINTER(LoudnessRequest), C.c_int32, C.POINTER(Loudness)]),
     "zlhip_group_handle_commands": (C.c_int, [_E, C.POINTER(ClipCommand), C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

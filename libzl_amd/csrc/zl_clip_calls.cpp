@@ -1,5 +1,5 @@
 // zl_clip_calls.cpp -- the clip services of include/zlhip.h: loading from raw PCM, re-render, rate conversion, and the seven analyses
-// (waveform overviews, transients, tempo, pitch, loudness, loop points, key), and the loop crossfade.  Every one is a call on a loaded clip that validates everything before its
+// (waveform overviews, transients, tempo, pitch, loudness, loop points, key), the loop crossfade and the warp.  Every one is a call on a loaded clip that validates everything before its
 // first HIP call, reserves buffers that only grow, queues its launches on the engine's stream and waits once.  What they share is
 // written once, below; the engine itself -- arena, sound slots, rendering, the resident kernel -- is zl_engine.cpp.
 #include <hip/hip_runtime.h>
@@ -20,6 +20,7 @@
 #include "zl_resample.h"
 #include "zl_stretch.h"
 #include "zl_tempo.h"
+#include "zl_warp.h"
 #include "zl_xfade.h"
 
 // ---- what every service does ---------------------------------------------------------------------------------------------------
@@ -1317,6 +1318,194 @@ int zlhip_debug_xfade_timings(zlhip_engine *e, float *measure_ms, float *render_
     if (!e) return ZLHIP_ERR_INVALID;
     if (measure_ms) *measure_ms = e->xf.measureMs;
     if (render_ms) *render_ms = e->xf.renderMs;
+    return ZLHIP_OK;
+}
+
+// ---- warp (zl_warp.h, zl_warp.hip) ------------------------------------------------------------------------------------------------
+// A clip fitted to the session grid: a time stretch cut at the clip's hits.  The scaffold is the loop crossfade's: every applied clip
+// gets a new arena extent, one copy each carries the call's job records, region records and seek list, one launch finds the seek
+// offsets of every stretched region of the call (a workgroup each), one synthesises every extent, zl_k_resample_publish switches the
+// sound-table entries (ZL_SOUND_FINITE from the device's verdict), and the call waits once.  The new extent becomes the slot's original.
+int zlhip_warp_resolve(double sample_rate, int32_t length, const zlhip_warp_anchor *anchors, int32_t count, zlhip_warp *summary)
+{
+    static_assert(sizeof(zlhip_warp) == sizeof(ZlWpSummary) && sizeof(zlhip_warp_anchor) == sizeof(ZlWpAnchor), "the warp's records");
+    static_assert(ZLHIP_WARP_MAX_ANCHORS == ZL_WP_MAX_ANCHORS, "the anchor limit");
+    if (!anchors || !summary) return ZLHIP_ERR_INVALID;
+    ZlWpSummary s;
+    if (zl_wp_resolve(sample_rate, length, (const ZlWpAnchor *)anchors, count, &s, nullptr) != 0) return ZLHIP_ERR_INVALID;
+    std::memcpy(summary, &s, sizeof s);
+    return ZLHIP_OK;
+}
+
+int zlhip_warp_plan(double sample_rate, int32_t length, const int32_t *onset_frames, int32_t n, double src_bpm, double dst_bpm, int32_t steps_per_beat,
+                    double strength, int32_t origin_frame, int32_t preroll_frames, zlhip_warp_anchor *anchors_out, int32_t capacity, int32_t *count, int32_t *dropped)
+{
+    if (capacity < 0) return ZLHIP_ERR_INVALID;
+    int32_t c = 0, d = 0;
+    // (planned into a buffer of its own: on any error the caller's is not written)
+    std::vector<ZlWpAnchor> tmp((size_t)std::max(capacity, 2));
+    const int rc = zl_wp_plan(sample_rate, length, onset_frames, n, src_bpm, dst_bpm, steps_per_beat, strength, origin_frame, preroll_frames,
+                              anchors_out ? tmp.data() : nullptr, capacity, &c, &d);
+    if (rc != 0) return rc == -2 ? ZLHIP_ERR_CAPACITY : ZLHIP_ERR_INVALID;
+    std::memcpy(anchors_out, tmp.data(), (size_t)c * sizeof(ZlWpAnchor));
+    if (count) *count = c;
+    if (dropped) *dropped = d;
+    return ZLHIP_OK;
+}
+
+int64_t zlhip_warp_map(const zlhip_warp_anchor *anchors, int32_t count, int64_t src_frame)
+{
+    if (!anchors || count < 2) return -1;
+    return zl_wp_map((const ZlWpAnchor *)anchors, count, src_frame);
+}
+
+int zlhip_sound_warp_batch(zlhip_engine *e, const zlhip_warp_request *reqs, int32_t count, zlhip_warp *out)
+{
+    static_assert(sizeof(zlhip_warp) == 24 && sizeof(zlhip_warp_anchor) == 8 && sizeof(zlhip_warp_request) == 16, "the warp's layouts");
+    if (!e || count < 0 || (count > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
+    if (count == 0) return ZLHIP_OK;
+    // validate and resolve everything before the first HIP call
+    std::vector<ZlWpSummary> sums((size_t)count);
+    std::vector<std::vector<ZlWpRegion>> regs((size_t)count);
+    int32_t njobs = 0;
+    {
+        std::vector<char> seen((size_t)e->cfg.max_sounds, 0);
+        int64_t wgs = 0, nreg = 0, nseg = 0;
+        for (int32_t i = 0; i < count; ++i) {
+            const zlhip_warp_request &q = reqs[i];
+            { const int rc = check_sound(e, "sound_warp", q.id); if (rc != ZLHIP_OK) return rc; }
+            if (seen[(size_t)q.id]) return fail(e, ZLHIP_ERR_INVALID, "sound_warp_batch: a clip appears twice");
+            seen[(size_t)q.id] = 1;
+            const ZlSound &o = e->soundSlots[(size_t)q.id].orig;
+            regs[(size_t)i].resize((size_t)(q.count > 1 && q.count <= ZL_WP_MAX_ANCHORS ? q.count - 1 : 0));
+            if (!q.anchors || zl_wp_resolve(o.sample_rate, o.length, (const ZlWpAnchor *)q.anchors, q.count, &sums[(size_t)i], regs[(size_t)i].data()) != 0)
+                return fail_in(e, ZLHIP_ERR_INVALID, "sound_warp", "the anchors do not start at (0, 0) and end at the sound's length, are not strictly increasing, or a region is outside its limits");
+            if (!sums[(size_t)i].applied) continue;
+            ZlWpJob J; std::memset(&J, 0, sizeof J);
+            J.N = sums[(size_t)i].length; J.channels = o.channels;
+            wgs += zl_wp_job_wgs(J); nreg += sums[(size_t)i].regions; nseg += sums[(size_t)i].segments; ++njobs;
+        }
+        if (wgs > (int64_t)INT32_MAX || nreg > (int64_t)INT32_MAX || nseg > (int64_t)INT32_MAX)
+            return fail(e, ZLHIP_ERR_INVALID, "sound_warp_batch: more than 2^31 - 1 workgroups, regions or segments in one call");
+        for (int32_t i = 0; i < count; ++i)
+            if (sums[(size_t)i].applied && e->soundSlots[(size_t)reqs[i].id].renderFloats != 0)
+                return fail(e, ZLHIP_ERR_STATE, "sound_warp: the clip plays a re-render (warp first, then tune and level; re-render it with gain 0, pitch 0, speed 1 first)");
+    }
+    if (njobs == 0) {                                              // the identity everywhere: no launch, no copy
+        std::memcpy(out, sums.data(), (size_t)count * sizeof(zlhip_warp));
+        return ZLHIP_OK;
+    }
+    { const int rc = call_begin(e, true); if (rc != ZLHIP_OK) return rc; }
+    // the new extents (all or none: an arena that cannot hold the call leaves every clip as it was)
+    std::vector<size_t> newOff((size_t)count, 0), newFloats((size_t)count, 0);
+    auto rollback = [&]() { for (int32_t i = count - 1; i >= 0; --i) free_extent(e, newOff[(size_t)i], newFloats[(size_t)i]); };
+    for (int32_t i = 0; i < count; ++i) {
+        if (!sums[(size_t)i].applied) continue;
+        const size_t floats = zl_extent_floats(sums[(size_t)i].length, e->soundSlots[(size_t)reqs[i].id].orig.channels);
+        const int rc = alloc_extent(e, floats, &newOff[(size_t)i]);
+        if (rc != ZLHIP_OK) { rollback(); return rc; }
+        newFloats[(size_t)i] = floats;
+    }
+    std::vector<ZlWpJob> jobs; std::vector<ZlWpRegion> table; std::vector<int32_t> seekList, jobReq; std::vector<ZlRsPublish> pub; std::vector<uint32_t> verdicts;
+    int32_t wgs = 0, offs = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        if (!sums[(size_t)i].applied) continue;
+        const ZlSound &o = e->soundSlots[(size_t)reqs[i].id].orig;
+        ZlWpJob J; std::memset(&J, 0, sizeof J);
+        J.src = (uint64_t)(uintptr_t)arena_ptr(e, o.offset);
+        J.dst = (uint64_t)(uintptr_t)arena_ptr(e, newOff[(size_t)i]);
+        J.len = o.length; J.channels = o.channels; J.N = sums[(size_t)i].length; J.O = sums[(size_t)i].overlap;
+        J.region_base = (int32_t)table.size(); J.nregions = sums[(size_t)i].regions;
+        J.wg_base = wgs; J.verdict = (int32_t)jobs.size();
+        wgs += zl_wp_job_wgs(J);
+        for (ZlWpRegion R : regs[(size_t)i]) {
+            R.off_base += offs; R.job = J.verdict;
+            if (R.nseg > 1) seekList.push_back((int32_t)table.size());
+            table.push_back(R);
+        }
+        offs += sums[(size_t)i].segments;
+        ZlSound s = o; s.offset = newOff[(size_t)i]; s.length = J.N; s.flags &= ~(int32_t)ZL_SOUND_FINITE;
+        pub.push_back(ZlRsPublish{ s, reqs[i].id, J.verdict });
+        verdicts.push_back((o.flags & ZL_SOUND_FINITE) ? 0u : 1u);  // (an original without the flag stays without it)
+        jobs.push_back(J);
+        jobReq.push_back(i);
+    }
+    const char *what = "sound_warp: no memory for the call's records";
+    const size_t nj = jobs.size(), n = std::max<size_t>(nj * 2, 64), nr = table.size(), ns = std::max<size_t>(seekList.size(), 1), no = (size_t)offs;
+    const int rsv = reserve(e, false, { { ZB_WP_JOBS, nj, sizeof(ZlWpJob), n, false, what }, { ZB_WP_REGIONS, nr, sizeof(ZlWpRegion), std::max<size_t>(nr * 2, 1024), false, what },
+                                       { ZB_WP_LIST, ns, sizeof(int32_t), std::max<size_t>(ns * 2, 1024), false, what }, { ZB_WP_OFFS, no, sizeof(int32_t), std::max<size_t>(no * 2, 4096), false, what },
+                                       { ZB_WP_PUB, nj, sizeof(ZlRsPublish), n, false, what }, { ZB_WP_VERDICTS, nj, sizeof(uint32_t), n, false, what } });
+    if (rsv != ZLHIP_OK) { rollback(); return rsv; }
+    ZlWpJob *const dJobs = (ZlWpJob *)e->scratch[ZB_WP_JOBS].d; ZlWpRegion *const dRegs = (ZlWpRegion *)e->scratch[ZB_WP_REGIONS].d;
+    int32_t *const dList = (int32_t *)e->scratch[ZB_WP_LIST].d, *const dOffs = (int32_t *)e->scratch[ZB_WP_OFFS].d;
+    ZlRsPublish *const dPub = (ZlRsPublish *)e->scratch[ZB_WP_PUB].d; uint32_t *const dVerdicts = (uint32_t *)e->scratch[ZB_WP_VERDICTS].d;
+    // everything is decided: from here on only a HIP error fails the call
+    auto hip_failed = [&](int krc) {
+        e->err = std::string("sound_warp: ") + hipGetErrorString((hipError_t)krc);
+        (void)hipStreamSynchronize(e->stream);
+        // (the table entries the device may have switched go back to what the host's mirror holds)
+        for (const ZlRsPublish &p : pub) (void)hipMemcpy(e->dSounds + p.id, &e->hc.sounds[p.id], sizeof(ZlSound), hipMemcpyHostToDevice);
+        rollback();
+        return ZLHIP_ERR_HIP;
+    };
+    zlhip_engine::Warp &t = e->wp;
+    t.timer.on = e->profiling;
+    std::vector<int32_t> hOffs(no, 0); std::vector<uint32_t> verdictsOut(nj, 0u);
+    int krc = (int)hipMemcpyAsync(dJobs, jobs.data(), nj * sizeof(ZlWpJob), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dRegs, table.data(), nr * sizeof(ZlWpRegion), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0 && !seekList.empty()) krc = (int)hipMemcpyAsync(dList, seekList.data(), seekList.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dVerdicts, verdicts.data(), nj * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, pub.data(), nj * sizeof(ZlRsPublish), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemsetAsync(dOffs, 0, no * sizeof(int32_t), e->stream);     // (off[0] of every region, the copy regions' included)
+    if (krc == 0) krc = (int)t.timer.mark(0, e->stream);
+    if (krc == 0) krc = zl_launch_warp_seek(dJobs, dRegs, dList, (int32_t)seekList.size(), dOffs, e->stream);
+    if (krc == 0) krc = (int)t.timer.mark(1, e->stream);
+    if (krc == 0) krc = zl_launch_warp_synth(dJobs, (int32_t)nj, wgs, dRegs, dOffs, dVerdicts, e->stream);
+    if (krc == 0) krc = zl_launch_resample_publish(dPub, (int32_t)nj, dVerdicts, e->dSounds, e->stream);
+    if (krc == 0) krc = (int)t.timer.mark(2, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(hOffs.data(), dOffs, no * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(verdictsOut.data(), dVerdicts, nj * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
+    if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);      // the call's one wait
+    if (krc == 0) krc = (int)t.timer.elapsed(0, 1, &t.seekMs);
+    if (krc == 0) krc = (int)t.timer.elapsed(1, 2, &t.synthMs);
+    if (krc != 0) return hip_failed(krc);
+    e->outstanding = false;
+    // the swap on the host: the warped extent is the slot's original from now on, the old one goes back to the arena
+    for (size_t j = 0; j < nj; ++j) {
+        const ZlRsPublish &p = pub[j];
+        zlhip_engine::SoundSlot &slot = e->soundSlots[(size_t)p.id];
+        const size_t oldOff = (size_t)slot.orig.offset, oldFloats = slot.floats;
+        ZlSound s = p.s;
+        if (verdictsOut[j] == 0u) s.flags |= ZL_SOUND_FINITE;
+        slot.orig = s; slot.floats = newFloats[(size_t)jobReq[j]];
+        slot.renderOffsets.clear();
+        const ZlWpRegion &first = table[(size_t)jobs[j].region_base];
+        slot.warpOffsets.assign(hOffs.begin() + first.off_base, hOffs.begin() + first.off_base + sums[(size_t)jobReq[j]].segments);
+        e->hc.sounds[p.id] = s;
+        free_extent(e, oldOff, oldFloats);
+    }
+    std::memcpy(out, sums.data(), (size_t)count * sizeof(zlhip_warp));
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_warp(zlhip_engine *e, const zlhip_warp_request *r, zlhip_warp *out) { return zlhip_sound_warp_batch(e, r, 1, out); }
+
+int zlhip_debug_warp_offsets(zlhip_engine *e, int32_t id, int32_t *out, int32_t capacity, int32_t *count)
+{
+    if (!e || id < 0 || id >= e->cfg.max_sounds || !e->hc.soundUsed[id]) return ZLHIP_ERR_INVALID;
+    const std::vector<int32_t> &o = e->soundSlots[(size_t)id].warpOffsets;
+    if (count) *count = (int32_t)o.size();
+    if (!out) return ZLHIP_OK;
+    if ((size_t)capacity < o.size()) return fail(e, ZLHIP_ERR_CAPACITY, "debug_warp_offsets: capacity below the count");
+    if (!o.empty()) std::memcpy(out, o.data(), o.size() * sizeof(int32_t));
+    return ZLHIP_OK;
+}
+
+int zlhip_debug_warp_timings(zlhip_engine *e, float *seek_ms, float *synth_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (seek_ms) *seek_ms = e->wp.seekMs;
+    if (synth_ms) *synth_ms = e->wp.synthMs;
     return ZLHIP_OK;
 }
 

@@ -32,6 +32,7 @@ enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a ca
        ZB_LP_REQ, ZB_LP_X, ZB_LP_E, ZB_LP_SHIFT, ZB_LP_ITEM, ZB_LP_COST,   // loop finder: a call's request records (with a host twin), the int16 strips, per candidate E, per request the shift, the item records, the cost matrix (small calls)
        ZB_KY_REQ, ZB_KY_BINS, ZB_KY_TABLE, ZB_KY_STAT, ZB_KY_ACC, ZB_KY_TOTAL,   // key: a call's request records, its bin tables and the paired cosine table (each with a host twin), per frame the gate's verdict, per frame and bin re and im, per bin the totals
        ZB_XF_JOBS, ZB_XF_WEIGHTS, ZB_XF_PUB, ZB_XF_VERDICTS,  // loop crossfade: a call's job records, its (a, b) pairs, its publish records, its verdict words
+       ZB_WP_JOBS, ZB_WP_REGIONS, ZB_WP_LIST, ZB_WP_OFFS, ZB_WP_PUB, ZB_WP_VERDICTS,   // warp: a call's job and region records, the regions whose seek runs, the seek offsets, its publish records, its verdict words
        ZB_COUNT };
 
 // Stage times of a call (zlhip_set_profiling): events 0 .. N-1 recorded between the call's launches.  `on` is set by every call from the
@@ -69,6 +70,7 @@ struct zlhip_engine {
         ZlSound orig{0, 0, 0, 0.0}; size_t floats = 0;   // the original upload, the floats it holds in the arena
         size_t renderFloats = 0;         // floats of the slot's rendered extent, 0 = it plays its original
         std::vector<int32_t> renderOffsets;   // the seek offsets of the slot's last render (zlhip_debug_rerender_offsets)
+        std::vector<int32_t> warpOffsets;     // the seek offsets of the slot's last warp (zlhip_debug_warp_offsets)
     };
     std::vector<SoundSlot> soundSlots;
     GrowBuf scratch[ZB_COUNT];           // a call's records and staging (grow_buf)
@@ -122,6 +124,8 @@ struct zlhip_engine {
         ZlMapped<ZlXfSums> sums;                                    // a call's measured sums, one record per applied request
         ZlStageTimer<4> timer; float measureMs = 0.0f, renderMs = 0.0f;   // marks: around the measuring launch, around the render and publish launches
     } xf;
+    // warp (zlhip_sound_warp; zl_warp.h)
+    struct Warp { ZlStageTimer<3> timer; float seekMs = 0.0f, synthMs = 0.0f; } wp;       // marks: before the seek, between the launches, behind the publish
     // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h)
     struct Pcm {
         std::vector<ZlEvent> ev;                                    // profiling: before every pass's copies and every decode launch, behind the last

@@ -1357,6 +1357,47 @@ int libzl_hotpath_clip_crossfade_loop(ClipAudioSource *c, float fade_ms, int cur
     return r.applied ? 1 : 0;
 }
 
+// Fit a loop to the session grid hit by hit: the clip's transients over its whole original (zlhip_sound_onsets, defaults), its tempo
+// (given, or detected as libzl_hotpath_clip_tempo(c, 0, 0, ...) does), the plan from hits to anchors on the host (zlhip_warp_plan; the
+// grid counts from the clip's start frame by the voice's own cast) and the warp on the device (zlhip_sound_warp).
+int libzl_hotpath_clip_warp_to_grid(ClipAudioSource *c, float src_bpm, int steps_per_beat, float strength, int *onsets_moved, int *new_length_frames)
+{
+    if (!c || !(src_bpm >= 0.0f) || !(src_bpm <= FLT_MAX) || steps_per_beat < 1 || steps_per_beat > 64 || !(strength >= 0.0f && strength <= 1.0f)) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    if (!G.engine || c->engineClip < 0) return ZLHIP_ERR_STATE;
+    zlhip_sound_info info; int64_t start, stop;
+    { const int rc = clip_region(c, &info, &start, &stop); if (rc != ZLHIP_OK) return rc; }
+    if (info.rendered) return ZLHIP_ERR_STATE;                     // warp first, then tune and level
+    double bpm = (double)src_bpm;
+    if (src_bpm == 0.0f) {
+        zlhip_tempo t;
+        { const int rc = clip_tempo(c, 0.0f, 0.0f, &t); if (rc != ZLHIP_OK) return rc; }
+        if (!(t.bpm > 0.0f)) return 0;                             // no tempo: nothing changes
+        bpm = (double)t.bpm;
+    }
+    const uint64_t session = G.seq.bpm;
+    if (!bpm_usable(session)) return ZLHIP_ERR_STATE;
+    zlhip_onset_request q = { c->engineClip, 0, info.length, 0, 0, 0, 0, 0 };
+    if (zlhip_onset_resolve(info.sample_rate, &q) != ZLHIP_OK) return ZLHIP_ERR_INVALID;
+    std::vector<zlhip_onset> on((size_t)q.max_onsets);
+    int32_t n = 0;
+    { const int rc = zlhip_sound_onsets(G.engine, &q, on.data(), q.max_onsets, &n); if (rc != ZLHIP_OK) return rc; }
+    std::vector<int32_t> frames((size_t)n);
+    for (int32_t i = 0; i < n; ++i) frames[(size_t)i] = on[(size_t)i].frame;
+    std::sort(frames.begin(), frames.end());
+    std::vector<zlhip_warp_anchor> anchors((size_t)n + 2);
+    int32_t count = 0, dropped = 0;
+    { const int rc = zlhip_warp_plan(info.sample_rate, info.length, frames.data(), n, bpm, (double)session, steps_per_beat, (double)strength,
+                                     (int32_t)std::min<int64_t>(start, (int64_t)info.length - 1), -1, anchors.data(), (int32_t)anchors.size(), &count, &dropped);
+      if (rc != ZLHIP_OK) return rc; }
+    const zlhip_warp_request w = { c->engineClip, count, anchors.data() };
+    zlhip_warp r;
+    { const int rc = zlhip_sound_warp(G.engine, &w, &r); if (rc != ZLHIP_OK) return rc; }
+    if (onsets_moved) *onsets_moved = r.applied ? count - 2 : 0;
+    if (new_length_frames) *new_length_frames = r.length;
+    return r.applied ? 1 : 0;
+}
+
 // A whole bank: ONE zlhip_sound_loop_batch with clips_snap_loops' logic, then ONE zlhip_sound_loop_crossfade_batch.
 int libzl_hotpath_clips_seal_loops(ClipAudioSource **clips, int count, float search_ms, float min_improvement_db, float fade_ms, int curve, int *results)
 {

@@ -227,6 +227,23 @@ def _xfade_call(fn, handle, requests):
     return rc, [{k: getattr(out[i], k) for k in XFADE_FIELDS} for i in range(len(requests))]
 
 
+WARP_FIELDS = tuple(name for name, _ in _abi.Warp._fields_)
+
+
+def _warp_call(fn, handle, requests):
+    """one zlhip_sound_warp_batch-shaped call over (clip, anchors) pairs, anchors a sequence of (src_frame, dst_frame)
+    -> (status, one dict of zlhip_warp's fields per request)"""
+    reqs = (_abi.WarpRequest * max(1, len(requests)))()
+    keep = []
+    for i, (clip, anchors) in enumerate(requests):
+        a = np.ascontiguousarray(np.asarray(anchors, np.int32).reshape(-1, 2))
+        keep.append(a)
+        reqs[i] = _abi.WarpRequest(int(clip), int(a.shape[0]), C.cast(a.ctypes.data, C.POINTER(_abi.WarpAnchor)))
+    out = (_abi.Warp * max(1, len(requests)))()
+    rc = fn(handle, reqs, len(requests), out)
+    return rc, [{k: getattr(out[i], k) for k in WARP_FIELDS} for i in range(len(requests))]
+
+
 KEY_FIELDS = tuple(name for name, _ in _abi.Key._fields_)
 _KEY_KEYS = ("first_frame", "num_frames", "hop", "max_frames", "a4_hz", "note_lo", "note_hi", "q", "gate")
 
@@ -667,6 +684,46 @@ class SamplerSynth:
         """device ms of the measuring launch and of the render and publishing launches of the last crossfade call made with profiling on"""
         a, b = C.c_float(0.0), C.c_float(0.0)
         self._ck(self._lib.zlhip_debug_xfade_timings(self._e, C.byref(a), C.byref(b)), "debug_xfade_timings")
+        return a.value, b.value
+
+    def clip_warp(self, clip: int, anchors) -> dict:
+        """Warp the clip's data on the device (zlhip_sound_warp): anchors is a sequence of (src_frame, dst_frame)
+        from (0, 0) to (length, new length), strictly increasing; every region between two anchors is stretched by its own ratio and
+        starts exactly at its anchor.  A dict of zlhip_warp's fields -- applied (0: the identity, the clip is untouched), regions,
+        stretched_regions, segments, length, overlap.  The clip keeps its id; the warp cannot be taken back."""
+        return self.clip_warp_batch([(clip, anchors)])[0]
+
+    def clip_warp_batch(self, requests: Sequence):
+        """Several clips in one call (zlhip_sound_warp_batch: three launches and one wait whatever the count; all or nothing).
+        requests: (clip, anchors) pairs; one dict each."""
+        rc, res = _warp_call(self._lib.zlhip_sound_warp_batch, self._e, requests)
+        self._ck(rc, "sound_warp_batch")
+        return res
+
+    def warp_plan(self, sample_rate: float, length: int, onset_frames, src_bpm: float, dst_bpm: float, steps_per_beat: int = 4, strength: float = 1.0,
+                  origin_frame: int = 0, preroll_frames: int = -1):
+        """From hits to anchors on the host (zlhip_warp_plan): every onset moved by `strength` towards the nearest step of the grid of
+        src_bpm counted from origin_frame, then scaled to dst_bpm.  -> (anchors [n][2] int32, candidates dropped)"""
+        on = np.ascontiguousarray(np.asarray(onset_frames, np.int32).reshape(-1))
+        out = np.zeros((on.size + 2, 2), np.int32)
+        n, dropped = C.c_int32(0), C.c_int32(0)
+        self._ck(self._lib.zlhip_warp_plan(float(sample_rate), int(length), on.ctypes.data, on.size, float(src_bpm), float(dst_bpm), int(steps_per_beat),
+                                           float(strength), int(origin_frame), int(preroll_frames), C.cast(out.ctypes.data, C.POINTER(_abi.WarpAnchor)),
+                                           out.shape[0], C.byref(n), C.byref(dropped)), "warp_plan")
+        return out[:n.value].copy(), dropped.value
+
+    def warp_offsets(self, clip: int) -> np.ndarray:
+        """the seek offsets of the clip's last warp, region by region in output order (zlhip_debug_warp_offsets)"""
+        n = C.c_int32(0)
+        self._ck(self._lib.zlhip_debug_warp_offsets(self._e, clip, None, 0, C.byref(n)), "debug_warp_offsets")
+        out = np.zeros(max(1, n.value), np.int32)
+        self._ck(self._lib.zlhip_debug_warp_offsets(self._e, clip, out.ctypes.data, out.size, C.byref(n)), "debug_warp_offsets")
+        return out[:n.value]
+
+    def warp_timings(self):
+        """device ms of the seek launch and of the synthesis and publishing launches of the last warp call made with profiling on"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        self._ck(self._lib.zlhip_debug_warp_timings(self._e, C.byref(a), C.byref(b)), "debug_warp_timings")
         return a.value, b.value
 
     def clip_key(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, hop: int = 0, max_frames: int = 0, a4_hz: float = 0.0,
@@ -1140,6 +1197,15 @@ class SamplerSynthGroup:
     def clip_loop_crossfade_batch(self, requests: Sequence):
         rc, res = _xfade_call(self._lib.zlhip_group_sound_loop_crossfade_batch, self._g, requests)
         self._ck(rc, "group_sound_loop_crossfade_batch")
+        return res
+
+    def clip_warp(self, clip: int, anchors) -> dict:
+        """SamplerSynth.clip_warp on every member; member 0's results (zlhip_group_sound_warp_batch)"""
+        return self.clip_warp_batch([(clip, anchors)])[0]
+
+    def clip_warp_batch(self, requests: Sequence):
+        rc, res = _warp_call(self._lib.zlhip_group_sound_warp_batch, self._g, requests)
+        self._ck(rc, "group_sound_warp_batch")
         return res
 
     def clip_key(self, clip: int, first_frame: int = 0, num_frames: Optional[int] = None, hop: int = 0, max_frames: int = 0, a4_hz: float = 0.0,
