@@ -1,12 +1,16 @@
 // zl_clip_calls.cpp -- the clip services of include/zlhip.h: loading from raw PCM, re-render, rate conversion, and the seven analyses
 // (waveform overviews, transients, tempo, pitch, loudness, loop points, key), the loop crossfade and the warp.  Every one is a call on a loaded clip that validates everything before its
 // first HIP call, reserves buffers that only grow, queues its launches on the engine's stream and waits once.  What they share is
-// written once, below; the engine itself -- arena, sound slots, rendering, the resident kernel -- is zl_engine.cpp.
+// written once, below: the checks and the buffers of every service, and for the five that replace a clip's data -- the PCM upload, the
+// re-render, the rate conversion, the loop crossfade, the warp -- the new arena extents of a call, taken all or none (ZlNewExtents), and
+// the switch of a clip to its new extent (ZlClipSwap).  The engine itself -- arena, sound slots, rendering, the resident kernel -- is
+// zl_engine.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <initializer_list>
 
 #include "zl_engine_impl.h"
@@ -68,6 +72,99 @@ static int reserve(zlhip_engine *e, bool stop, std::initializer_list<ZlBufNeed> 
     return ZLHIP_OK;
 }
 
+// ---- what the services that replace a clip's data do -------------------------------------------------------------------------
+// No clip twice in a call.  Asked request by request, between a service's own checks: the first thing wrong with the first wrong
+// request is what the caller reads.
+struct ZlDistinct {
+    std::vector<char> seen;
+    explicit ZlDistinct(const zlhip_engine *e) : seen((size_t)e->cfg.max_sounds, 0) {}
+    int check(zlhip_engine *e, const char *svc, int32_t id)
+    {
+        { const int rc = check_sound(e, svc, id); if (rc != ZLHIP_OK) return rc; }
+        if (seen[(size_t)id]) return fail_in(e, ZLHIP_ERR_INVALID, (std::string(svc) + "_batch").c_str(), "a clip appears twice");
+        seen[(size_t)id] = 1;
+        return ZLHIP_OK;
+    }
+};
+
+// A clip that plays a re-render keeps its original for the next one: a service that would replace the original refuses, with its own advice.
+static int check_plays_original(zlhip_engine *e, int32_t id, const char *refusal)
+{
+    return e->soundSlots[(size_t)id].renderFloats != 0 ? fail(e, ZLHIP_ERR_STATE, refusal) : ZLHIP_OK;
+}
+
+// The new arena extents of a call, one per request that gets one, all or none: an arena that cannot hold the call keeps nothing of it
+// and leaves every clip as it was; a segment the arena grew by goes back to the device (free_extent).  After call_begin(e, true).
+struct ZlNewExtents {
+    zlhip_engine *e;
+    std::vector<size_t> off, floats;                               // per request; 0 floats: nothing taken
+    std::function<void()> undo_first;                              // what else a failed call undoes, before its extents go back
+    ZlNewExtents(zlhip_engine *e_, int32_t count) : e(e_), off((size_t)count, 0), floats((size_t)count, 0) {}
+    int take(int32_t i, int64_t frames, int channels)
+    {
+        const size_t n = zl_extent_floats(frames, channels);
+        const int rc = alloc_extent(e, n, &off[(size_t)i]);
+        if (rc != ZLHIP_OK) { rollback(); return rc; }
+        floats[(size_t)i] = n;
+        return ZLHIP_OK;
+    }
+    void rollback()                                                // last taken first
+    {
+        if (undo_first) undo_first();
+        for (size_t k = off.size(); k-- > 0;) { free_extent(e, off[k], floats[k]); floats[k] = 0; }
+    }
+    float *ptr(int32_t i) const { return arena_ptr(e, off[(size_t)i]); }
+};
+
+// The switch of a call's clips to their new extents, which become the slots' originals.  On the device zl_k_resample_publish switches
+// the sound-table entries from one ZlRsPublish per job, ZL_SOUND_FINITE from the job's verdict word; `words` is what the words start
+// as for a service that copies the original's samples -- set where the original lacks the flag, so that it stays without it.  The
+// service reserves, copies and launches; this is what it fills while it adds its jobs, what a HIP error undoes, and the host's half
+// behind the wait.
+struct ZlClipSwap {
+    zlhip_engine *e; const char *svc; ZlNewExtents &ext;
+    std::vector<ZlRsPublish> pub; std::vector<uint32_t> words; std::vector<int32_t> jobReq;     // per job; jobReq: its request
+    // request i's clip `id` will play `s`, its original with the length and rate the service gives it, from the request's extent.
+    // Returns the job, which is the index of its verdict word as well.
+    int32_t add(int32_t i, int32_t id, ZlSound s)
+    {
+        const int32_t j = (int32_t)pub.size();
+        words.push_back((s.flags & ZL_SOUND_FINITE) ? 0u : 1u);
+        s.offset = ext.off[(size_t)i]; s.flags &= ~(int32_t)ZL_SOUND_FINITE;
+        pub.push_back(ZlRsPublish{ s, id, j });
+        jobReq.push_back(i);
+        return j;
+    }
+    int hip_failed(int krc)
+    {
+        e->err = std::string(svc) + ": " + hipGetErrorString((hipError_t)krc);
+        (void)hipStreamSynchronize(e->stream);
+        // (the table entries the device may have switched go back to what the host's mirror holds)
+        for (const ZlRsPublish &p : pub) (void)hipMemcpy(e->dSounds + p.id, &e->hc.sounds[p.id], sizeof(ZlSound), hipMemcpyHostToDevice);
+        ext.rollback();
+        return ZLHIP_ERR_HIP;
+    }
+    // behind the call's last wait, with the verdict words read back: the new extent is the slot's original from now on, the old one
+    // goes back to the arena.  per_job(job, slot): what a service keeps besides.
+    template <typename PerJob> void commit(const std::vector<uint32_t> &verdicts, PerJob per_job)
+    {
+        e->outstanding = false;
+        for (size_t j = 0; j < pub.size(); ++j) {
+            const ZlRsPublish &p = pub[j];
+            zlhip_engine::SoundSlot &slot = e->soundSlots[(size_t)p.id];
+            const size_t oldOff = (size_t)slot.orig.offset, oldFloats = slot.floats;
+            ZlSound s = p.s;
+            if (verdicts[j] == 0u) s.flags |= ZL_SOUND_FINITE;
+            slot.orig = s; slot.floats = ext.floats[(size_t)jobReq[j]];
+            slot.renderOffsets.clear();
+            per_job(j, slot);
+            e->hc.sounds[p.id] = s;
+            free_extent(e, oldOff, oldFloats);
+        }
+    }
+    void commit(const std::vector<uint32_t> &verdicts) { commit(verdicts, [](size_t, zlhip_engine::SoundSlot &) {}); }
+};
+
 extern "C" {
 
 // ---- clips from raw PCM (zl_decode.h, zl_decode.hip) ---------------------------------------------------------------------
@@ -97,25 +194,18 @@ int zlhip_sound_upload_pcm_batch(zlhip_engine *e, const zlhip_pcm_source *srcs, 
     for (int i = 0; i < e->cfg.max_sounds && (int32_t)ids.size() < count; ++i) if (!e->hc.soundUsed[i]) ids.push_back(i);
     if ((int32_t)ids.size() < count) return fail(e, ZLHIP_ERR_CAPACITY, "sound_upload_pcm: too few free sound slots for the call");
     { const int rc = call_begin(e, true); if (rc != ZLHIP_OK) return rc; }     // (an extent freed earlier may be handed out again here)
-    // the extents (all or none: an arena that cannot hold the call keeps nothing; a segment it grew by goes back)
-    std::vector<size_t> off((size_t)count, 0), floats((size_t)count, 0);
-    auto rollback = [&]() { for (int32_t k = count - 1; k >= 0; --k) free_extent(e, off[(size_t)k], floats[(size_t)k]); };   // (0 floats: nothing taken)
-    for (int32_t i = 0; i < count; ++i) {
-        const size_t n = zl_extent_floats(srcs[i].length, zl_dec_out_channels(srcs[i].channels));
-        const int rc = alloc_extent(e, n, &off[(size_t)i]);
-        if (rc != ZLHIP_OK) { rollback(); return rc; }
-        floats[(size_t)i] = n;
-    }
+    ZlNewExtents ext(e, count);                                    // the extents, all or none
+    for (int32_t i = 0; i < count; ++i) { const int rc = ext.take(i, srcs[i].length, zl_dec_out_channels(srcs[i].channels)); if (rc != ZLHIP_OK) return rc; }
     // the cut into passes and pieces, the records
     const uint32_t stageBytes = zl_pcm_stage_switch();
     std::vector<ZlDecClip> clips((size_t)count);
     for (int32_t i = 0; i < count; ++i) clips[(size_t)i] = ZlDecClip{ srcs[i].length, srcs[i].channels, srcs[i].format };
     std::vector<ZlDecPiece> pieces; std::vector<ZlDecPass> passes;
     zl_dec_plan(clips.data(), count, stageBytes, pieces, passes);
-    for (ZlDecPiece &R : pieces) R.dst = (uint64_t)(uintptr_t)arena_ptr(e, off[(size_t)R.verdict]);
+    for (ZlDecPiece &R : pieces) R.dst = (uint64_t)(uintptr_t)ext.ptr(R.verdict);
     std::vector<ZlDecPublish> pub((size_t)count);
     for (int32_t i = 0; i < count; ++i) {
-        ZlSound s; s.offset = off[(size_t)i]; s.length = srcs[i].length; s.channels = zl_dec_out_channels(srcs[i].channels);
+        ZlSound s; s.offset = ext.off[(size_t)i]; s.length = srcs[i].length; s.channels = zl_dec_out_channels(srcs[i].channels);
         s.sample_rate = srcs[i].sample_rate; s.flags = 0; s.pad = 0;
         pub[(size_t)i] = ZlDecPublish{ s, ids[(size_t)i], zl_dec_is_float(srcs[i].format) ? 1 : 0 };
     }
@@ -124,7 +214,7 @@ int zlhip_sound_upload_pcm_batch(zlhip_engine *e, const zlhip_pcm_source *srcs, 
     const size_t np = std::max<size_t>(pieces.size() * 2, 64), nc = std::max<size_t>((size_t)count * 2, 64);
     const int rsv = reserve(e, false, { { ZB_PCM_STAGE, stageBytes, 1, stageBytes, false, what }, { ZB_PCM_PIECES, pieces.size(), sizeof(ZlDecPiece), np, false, what, np },
                                        { ZB_PCM_PUB, (size_t)count, sizeof(ZlDecPublish), nc, false, what }, { ZB_PCM_VERDICTS, (size_t)count, sizeof(uint32_t), nc, false, what } });
-    if (rsv != ZLHIP_OK) { rollback(); return rsv; }
+    if (rsv != ZLHIP_OK) { ext.rollback(); return rsv; }
     zlhip_engine::Pcm &P = e->pcm;
     unsigned char *const stage = (unsigned char *)e->scratch[ZB_PCM_STAGE].d; ZlDecPiece *const dPieces = (ZlDecPiece *)e->scratch[ZB_PCM_PIECES].d;
     ZlDecPublish *const dPub = (ZlDecPublish *)e->scratch[ZB_PCM_PUB].d; uint32_t *const dVerdicts = (uint32_t *)e->scratch[ZB_PCM_VERDICTS].d;
@@ -151,11 +241,11 @@ int zlhip_sound_upload_pcm_batch(zlhip_engine *e, const zlhip_pcm_source *srcs, 
     if (prof && krc == 0) krc = (int)hipEventRecord(P.ev[2 * passes.size()], e->stream);
     if (krc == 0) krc = zl_launch_pcm_publish(dPub, count, dVerdicts, e->dSounds, e->stream);
     if (krc == 0) krc = (int)hipMemcpyAsync(verdicts.data(), dVerdicts, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
-    if (krc == 0) { const int w_ = engine_wait(e); if (w_ != ZLHIP_OK) { rollback(); return w_; } }     // the call's one wait
+    if (krc == 0) { const int w_ = engine_wait(e); if (w_ != ZLHIP_OK) { ext.rollback(); return w_; } }     // the call's one wait
     if (krc != 0) {
         e->err = std::string("sound_upload_pcm: ") + hipGetErrorString((hipError_t)krc);
         (void)hipStreamSynchronize(e->stream);
-        rollback();
+        ext.rollback();
         return ZLHIP_ERR_HIP;
     }
     if (prof) {
@@ -173,7 +263,7 @@ int zlhip_sound_upload_pcm_batch(zlhip_engine *e, const zlhip_pcm_source *srcs, 
         const int id = ids[(size_t)i];
         ZlSound s = pub[(size_t)i].s;
         if (!pub[(size_t)i].check || verdicts[(size_t)i] == 0u) s.flags |= ZL_SOUND_FINITE;
-        adopt_sound(e, id, s, floats[(size_t)i]);
+        adopt_sound(e, id, s, ext.floats[(size_t)i]);
         zlhip_clip_params p;
         zlhip_clip_params_default(&p, (float)(s.length / s.sample_rate));
         e->hc.forget_clip_params(id);                              // (the first edit of a slot carries the whole record)
@@ -224,12 +314,10 @@ int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_
     std::vector<ZlStretchGeom> geo((size_t)count);
     std::vector<char> ident((size_t)count, 0);
     {
-        std::vector<char> seen((size_t)e->cfg.max_sounds, 0);
+        ZlDistinct distinct(e);
         for (int32_t i = 0; i < count; ++i) {
             const int32_t id = ids[i];
-            { const int rc = check_sound(e, "sound_rerender", id); if (rc != ZLHIP_OK) return rc; }
-            if (seen[(size_t)id]) return fail(e, ZLHIP_ERR_INVALID, "sound_rerender_batch: a clip appears twice");
-            seen[(size_t)id] = 1;
+            { const int rc = distinct.check(e, "sound_rerender", id); if (rc != ZLHIP_OK) return rc; }
             const zlhip_rerender_params &q = params[i];
             const ZlSound &o = e->soundSlots[(size_t)id].orig;
             if (zl_st_geometry(o.sample_rate, o.length, q.gain_db, q.pitch_semitones, q.speed_ratio, &geo[(size_t)i]) != 0)
@@ -239,9 +327,7 @@ int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_
     }
     { const int rc = call_begin(e, true); if (rc != ZLHIP_OK) return rc; }
 
-    // the new extents (all or none: an arena that cannot hold the call leaves every clip as it was)
-    std::vector<size_t> newOff((size_t)count, 0), newFloats((size_t)count, 0);
-    auto rollback = [&]() { for (int32_t i = 0; i < count; ++i) free_extent(e, newOff[(size_t)i], newFloats[(size_t)i]); };
+    ZlNewExtents ext(e, count);                                    // the rendered extents; an identity request gets none
     std::vector<ZlStretchJob> jobs;
     std::vector<int32_t> seekList, jobClip;
     int64_t maxFrames = 0, offs = 0;
@@ -249,14 +335,11 @@ int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_
         if (ident[(size_t)i]) continue;
         const ZlSound &o = e->soundSlots[(size_t)ids[i]].orig;
         const ZlStretchGeom &g = geo[(size_t)i];
-        const size_t floats = zl_extent_floats(g.N, o.channels);
-        const int rc = alloc_extent(e, floats, &newOff[(size_t)i]);
-        if (rc != ZLHIP_OK) { rollback(); return rc; }
-        newFloats[(size_t)i] = floats;
+        { const int rc = ext.take(i, g.N, o.channels); if (rc != ZLHIP_OK) return rc; }
         ZlStretchJob J; std::memset(&J, 0, sizeof J);
         J.geom = g;
         J.src = (uint64_t)(uintptr_t)arena_ptr(e, o.offset);
-        J.dst = (uint64_t)(uintptr_t)arena_ptr(e, newOff[(size_t)i]);
+        J.dst = (uint64_t)(uintptr_t)ext.ptr(i);
         J.channels = o.channels;
         J.off_base = offs;
         if (g.stretch && g.nseg > 0) { seekList.push_back((int32_t)jobs.size()); offs += g.nseg; }
@@ -269,7 +352,7 @@ int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_
         int rc = st_reserve(e, e->scratch[ZB_ST_JOBS], jobs.size(), sizeof(ZlStretchJob));
         if (rc == ZLHIP_OK) rc = st_reserve(e, e->scratch[ZB_ST_LIST], std::max<size_t>(seekList.size(), 1), sizeof(int32_t));
         if (rc == ZLHIP_OK) rc = st_reserve(e, e->scratch[ZB_ST_OFFS], std::max<size_t>((size_t)offs, 1), sizeof(int32_t));
-        if (rc != ZLHIP_OK) { rollback(); return rc; }
+        if (rc != ZLHIP_OK) { ext.rollback(); return rc; }
         ZlStretchJob *const dStJobs = (ZlStretchJob *)e->scratch[ZB_ST_JOBS].d;
         int32_t *const dStList = (int32_t *)e->scratch[ZB_ST_LIST].d, *const dStOffs = (int32_t *)e->scratch[ZB_ST_OFFS].d;
         hipError_t st = hipMemcpyAsync(dStJobs, jobs.data(), jobs.size() * sizeof(ZlStretchJob), hipMemcpyHostToDevice, e->stream);
@@ -290,7 +373,7 @@ int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_
         if (krc != 0) {
             e->err = std::string("sound_rerender: ") + hipGetErrorString((hipError_t)krc);
             (void)hipStreamSynchronize(e->stream);
-            rollback();
+            ext.rollback();
             return ZLHIP_ERR_HIP;
         }
     }
@@ -301,9 +384,9 @@ int zlhip_sound_rerender_batch(zlhip_engine *e, const int32_t *ids, const zlhip_
         free_extent(e, (size_t)e->hc.sounds[id].offset, slot.renderFloats);
         ZlSound s = slot.orig;
         // (a rendered extent has not been looked at: it plays without ZL_SOUND_FINITE; identity parameters play the original, with its own flag)
-        if (!ident[(size_t)i]) { s.offset = newOff[(size_t)i]; s.length = (int32_t)geo[(size_t)i].N; s.flags &= ~(int32_t)ZL_SOUND_FINITE; }
+        if (!ident[(size_t)i]) { s.offset = ext.off[(size_t)i]; s.length = (int32_t)geo[(size_t)i].N; s.flags &= ~(int32_t)ZL_SOUND_FINITE; }
         e->hc.sounds[id] = s;
-        slot.renderFloats = newFloats[(size_t)i];
+        slot.renderFloats = ext.floats[(size_t)i];
         slot.renderOffsets.clear();
     }
     for (size_t j = 0; j < jobs.size(); ++j) {
@@ -392,14 +475,9 @@ int zlhip_sound_convert_rate_batch(zlhip_engine *e, const int32_t *ids, int32_t 
     std::vector<int64_t> outN((size_t)count, 0);
     std::vector<char> skip((size_t)count, 0);
     {
-        std::vector<char> seen((size_t)e->cfg.max_sounds, 0);
+        ZlDistinct distinct(e);
         int64_t wgs = 0;
-        for (int32_t i = 0; i < count; ++i) {
-            const int32_t id = ids[i];
-            { const int rc = check_sound(e, "sound_convert_rate", id); if (rc != ZLHIP_OK) return rc; }
-            if (seen[(size_t)id]) return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate_batch: a clip appears twice");
-            seen[(size_t)id] = 1;
-        }
+        for (int32_t i = 0; i < count; ++i) { const int rc = distinct.check(e, "sound_convert_rate", ids[i]); if (rc != ZLHIP_OK) return rc; }
         for (int32_t i = 0; i < count; ++i) {
             const ZlSound &o = e->soundSlots[(size_t)ids[i]].orig;
             skip[(size_t)i] = o.sample_rate == ft ? 1 : 0;           // (already at the rate, whatever the rate: nothing to check, nothing to do)
@@ -411,9 +489,11 @@ int zlhip_sound_convert_rate_batch(zlhip_engine *e, const int32_t *ids, int32_t 
             wgs += zl_rs_job_wgs((int32_t)outN[(size_t)i]);
         }
         if (wgs > (int64_t)INT32_MAX) return fail(e, ZLHIP_ERR_INVALID, "sound_convert_rate_batch: more than 2^31 - 1 workgroups in one call");
-        for (int32_t i = 0; i < count; ++i)
-            if (!skip[(size_t)i] && e->soundSlots[(size_t)ids[i]].renderFloats != 0)
-                return fail(e, ZLHIP_ERR_STATE, "sound_convert_rate: the clip plays a re-render (re-render it with gain 0, pitch 0, speed 1 first)");
+        for (int32_t i = 0; i < count; ++i) {
+            if (skip[(size_t)i]) continue;
+            const int rc = check_plays_original(e, ids[i], "sound_convert_rate: the clip plays a re-render (re-render it with gain 0, pitch 0, speed 1 first)");
+            if (rc != ZLHIP_OK) return rc;
+        }
     }
     int32_t njobs = 0;
     for (int32_t i = 0; i < count; ++i) njobs += skip[(size_t)i] ? 0 : 1;
@@ -428,81 +508,52 @@ int zlhip_sound_convert_rate_batch(zlhip_engine *e, const int32_t *ids, int32_t 
         const int rc = rs_table(e, geo[(size_t)i], &tables[(size_t)i]);
         if (rc != ZLHIP_OK) { rs_tables_undo(e, tables0); return rc; }
     }
-    // the new extents (all or none: an arena that cannot hold the call leaves every clip as it was)
-    std::vector<size_t> newOff((size_t)count, 0), newFloats((size_t)count, 0);
-    auto rollback = [&]() {
-        rs_tables_undo(e, tables0);
-        for (int32_t i = count - 1; i >= 0; --i) free_extent(e, newOff[(size_t)i], newFloats[(size_t)i]);
-    };
-    for (int32_t i = 0; i < count; ++i) {
-        if (skip[(size_t)i]) continue;
-        const size_t floats = zl_extent_floats(outN[(size_t)i], e->soundSlots[(size_t)ids[i]].orig.channels);
-        const int rc = alloc_extent(e, floats, &newOff[(size_t)i]);
-        if (rc != ZLHIP_OK) { rollback(); return rc; }
-        newFloats[(size_t)i] = floats;
-    }
-    std::vector<ZlRsJob> jobs; std::vector<ZlRsPublish> pub;
+    // the new extents and the jobs; a call that fails from here on gives its tables back before its extents
+    ZlNewExtents ext(e, count);
+    ext.undo_first = [&]() { rs_tables_undo(e, tables0); };
+    ZlClipSwap swap{ e, "sound_convert_rate", ext };
+    std::vector<ZlRsJob> jobs;
     int32_t wgs = 0;
     for (int32_t i = 0; i < count; ++i) {
         if (skip[(size_t)i]) continue;
         const ZlSound &o = e->soundSlots[(size_t)ids[i]].orig;
         const ZlRsGeom &g = geo[(size_t)i];
-        float *const table = tables[(size_t)i];
+        { const int rc = ext.take(i, outN[(size_t)i], o.channels); if (rc != ZLHIP_OK) return rc; }
         ZlRsJob J; std::memset(&J, 0, sizeof J);
         J.src = (uint64_t)(uintptr_t)arena_ptr(e, o.offset);
-        J.dst = (uint64_t)(uintptr_t)arena_ptr(e, newOff[(size_t)i]);
-        J.table = (uint64_t)(uintptr_t)table;
+        J.dst = (uint64_t)(uintptr_t)ext.ptr(i);
+        J.table = (uint64_t)(uintptr_t)tables[(size_t)i];
         J.len = o.length; J.N = (int32_t)outN[(size_t)i]; J.channels = o.channels;
         J.L = g.L; J.M = g.M; J.half = g.half; J.taps = g.taps; J.row = g.row;
-        J.wg_base = wgs; J.verdict = (int32_t)jobs.size();
+        J.wg_base = wgs;
         wgs += zl_rs_job_wgs(J.N);
-        ZlSound s = o; s.offset = newOff[(size_t)i]; s.length = J.N; s.sample_rate = ft; s.flags &= ~(int32_t)ZL_SOUND_FINITE;
-        pub.push_back(ZlRsPublish{ s, ids[i], J.verdict });
+        ZlSound s = o; s.length = J.N; s.sample_rate = ft;
+        J.verdict = swap.add(i, ids[i], s);
         jobs.push_back(J);
     }
     const char *what = "sound_convert_rate: no device memory for the call's records";
     const size_t nj = jobs.size(), n = std::max<size_t>(nj * 2, 64);
     const int rsv = reserve(e, false, { { ZB_RS_JOBS, nj, sizeof(ZlRsJob), n, false, what }, { ZB_RS_PUB, nj, sizeof(ZlRsPublish), n, false, what },
                                        { ZB_RS_VERDICTS, nj, sizeof(uint32_t), n, false, what } });
-    if (rsv != ZLHIP_OK) { rollback(); return rsv; }
+    if (rsv != ZLHIP_OK) { ext.rollback(); return rsv; }
     ZlRsJob *const dJobs = (ZlRsJob *)e->scratch[ZB_RS_JOBS].d; ZlRsPublish *const dPub = (ZlRsPublish *)e->scratch[ZB_RS_PUB].d;
     uint32_t *const dVerdicts = (uint32_t *)e->scratch[ZB_RS_VERDICTS].d;
     // everything is decided: from here on only a HIP error fails the call
     std::vector<uint32_t> verdicts(jobs.size(), 0u);
     e->rs.timer.on = e->profiling;
-    int krc = (int)hipMemsetAsync(dVerdicts, 0, jobs.size() * sizeof(uint32_t), e->stream);
+    int krc = (int)hipMemsetAsync(dVerdicts, 0, jobs.size() * sizeof(uint32_t), e->stream);     // (every word starts clear here, not as swap.words)
     if (krc == 0) krc = (int)hipMemcpyAsync(dJobs, jobs.data(), jobs.size() * sizeof(ZlRsJob), hipMemcpyHostToDevice, e->stream);
-    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, pub.data(), pub.size() * sizeof(ZlRsPublish), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, swap.pub.data(), nj * sizeof(ZlRsPublish), hipMemcpyHostToDevice, e->stream);
     if (krc == 0) krc = (int)e->rs.timer.mark(0, e->stream);
     if (krc == 0) krc = zl_launch_resample(dJobs, (int32_t)jobs.size(), wgs, dVerdicts, e->stream);
-    if (krc == 0) krc = zl_launch_resample_publish(dPub, (int32_t)pub.size(), dVerdicts, e->dSounds, e->stream);
+    if (krc == 0) krc = zl_launch_resample_publish(dPub, (int32_t)nj, dVerdicts, e->dSounds, e->stream);
     if (krc == 0) krc = (int)e->rs.timer.mark(1, e->stream);
     if (krc == 0) krc = (int)hipMemcpyAsync(verdicts.data(), dVerdicts, jobs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
     if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);      // the call's one wait
     if (krc == 0) krc = (int)e->rs.timer.elapsed(0, 1, &e->rs.ms);
-    if (krc != 0) {
-        e->err = std::string("sound_convert_rate: ") + hipGetErrorString((hipError_t)krc);
-        (void)hipStreamSynchronize(e->stream);
-        // (the table entries the device may have switched go back to what the host's mirror holds)
-        for (const ZlRsPublish &p : pub) (void)hipMemcpy(e->dSounds + p.id, &e->hc.sounds[p.id], sizeof(ZlSound), hipMemcpyHostToDevice);
-        rollback();
-        return ZLHIP_ERR_HIP;
-    }
-    e->outstanding = false;
+    if (krc != 0) return swap.hip_failed(krc);
     rs_tables_settled(e);
-    // the swap on the host: the converted extent is the slot's original from now on, the old one goes back to the arena
-    for (const ZlRsPublish &p : pub) {
-        zlhip_engine::SoundSlot &slot = e->soundSlots[(size_t)p.id];
-        const size_t oldOff = (size_t)slot.orig.offset, oldFloats = slot.floats;
-        ZlSound s = p.s;
-        if (verdicts[(size_t)p.verdict] == 0u) s.flags |= ZL_SOUND_FINITE;
-        int32_t i = 0;
-        while (ids[i] != p.id) ++i;
-        slot.orig = s; slot.floats = newFloats[(size_t)i];
-        slot.renderOffsets.clear();
-        e->hc.sounds[p.id] = s;
-        free_extent(e, oldOff, oldFloats);
-    }
+    swap.commit(verdicts);
     return ZLHIP_OK;
 }
 
@@ -1155,11 +1206,10 @@ int zlhip_debug_loop_timings(zlhip_engine *e, float *pairs_ms, float *rest_ms)
 
 // ---- loop crossfade (zl_xfade.h, zl_xfade.hip) ---------------------------------------------------------------------------------
 // The loop finder chooses among points that exist; this bakes a crossfade into the data, so that the wrap from the loop's last frame to
-// its start is the original's own step.  The scaffold is the rate conversion's: every applied clip gets a new arena extent, one launch
-// measures the correlation of every request's two regions into mapped host memory, the call waits, the weight tables are made here in
-// double from the measured or the fixed rho, one launch copies and fades every clip, zl_k_resample_publish switches the sound-table
-// entries (ZL_SOUND_FINITE from the device's verdict: a clip whose original lacks the flag starts with its word set), and the call waits
-// a second time.  The new extent becomes the slot's original.
+// its start is the original's own step.  Every applied clip gets a new arena extent (ZlNewExtents), one launch measures the correlation
+// of every request's two regions into mapped host memory, the call waits, the weight tables are made here in double from the measured
+// or the fixed rho, one launch copies and fades every clip, the sound-table entries switch (ZlClipSwap: a clip whose original lacks
+// ZL_SOUND_FINITE starts with its word set), and the call waits a second time.  The new extent becomes the slot's original.
 int zlhip_xfade_resolve(double sample_rate, int32_t length, zlhip_xfade_request *r)
 {
     if (!r) return ZLHIP_ERR_INVALID;
@@ -1186,14 +1236,12 @@ int zlhip_sound_loop_crossfade_batch(zlhip_engine *e, const zlhip_xfade_request 
     std::vector<zlhip_xfade_request> res((size_t)count);
     int32_t njobs = 0;
     {
-        std::vector<char> seen((size_t)e->cfg.max_sounds, 0);
+        ZlDistinct distinct(e);
         int64_t wgs = 0, pairs = 0;
         for (int32_t i = 0; i < count; ++i) {
             zlhip_xfade_request &q = res[(size_t)i];
             q = reqs[i];
-            { const int rc = check_sound(e, "sound_loop_crossfade", q.id); if (rc != ZLHIP_OK) return rc; }
-            if (seen[(size_t)q.id]) return fail(e, ZLHIP_ERR_INVALID, "sound_loop_crossfade_batch: a clip appears twice");
-            seen[(size_t)q.id] = 1;
+            { const int rc = distinct.check(e, "sound_loop_crossfade", q.id); if (rc != ZLHIP_OK) return rc; }
             const ZlSound &o = e->soundSlots[(size_t)q.id].orig;
             if (zlhip_xfade_resolve(o.sample_rate, o.length, &q) != ZLHIP_OK)
                 return fail_in(e, ZLHIP_ERR_INVALID, "sound_loop_crossfade", "the loop does not lie inside the sound's data, fade_frames outside 1 .. min(start, stop - start, 65536), or no such curve");
@@ -1203,70 +1251,54 @@ int zlhip_sound_loop_crossfade_batch(zlhip_engine *e, const zlhip_xfade_request 
             wgs += zl_xf_job_wgs(J); pairs += q.fade_frames; ++njobs;
         }
         if (wgs > (int64_t)INT32_MAX || pairs > (int64_t)INT32_MAX) return fail(e, ZLHIP_ERR_INVALID, "sound_loop_crossfade_batch: more than 2^31 - 1 workgroups or fade frames in one call");
-        for (int32_t i = 0; i < count; ++i)
-            if (res[(size_t)i].fade_frames != 0 && e->soundSlots[(size_t)res[(size_t)i].id].renderFloats != 0)
-                return fail(e, ZLHIP_ERR_STATE, "sound_loop_crossfade: the clip plays a re-render (crossfade first, re-render afterwards; re-render it with gain 0, pitch 0, speed 1 first)");
+        for (int32_t i = 0; i < count; ++i) {
+            if (res[(size_t)i].fade_frames == 0) continue;
+            const int rc = check_plays_original(e, res[(size_t)i].id, "sound_loop_crossfade: the clip plays a re-render (crossfade first, re-render afterwards; re-render it with gain 0, pitch 0, speed 1 first)");
+            if (rc != ZLHIP_OK) return rc;
+        }
     }
     if (njobs == 0) {                                              // nothing to fade anywhere: no launch, no copy
         std::memset(out, 0, (size_t)count * sizeof(zlhip_xfade));
         return ZLHIP_OK;
     }
     { const int rc = call_begin(e, true); if (rc != ZLHIP_OK) return rc; }
-    // the new extents (all or none: an arena that cannot hold the call leaves every clip as it was)
-    std::vector<size_t> newOff((size_t)count, 0), newFloats((size_t)count, 0);
-    auto rollback = [&]() { for (int32_t i = count - 1; i >= 0; --i) free_extent(e, newOff[(size_t)i], newFloats[(size_t)i]); };
-    for (int32_t i = 0; i < count; ++i) {
-        if (res[(size_t)i].fade_frames == 0) continue;
-        const ZlSound &o = e->soundSlots[(size_t)res[(size_t)i].id].orig;
-        const size_t floats = zl_extent_floats(o.length, o.channels);
-        const int rc = alloc_extent(e, floats, &newOff[(size_t)i]);
-        if (rc != ZLHIP_OK) { rollback(); return rc; }
-        newFloats[(size_t)i] = floats;
-    }
-    std::vector<ZlXfJob> jobs; std::vector<ZlRsPublish> pub; std::vector<int32_t> jobReq; std::vector<uint32_t> verdicts;
+    // the new extents and the jobs
+    ZlNewExtents ext(e, count);
+    ZlClipSwap swap{ e, "sound_loop_crossfade", ext };
+    std::vector<ZlXfJob> jobs;
     int32_t wgs = 0, pairs = 0;
     for (int32_t i = 0; i < count; ++i) {
         const zlhip_xfade_request &q = res[(size_t)i];
         if (q.fade_frames == 0) continue;
         const ZlSound &o = e->soundSlots[(size_t)q.id].orig;
+        { const int rc = ext.take(i, o.length, o.channels); if (rc != ZLHIP_OK) return rc; }
         ZlXfJob J; std::memset(&J, 0, sizeof J);
         J.src = (uint64_t)(uintptr_t)arena_ptr(e, o.offset);
-        J.dst = (uint64_t)(uintptr_t)arena_ptr(e, newOff[(size_t)i]);
+        J.dst = (uint64_t)(uintptr_t)ext.ptr(i);
         J.length = o.length; J.channels = o.channels;
         J.s = q.start_frame; J.e = q.stop_frame; J.X = q.fade_frames;
-        J.wg_base = wgs; J.weights = pairs; J.verdict = (int32_t)jobs.size();
+        J.wg_base = wgs; J.weights = pairs; J.verdict = swap.add(i, q.id, o);
         wgs += zl_xf_job_wgs(J); pairs += J.X;
-        ZlSound s = o; s.offset = newOff[(size_t)i]; s.flags &= ~(int32_t)ZL_SOUND_FINITE;
-        pub.push_back(ZlRsPublish{ s, q.id, J.verdict });
-        verdicts.push_back((o.flags & ZL_SOUND_FINITE) ? 0u : 1u); // (an original without the flag stays without it)
         jobs.push_back(J);
-        jobReq.push_back(i);
     }
+    const std::vector<int32_t> &jobReq = swap.jobReq;
     const char *what = "sound_loop_crossfade: no memory for the call's records";
     const size_t nj = jobs.size(), n = std::max<size_t>(nj * 2, 64), np = (size_t)pairs;
     zlhip_engine::Xfade &t = e->xf;
     const int rsv = reserve(e, false, { { ZB_XF_JOBS, nj, sizeof(ZlXfJob), n, false, what }, { ZB_XF_WEIGHTS, np, 2 * sizeof(float), std::max<size_t>(np * 2, 4096), false, what },
                                        { ZB_XF_PUB, nj, sizeof(ZlRsPublish), n, false, what }, { ZB_XF_VERDICTS, nj, sizeof(uint32_t), n, false, what } },
                             { mapped_need(t.sums, std::max<size_t>(nj, 32)) });
-    if (rsv != ZLHIP_OK) { rollback(); return rsv; }
+    if (rsv != ZLHIP_OK) { ext.rollback(); return rsv; }
     ZlXfJob *const dJobs = (ZlXfJob *)e->scratch[ZB_XF_JOBS].d; float *const dWeights = (float *)e->scratch[ZB_XF_WEIGHTS].d;
     ZlRsPublish *const dPub = (ZlRsPublish *)e->scratch[ZB_XF_PUB].d; uint32_t *const dVerdicts = (uint32_t *)e->scratch[ZB_XF_VERDICTS].d;
     // everything is decided: from here on only a HIP error fails the call
-    auto hip_failed = [&](int krc) {
-        e->err = std::string("sound_loop_crossfade: ") + hipGetErrorString((hipError_t)krc);
-        (void)hipStreamSynchronize(e->stream);
-        // (the table entries the device may have switched go back to what the host's mirror holds)
-        for (const ZlRsPublish &p : pub) (void)hipMemcpy(e->dSounds + p.id, &e->hc.sounds[p.id], sizeof(ZlSound), hipMemcpyHostToDevice);
-        rollback();
-        return ZLHIP_ERR_HIP;
-    };
     t.timer.on = e->profiling;
     int krc = (int)hipMemcpyAsync(dJobs, jobs.data(), nj * sizeof(ZlXfJob), hipMemcpyHostToDevice, e->stream);
     if (krc == 0) krc = (int)t.timer.mark(0, e->stream);
     if (krc == 0) krc = zl_launch_xfade_measure(dJobs, (int32_t)nj, t.sums.d, e->stream);
     if (krc == 0) krc = (int)t.timer.mark(1, e->stream);
     if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);      // the call's first wait: the sums are in host memory
-    if (krc != 0) return hip_failed(krc);
+    if (krc != 0) return swap.hip_failed(krc);
     // the tables, from the measured or the fixed rho
     std::vector<zlhip_xfade> results((size_t)count);
     std::memset(results.data(), 0, results.size() * sizeof(zlhip_xfade));
@@ -1283,8 +1315,8 @@ int zlhip_sound_loop_crossfade_batch(zlhip_engine *e, const zlhip_xfade_request 
     }
     std::vector<uint32_t> verdictsOut(nj, 0u);
     krc = (int)hipMemcpyAsync(dWeights, weights.data(), weights.size() * sizeof(float), hipMemcpyHostToDevice, e->stream);
-    if (krc == 0) krc = (int)hipMemcpyAsync(dVerdicts, verdicts.data(), nj * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream);
-    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, pub.data(), nj * sizeof(ZlRsPublish), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dVerdicts, swap.words.data(), nj * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, swap.pub.data(), nj * sizeof(ZlRsPublish), hipMemcpyHostToDevice, e->stream);
     if (krc == 0) krc = (int)t.timer.mark(2, e->stream);
     if (krc == 0) krc = zl_launch_xfade_render(dJobs, (int32_t)nj, wgs, dWeights, dVerdicts, e->stream);
     if (krc == 0) krc = zl_launch_resample_publish(dPub, (int32_t)nj, dVerdicts, e->dSounds, e->stream);
@@ -1293,20 +1325,8 @@ int zlhip_sound_loop_crossfade_batch(zlhip_engine *e, const zlhip_xfade_request 
     if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);      // the call's second wait
     if (krc == 0) krc = (int)t.timer.elapsed(0, 1, &t.measureMs);
     if (krc == 0) krc = (int)t.timer.elapsed(2, 3, &t.renderMs);
-    if (krc != 0) return hip_failed(krc);
-    e->outstanding = false;
-    // the swap on the host: the crossfaded extent is the slot's original from now on, the old one goes back to the arena
-    for (size_t j = 0; j < nj; ++j) {
-        const ZlRsPublish &p = pub[j];
-        zlhip_engine::SoundSlot &slot = e->soundSlots[(size_t)p.id];
-        const size_t oldOff = (size_t)slot.orig.offset, oldFloats = slot.floats;
-        ZlSound s = p.s;
-        if (verdictsOut[j] == 0u) s.flags |= ZL_SOUND_FINITE;
-        slot.orig = s; slot.floats = newFloats[(size_t)jobReq[j]];
-        slot.renderOffsets.clear();
-        e->hc.sounds[p.id] = s;
-        free_extent(e, oldOff, oldFloats);
-    }
+    if (krc != 0) return swap.hip_failed(krc);
+    swap.commit(verdictsOut);
     std::memcpy(out, results.data(), results.size() * sizeof(zlhip_xfade));
     return ZLHIP_OK;
 }
@@ -1322,10 +1342,10 @@ int zlhip_debug_xfade_timings(zlhip_engine *e, float *measure_ms, float *render_
 }
 
 // ---- warp (zl_warp.h, zl_warp.hip) ------------------------------------------------------------------------------------------------
-// A clip fitted to the session grid: a time stretch cut at the clip's hits.  The scaffold is the loop crossfade's: every applied clip
-// gets a new arena extent, one copy each carries the call's job records, region records and seek list, one launch finds the seek
-// offsets of every stretched region of the call (a workgroup each), one synthesises every extent, zl_k_resample_publish switches the
-// sound-table entries (ZL_SOUND_FINITE from the device's verdict), and the call waits once.  The new extent becomes the slot's original.
+// A clip fitted to the session grid: a time stretch cut at the clip's hits.  Every applied clip gets a new arena extent (ZlNewExtents),
+// one copy each carries the call's job records, region records and seek list, one launch finds the seek offsets of every stretched
+// region of the call (a workgroup each), one synthesises every extent, the sound-table entries switch (ZlClipSwap), and the call waits
+// once.  The new extent becomes the slot's original.
 int zlhip_warp_resolve(double sample_rate, int32_t length, const zlhip_warp_anchor *anchors, int32_t count, zlhip_warp *summary)
 {
     static_assert(sizeof(zlhip_warp) == sizeof(ZlWpSummary) && sizeof(zlhip_warp_anchor) == sizeof(ZlWpAnchor), "the warp's records");
@@ -1369,13 +1389,11 @@ int zlhip_sound_warp_batch(zlhip_engine *e, const zlhip_warp_request *reqs, int3
     std::vector<std::vector<ZlWpRegion>> regs((size_t)count);
     int32_t njobs = 0;
     {
-        std::vector<char> seen((size_t)e->cfg.max_sounds, 0);
+        ZlDistinct distinct(e);
         int64_t wgs = 0, nreg = 0, nseg = 0;
         for (int32_t i = 0; i < count; ++i) {
             const zlhip_warp_request &q = reqs[i];
-            { const int rc = check_sound(e, "sound_warp", q.id); if (rc != ZLHIP_OK) return rc; }
-            if (seen[(size_t)q.id]) return fail(e, ZLHIP_ERR_INVALID, "sound_warp_batch: a clip appears twice");
-            seen[(size_t)q.id] = 1;
+            { const int rc = distinct.check(e, "sound_warp", q.id); if (rc != ZLHIP_OK) return rc; }
             const ZlSound &o = e->soundSlots[(size_t)q.id].orig;
             regs[(size_t)i].resize((size_t)(q.count > 1 && q.count <= ZL_WP_MAX_ANCHORS ? q.count - 1 : 0));
             if (!q.anchors || zl_wp_resolve(o.sample_rate, o.length, (const ZlWpAnchor *)q.anchors, q.count, &sums[(size_t)i], regs[(size_t)i].data()) != 0)
@@ -1387,36 +1405,34 @@ int zlhip_sound_warp_batch(zlhip_engine *e, const zlhip_warp_request *reqs, int3
         }
         if (wgs > (int64_t)INT32_MAX || nreg > (int64_t)INT32_MAX || nseg > (int64_t)INT32_MAX)
             return fail(e, ZLHIP_ERR_INVALID, "sound_warp_batch: more than 2^31 - 1 workgroups, regions or segments in one call");
-        for (int32_t i = 0; i < count; ++i)
-            if (sums[(size_t)i].applied && e->soundSlots[(size_t)reqs[i].id].renderFloats != 0)
-                return fail(e, ZLHIP_ERR_STATE, "sound_warp: the clip plays a re-render (warp first, then tune and level; re-render it with gain 0, pitch 0, speed 1 first)");
+        for (int32_t i = 0; i < count; ++i) {
+            if (!sums[(size_t)i].applied) continue;
+            const int rc = check_plays_original(e, reqs[i].id, "sound_warp: the clip plays a re-render (warp first, then tune and level; re-render it with gain 0, pitch 0, speed 1 first)");
+            if (rc != ZLHIP_OK) return rc;
+        }
     }
     if (njobs == 0) {                                              // the identity everywhere: no launch, no copy
         std::memcpy(out, sums.data(), (size_t)count * sizeof(zlhip_warp));
         return ZLHIP_OK;
     }
     { const int rc = call_begin(e, true); if (rc != ZLHIP_OK) return rc; }
-    // the new extents (all or none: an arena that cannot hold the call leaves every clip as it was)
-    std::vector<size_t> newOff((size_t)count, 0), newFloats((size_t)count, 0);
-    auto rollback = [&]() { for (int32_t i = count - 1; i >= 0; --i) free_extent(e, newOff[(size_t)i], newFloats[(size_t)i]); };
-    for (int32_t i = 0; i < count; ++i) {
-        if (!sums[(size_t)i].applied) continue;
-        const size_t floats = zl_extent_floats(sums[(size_t)i].length, e->soundSlots[(size_t)reqs[i].id].orig.channels);
-        const int rc = alloc_extent(e, floats, &newOff[(size_t)i]);
-        if (rc != ZLHIP_OK) { rollback(); return rc; }
-        newFloats[(size_t)i] = floats;
-    }
-    std::vector<ZlWpJob> jobs; std::vector<ZlWpRegion> table; std::vector<int32_t> seekList, jobReq; std::vector<ZlRsPublish> pub; std::vector<uint32_t> verdicts;
+    // the new extents and the jobs
+    ZlNewExtents ext(e, count);
+    ZlClipSwap swap{ e, "sound_warp", ext };
+    std::vector<ZlWpJob> jobs; std::vector<ZlWpRegion> table; std::vector<int32_t> seekList;
     int32_t wgs = 0, offs = 0;
     for (int32_t i = 0; i < count; ++i) {
         if (!sums[(size_t)i].applied) continue;
         const ZlSound &o = e->soundSlots[(size_t)reqs[i].id].orig;
+        { const int rc = ext.take(i, sums[(size_t)i].length, o.channels); if (rc != ZLHIP_OK) return rc; }
         ZlWpJob J; std::memset(&J, 0, sizeof J);
         J.src = (uint64_t)(uintptr_t)arena_ptr(e, o.offset);
-        J.dst = (uint64_t)(uintptr_t)arena_ptr(e, newOff[(size_t)i]);
+        J.dst = (uint64_t)(uintptr_t)ext.ptr(i);
         J.len = o.length; J.channels = o.channels; J.N = sums[(size_t)i].length; J.O = sums[(size_t)i].overlap;
         J.region_base = (int32_t)table.size(); J.nregions = sums[(size_t)i].regions;
-        J.wg_base = wgs; J.verdict = (int32_t)jobs.size();
+        J.wg_base = wgs;
+        ZlSound s = o; s.length = J.N;
+        J.verdict = swap.add(i, reqs[i].id, s);
         wgs += zl_wp_job_wgs(J);
         for (ZlWpRegion R : regs[(size_t)i]) {
             R.off_base += offs; R.job = J.verdict;
@@ -1424,38 +1440,26 @@ int zlhip_sound_warp_batch(zlhip_engine *e, const zlhip_warp_request *reqs, int3
             table.push_back(R);
         }
         offs += sums[(size_t)i].segments;
-        ZlSound s = o; s.offset = newOff[(size_t)i]; s.length = J.N; s.flags &= ~(int32_t)ZL_SOUND_FINITE;
-        pub.push_back(ZlRsPublish{ s, reqs[i].id, J.verdict });
-        verdicts.push_back((o.flags & ZL_SOUND_FINITE) ? 0u : 1u);  // (an original without the flag stays without it)
         jobs.push_back(J);
-        jobReq.push_back(i);
     }
     const char *what = "sound_warp: no memory for the call's records";
     const size_t nj = jobs.size(), n = std::max<size_t>(nj * 2, 64), nr = table.size(), ns = std::max<size_t>(seekList.size(), 1), no = (size_t)offs;
     const int rsv = reserve(e, false, { { ZB_WP_JOBS, nj, sizeof(ZlWpJob), n, false, what }, { ZB_WP_REGIONS, nr, sizeof(ZlWpRegion), std::max<size_t>(nr * 2, 1024), false, what },
                                        { ZB_WP_LIST, ns, sizeof(int32_t), std::max<size_t>(ns * 2, 1024), false, what }, { ZB_WP_OFFS, no, sizeof(int32_t), std::max<size_t>(no * 2, 4096), false, what },
                                        { ZB_WP_PUB, nj, sizeof(ZlRsPublish), n, false, what }, { ZB_WP_VERDICTS, nj, sizeof(uint32_t), n, false, what } });
-    if (rsv != ZLHIP_OK) { rollback(); return rsv; }
+    if (rsv != ZLHIP_OK) { ext.rollback(); return rsv; }
     ZlWpJob *const dJobs = (ZlWpJob *)e->scratch[ZB_WP_JOBS].d; ZlWpRegion *const dRegs = (ZlWpRegion *)e->scratch[ZB_WP_REGIONS].d;
     int32_t *const dList = (int32_t *)e->scratch[ZB_WP_LIST].d, *const dOffs = (int32_t *)e->scratch[ZB_WP_OFFS].d;
     ZlRsPublish *const dPub = (ZlRsPublish *)e->scratch[ZB_WP_PUB].d; uint32_t *const dVerdicts = (uint32_t *)e->scratch[ZB_WP_VERDICTS].d;
     // everything is decided: from here on only a HIP error fails the call
-    auto hip_failed = [&](int krc) {
-        e->err = std::string("sound_warp: ") + hipGetErrorString((hipError_t)krc);
-        (void)hipStreamSynchronize(e->stream);
-        // (the table entries the device may have switched go back to what the host's mirror holds)
-        for (const ZlRsPublish &p : pub) (void)hipMemcpy(e->dSounds + p.id, &e->hc.sounds[p.id], sizeof(ZlSound), hipMemcpyHostToDevice);
-        rollback();
-        return ZLHIP_ERR_HIP;
-    };
     zlhip_engine::Warp &t = e->wp;
     t.timer.on = e->profiling;
     std::vector<int32_t> hOffs(no, 0); std::vector<uint32_t> verdictsOut(nj, 0u);
     int krc = (int)hipMemcpyAsync(dJobs, jobs.data(), nj * sizeof(ZlWpJob), hipMemcpyHostToDevice, e->stream);
     if (krc == 0) krc = (int)hipMemcpyAsync(dRegs, table.data(), nr * sizeof(ZlWpRegion), hipMemcpyHostToDevice, e->stream);
     if (krc == 0 && !seekList.empty()) krc = (int)hipMemcpyAsync(dList, seekList.data(), seekList.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    if (krc == 0) krc = (int)hipMemcpyAsync(dVerdicts, verdicts.data(), nj * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream);
-    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, pub.data(), nj * sizeof(ZlRsPublish), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dVerdicts, swap.words.data(), nj * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, swap.pub.data(), nj * sizeof(ZlRsPublish), hipMemcpyHostToDevice, e->stream);
     if (krc == 0) krc = (int)hipMemsetAsync(dOffs, 0, no * sizeof(int32_t), e->stream);     // (off[0] of every region, the copy regions' included)
     if (krc == 0) krc = (int)t.timer.mark(0, e->stream);
     if (krc == 0) krc = zl_launch_warp_seek(dJobs, dRegs, dList, (int32_t)seekList.size(), dOffs, e->stream);
@@ -1468,22 +1472,11 @@ int zlhip_sound_warp_batch(zlhip_engine *e, const zlhip_warp_request *reqs, int3
     if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);      // the call's one wait
     if (krc == 0) krc = (int)t.timer.elapsed(0, 1, &t.seekMs);
     if (krc == 0) krc = (int)t.timer.elapsed(1, 2, &t.synthMs);
-    if (krc != 0) return hip_failed(krc);
-    e->outstanding = false;
-    // the swap on the host: the warped extent is the slot's original from now on, the old one goes back to the arena
-    for (size_t j = 0; j < nj; ++j) {
-        const ZlRsPublish &p = pub[j];
-        zlhip_engine::SoundSlot &slot = e->soundSlots[(size_t)p.id];
-        const size_t oldOff = (size_t)slot.orig.offset, oldFloats = slot.floats;
-        ZlSound s = p.s;
-        if (verdictsOut[j] == 0u) s.flags |= ZL_SOUND_FINITE;
-        slot.orig = s; slot.floats = newFloats[(size_t)jobReq[j]];
-        slot.renderOffsets.clear();
+    if (krc != 0) return swap.hip_failed(krc);
+    swap.commit(verdictsOut, [&](size_t j, zlhip_engine::SoundSlot &slot) {     // (and the seek offsets of the slot's last warp)
         const ZlWpRegion &first = table[(size_t)jobs[j].region_base];
-        slot.warpOffsets.assign(hOffs.begin() + first.off_base, hOffs.begin() + first.off_base + sums[(size_t)jobReq[j]].segments);
-        e->hc.sounds[p.id] = s;
-        free_extent(e, oldOff, oldFloats);
-    }
+        slot.warpOffsets.assign(hOffs.begin() + first.off_base, hOffs.begin() + first.off_base + sums[(size_t)swap.jobReq[j]].segments);
+    });
     std::memcpy(out, sums.data(), (size_t)count * sizeof(zlhip_warp));
     return ZLHIP_OK;
 }

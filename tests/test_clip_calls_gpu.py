@@ -4,7 +4,10 @@ a mixed-up buffer index, a timer shared by mistake, a read-back table overwritte
 restatements' (tests/overview_ref.py, onset_ref.py, tempo_ref.py, pitch_ref.py, loudness_ref.py, loop_ref.py, key_ref.py), compared as the
 per-service tests compare them: every integer and every debug array bit for bit, bpm, hz and confidence with ==, note and cents within
 1e-9, lufs within 1e-9, the loop's three dB fields within 1e-9, the key's two confidences with == (tests/test_pitch_gpu.py,
-tests/test_loudness_gpu.py, tests/test_loop_gpu.py, tests/test_key_gpu.py)."""
+tests/test_loudness_gpu.py, tests/test_loop_gpu.py, tests/test_key_gpu.py).
+
+And, at the end, the five calls that replace clip data -- PCM upload, re-render, rate conversion, loop crossfade, warp -- through the one
+path none of their own tests reaches: a call that fails after the arena has grown by a segment."""
 import ctypes as C
 import math
 
@@ -222,3 +225,74 @@ def test_read_backs_belong_to_their_own_service(wants):
         assert not np.array_equal(wants[0]["onsets"][1], wants[1]["onsets"][1])
     finally:
         syn.close()
+
+
+# ---- the five calls that replace clip data: a batch that fails after the arena grew ---------------------------------------------
+# Their all-or-none tests elsewhere pin sound_arena_max_bytes to sound_arena_bytes, so nothing there gives back a segment the failed
+# call itself added.  Here the first arena has 1 MiB (262144 floats).  A further segment is never smaller than the first arena, so
+# a cap of 2 MiB allows exactly one.  Request 0's new extent is larger than what the first arena has free: it gets the segment.
+# Request 1's is larger than what either has free then, and a second segment would pass the cap: ZLHIP_ERR_CAPACITY.
+ARENA = 1 << 20
+
+
+def _noise(frames, seed):
+    return (0.25 * np.random.default_rng(seed).standard_normal(frames)).astype(f32)
+
+
+def _grown_rerender(s):
+    """120008 floats each, 22128 free: gain only, request 0 takes 120008 of the segment; at half speed request 1 wants 240008"""
+    ids = [s.register_clip(_noise(120000, k), None, SR) for k in (0, 1)]
+    return ids, lambda which: s.rerender_clips([ids[k] for k in which], gain_db=-6.0, speed=[(1.0, 0.5)[k] for k in which])
+
+
+def _grown_convert(s):
+    """60008 and 120008 floats at 24 kHz, 82128 free: at 48 kHz request 0 takes 120008 of the segment, request 1 wants 240008.  The
+    filter table of the ratio is made before the extents: the failed call gives that back too."""
+    ids = [s.register_clip(_noise(n, k), None, SR / 2) for k, n in enumerate((60000, 120000))]
+    return ids, lambda which: s.convert_clips([ids[k] for k in which])
+
+
+def _grown_warp(s):
+    """100008 floats each, 62128 free: request 0 is stretched to 125008, request 1 to 200008"""
+    ids = [s.register_clip(_noise(100000, k), None, SR) for k in (0, 1)]
+    return ids, lambda which: s.clip_warp_batch([(ids[k], [(0, 0), (100000, (125000, 200000)[k])]) for k in which])
+
+
+def _grown_pcm(s):
+    """a clip of 100008 floats, 162136 free: request 0 wants 200008, request 1 180008; a failed call takes no slot either"""
+    ids = [s.register_clip(_noise(100000, 0), None, SR)]
+    pcm = [(8192.0 * _noise(n, k)).astype(np.int16) for k, n in ((1, 200000), (2, 180000))]
+
+    def call(which):
+        assert s.register_clips_pcm([(pcm[k], None, 1, SR) for k in which]) == list(range(1, 1 + len(which)))
+    return ids, call
+
+
+def _grown_xfade(s):
+    """A crossfaded extent is as large as its original, and two originals that share the first arena fit one segment: with a cap of
+    2 MiB no crossfade call fails after the arena grew.  So the cap is 3 MiB and the second clip's upload adds the first segment
+    (200008 floats each, 62136 free in either allocation).  Request 0 gets the second segment, request 1 would need a third."""
+    ids = [s.register_clip(_noise(200000, k), None, SR) for k in (0, 1)]
+    assert s.memory_bytes()[1] == 2 * ARENA
+    return ids, lambda which: s.clip_loop_crossfade_batch([(ids[k], 50000, 150000, 1000) for k in which])
+
+
+GROWN = {"rerender": (2 * ARENA, _grown_rerender), "convert_rate": (2 * ARENA, _grown_convert), "loop_crossfade": (3 * ARENA, _grown_xfade),
+         "warp": (2 * ARENA, _grown_warp), "upload_pcm": (2 * ARENA, _grown_pcm)}
+
+
+@pytest.mark.parametrize("service", sorted(GROWN))
+def test_a_call_that_fails_after_the_arena_grew_gives_the_segment_back(built, service):
+    """The call fails with ZLHIP_ERR_CAPACITY, zlhip_memory_bytes is what it was before the call (the segment went back to the device),
+    every clip's extent has the bits it had, and the same call without the request that did not fit succeeds and keeps the segment."""
+    from libzl_amd import SamplerSynth, ZlHipError
+    cap, scene = GROWN[service]
+    with SamplerSynth(num_buses=1, voices_per_bus=2, max_sounds=8, sound_arena_bytes=ARENA, sound_arena_max_bytes=cap) as s:
+        ids, call = scene(s)
+        exts, mem = [s.clip_extent(i) for i in ids], s.memory_bytes()
+        with pytest.raises(ZlHipError, match=r"\(-4\)"):
+            call((0, 1))
+        assert s.memory_bytes() == mem
+        assert all(np.array_equal(s.clip_extent(i).view(np.uint32), x.view(np.uint32)) for i, x in zip(ids, exts))
+        call((0,))
+        assert s.memory_bytes()[1] == mem[1] + ARENA and s.memory_bytes()[0] > mem[0] + ARENA
