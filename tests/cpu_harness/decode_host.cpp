@@ -37,6 +37,24 @@ uint32_t zldec_stage_bytes(int64_t asked) { return zl_dec_stage_bytes(asked); }
 uint64_t zldec_extent_floats(int64_t length, int out_channels) { return zl_dec_extent_floats(length, out_channels); }
 int zldec_piece_record_bytes(void) { return (int)sizeof(ZlDecPiece); }
 
+// The header's cut of one call (zl_dec_plan): per piece its clip, its pass, its item_base and its items (arrays of `capacity`, filled
+// up to it); returns the number of pieces and leaves the number of passes.
+int32_t zldec_plan(int32_t count, const int32_t *lengths, const int32_t *channels, const int32_t *formats, int64_t stage_asked, int32_t capacity,
+                   int32_t *clip, int32_t *pass, int32_t *item_base, int32_t *items, int32_t *npasses)
+{
+    std::vector<ZlDecClip> clips((size_t)count);
+    for (int32_t c = 0; c < count; ++c) clips[(size_t)c] = ZlDecClip{ lengths[c], channels[c], formats[c] };
+    std::vector<ZlDecPiece> pieces; std::vector<ZlDecPass> passes;
+    zl_dec_plan(clips.data(), count, zl_dec_stage_bytes(stage_asked), pieces, passes);
+    *npasses = (int32_t)passes.size();
+    for (size_t a = 0; a < passes.size(); ++a)
+        for (int32_t k = passes[a].first_piece; k < passes[a].first_piece + passes[a].npieces && k < capacity; ++k) {
+            const ZlDecPiece &R = pieces[(size_t)k];
+            clip[k] = R.verdict; pass[k] = (int32_t)a; item_base[k] = R.item_base; items[k] = zl_dec_piece_items(R);
+        }
+    return (int32_t)pieces.size();
+}
+
 // n samples of one format, one by one, with the header's widening and conversion
 void zldec_convert(int format, const unsigned char *src, int64_t n, uint32_t *out)
 {

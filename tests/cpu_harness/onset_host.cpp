@@ -16,6 +16,7 @@ extern "C" {
 int32_t zlon_level(uint64_t x) { return zl_on_level(x); }
 int32_t zlon_q(float v) { return zl_st_q(v); }
 int32_t zlon_resolve(double sr, int32_t *five) { return zl_on_resolve(sr, &five[0], &five[1], &five[2], &five[3], &five[4]); }
+int64_t zlon_hops(int64_t frames, int64_t hop) { return zl_on_hops(frames, hop); }
 
 // data: the extent as floats, (length + 8) * channels words rounded up to 4 (interleaved, the pad behind the sound included).
 // visits [extent words]: += 1 for every word that enters a sum.  E [hops].  Returns the largest word index LOADED (masked or not).
