@@ -259,6 +259,28 @@ int  libzl_hotpath_clip_crossfade_loop(ClipAudioSource *c, float fade_ms, int cu
  * (may be NULL): bit 0 = clip i's loop was moved, bit 1 = its loop was crossfaded.  A clip that is NULL, not in the engine or playing a
  * re-render stays as it is.  Duplicate clips are ZLHIP_ERR_INVALID.  Returns the number of clips crossfaded, or a negative status. */
 int  libzl_hotpath_clips_seal_loops(ClipAudioSource **clips, int count, float search_ms, float min_improvement_db, float fade_ms, int curve, int *results);
+/* extension (build-defined: the reference has no such edit): cuts the silence off the front and the back of the clip's data, on the
+ * device and under the clip's own id (zlhip_sound_edit with ZLHIP_EDIT_TRIM over the whole data).  threshold_db:
+ * a frame at or above it in any channel is loud (0: the default, 2^-10 of full scale, about -60 dBFS); pre_roll_ms, hold_ms: what is
+ * kept in front of the first and behind the last loud frame.  Afterwards the duration is the new data's, startPositionInSeconds has
+ * moved back by the frames removed in front (not below 0) and lengthInSeconds is cut to what lies behind the start, both as the float
+ * seconds from which a voice derives exactly those frames.  *removed_front_frames, *new_length_frames may be NULL.  The trim cannot be
+ * taken back: reload the clip.  A clip that plays a re-render is refused with ZLHIP_ERR_STATE: trim first, then tune and level.
+ * Returns 1, or 0 for a silent or already tight clip (nothing has changed), or a negative status (nothing has changed). */
+int  libzl_hotpath_clip_trim_silence(ClipAudioSource *c, float threshold_db, float pre_roll_ms, float hold_ms, int *removed_front_frames, int *new_length_frames);
+/* A bank: ONE zlhip_sound_edit_batch call for all clips.  A clip that is NULL, not in the engine or playing a re-render stays as it is;
+ * applied_out[i] (may be NULL) is 1 where clip i was trimmed.  Duplicate clips are ZLHIP_ERR_INVALID.  Returns the number of clips
+ * trimmed, or a negative status (nothing has changed then). */
+int  libzl_hotpath_clips_trim(ClipAudioSource **clips, int count, float threshold_db, float pre_roll_ms, float hold_ms, int *applied_out);
+/* Crops the clip's data to its selected region -- exactly the frames a voice derives from start .. start + length -- and fades its ends:
+ * fade_in_ms, fade_out_ms (each cut to half the region), curve ZLHIP_EDIT_LINEAR, _SQRT or _SMOOTH.  Afterwards the start is 0 and the
+ * length and the duration are the data's.  *new_length_frames may be NULL.  No undo; a clip that plays a re-render is ZLHIP_ERR_STATE.
+ * Returns 1, or 0 where the region is the whole data and nothing fades, or a negative status (nothing has changed then). */
+int  libzl_hotpath_clip_crop(ClipAudioSource *c, float fade_in_ms, float fade_out_ms, int curve, int *new_length_frames);
+/* Turns the clip's whole data round.  The start becomes duration - (start + length), computed in frames, so that the clip plays the same
+ * region backwards; the length stays.  Reversing twice restores the data bit for bit.  A clip that plays a re-render is
+ * ZLHIP_ERR_STATE.  Returns 1, or a negative status (nothing has changed then). */
+int  libzl_hotpath_clip_reverse(ClipAudioSource *c);
 /* extension (build-defined: the reference has no warp): fits a loop to the session grid hit by hit, on the device (zlhip_sound_warp,
  * DESIGN.md section 19) -- what a sampler calls "warp" or "quantise audio".  The clip's transients are found over its whole original
  * (zlhip_sound_onsets with its defaults); every hit is moved by `strength` (0 .. 1) towards the nearest step of the grid of src_bpm

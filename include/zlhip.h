@@ -44,7 +44,9 @@ extern "C" {
  *    loudness, measured on the device), zlhip_loudness_resolve, zlhip_loudness_design, zlhip_sound_loop / _batch (a clip's seamless
  *    loop points, found on the device), zlhip_loop_resolve, zlhip_loop_seconds, zlhip_sound_key / _batch (a clip's musical
  *    key, detected on the device), zlhip_key_resolve, zlhip_key_design, zlhip_debug_live_resources, zlhip_sound_loop_crossfade / _batch (a loop crossfade
- *    baked into a clip's data on the device), zlhip_xfade_resolve, zlhip_xfade_design. */
+ *    baked into a clip's data on the device), zlhip_xfade_resolve, zlhip_xfade_design, zlhip_sound_edit / _batch (a clip's data cropped,
+ *    trimmed of silence, reversed and faded on the device), zlhip_edit_resolve, zlhip_edit_design, zlhip_debug_edit_timings,
+ *    zlhip_group_sound_edit_batch. */
 #define ZLHIP_ABI_VERSION 3
 
 /* status codes */
@@ -483,6 +485,59 @@ int zlhip_sound_loop_crossfade(zlhip_engine *e, const zlhip_xfade_request *r, zl
 int zlhip_sound_loop_crossfade_batch(zlhip_engine *e, const zlhip_xfade_request *reqs, int32_t count, zlhip_xfade *out);
 /* measurement: device time of the measuring launch and of the render and publishing launches of the last call made with profiling on */
 int zlhip_debug_xfade_timings(zlhip_engine *e, float *measure_ms, float *render_ms);
+/* Clip edit: a clip's data cropped to a region, trimmed of the silence at its ends, reversed, its ends faded -- on the device, under the
+ * clip's own id (a build-defined extension, the reference has no such edit).  The route without it is
+ * zlhip_sound_read, a host loop and zlhip_sound_upload, which gives the clip a new id: every voice and command that names it loses it.
+ *   A request acts on the slot's ORIGINAL data of `length` frames.  first_frame a, num_frames: the region to keep is [a, b);
+ *   num_frames 0 means "to the end" (a < length), else 0 <= a, num_frames >= 1, a + num_frames <= length.  flags: ZLHIP_EDIT_TRIM |
+ *   ZLHIP_EDIT_REVERSE, no other bit.  threshold (fp32; used with TRIM only): 0 means 2^-10 (about -60 dBFS), else finite and above 0.
+ *   pre_roll_frames, hold_frames (TRIM only), fade_in_frames, fade_out_frames: >= 0.  curve: ZLHIP_EDIT_LINEAR, _SQRT or _SMOOTH.
+ *   Anything else is ZLHIP_ERR_INVALID, as are ids not in use or repeated and count < 0 -- all decided before the first HIP call.
+ *   Trim: exact, no quantisation.  Frame f is loud iff for some channel !(fabsf(x[f][c]) < threshold) in fp32: NaN and +-inf are loud,
+ *   |x| == threshold is loud.  F and Z are the smallest and the largest loud frame of [a, b).  No loud frame: silent = 1, applied = 0,
+ *   the clip is untouched, no error.  Else a' = max(a, F - pre_roll_frames), b' = min(b, Z + 1 + hold_frames) (int64).  Without TRIM
+ *   a' = a, b' = b.  n = b' - a'.
+ *   Fades: cut so that they never overlap, Xi = min(fade_in_frames, n / 2), Xo = min(fade_out_frames, n / 2); the weights are made on
+ *   the host in double, for i in [0, X) with t = i / X: LINEAR w = t, SQRT w = sqrt(t) (two clips faded against each other keep constant
+ *   power), SMOOTH w = (t t) (3 - (2 t)), then rounded to fp32; w[0] = 0.
+ *   Output: n frames, the original's channels and rate.  Output frame i is source frame b' - 1 - i with REVERSE, a' + i without; a
+ *   frame i < Xi is multiplied by w_in[i], a frame i >= n - Xo by w_out[n - 1 - i], one rounded fp32 multiply per sample (the fades act
+ *   on the data after the reversal); every other sample is copied bit for bit into a new arena extent.
+ *   Identity: a' = 0, n = length, no REVERSE, Xi = Xo = 0 answers applied = 0, takes no extent and is copied by no launch; a TRIM that
+ *   finds nothing to cut is such a request.
+ *   ZL_SOUND_FINITE stays set iff the original had it and every written faded sample is finite.  A clip without the flag never gains
+ *   it, even when its non-finite samples were cropped away: copied samples are not looked at.
+ *   The result: applied, silent; first_frame, num_frames: the kept region [a', b') in source frames (the asked region where silent);
+ *   first_loud, last_loud: F and Z (-1 without TRIM or where silent); fade_in_frames, fade_out_frames as cut (0 where not applied);
+ *   length: the clip's length now; reversed; curve.
+ *   A clip that currently plays a re-render is ZLHIP_ERR_STATE; an arena that cannot hold the whole call is ZLHIP_ERR_CAPACITY, decided
+ *   behind the scan, which changes nothing.  All or nothing: on any error every clip is as it was and out is not written.
+ *   Synchronisation is zlhip_sound_convert_rate's.  A call with a TRIM request is a scanning launch, a wait, one render launch and one
+ *   publishing launch, a second wait; a call without one skips the scan and its wait -- whatever the number of requests; a call whose
+ *   every request answers applied = 0 copies and renders nothing.
+ *   Consequences.  There is no undo: reload the clip.  The new extent becomes the clip's ORIGINAL: a later re-render starts from the
+ *   edited data.  Clip parameters are seconds and keep their values: the caller moves start and length (libzl_hotpath_clip_trim_silence,
+ *   _crop and _reverse do).  A voice that plays the clip during the call keeps its frame position, which is safe and musically wrong:
+ *   edit before playing.
+ *   Not provided: undo; extracting a region into a NEW clip, or slices into clips; a baked gain or peak normalise (the clip's gain
+ *   re-render stays the reversible route); DC removal; editing under a re-render; fades at a region inside the data. */
+enum { ZLHIP_EDIT_TRIM = 1, ZLHIP_EDIT_REVERSE = 2 };
+enum { ZLHIP_EDIT_LINEAR = 0, ZLHIP_EDIT_SQRT = 1, ZLHIP_EDIT_SMOOTH = 2 };
+typedef struct zlhip_edit_request { int32_t id, first_frame, num_frames, flags, pre_roll_frames, hold_frames, fade_in_frames, fade_out_frames, curve;
+                                    float threshold; } zlhip_edit_request;
+typedef struct zlhip_edit { int32_t applied, silent, first_frame, num_frames, first_loud, last_loud, fade_in_frames, fade_out_frames, length,
+                            reversed, curve, reserved; } zlhip_edit;
+/* host only: checks the request against a sound of `length` frames and fills num_frames and threshold where they were given as 0; a
+ * refused request is left as it was */
+int zlhip_edit_resolve(int32_t length, zlhip_edit_request *r);
+/* host only: the X weights of a fade, rising from w[0] = 0, w: [X]; X < 1 or an unknown curve is ZLHIP_ERR_INVALID.  The engine builds
+ * its tables with this code */
+int zlhip_edit_design(int32_t fade_frames, int32_t curve, float *w);
+int zlhip_sound_edit(zlhip_engine *e, const zlhip_edit_request *r, zlhip_edit *out);
+int zlhip_sound_edit_batch(zlhip_engine *e, const zlhip_edit_request *reqs, int32_t count, zlhip_edit *out);
+/* measurement: device time of the scanning launch (0 for a call without TRIM) and of the render and publishing launches of the last
+ * call made with profiling on */
+int zlhip_debug_edit_timings(zlhip_engine *e, float *scan_ms, float *render_ms);
 /* Warp: a clip fitted to the session grid on the device, a time stretch cut at the clip's hits (a build-defined
  * extension, the reference has no warp).  A uniform stretch leaves a hit that is early or late early or late; here every region between
  * two anchors gets its own ratio, starts exactly at its anchor with no seek (the attack is copied 1:1) and is searched by its own
@@ -812,6 +867,9 @@ int  zlhip_group_sound_loop_batch(zlhip_group *g, const zlhip_loop_request *reqs
  * that is invalid, refused or does not fit fails on member 0 and changes nothing.  out receives member 0's results (the members hold
  * the same data: every member measures the same integers) */
 int  zlhip_group_sound_loop_crossfade_batch(zlhip_group *g, const zlhip_xfade_request *reqs, int32_t count, zlhip_xfade *out);
+/* zlhip_sound_edit_batch on every member, in member order, with zlhip_group_sound_convert_rate_batch's semantics; out receives member
+ * 0's results (the members hold the same data: every member finds the same frames) */
+int  zlhip_group_sound_edit_batch(zlhip_group *g, const zlhip_edit_request *reqs, int32_t count, zlhip_edit *out);
 /* zlhip_sound_warp_batch on every member, in member order, with zlhip_group_sound_convert_rate_batch's semantics; out receives member
  * 0's results (the members hold the same data: every member finds the same offsets) */
 int  zlhip_group_sound_warp_batch(zlhip_group *g, const zlhip_warp_request *reqs, int32_t count, zlhip_warp *out);

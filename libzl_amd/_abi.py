@@ -181,6 +181,23 @@ class Xfade(C.Structure):
 XFADE_AUTO, XFADE_LINEAR, XFADE_EQUAL_POWER = 0, 1, 2
 
 
+class EditRequest(C.Structure):
+    _fields_ = [("id", C.c_int32), ("first_frame", C.c_int32), ("num_frames", C.c_int32), ("flags", C.c_int32), ("pre_roll_frames", C.c_int32),
+                ("hold_frames", C.c_int32), ("fade_in_frames", C.c_int32), ("fade_out_frames", C.c_int32), ("curve", C.c_int32), ("threshold", C.c_float)]
+
+
+class Edit(C.Structure):
+    _fields_ = [("applied", C.c_int32), ("silent", C.c_int32), ("first_frame", C.c_int32), ("num_frames", C.c_int32), ("first_loud", C.c_int32),
+                ("last_loud", C.c_int32), ("fade_in_frames", C.c_int32), ("fade_out_frames", C.c_int32), ("length", C.c_int32), ("reversed", C.c_int32),
+                ("curve", C.c_int32), ("reserved", C.c_int32)]
+
+
+EDIT_TRIM, EDIT_REVERSE = 1, 2
+EDIT_LINEAR, EDIT_SQRT, EDIT_SMOOTH = 0, 1, 2
+# the sizes the library asserts for the edit's two records (zl_clip_calls.cpp)
+STRUCT_SIZES = {"zlhip_edit_request": (EditRequest, 40), "zlhip_edit": (Edit, 48)}
+
+
 class WarpAnchor(C.Structure):
     _fields_ = [("src_frame", C.c_int32), ("dst_frame", C.c_int32)]
 
@@ -303,6 +320,11 @@ SIGNATURES = {
     "zlhip_sound_loop_crossfade": (C.c_int, [_E, C.POINTER(XfadeRequest), C.POINTER(Xfade)]),
     "zlhip_sound_loop_crossfade_batch": (C.c_int, [_E, C.POINTER(XfadeRequest), C.c_int32, C.POINTER(Xfade)]),
     "zlhip_debug_xfade_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "zlhip_edit_resolve": (C.c_int, [C.c_int32, C.POINTER(EditRequest)]),
+    "zlhip_edit_design": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p]),
+    "zlhip_sound_edit": (C.c_int, [_E, C.POINTER(EditRequest), C.POINTER(Edit)]),
+    "zlhip_sound_edit_batch": (C.c_int, [_E, C.POINTER(EditRequest), C.c_int32, C.POINTER(Edit)]),
+    "zlhip_debug_edit_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "zlhip_warp_resolve": (C.c_int, [C.c_double, C.c_int32, C.POINTER(WarpAnchor), C.c_int32, C.POINTER(Warp)]),
     "zlhip_warp_plan": (C.c_int, [C.c_double, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32,
                                   C.POINTER(WarpAnchor), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -388,6 +410,7 @@ SIGNATURES = {
     "zlhip_group_sound_pitch_batch": (C.c_int, [_E, C.POINTER(PitchRequest), C.c_int32, C.POINTER(Pitch)]),
     "zlhip_group_sound_loop_batch": (C.c_int, [_E, C.POINTER(LoopRequest), C.c_int32, C.POINTER(Loop)]),
     "zlhip_group_sound_loop_crossfade_batch": (C.c_int, [_E, C.POINTER(XfadeRequest), C.c_int32, C.POINTER(Xfade)]),
+    "zlhip_group_sound_edit_batch": (C.c_int, [_E, C.POINTER(EditRequest), C.c_int32, C.POINTER(Edit)]),
     "zlhip_group_sound_warp_batch": (C.c_int, [_E, C.POINTER(WarpRequest), C.c_int32, C.POINTER(Warp)]),
     "zlhip_group_sound_key_batch": (C.c_int, [_E, C.POINTER(KeyRequest), C.c_int32, C.POINTER(Key)]),
     "zlhip_group_sound_loudness_batch": (C.c_int, [_E, C.POINTER(LoudnessRequest), C.c_int32, C.POINTER(Loudness)]),

@@ -1,8 +1,8 @@
 // zl_clip_calls.cpp -- the clip services of include/zlhip.h: loading from raw PCM, re-render, rate conversion, and the seven analyses
-// (waveform overviews, transients, tempo, pitch, loudness, loop points, key), the loop crossfade and the warp.  Every one is a call on a loaded clip that validates everything before its
+// (waveform overviews, transients, tempo, pitch, loudness, loop points, key), the loop crossfade, the clip edit and the warp.  Every one is a call on a loaded clip that validates everything before its
 // first HIP call, reserves buffers that only grow, queues its launches on the engine's stream and waits once.  What they share is
-// written once, below: the checks and the buffers of every service, and for the five that replace a clip's data -- the PCM upload, the
-// re-render, the rate conversion, the loop crossfade, the warp -- the new arena extents of a call, taken all or none (ZlNewExtents), and
+// written once, below: the checks and the buffers of every service, and for the six that replace a clip's data -- the PCM upload, the
+// re-render, the rate conversion, the loop crossfade, the clip edit, the warp -- the new arena extents of a call, taken all or none (ZlNewExtents), and
 // the switch of a clip to its new extent (ZlClipSwap).  The engine itself -- arena, sound slots, rendering, the resident kernel -- is
 // zl_engine.cpp.
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@
 
 #include "zl_engine_impl.h"
 #include "zl_decode.h"
+#include "zl_edit.h"
 #include "zl_key.h"
 #include "zl_loop.h"
 #include "zl_loudness.h"
@@ -1338,6 +1339,197 @@ int zlhip_debug_xfade_timings(zlhip_engine *e, float *measure_ms, float *render_
     if (!e) return ZLHIP_ERR_INVALID;
     if (measure_ms) *measure_ms = e->xf.measureMs;
     if (render_ms) *render_ms = e->xf.renderMs;
+    return ZLHIP_OK;
+}
+
+// ---- clip edit (zl_edit.h, zl_edit.hip) -----------------------------------------------------------------------------------------
+// Crop, trim silence, reverse, fade the ends: the clip's data changes under its own id.  The order is the loop crossfade's, but for the
+// extents: a trimmed clip's new length is known only behind the scan, so the scan launch and the call's first wait come first -- the
+// scan writes nothing but its own words, so that an arena that cannot hold the call still leaves every clip as it was -- and only
+// then every applied clip gets its new extent (ZlNewExtents), the weight tables are made here in double, one launch copies and fades
+// every clip, the sound-table entries switch (ZlClipSwap) and the call waits a last time.  A call without a TRIM request skips the
+// scan and its wait.  The new extent becomes the slot's original.
+int zlhip_edit_resolve(int32_t length, zlhip_edit_request *r)
+{
+    static_assert(sizeof(zlhip_edit_request) == 40 && sizeof(zlhip_edit_request) == sizeof(ZlEdRequest), "zlhip_edit_request's layout");
+    if (!r) return ZLHIP_ERR_INVALID;
+    ZlEdRequest q;
+    std::memcpy(&q, r, sizeof q);
+    if (zl_ed_resolve(length, &q) != 0) return ZLHIP_ERR_INVALID;
+    std::memcpy(r, &q, sizeof q);
+    return ZLHIP_OK;
+}
+
+int zlhip_edit_design(int32_t fade_frames, int32_t curve, float *w)
+{
+    if (!w || fade_frames < 1 || (curve != ZL_ED_LINEAR && curve != ZL_ED_SQRT && curve != ZL_ED_SMOOTH)) return ZLHIP_ERR_INVALID;
+    zl_ed_design(fade_frames, curve, w);
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_edit_batch(zlhip_engine *e, const zlhip_edit_request *reqs, int32_t count, zlhip_edit *out)
+{
+    static_assert(sizeof(zlhip_edit) == 48, "zlhip_edit's layout");
+    static_assert(ZLHIP_EDIT_TRIM == ZL_ED_TRIM && ZLHIP_EDIT_REVERSE == ZL_ED_REVERSE, "the flags");
+    static_assert(ZLHIP_EDIT_LINEAR == ZL_ED_LINEAR && ZLHIP_EDIT_SQRT == ZL_ED_SQRT && ZLHIP_EDIT_SMOOTH == ZL_ED_SMOOTH, "the curves");
+    if (!e || count < 0 || (count > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
+    if (count == 0) return ZLHIP_OK;
+    // validate and resolve everything before the first HIP call
+    std::vector<zlhip_edit_request> res((size_t)count);
+    std::vector<ZlEdScan> scans; std::vector<int32_t> scanReq;
+    int32_t scanWgs = 0;
+    const char *const refusal = "sound_edit: the clip plays a re-render (edit first, re-render afterwards; re-render it with gain 0, pitch 0, speed 1 first)";
+    {
+        ZlDistinct distinct(e);
+        int64_t wgs = 0, swgs = 0, fades = 0;                      // (the render's workgroups and weights: what the asked regions need at most)
+        for (int32_t i = 0; i < count; ++i) {
+            zlhip_edit_request &q = res[(size_t)i];
+            q = reqs[i];
+            { const int rc = distinct.check(e, "sound_edit", q.id); if (rc != ZLHIP_OK) return rc; }
+            const ZlSound &o = e->soundSlots[(size_t)q.id].orig;
+            if (zlhip_edit_resolve(o.length, &q) != ZLHIP_OK)
+                return fail_in(e, ZLHIP_ERR_INVALID, "sound_edit", "the region does not lie inside the sound's data, an unknown flag or curve, a negative count of frames, or a threshold that is not finite and above 0");
+            ZlEdJob J; std::memset(&J, 0, sizeof J);
+            J.n = q.num_frames; J.channels = o.channels;
+            wgs += zl_ed_job_wgs(J); fades += (int64_t)(q.num_frames / 2) * 2;
+            if (q.flags & ZL_ED_TRIM) {
+                ZlEdScan S; std::memset(&S, 0, sizeof S);
+                S.channels = o.channels; S.a = q.first_frame; S.b = q.first_frame + q.num_frames; S.threshold = q.threshold;
+                S.wg_base = (int32_t)swgs; S.found = (int32_t)scans.size();
+                swgs += zl_ed_scan_wgs(S);
+                scans.push_back(S); scanReq.push_back(i);
+            }
+        }
+        if (wgs > (int64_t)INT32_MAX || swgs > (int64_t)INT32_MAX || fades > (int64_t)INT32_MAX)
+            return fail(e, ZLHIP_ERR_INVALID, "sound_edit_batch: more than 2^31 - 1 workgroups or fade frames in one call");
+        scanWgs = (int32_t)swgs;
+        for (int32_t i = 0; i < count; ++i) {                      // (a request that is the identity whatever the scan finds touches nothing)
+            const zlhip_edit_request &q = res[(size_t)i];
+            const ZlSound &o = e->soundSlots[(size_t)q.id].orig;
+            int32_t Xi, Xo;
+            zl_ed_fades(q.num_frames, q.fade_in_frames, q.fade_out_frames, &Xi, &Xo);
+            if (!(q.flags & ZL_ED_TRIM) && zl_ed_identity(o.length, q.first_frame, q.num_frames, (q.flags & ZL_ED_REVERSE) != 0, Xi, Xo)) continue;
+            const int rc = check_plays_original(e, q.id, refusal);
+            if (rc != ZLHIP_OK) return rc;
+        }
+    }
+    zlhip_engine::Edit &t = e->ed;
+    t.timer.on = e->profiling;
+    if (e->profiling) { t.scanMs = 0.0f; t.renderMs = 0.0f; }
+    const char *what = "sound_edit: no memory for the call's records";
+    bool begun = false;
+    // the scan: F and Z of every TRIM request
+    std::vector<ZlEdFound> found(scans.size(), ZlEdFound{ INT32_MAX, -1 });
+    if (!scans.empty()) {
+        { const int rc = call_begin(e, true); if (rc != ZLHIP_OK) return rc; }
+        begun = true;
+        const size_t ns = scans.size(), n = std::max<size_t>(ns * 2, 64);
+        const int rsv = reserve(e, false, { { ZB_ED_SCAN, ns, sizeof(ZlEdScan), n, false, what }, { ZB_ED_FOUND, ns, sizeof(ZlEdFound), n, false, what } });
+        if (rsv != ZLHIP_OK) return rsv;
+        ZlEdScan *const dScan = (ZlEdScan *)e->scratch[ZB_ED_SCAN].d; ZlEdFound *const dFound = (ZlEdFound *)e->scratch[ZB_ED_FOUND].d;
+        for (size_t k = 0; k < ns; ++k) scans[k].src = (uint64_t)(uintptr_t)arena_ptr(e, e->soundSlots[(size_t)res[(size_t)scanReq[k]].id].orig.offset);
+        int krc = (int)hipMemcpyAsync(dScan, scans.data(), ns * sizeof(ZlEdScan), hipMemcpyHostToDevice, e->stream);
+        if (krc == 0) krc = (int)hipMemcpyAsync(dFound, found.data(), ns * sizeof(ZlEdFound), hipMemcpyHostToDevice, e->stream);
+        if (krc == 0) krc = (int)t.timer.mark(0, e->stream);
+        if (krc == 0) krc = zl_launch_edit_scan(dScan, (int32_t)ns, scanWgs, dFound, e->stream);
+        if (krc == 0) krc = (int)t.timer.mark(1, e->stream);
+        if (krc == 0) krc = (int)hipMemcpyAsync(found.data(), dFound, ns * sizeof(ZlEdFound), hipMemcpyDeviceToHost, e->stream);
+        if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);  // the call's first wait: F and Z are in host memory
+        if (krc == 0) krc = (int)t.timer.elapsed(0, 1, &t.scanMs);
+        if (krc != 0) {                                            // (the scan has changed nothing: nothing to undo)
+            e->err = std::string("sound_edit: ") + hipGetErrorString((hipError_t)krc);
+            (void)hipStreamSynchronize(e->stream);
+            return ZLHIP_ERR_HIP;
+        }
+    }
+    // the regions, from F and Z
+    std::vector<zlhip_edit> results((size_t)count);
+    std::vector<ZlEdJob> plan((size_t)count);                      // per request; n = 0: not applied
+    std::memset(plan.data(), 0, plan.size() * sizeof(ZlEdJob));
+    int32_t njobs = 0;
+    for (int32_t i = 0, k = 0; i < count; ++i) {
+        const zlhip_edit_request &q = res[(size_t)i];
+        const ZlSound &o = e->soundSlots[(size_t)q.id].orig;
+        const bool trim = (q.flags & ZL_ED_TRIM) != 0, reverse = (q.flags & ZL_ED_REVERSE) != 0;
+        const ZlEdFound f = trim ? found[(size_t)k++] : ZlEdFound{ INT32_MAX, -1 };
+        zlhip_edit &r = results[(size_t)i];
+        std::memset(&r, 0, sizeof r);
+        r.curve = q.curve; r.first_loud = -1; r.last_loud = -1;
+        int32_t a2, b2, Xi = 0, Xo = 0;
+        if (!zl_ed_region(q.first_frame, q.first_frame + q.num_frames, trim, f.first, f.last, q.pre_roll_frames, q.hold_frames, &a2, &b2)) {
+            r.silent = 1; r.first_frame = q.first_frame; r.num_frames = q.num_frames; r.length = o.length;
+            continue;
+        }
+        if (trim) { r.first_loud = f.first; r.last_loud = f.last; }
+        zl_ed_fades(b2 - a2, q.fade_in_frames, q.fade_out_frames, &Xi, &Xo);
+        r.first_frame = a2; r.num_frames = b2 - a2; r.length = b2 - a2;
+        if (zl_ed_identity(o.length, a2, b2 - a2, reverse, Xi, Xo)) continue;
+        r.applied = 1; r.fade_in_frames = Xi; r.fade_out_frames = Xo; r.reversed = reverse ? 1 : 0;
+        ZlEdJob &J = plan[(size_t)i];
+        J.channels = o.channels; J.a = a2; J.n = b2 - a2; J.reverse = reverse ? 1 : 0; J.Xi = Xi; J.Xo = Xo;
+        ++njobs;
+    }
+    if (njobs == 0) {                                              // nothing to change anywhere: no extent, no copy, no render
+        std::memcpy(out, results.data(), results.size() * sizeof(zlhip_edit));
+        return ZLHIP_OK;
+    }
+    if (!begun) { const int rc = call_begin(e, true); if (rc != ZLHIP_OK) return rc; }
+    // only now the new extents, and the jobs
+    ZlNewExtents ext(e, count);
+    ZlClipSwap swap{ e, "sound_edit", ext };
+    std::vector<ZlEdJob> jobs;
+    int32_t wgs = 0, nw = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        if (plan[(size_t)i].n == 0) continue;
+        const ZlSound &o = e->soundSlots[(size_t)res[(size_t)i].id].orig;
+        ZlEdJob J = plan[(size_t)i];
+        { const int rc = ext.take(i, J.n, o.channels); if (rc != ZLHIP_OK) return rc; }
+        J.src = (uint64_t)(uintptr_t)arena_ptr(e, o.offset);
+        J.dst = (uint64_t)(uintptr_t)ext.ptr(i);
+        J.wg_base = wgs; J.w_in = nw; J.w_out = nw + J.Xi;
+        ZlSound s = o; s.length = J.n;
+        J.verdict = swap.add(i, res[(size_t)i].id, s);
+        wgs += zl_ed_job_wgs(J); nw += J.Xi + J.Xo;
+        jobs.push_back(J);
+    }
+    const size_t nj = jobs.size(), n = std::max<size_t>(nj * 2, 64), np = (size_t)nw;
+    const int rsv = reserve(e, false, { { ZB_ED_JOBS, nj, sizeof(ZlEdJob), n, false, what }, { ZB_ED_WEIGHTS, np, sizeof(float), std::max<size_t>(np * 2, 4096), false, what },
+                                       { ZB_ED_PUB, nj, sizeof(ZlRsPublish), n, false, what }, { ZB_ED_VERDICTS, nj, sizeof(uint32_t), n, false, what } });
+    if (rsv != ZLHIP_OK) { ext.rollback(); return rsv; }
+    ZlEdJob *const dJobs = (ZlEdJob *)e->scratch[ZB_ED_JOBS].d; float *const dWeights = (float *)e->scratch[ZB_ED_WEIGHTS].d;
+    ZlRsPublish *const dPub = (ZlRsPublish *)e->scratch[ZB_ED_PUB].d; uint32_t *const dVerdicts = (uint32_t *)e->scratch[ZB_ED_VERDICTS].d;
+    // everything is decided: from here on only a HIP error fails the call.  The tables
+    std::vector<float> weights(np);
+    for (size_t j = 0; j < nj; ++j) {
+        const int32_t curve = res[(size_t)swap.jobReq[j]].curve;
+        zl_ed_design(jobs[j].Xi, curve, weights.data() + jobs[j].w_in);
+        zl_ed_design(jobs[j].Xo, curve, weights.data() + jobs[j].w_out);
+    }
+    std::vector<uint32_t> verdictsOut(nj, 0u);
+    int krc = (int)hipMemcpyAsync(dJobs, jobs.data(), nj * sizeof(ZlEdJob), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0 && np > 0) krc = (int)hipMemcpyAsync(dWeights, weights.data(), np * sizeof(float), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dVerdicts, swap.words.data(), nj * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, swap.pub.data(), nj * sizeof(ZlRsPublish), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)t.timer.mark(2, e->stream);
+    if (krc == 0) krc = zl_launch_edit_render(dJobs, (int32_t)nj, wgs, dWeights, dVerdicts, e->stream);
+    if (krc == 0) krc = zl_launch_resample_publish(dPub, (int32_t)nj, dVerdicts, e->dSounds, e->stream);
+    if (krc == 0) krc = (int)t.timer.mark(3, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(verdictsOut.data(), dVerdicts, nj * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
+    if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);      // the call's last wait
+    if (krc == 0) krc = (int)t.timer.elapsed(2, 3, &t.renderMs);
+    if (krc != 0) return swap.hip_failed(krc);
+    swap.commit(verdictsOut);
+    std::memcpy(out, results.data(), results.size() * sizeof(zlhip_edit));
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_edit(zlhip_engine *e, const zlhip_edit_request *r, zlhip_edit *out) { return zlhip_sound_edit_batch(e, r, 1, out); }
+
+int zlhip_debug_edit_timings(zlhip_engine *e, float *scan_ms, float *render_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (scan_ms) *scan_ms = e->ed.scanMs;
+    if (render_ms) *render_ms = e->ed.renderMs;
     return ZLHIP_OK;
 }
 

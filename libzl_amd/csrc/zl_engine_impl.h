@@ -32,6 +32,7 @@ enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a ca
        ZB_LP_REQ, ZB_LP_X, ZB_LP_E, ZB_LP_SHIFT, ZB_LP_ITEM, ZB_LP_COST,   // loop finder: a call's request records (with a host twin), the int16 strips, per candidate E, per request the shift, the item records, the cost matrix (small calls)
        ZB_KY_REQ, ZB_KY_BINS, ZB_KY_TABLE, ZB_KY_STAT, ZB_KY_ACC, ZB_KY_TOTAL,   // key: a call's request records, its bin tables and the paired cosine table (each with a host twin), per frame the gate's verdict, per frame and bin re and im, per bin the totals
        ZB_XF_JOBS, ZB_XF_WEIGHTS, ZB_XF_PUB, ZB_XF_VERDICTS,  // loop crossfade: a call's job records, its (a, b) pairs, its publish records, its verdict words
+       ZB_ED_SCAN, ZB_ED_FOUND, ZB_ED_JOBS, ZB_ED_WEIGHTS, ZB_ED_PUB, ZB_ED_VERDICTS,   // clip edit: a call's scan records and their two words each, its job records, its fade weights, its publish records, its verdict words
        ZB_WP_JOBS, ZB_WP_REGIONS, ZB_WP_LIST, ZB_WP_OFFS, ZB_WP_PUB, ZB_WP_VERDICTS,   // warp: a call's job and region records, the regions whose seek runs, the seek offsets, its publish records, its verdict words
        ZB_COUNT };
 
@@ -124,6 +125,8 @@ struct zlhip_engine {
         ZlMapped<ZlXfSums> sums;                                    // a call's measured sums, one record per applied request
         ZlStageTimer<4> timer; float measureMs = 0.0f, renderMs = 0.0f;   // marks: around the measuring launch, around the render and publish launches
     } xf;
+    // clip edit (zlhip_sound_edit; zl_edit.h)
+    struct Edit { ZlStageTimer<4> timer; float scanMs = 0.0f, renderMs = 0.0f; } ed;      // marks: around the scanning launch, around the render and publish launches
     // warp (zlhip_sound_warp; zl_warp.h)
     struct Warp { ZlStageTimer<3> timer; float seekMs = 0.0f, synthMs = 0.0f; } wp;       // marks: before the seek, between the launches, behind the publish
     // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h)

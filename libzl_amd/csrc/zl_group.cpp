@@ -352,6 +352,18 @@ int zlhip_group_sound_loop_crossfade_batch(zlhip_group *g, const zlhip_xfade_req
     return ZLHIP_OK;
 }
 
+int zlhip_group_sound_edit_batch(zlhip_group *g, const zlhip_edit_request *reqs, int32_t count, zlhip_edit *out)
+{
+    if (!g) return ZLHIP_ERR_INVALID;
+    // (as zlhip_group_sound_loop_crossfade_batch: a call that is invalid or does not fit fails on member 0 and leaves every member as it was)
+    std::vector<zlhip_edit> rest((size_t)(count > 0 ? count : 0));
+    for (int r = 0; r < g->L.n; ++r) {
+        const int rc = zlhip_sound_edit_batch(g->m[(size_t)r], reqs, count, r == 0 ? out : rest.data());
+        if (rc != ZLHIP_OK) return member_fail(g, r, rc);
+    }
+    return ZLHIP_OK;
+}
+
 int zlhip_group_sound_warp_batch(zlhip_group *g, const zlhip_warp_request *reqs, int32_t count, zlhip_warp *out)
 {
     if (!g) return ZLHIP_ERR_INVALID;

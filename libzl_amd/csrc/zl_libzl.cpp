@@ -1357,6 +1357,156 @@ int libzl_hotpath_clip_crossfade_loop(ClipAudioSource *c, float fade_ms, int cur
     return r.applied ? 1 : 0;
 }
 
+// A sampler's editor cuts the silence off a recording, crops a clip to its selected region and turns it round; the reference can only
+// move the start and the length over data that stays.  Here the data itself changes on the device under the clip's own id
+// (zlhip_sound_edit) and the clip's seconds move with it, in frames: the start and the length become the float
+// seconds from which a voice derives exactly the intended frames (zl_clip_start / zl_clip_stop and K1's casts, zl_plan.h).
+// Build-defined: the reference has no such edit.
+static int clip_edit_ready(ClipAudioSource *c, zlhip_sound_info *info)      // call with G.mu held
+{
+    if (!G.engine || c->engineClip < 0) return ZLHIP_ERR_STATE;
+    { const int rc = zlhip_sound_info_get(G.engine, c->engineClip, info); if (rc != ZLHIP_OK) return rc; }
+    return info->rendered ? ZLHIP_ERR_STATE : ZLHIP_OK;            // edit first, level afterwards
+}
+
+// the frames a voice derives from the clip's start and start + length, the stop cut to the data (clip_xfade_request's two formulas)
+static int clip_voice_frames(ClipAudioSource *c, const zlhip_sound_info &info, int64_t *start, int64_t *stop)
+{
+    float startSec, lengthSec;
+    { std::lock_guard<std::mutex> sl(c->setMu); startSec = c->startPositionInSeconds; lengthSec = c->lengthInSeconds; }
+    const float stopSec = startSec + lengthSec;
+    const double a = (double)startSec * info.sample_rate, b = (double)stopSec * info.sample_rate;
+    if (!(a >= 0.0) || !(b > a) || a >= (double)info.length) return ZLHIP_ERR_INVALID;     // (a NaN fails here)
+    const int64_t s = (int64_t)a, e = b >= (double)info.length ? (int64_t)info.length : (int64_t)b;
+    if (s >= e) return ZLHIP_ERR_INVALID;                          // (a start behind the data; start and stop are not written)
+    *start = s; *stop = e;
+    return ZLHIP_OK;
+}
+
+// the clip plays frames [start, stop) of its new data of `length` frames: duration, start and length, under the setters' lock and
+// through their publish.  A start of frame 0 is 0 seconds exactly.
+static void clip_set_frames(ClipAudioSource *c, double rate, int32_t length, int64_t start, int64_t stop)
+{
+    float startSec = 0.0f, lengthSec = 0.0f;
+    bool ok = false;
+    if (start == 0) {
+        lengthSec = (float)(((double)stop + 0.5) / rate);
+        for (int n = 0; n <= 8 && !ok; ++n) {
+            const int64_t m = (int64_t)((double)lengthSec * rate);
+            ok = m == stop;
+            if (!ok) lengthSec = std::nextafterf(lengthSec, m < stop ? INFINITY : -INFINITY);
+        }
+    } else {
+        ok = zlhip_loop_seconds(rate, start, stop, &startSec, &lengthSec) == ZLHIP_OK;
+    }
+    if (!ok) { startSec = (float)((double)start / rate); lengthSec = (float)((double)(stop - start) / rate); }     // (beyond a float's 24 bits: the nearest)
+    std::lock_guard<std::mutex> sl(c->setMu);
+    c->lengthFrames = length;
+    c->duration = (float)(length / rate);
+    c->startPositionInSeconds = startSec;
+    c->lengthInSeconds = lengthSec;
+    publish_params(c);
+}
+
+static int clip_trim_request(ClipAudioSource *c, float threshold_db, float pre_roll_ms, float hold_ms, zlhip_sound_info *info, zlhip_edit_request *q)     // call with G.mu held
+{
+    { const int rc = clip_edit_ready(c, info); if (rc != ZLHIP_OK) return rc; }
+    const double pre = std::rint((double)pre_roll_ms * info->sample_rate / 1000.0), hold = std::rint((double)hold_ms * info->sample_rate / 1000.0);
+    if (!(pre >= 0.0 && pre <= 2147483647.0) || !(hold >= 0.0 && hold <= 2147483647.0)) return ZLHIP_ERR_INVALID;      // (a NaN fails here)
+    const float thr = threshold_db == 0.0f ? 0.0f : (float)std::pow(10.0, (double)threshold_db / 20.0);
+    if (threshold_db != 0.0f && !(thr > 0.0f && thr <= FLT_MAX)) return ZLHIP_ERR_INVALID;
+    *q = zlhip_edit_request{ c->engineClip, 0, 0, ZLHIP_EDIT_TRIM, (int32_t)pre, (int32_t)hold, 0, 0, ZLHIP_EDIT_LINEAR, thr };
+    return ZLHIP_OK;
+}
+
+// what a trim that was applied does to the clip's seconds: the start moves back by the frames removed in front, not below 0; the length
+// is cut to what lies behind the start
+static void clip_after_trim(ClipAudioSource *c, const zlhip_sound_info &before, int64_t start, int64_t stop, const zlhip_edit &r)
+{
+    const int64_t s = std::min<int64_t>(std::max<int64_t>(start - r.first_frame, 0), r.length - 1);
+    const int64_t e = std::min<int64_t>(std::max<int64_t>(stop - r.first_frame, s + 1), r.length);
+    clip_set_frames(c, before.sample_rate, r.length, s, e);
+}
+
+int libzl_hotpath_clip_trim_silence(ClipAudioSource *c, float threshold_db, float pre_roll_ms, float hold_ms, int *removed_front_frames, int *new_length_frames)
+{
+    if (!c) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    zlhip_sound_info info; zlhip_edit_request q; zlhip_edit r;
+    { const int rc = clip_trim_request(c, threshold_db, pre_roll_ms, hold_ms, &info, &q); if (rc != ZLHIP_OK) return rc; }
+    int64_t start = 0, stop = info.length;
+    (void)clip_voice_frames(c, info, &start, &stop);               // (a clip without a region keeps the whole data)
+    { const int rc = zlhip_sound_edit(G.engine, &q, &r); if (rc != ZLHIP_OK) return rc; }
+    if (removed_front_frames) *removed_front_frames = r.applied ? r.first_frame : 0;
+    if (new_length_frames) *new_length_frames = r.length;
+    if (!r.applied) return 0;
+    clip_after_trim(c, info, start, stop, r);
+    return 1;
+}
+
+// A whole bank: ONE zlhip_sound_edit_batch.
+int libzl_hotpath_clips_trim(ClipAudioSource **clips, int count, float threshold_db, float pre_roll_ms, float hold_ms, int *applied_out)
+{
+    if (count < 0 || (count > 0 && !clips)) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    if (!G.engine) return ZLHIP_ERR_STATE;
+    for (int i = 0; i < count; ++i)
+        for (int j = 0; clips[i] && j < i; ++j) if (clips[j] == clips[i]) return ZLHIP_ERR_INVALID;
+    std::vector<int> who; std::vector<zlhip_edit_request> reqs; std::vector<zlhip_sound_info> infos; std::vector<std::pair<int64_t, int64_t>> regions;
+    for (int i = 0; i < count; ++i) {
+        zlhip_edit_request q; zlhip_sound_info info;
+        if (!clips[i]) continue;
+        const int rc = clip_trim_request(clips[i], threshold_db, pre_roll_ms, hold_ms, &info, &q);
+        if (rc == ZLHIP_ERR_INVALID) return rc;                    // (the arguments are the call's: wrong for one clip, wrong for all)
+        if (rc != ZLHIP_OK) continue;                              // not in the engine, plays a re-render: stays as it is
+        int64_t start = 0, stop = info.length;
+        (void)clip_voice_frames(clips[i], info, &start, &stop);
+        who.push_back(i); reqs.push_back(q); infos.push_back(info); regions.push_back({ start, stop });
+    }
+    std::vector<zlhip_edit> res(reqs.size());
+    if (!reqs.empty()) { const int rc = zlhip_sound_edit_batch(G.engine, reqs.data(), (int32_t)reqs.size(), res.data()); if (rc != ZLHIP_OK) return rc; }
+    if (applied_out) for (int i = 0; i < count; ++i) applied_out[i] = 0;
+    int applied = 0;
+    for (size_t n = 0; n < who.size(); ++n) {
+        if (!res[n].applied) continue;
+        clip_after_trim(clips[who[n]], infos[n], regions[n].first, regions[n].second, res[n]);
+        if (applied_out) applied_out[who[n]] = 1;
+        ++applied;
+    }
+    return applied;
+}
+
+int libzl_hotpath_clip_crop(ClipAudioSource *c, float fade_in_ms, float fade_out_ms, int curve, int *new_length_frames)
+{
+    if (!c) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    zlhip_sound_info info; int64_t start, stop; zlhip_edit r;
+    { const int rc = clip_edit_ready(c, &info); if (rc != ZLHIP_OK) return rc; }
+    { const int rc = clip_voice_frames(c, info, &start, &stop); if (rc != ZLHIP_OK) return rc; }
+    const double fin = std::rint((double)fade_in_ms * info.sample_rate / 1000.0), fout = std::rint((double)fade_out_ms * info.sample_rate / 1000.0);
+    if (!(fin >= 0.0 && fin <= 2147483647.0) || !(fout >= 0.0 && fout <= 2147483647.0)) return ZLHIP_ERR_INVALID;
+    const zlhip_edit_request q = { c->engineClip, (int32_t)start, (int32_t)(stop - start), 0, 0, 0, (int32_t)fin, (int32_t)fout, curve, 0.0f };
+    { const int rc = zlhip_sound_edit(G.engine, &q, &r); if (rc != ZLHIP_OK) return rc; }
+    if (new_length_frames) *new_length_frames = r.length;
+    if (!r.applied) return 0;
+    clip_set_frames(c, info.sample_rate, r.length, 0, r.length);
+    return 1;
+}
+
+int libzl_hotpath_clip_reverse(ClipAudioSource *c)
+{
+    if (!c) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    zlhip_sound_info info; zlhip_edit r;
+    { const int rc = clip_edit_ready(c, &info); if (rc != ZLHIP_OK) return rc; }
+    int64_t start = 0, stop = info.length;
+    (void)clip_voice_frames(c, info, &start, &stop);
+    const zlhip_edit_request q = { c->engineClip, 0, 0, ZLHIP_EDIT_REVERSE, 0, 0, 0, 0, ZLHIP_EDIT_LINEAR, 0.0f };
+    { const int rc = zlhip_sound_edit(G.engine, &q, &r); if (rc != ZLHIP_OK) return rc; }
+    clip_set_frames(c, info.sample_rate, r.length, (int64_t)info.length - stop, (int64_t)info.length - start);      // the same region, played backwards
+    return 1;
+}
+
 // Fit a loop to the session grid hit by hit: the clip's transients over its whole original (zlhip_sound_onsets, defaults), its tempo
 // (given, or detected as libzl_hotpath_clip_tempo(c, 0, 0, ...) does), the plan from hits to anchors on the host (zlhip_warp_plan; the
 // grid counts from the clip's start frame by the voice's own cast) and the warp on the device (zlhip_sound_warp).

@@ -227,6 +227,21 @@ def _xfade_call(fn, handle, requests):
     return rc, [{k: getattr(out[i], k) for k in XFADE_FIELDS} for i in range(len(requests))]
 
 
+EDIT_FIELDS = tuple(name for name, _ in _abi.Edit._fields_ if name != "reserved")
+_EDIT_KEYS = tuple(name for name, _ in _abi.EditRequest._fields_[1:])
+
+
+def _edit_call(fn, handle, requests):
+    """one zlhip_sound_edit_batch-shaped call over dicts with "clip" and any of zlhip_edit_request's other fields (missing = 0: the
+    whole clip, no flag, no fade, the default threshold) -> (status, one dict of zlhip_edit's fields per request)"""
+    reqs = (_abi.EditRequest * max(1, len(requests)))()
+    for i, r in enumerate(requests):
+        reqs[i] = _abi.EditRequest(int(r["clip"]), *(int(r.get(k, 0)) for k in _EDIT_KEYS[:-1]), float(r.get("threshold", 0.0)))
+    out = (_abi.Edit * max(1, len(requests)))()
+    rc = fn(handle, reqs, len(requests), out)
+    return rc, [{k: getattr(out[i], k) for k in EDIT_FIELDS} for i in range(len(requests))]
+
+
 WARP_FIELDS = tuple(name for name, _ in _abi.Warp._fields_)
 
 
@@ -684,6 +699,30 @@ class SamplerSynth:
         """device ms of the measuring launch and of the render and publishing launches of the last crossfade call made with profiling on"""
         a, b = C.c_float(0.0), C.c_float(0.0)
         self._ck(self._lib.zlhip_debug_xfade_timings(self._e, C.byref(a), C.byref(b)), "debug_xfade_timings")
+        return a.value, b.value
+
+    def clip_edit(self, clip: int, first_frame: int = 0, num_frames: int = 0, flags: int = 0, pre_roll_frames: int = 0, hold_frames: int = 0,
+                  fade_in_frames: int = 0, fade_out_frames: int = 0, curve: int = 0, threshold: float = 0.0) -> dict:
+        """Edit the clip's data on the device under its own id (zlhip_sound_edit): keep [first_frame, first_frame +
+        num_frames) (num_frames 0: to the end), flags 1 trims the silence off both ends of it (threshold 0: 2^-10; pre_roll_frames and
+        hold_frames are kept around the loud part), flags 2 reverses it, then the ends are faded in and out (curve 0 linear, 1 square
+        root, 2 smoothstep; each fade cut to half the result).  A dict of zlhip_edit's fields -- applied (0: nothing to change, the clip is
+        untouched), silent, the kept region first_frame and num_frames, first_loud, last_loud, the fades as cut, length, reversed, curve.
+        There is no undo; the clip's parameters are seconds and stay.  A clip that plays a re-render is refused."""
+        return self.clip_edit_batch([dict(clip=clip, first_frame=first_frame, num_frames=num_frames, flags=flags, pre_roll_frames=pre_roll_frames, hold_frames=hold_frames,
+                                          fade_in_frames=fade_in_frames, fade_out_frames=fade_out_frames, curve=curve, threshold=threshold)])[0]
+
+    def clip_edit_batch(self, requests: Sequence):
+        """Several clips in one call (zlhip_sound_edit_batch: a scan and a wait where a request trims, one render launch whatever the
+        count; all or nothing).  requests: dicts with "clip" and any of clip_edit's other arguments"""
+        rc, res = _edit_call(self._lib.zlhip_sound_edit_batch, self._e, requests)
+        self._ck(rc, "sound_edit_batch")
+        return res
+
+    def edit_timings(self):
+        """device ms of the scanning launch (0 for a call that trims nothing) and of the render and publishing launches of the last edit call made with profiling on"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        self._ck(self._lib.zlhip_debug_edit_timings(self._e, C.byref(a), C.byref(b)), "debug_edit_timings")
         return a.value, b.value
 
     def clip_warp(self, clip: int, anchors) -> dict:
@@ -1197,6 +1236,12 @@ class SamplerSynthGroup:
     def clip_loop_crossfade_batch(self, requests: Sequence):
         rc, res = _xfade_call(self._lib.zlhip_group_sound_loop_crossfade_batch, self._g, requests)
         self._ck(rc, "group_sound_loop_crossfade_batch")
+        return res
+
+    def clip_edit_batch(self, requests: Sequence):
+        """SamplerSynth.clip_edit_batch on every member; member 0's results (zlhip_group_sound_edit_batch)"""
+        rc, res = _edit_call(self._lib.zlhip_group_sound_edit_batch, self._g, requests)
+        self._ck(rc, "group_sound_edit_batch")
         return res
 
     def clip_warp(self, clip: int, anchors) -> dict:
