@@ -294,6 +294,15 @@ def build_pair_scalar_harness(force: bool = False) -> str:
                           _NO_CONTRACT + ["-Wall", "-Wno-unused-function"], force)
 
 
+def build_pair_laps_harness(force: bool = False) -> str:
+    """The pair kernels' two-slot workgroups (zl_launch.h: zl_k2_launch with pair_laps, zl_k2_pair_laps), with the host planner, the scalar
+    records and the host order."""
+    hdir = os.path.join("..", "..", "tests", "cpu_harness")
+    return _build_harness("zl_pair_laps_host", "pair_laps_host.cpp", ["zl_types.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_host.h", _ZLHIP_H,
+                                                                      os.path.join(hdir, "plan_host.cpp"), os.path.join(hdir, "pair_scalar_host.cpp")],
+                          _NO_CONTRACT + ["-Wall", "-Wno-unused-function"], force)
+
+
 def build_group_harness(force: bool = False) -> str:
     """The engine group's partition arithmetic and command routing (zl_group.h)."""
     return _build_harness("zl_group_host", "group_host.cpp", ["zl_types.h", "zl_plan.h", "zl_host.h", "zl_group.h", _ZLHIP_H], _NO_CONTRACT + ["-Wall", "-Wno-unused-function"], force)

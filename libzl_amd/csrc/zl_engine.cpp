@@ -959,16 +959,21 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
     //      window that zl_k2_pair_phase_render renders, and that launch's workgroups whose bus is on-grid throughout do not stage (default),
     //      0 = no records, every workgroup stages; read per call.  Results do not depend on it.
     const int pairScalar = [] { const char *v = std::getenv("ZL_K2_PAIR_SCALAR"); return v ? (std::atoi(v) != 0 ? 1 : 0) : 1; }();
+    // ---- two phase-neighbour slots per workgroup (zl_launch.h, zl_k2_pair_laps): ZL_K2_PAIR_LAPS 2 = a window with the scalar records
+    //      is launched with one workgroup per two slots of a bus's order, and a workgroup whose two blocks are both fast loads them voice by voice,
+    //      the second block's load directly behind the first one's (default), 1 = one block per workgroup; read per call.  Results do not depend on it.
+    const int pairLaps = [] { const char *v = std::getenv("ZL_K2_PAIR_LAPS"); return v ? std::atoi(v) : 2; }();
     // offline bounce, direct delivery: K2 itself also stores the finished bus into the caller's page-locked host buffer
     const bool direct = e->bnc.sink.on && e->bnc.sink.hostDev && A.groups == 1;
     // ---- which kernel a window of K blocks gets, its grid, and what follows from it (zl_launch.h) ----
     const ZlK2Switches &k2sw = zl_k2_switches();
-    auto k2Launch = [&](int K, bool orderTable) {
+    auto k2Launch = [&](int K, bool orderTable, bool pairTab = false) {
         ZlK2In in;
         in.mode = A.mode; in.N = nframes; in.K = K; in.B = A.B; in.groups = A.groups; in.NB = A.NB;
         in.staged = A.staged; in.trace = A.trace; in.ongrid = A.ongrid; in.fan = fan_out_dev != nullptr; in.host_out = direct;
         in.order_mode = phaseMode; in.call_blocks = nblocks; in.bounce = e->bnc.sink.on; in.order_table = orderTable; in.loop_frames = loopFrames;
         in.pair_mode = pairMode; in.cheap = cheap;
+        in.pair_laps = zl_k2_pair_laps(pairLaps, zl_pair_scalar_window(pairScalar, true, true, pairTab && K <= e->windowCap, A.VPB));
         return zl_k2_launch(in, k2sw);
     };
     {
@@ -1036,7 +1041,7 @@ static int render_batch_impl(zlhip_engine *e, int32_t nblocks, int32_t nframes, 
         // every (block, voice) of a window asks for at most one slot: the next window of this set counts from past that
         Aw.ctl_base = q.ctlBase;
         q.ctlBase += (unsigned long long)Aw.K * (unsigned long long)e->V + 1ull;
-        const ZlK2Launch L = k2Launch(Aw.K, q.order != nullptr);
+        const ZlK2Launch L = k2Launch(Aw.K, q.order != nullptr, q.pairTab != nullptr);
         Aw.order = L.order ? q.order : nullptr;
         // the pair kernels' scalar records: this window's K1c writes them and its launch reads them (bit 2 of ongrid, seen by those two alone)
         if (zl_pair_scalar_window(pairScalar, L.kernel == ZL_K2_PAIR_PHASE_RENDER, L.order, q.pairTab != nullptr && Aw.K <= e->windowCap, A.VPB)) {

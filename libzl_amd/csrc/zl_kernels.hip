@@ -185,8 +185,34 @@ __global__ void __launch_bounds__(64) zl_k1c_assemble(const ZlBatch A, int block
 
 // K1o: K2's launch order of the window's blocks, sorted by the loop phase of each z-slot's key voice (zl_order.h).  One
 // workgroup per z-slot: a counting sort over at most ZL_ORDER_MAXBKT buckets in LDS.  It runs beside a rendering K2 (the
-// planner's free wave slot, 9 KB of LDS), so it is small: 4 waves, a few us.  Without a key voice, or when the window is no
-// longer than the key voice's pass, the slot's order is the identity.
+// planner's free wave slot, 9 KB of LDS), so it is small: 4 waves of at most 96 registers, 34 us at 8192 blocks.  Then each
+// bucket's segment is put in the order of the exact phase (below).  Without a key voice, or when the window is no longer than
+// the key voice's pass, the slot's order is the identity.
+// a segment of n <= M packed words (zl_order_pack: non-negative as ints), sorted ascending in registers by a bitonic network and stored as their
+// low 16 bits; the slots past n hold INT_MAX and stay behind
+template <int M>
+static __device__ __forceinline__ void zl_k1o_sort_segment(int32_t *seg, int n)
+{
+    int w[M];
+#pragma unroll
+    for (int i = 0; i < M; ++i) w[i] = i < n ? seg[i] : INT_MAX;
+#pragma unroll
+    for (int size = 2; size <= M; size <<= 1)
+#pragma unroll
+        for (int stride = size >> 1; stride > 0; stride >>= 1)
+#pragma unroll
+            for (int i = 0; i < M; ++i) {
+                const int j = i ^ stride;
+                if (j > i) {
+                    const int lo = w[i] < w[j] ? w[i] : w[j], hi = w[i] < w[j] ? w[j] : w[i];
+                    const bool up = (i & size) == 0;
+                    w[i] = up ? lo : hi; w[j] = up ? hi : lo;
+                }
+            }
+#pragma unroll
+    for (int i = 0; i < M; ++i) if (i < n) seg[i] = w[i] & 0xffff;
+}
+
 __global__ void __launch_bounds__(256) zl_k1o_order(const ZlBatch A, int32_t *order, int norun)
 {
     __shared__ int s_hist[ZL_ORDER_MAXBKT];
@@ -233,7 +259,19 @@ __global__ void __launch_bounds__(256) zl_k1o_order(const ZlBatch A, int32_t *or
     for (int b = b0; b < b1; ++b) { const int c = s_hist[b]; s_hist[b] = run; run += c; }
     __syncthreads();
     // (the blocks of one bucket land in any order: every bijection renders the same bits)
-    for (int k = tid; k < K; k += 256) out[atomicAdd(&s_hist[zl_order_bucket(key, k)], 1)] = k;
+    const bool sorts = zl_order_sorts(key, K);
+    for (int k = tid; k < K; k += 256) out[atomicAdd(&s_hist[zl_order_bucket(key, k)], 1)] = sorts ? (int)zl_order_pack(key, k) : k;
+    if (!sorts) return;
+    __syncthreads();
+    // inside a bucket: by exact phase, ties by block number (zl_order.h) -- neighbours in the order share a workgroup (ZL_K2_PAIR_LAPS).  One
+    // thread per bucket (s_hist[b] is now the end of its segment): the segment's packed words into registers with independent loads, a
+    // sorting network of constant indices, and back as block numbers.  A longer segment is only unpacked.
+    for (int b = tid; b < key.nbkt; b += 256) {
+        const int s = b ? s_hist[b - 1] : 0, n = s_hist[b] - s;
+        if (n <= 32) zl_k1o_sort_segment<32>(out + s, n);
+        else if (n <= ZL_ORDER_SORT_MAX) zl_k1o_sort_segment<ZL_ORDER_SORT_MAX>(out + s, n);
+        else for (int i = 0; i < n; ++i) out[s + i] &= 0xffff;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1919,6 +1957,56 @@ static __device__ __forceinline__ void zl_k2_pair_fast(const uint64_t *addr, con
     }
     accL0 = acc0.x; accR0 = acc0.y; accL1 = acc1.x; accR1 = acc1.y;
 }
+// THE TWO-SLOT WALK (ZL_K2_PAIR_LAPS; zl_launch.h): a workgroup that holds two neighbouring slots of its bus's phase order renders both blocks in
+// one pass over the voices.  Neighbours in the phase order read, voice for voice, nearly the same source lines (the key voice's windows lie less
+// than a bucket apart), and each re-read of a line by another workgroup is a fresh L2-to-L1 transfer: here block B's load of voice u is issued
+// directly behind block A's, so it finds A's lines in, or on their way into, this CU's L1.  Four voices per step: 2 x 4 addresses, 2 x 4 next
+// addresses and 4 pan pairs in SGPRs, eight source loads in flight as in zl_k2_pair_fast.  Each block mixes its voices in voice order into its own
+// accumulator pairs through zl_mix_acc_ongrid_pk_s: the operations, operands and bits of zl_k2_pair_fast.  nst = steps of 4 voices.
+typedef uint64_t zl_u64x4 __attribute__((ext_vector_type(4)));
+typedef float zl_f8 __attribute__((ext_vector_type(8)));
+template <bool MONO>
+static __device__ __forceinline__ void zl_k2_pair_fast2(const uint64_t *addrA, const uint64_t *addrB, const uint64_t *pan, int nst, int f0,
+                                                        float (&accA)[4], float (&accB)[4])
+{
+    constexpr int U = 4;
+    const ZL_CONST_AS zl_u64x4 *atA = reinterpret_cast<const ZL_CONST_AS zl_u64x4 *>(reinterpret_cast<uintptr_t>(addrA));
+    const ZL_CONST_AS zl_u64x4 *atB = reinterpret_cast<const ZL_CONST_AS zl_u64x4 *>(reinterpret_cast<uintptr_t>(addrB));
+    const ZL_CONST_AS zl_f8 *pt = reinterpret_cast<const ZL_CONST_AS zl_f8 *>(reinterpret_cast<uintptr_t>(pan));
+    zl_f2 a0 = {accA[0], accA[1]}, a1 = {accA[2], accA[3]}, b0 = {accB[0], accB[1]}, b1 = {accB[2], accB[3]};
+    zl_u64x4 aA = atA[0], aB = atB[0];
+    for (int c = 0; c < nst; ++c) {
+        zl_f4a8 dA4[MONO ? 1 : U], dB4[MONO ? 1 : U];
+        zl_f2   dA2[MONO ? U : 1], dB2[MONO ? U : 1];
+        const uint32_t ob = zl_k2_ongrid_offset((uint32_t)f0 << (MONO ? 2 : 3));   // interior in both blocks (each passed the fast gate)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {                             // A's and B's load of a voice adjacent in program order: that is the point
+            if (MONO) { dA2[u] = zl_k2_ongrid_load<zl_f2a4b>(aA[u], ob); dB2[u] = zl_k2_ongrid_load<zl_f2a4b>(aB[u], ob); }
+            else      { dA4[u] = zl_k2_ongrid_load<zl_f4a8>(aA[u], ob);  dB4[u] = zl_k2_ongrid_load<zl_f4a8>(aB[u], ob); }
+        }
+        const zl_f8 p = pt[c];
+        const int cn = c + 1 < nst ? c + 1 : c;
+        aA = atA[cn]; aB = atB[cn];                               // the next step's addresses, behind this step's source loads
+        __builtin_amdgcn_sched_barrier(0);                        // (all loads in flight before the first mix, as in zl_k2_pair_fast)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const zl_f2 pu = {p[2 * u], p[2 * u + 1]};
+            if (MONO) {
+                zl_mix_acc_ongrid_pk_s<1>(a0, dA2[u], pu);
+                zl_mix_acc_ongrid_pk_s<2>(a1, dA2[u], pu);
+                zl_mix_acc_ongrid_pk_s<1>(b0, dB2[u], pu);
+                zl_mix_acc_ongrid_pk_s<2>(b1, dB2[u], pu);
+            } else {
+                zl_mix_acc_ongrid_pk_s<0>(a0, __builtin_shufflevector(dA4[u], dA4[u], 0, 1), pu);
+                zl_mix_acc_ongrid_pk_s<0>(a1, __builtin_shufflevector(dA4[u], dA4[u], 2, 3), pu);
+                zl_mix_acc_ongrid_pk_s<0>(b0, __builtin_shufflevector(dB4[u], dB4[u], 0, 1), pu);
+                zl_mix_acc_ongrid_pk_s<0>(b1, __builtin_shufflevector(dB4[u], dB4[u], 2, 3), pu);
+            }
+        }
+    }
+    accA[0] = a0.x; accA[1] = a0.y; accA[2] = a1.x; accA[3] = a1.y;
+    accB[0] = b0.x; accB[1] = b0.y; accB[2] = b1.x; accB[3] = b1.y;
+}
 // May the workgroup of (block k, voices [v0, v1)) take it?  Every chunk bit of its voices set, and one layout for the whole bus (a bus of
 // mono and stereo chunks stages: the walk is compiled once per layout).  1 = stereo, 2 = mono, 0 = no.  Scalar loads of 16-bit entries, two to a word.
 static __device__ __forceinline__ int zl_k2_pair_fast_kind(const uint64_t *tab, int K, int V, int k, int v0, int v1)
@@ -1957,15 +2045,89 @@ static __device__ __forceinline__ void zl_k2_pair_body(const ZlBatch &A)
     const unsigned by = blockIdx.y, bz = blockIdx.z;
     const int ky = (int)gridDim.y, xq = ky >> 3, xr = ky & 7, xx = (int)(by & 7u);
     const int ys = xx * xq + (xx < xr ? xx : xr) + (int)(by >> 3);
-    const int k = ORD ? A.order[(size_t)bz * A.K + ys] : ys;
-    __builtin_assume(k >= 0 && k < 65536);                         // (a launch slot's block: what the compiler knows of ys it may know of the table's entry)
+    // slots of the bus's order this workgroup holds: one, or -- a launch of ceil(K / 2) workgroups per bus (ZL_K2_PAIR_LAPS, zl_k2_launch; only
+    // with the scalar records) -- slots 2 ys and 2 ys + 1, as many as exist.  The XCD mapping above is of workgroup numbers: an XCD still
+    // gets a contiguous range of the order.
+    const int laps = (ORD && (A.ongrid & ZL_ONGRID_SCALAR) && ky < A.K) ? 2 : 1;
+    const int s0 = laps * ys, nb = !ORD || s0 + laps <= A.K ? laps : A.K - s0;
     const int bus = (int)bz;
     const int v0 = bus * A.VPB, vlim = (bus + 1) * A.VPB;
     const int v1 = (v0 + A.G < vlim) ? v0 + A.G : vlim;
-    const bool wantPeak = __builtin_amdgcn_readfirstlane((int)(A.k0 + k == A.Ktot - 1)) != 0;
     // the tail K1o leaves behind the table: from block run_end on, no voice of this bus has an inline run -- staging leaves the run lists alone
     const int32_t *dead_tail = ORD ? A.order + zl_order_tail_dead((int)gridDim.z, A.K, 0) : nullptr;
-    const bool norun = ORD && __builtin_amdgcn_readfirstlane((int)(k >= A.order[zl_order_tail_run_end((int)gridDim.z, A.K, (int)bz)])) != 0;
+    const int run_end = ORD ? __builtin_amdgcn_readfirstlane(A.order[zl_order_tail_run_end((int)gridDim.z, A.K, (int)bz)]) : 0;
+
+    // ---- the finished bus of block k.  Quirk Q2: frame f lands in out[f + 1], out[0] stays 0 and the sample of frame N - 1 is dropped
+    auto finish = [&](int k, int f0, float accL0, float accR0, float accL1, float accR1) {
+        const unsigned tx = (unsigned)f0 >> 1;                  // (the lane's number from the caller's own copy: see the block loop)
+        const long long KN = (long long)A.Ktot * N;
+        float *outL = A.bus + (long long)bus * (A.bus_stride ? A.bus_stride : 2 * KN) + (long long)(A.k0 + k) * N;
+        float *outR = outL + (A.ch_stride ? A.ch_stride : KN);
+        const bool written1 = f0 + 2 < N;
+        outL[f0 + 1] = accL0; outR[f0 + 1] = accR0;
+        if (written1) { outL[f0 + 2] = accL1; outR[f0 + 2] = accR1; }
+        if (f0 == 0)  { outL[0] = 0.0f; outR[0] = 0.0f; }
+        // ---- fused AudioLevels block scan (AudioLevels.cpp:361-383) in its defined order: tiles of 64 frames from out[1], a balanced
+        //      pairwise tree inside a tile, tiles added in order.  This lane holds elements 2 j', 2 j' + 1 (j' = lane mod 32) of tile
+        //      2 * wave + (lane >= 32): level 1 of the tree is the in-lane add, the rest zl_wave_levels4_pair.  The dropped frame scans as 0.
+        if (A.levels) {
+            const float bL = written1 ? accL1 : 0.0f, bR = written1 ? accR1 : 0.0f;
+            const int pa = zl_sample_to_peak_int(accL0), pb = zl_sample_to_peak_int(bL), pc = zl_sample_to_peak_int(accR0), pd = zl_sample_to_peak_int(bR);
+            int pkL[2], pkR[2]; float sqL[2], sqR[2];
+            zl_wave_levels4_pair(pb > pa ? pb : pa, pd > pc ? pd : pc, accL0 * accL0 + bL * bL, accR0 * accR0 + bR * bR, pkL, pkR, sqL, sqR);
+            const int w = (int)(tx >> 6) * 2;
+            if ((tx & 63) == 0) {
+                s_pk[0][w] = pkL[0]; s_pk[1][w] = pkR[0]; s_sq[0][w] = sqL[0]; s_sq[1][w] = sqR[0];
+                s_pk[0][w + 1] = pkL[1]; s_pk[1][w + 1] = pkR[1]; s_sq[0][w + 1] = sqL[1]; s_sq[1][w + 1] = sqR[1];
+            }
+            __syncthreads();
+            if (tx == 0) {
+                ZlBlockLevels lv; lv.peak_l = 0; lv.peak_r = 0; lv.sumsq_l = 0.0f; lv.sumsq_r = 0.0f;
+                for (int t = 0; t < 4; ++t) {
+                    lv.peak_l = s_pk[0][t] > lv.peak_l ? s_pk[0][t] : lv.peak_l;
+                    lv.peak_r = s_pk[1][t] > lv.peak_r ? s_pk[1][t] : lv.peak_r;
+                    lv.sumsq_l += s_sq[0][t]; lv.sumsq_r += s_sq[1][t];
+                }
+                A.levels[(size_t)k * A.B + bus] = lv;
+            }
+        }
+    };
+
+    // ---- the two-slot walk (zl_k2_pair_fast2): both blocks pass the fast gate below -- behind run_end, neither the call's last block, every
+    //      chunk of the bus fast -- with one layout.  Every other workgroup renders its blocks one after the other through the text below.
+    if (ORD && nb == 2) {
+        const int kA = __builtin_amdgcn_readfirstlane(A.order[(size_t)bz * A.K + s0]), kB = __builtin_amdgcn_readfirstlane(A.order[(size_t)bz * A.K + s0 + 1]);
+        __builtin_assume(kA >= 0 && kA < 65536 && kB >= 0 && kB < 65536);
+        if (zl_pair_laps_blocks(kA, kB, run_end, A.Ktot - 1 - A.k0)) {
+            const int kindA = zl_k2_pair_fast_kind(zl_batch_pair_tab(A), A.K, V, kA, v0, v1);
+            const int kindB = kindA != 0 ? zl_k2_pair_fast_kind(zl_batch_pair_tab(A), A.K, V, kB, v0, v1) : 0;
+            if (zl_pair_laps_kind(kindA, kindB) != 0) {
+                const uint64_t *addrA = zl_batch_pair_tab(A) + (size_t)kA * (size_t)V + (size_t)v0;
+                const uint64_t *addrB = zl_batch_pair_tab(A) + (size_t)kB * (size_t)V + (size_t)v0;
+                const uint64_t *pan = zl_batch_pair_tab(A) + zl_pair_tab_pan(A.K, V) + (size_t)v0;
+                float accA[4] = {0.0f, 0.0f, 0.0f, 0.0f}, accB[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (kindA == 2) zl_k2_pair_fast2<true>(addrA, addrB, pan, (v1 - v0) >> 2, f0, accA, accB);
+                else            zl_k2_pair_fast2<false>(addrA, addrB, pan, (v1 - v0) >> 2, f0, accA, accB);
+                finish(kA, f0, accA[0], accA[1], accA[2], accA[3]);
+                __syncthreads();                                  // (s_pk, s_sq are reused)
+                finish(kB, f0, accB[0], accB[1], accB[2], accB[3]);
+                return;
+            }
+        }
+    }
+
+#pragma nounroll
+    for (int ib = 0; ib < nb; ++ib) {
+    // (the lane's number as the loop body's own value: what is derived from it is formed per block, not held across the loop -- 103 registers
+    // instead of 108.  tests/test_kernel_resources_pair.py allows 104 and fails if a compiler brings the count back up: look here first)
+    unsigned tx = threadIdx.x;
+    asm volatile("" : "+v"(tx));
+    const int f0i = 2 * (int)tx;
+    if (ib != 0) __syncthreads();                                  // (the second block restages: the first one's report path and level scan are done with LDS)
+    const int k = ORD ? A.order[(size_t)bz * A.K + s0 + ib] : ys;
+    __builtin_assume(k >= 0 && k < 65536);                         // (a launch slot's block: what the compiler knows of ys it may know of the table's entry)
+    const bool wantPeak = __builtin_amdgcn_readfirstlane((int)(A.k0 + k == A.Ktot - 1)) != 0;
+    const bool norun = ORD && __builtin_amdgcn_readfirstlane((int)(k >= run_end)) != 0;
 
     float accL0 = 0.0f, accR0 = 0.0f, accL1 = 0.0f, accR1 = 0.0f;
     // the fast workgroup (zl_k2_pair_fast): the window has the scalar records, every record of the block is an explicit one (norun), it is not
@@ -1976,13 +2138,13 @@ static __device__ __forceinline__ void zl_k2_pair_body(const ZlBatch &A)
     if (fastKind != 0) {
         const uint64_t *addr = zl_batch_pair_tab(A) + (size_t)__builtin_amdgcn_readfirstlane(k) * (size_t)V + (size_t)v0;
         const uint64_t *pan = zl_batch_pair_tab(A) + zl_pair_tab_pan(A.K, V) + (size_t)v0;
-        if (fastKind == 2) zl_k2_pair_fast<true>(addr, pan, (v1 - v0) >> 3, f0, accL0, accR0, accL1, accR1);
-        else               zl_k2_pair_fast<false>(addr, pan, (v1 - v0) >> 3, f0, accL0, accR0, accL1, accR1);
+        if (fastKind == 2) zl_k2_pair_fast<true>(addr, pan, (v1 - v0) >> 3, f0i, accL0, accR0, accL1, accR1);
+        else               zl_k2_pair_fast<false>(addr, pan, (v1 - v0) >> 3, f0i, accL0, accR0, accL1, accR1);
     } else
     for (int vb = v0; vb < v1; vb += CH) {
         const int nv = (v1 - vb < CH) ? v1 - vb : CH;
         if (vb != v0) __syncthreads();                            // (nothing to wait for before the first pass)
-        for (int i = threadIdx.x; i < CH; i += blockDim.x) {
+        for (int i = tx; i < CH; i += blockDim.x) {
             ZlVoiceConst vc;
             ZlBlockPlan pl;
             if (norun) zl_k2_stage_load<false>(A, k, vb, i, nv, vc, pl, dead_tail);
@@ -2003,24 +2165,24 @@ static __device__ __forceinline__ void zl_k2_pair_body(const ZlBatch &A)
 #pragma unroll
                 for (int h = 0; h < U; h += UP) {
                     if (wantPeak) {
-                        if (cc & 16) zl_k2_chunk_ongrid_pair<true, UP, true>(A, s_vc, s_unit, c0 + h, vb, f0, accL0, accR0, accL1, accR1);
-                        else         zl_k2_chunk_ongrid_pair<false, UP, true>(A, s_vc, s_unit, c0 + h, vb, f0, accL0, accR0, accL1, accR1);
+                        if (cc & 16) zl_k2_chunk_ongrid_pair<true, UP, true>(A, s_vc, s_unit, c0 + h, vb, f0i, accL0, accR0, accL1, accR1);
+                        else         zl_k2_chunk_ongrid_pair<false, UP, true>(A, s_vc, s_unit, c0 + h, vb, f0i, accL0, accR0, accL1, accR1);
                     }
-                    else if (cc & 16) zl_k2_chunk_ongrid_pair<true, UP, false>(A, s_vc, s_unit, c0 + h, vb, f0, accL0, accR0, accL1, accR1);
-                    else              zl_k2_chunk_ongrid_pair<false, UP, false>(A, s_vc, s_unit, c0 + h, vb, f0, accL0, accR0, accL1, accR1);
+                    else if (cc & 16) zl_k2_chunk_ongrid_pair<true, UP, false>(A, s_vc, s_unit, c0 + h, vb, f0i, accL0, accR0, accL1, accR1);
+                    else              zl_k2_chunk_ongrid_pair<false, UP, false>(A, s_vc, s_unit, c0 + h, vb, f0i, accL0, accR0, accL1, accR1);
                 }
             } else if ((cc & 256) && !wantPeak) {
                 // every voice on-grid, one or more of them with a loop restart inside the block (not in the call's last block)
 #pragma unroll
                 for (int h = 0; h < U; h += UW) {
-                    if (cc & 16) zl_k2_chunk_ongrid_pair_wrap<true, UW>(A, s_plan, s_vc, s_unit, c0 + h, f0, accL0, accR0, accL1, accR1);
-                    else         zl_k2_chunk_ongrid_pair_wrap<false, UW>(A, s_plan, s_vc, s_unit, c0 + h, f0, accL0, accR0, accL1, accR1);
+                    if (cc & 16) zl_k2_chunk_ongrid_pair_wrap<true, UW>(A, s_plan, s_vc, s_unit, c0 + h, f0i, accL0, accR0, accL1, accR1);
+                    else         zl_k2_chunk_ongrid_pair_wrap<false, UW>(A, s_plan, s_vc, s_unit, c0 + h, f0i, accL0, accR0, accL1, accR1);
                 }
             } else {
                 // the other classes: zl_k2_body's dispatch, one frame of the lane after the other
 #pragma nounroll
                 for (int h = 0; h < 2; ++h) {
-                    const int fc = f0 + h;
+                    const int fc = f0i + h;
                     const double fd = (double)fc;
                     float accL = h ? accL1 : accL0, accR = h ? accR1 : accR0;
                     if ((cc & 124) == 100)      zl_k2_chunk_simple<MODE, false, true, true, U>(A, s_plan, s_vc, s_unit, c0, vb, fc, fd, wantPeak, accL, accR);
@@ -2045,45 +2207,12 @@ static __device__ __forceinline__ void zl_k2_pair_body(const ZlBatch &A)
         }
     }
 
-    // ---- the finished bus.  Quirk Q2: frame f lands in out[f + 1], out[0] stays 0 and the sample of frame N - 1 is dropped
-    {
-        const long long KN = (long long)A.Ktot * N;
-        float *outL = A.bus + (long long)bus * (A.bus_stride ? A.bus_stride : 2 * KN) + (long long)(A.k0 + k) * N;
-        float *outR = outL + (A.ch_stride ? A.ch_stride : KN);
-        const bool written1 = f0 + 2 < N;
-        outL[f0 + 1] = accL0; outR[f0 + 1] = accR0;
-        if (written1) { outL[f0 + 2] = accL1; outR[f0 + 2] = accR1; }
-        if (f0 == 0)  { outL[0] = 0.0f; outR[0] = 0.0f; }
-        // ---- fused AudioLevels block scan (AudioLevels.cpp:361-383) in its defined order: tiles of 64 frames from out[1], a balanced
-        //      pairwise tree inside a tile, tiles added in order.  This lane holds elements 2 j', 2 j' + 1 (j' = lane mod 32) of tile
-        //      2 * wave + (lane >= 32): level 1 of the tree is the in-lane add, the rest zl_wave_levels4_pair.  The dropped frame scans as 0.
-        if (A.levels) {
-            const float bL = written1 ? accL1 : 0.0f, bR = written1 ? accR1 : 0.0f;
-            const int pa = zl_sample_to_peak_int(accL0), pb = zl_sample_to_peak_int(bL), pc = zl_sample_to_peak_int(accR0), pd = zl_sample_to_peak_int(bR);
-            int pkL[2], pkR[2]; float sqL[2], sqR[2];
-            zl_wave_levels4_pair(pb > pa ? pb : pa, pd > pc ? pd : pc, accL0 * accL0 + bL * bL, accR0 * accR0 + bR * bR, pkL, pkR, sqL, sqR);
-            const int w = (int)(threadIdx.x >> 6) * 2;
-            if ((threadIdx.x & 63) == 0) {
-                s_pk[0][w] = pkL[0]; s_pk[1][w] = pkR[0]; s_sq[0][w] = sqL[0]; s_sq[1][w] = sqR[0];
-                s_pk[0][w + 1] = pkL[1]; s_pk[1][w + 1] = pkR[1]; s_sq[0][w + 1] = sqL[1]; s_sq[1][w + 1] = sqR[1];
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                ZlBlockLevels lv; lv.peak_l = 0; lv.peak_r = 0; lv.sumsq_l = 0.0f; lv.sumsq_r = 0.0f;
-                for (int t = 0; t < 4; ++t) {
-                    lv.peak_l = s_pk[0][t] > lv.peak_l ? s_pk[0][t] : lv.peak_l;
-                    lv.peak_r = s_pk[1][t] > lv.peak_r ? s_pk[1][t] : lv.peak_r;
-                    lv.sumsq_l += s_sq[0][t]; lv.sumsq_r += s_sq[1][t];
-                }
-                A.levels[(size_t)k * A.B + bus] = lv;
-            }
-        }
-    }
+    finish(k, f0i, accL0, accR0, accL1, accR1);
 
     // ---- the call's reports, by the workgroups that hold the call's last block (as in zl_k2_body)
     if (A.fused_reports && A.k0 + k == A.Ktot - 1) {
         __syncthreads();
-        for (int v = v0 + (int)threadIdx.x; v < v1; v += (int)blockDim.x) {
+        for (int v = v0 + (int)tx; v < v1; v += (int)blockDim.x) {
             const uint4 *src = reinterpret_cast<const uint4 *>(&A.reports[v]);
             uint4 a = src[0];
             const uint4 b = src[1];
@@ -2092,11 +2221,12 @@ static __device__ __forceinline__ void zl_k2_pair_body(const ZlBatch &A)
             A.rep_gain[v] = gn;
             if (A.rep_host) { uint4 *dst = reinterpret_cast<uint4 *>(&A.rep_host[v]); dst[0] = a; dst[1] = b; A.rep_host_gain[v] = gn; }
         }
-        if (bus == 0 && threadIdx.x == 0 && A.rep_host_stats) {
+        if (bus == 0 && tx == 0 && A.rep_host_stats) {
             const unsigned long long sb = A.stats->source_bytes, sl = A.stats->slow_blocks, af = A.stats->active_frames;
             A.rep_host_stats->source_bytes = sb; A.rep_host_stats->slow_blocks = sl; A.rep_host_stats->active_frames = af;
             A.stats->source_bytes = 0; A.stats->slow_blocks = 0; A.stats->active_frames = 0;   // cleared for the call that reuses this slot
         }
+    }
     }
 }
 

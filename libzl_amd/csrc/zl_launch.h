@@ -96,6 +96,9 @@ struct ZlK2In {
     // two frames per lane (zl_pair.h): ZL_K2_PAIR, and the call's "every playing voice is cheap to plan"
     int pair_mode;
     bool cheap;
+    // phase-neighbour slots per workgroup of zl_k2_pair_phase_render (zl_k2_pair_laps): ZL_K2_PAIR_LAPS where the window can have the scalar
+    // records (zl_pair_scalar_window with the launch's own two answers taken as yes), else 1
+    int pair_laps = 1;
 };
 
 enum ZlK2Kernel { ZL_K2_RENDER, ZL_K2_PHASE_RENDER, ZL_K2_PAIR_RENDER, ZL_K2_PAIR_PHASE_RENDER };
@@ -107,12 +110,19 @@ struct ZlK2Launch {
     int tail_from, tail_split, tail_nb;   // ZlBatch's fields of the same names (tail_from 0: no split tail)
     bool order;                   // the launch reads A.order: K1o runs for the window, the table holds gz * K entries
     bool scans_levels;            // K2 writes the window's ZlBlockLevels itself: no K3
+    int laps;                     // slots of a bus's order per workgroup (1; 2 in a zl_k2_pair_phase_render launch that asked for it: gy = ceil(K / laps))
 };
+
+// slots per workgroup of a pair launch: sw = ZL_K2_PAIR_LAPS (1 = one block per workgroup, 2 = default; the kernel is built for 1 and 2),
+// scalar = the window has the scalar records once its launch is zl_k2_pair_phase_render (zl_pair_scalar_window) -- the two-slot walk
+// exists in the scalar-record text only
+inline int zl_k2_pair_laps(int sw, bool scalar) { return scalar && sw >= 2 ? 2 : 1; }
 
 inline ZlK2Launch zl_k2_launch(const ZlK2In &in, const ZlK2Switches &sw)
 {
     const int N = in.N, K = in.K, NB = in.NB;
     ZlK2Launch L{};
+    L.laps = 1;
     // blocks of 64 / 128 frames: 4 / 2 blocks per workgroup (batches only; a single block keeps its small workgroup; other lengths
     // below 256 -- 16, 32, 48, 100 ... -- are real-time periods: one block per workgroup of whole waves)
     L.bpw = ((N == 64 || N == 128) && K > 1) ? 256 / N : 1;
@@ -132,6 +142,8 @@ inline ZlK2Launch zl_k2_launch(const ZlK2In &in, const ZlK2Switches &sw)
     if (pair) {
         L.kernel = L.order ? ZL_K2_PAIR_PHASE_RENDER : ZL_K2_PAIR_RENDER;
         L.threads = 128;
+        // two phase-neighbour slots per workgroup: workgroup w of a bus holds slots 2 w and 2 w + 1 of its order (the last one alone when K is odd)
+        if (L.kernel == ZL_K2_PAIR_PHASE_RENDER && in.pair_laps > 1) { L.laps = 2; L.gy = (unsigned)((K + 1) / 2); }
         L.dyn_lds = (unsigned)(sw.pair_pad >= 0 ? sw.pair_pad : std::max(0, sw.pair_lds - sw.pair_static_lds));
         return L;
     }

@@ -40,12 +40,31 @@ ZL_HD inline bool zl_order_setup(const ZlRunList &rl, int K, int N, ZlOrderKey &
     return true;
 }
 
-// bucket of block k: its first frame's offset into the key voice's pass, in buckets (0 .. nbkt - 1)
-ZL_HD inline int zl_order_bucket(const ZlOrderKey &key, int k)
+// exact phase of block k: its first frame's offset into the key voice's pass, in frames (0 .. M - 1)
+ZL_HD inline long long zl_order_phase(const ZlOrderKey &key, int k)
 {
     long long p = ((long long)k * key.N - key.t0) % key.M;
     if (p < 0) p += key.M;
-    return (int)(p / key.width);
+    return p;
+}
+
+// bucket of block k: that offset in buckets (0 .. nbkt - 1)
+ZL_HD inline int zl_order_bucket(const ZlOrderKey &key, int k)
+{
+    return (int)(zl_order_phase(key, k) / key.width);
+}
+
+// ---- the order INSIDE a bucket: by exact phase, ties by block number.  Two neighbouring slots share a workgroup (ZL_K2_PAIR_LAPS, zl_launch.h),
+// and what they share of the source is largest between neighbours by exact phase.  A segment of at most ZL_ORDER_SORT_MAX entries is sorted; a
+// longer one stays as placed (nothing depends on the order but speed).  K1o sorts the packed word (phase - bucket * width) << 16 | k, which needs
+// the bucket's width within 15 bits and k within 16: wider buckets (width = per * N above 32768: blocks of more than 32768 frames, or a pass of
+// more than 2048 such blocks that 32768 frames do not hold) stay as placed too, on the device and here.
+#define ZL_ORDER_SORT_MAX 64
+ZL_HD inline bool zl_order_sorts(const ZlOrderKey &key, int K) { return key.width <= 32768 && K <= 65536; }
+ZL_HD inline unsigned zl_order_pack(const ZlOrderKey &key, int k)
+{
+    const long long p = zl_order_phase(key, k);
+    return ((unsigned)(p - (p / key.width) * key.width) << 16) | (unsigned)k;
 }
 
 // ---- the slot's summary of its voices' inline runs, kept behind the order table.  K1o reads every run list of its slot anyway; the
@@ -89,8 +108,8 @@ inline bool zl_order_window(int mode, bool shape, bool bounce, int nframes, int 
     return mode == 1 && shape && !bounce && nframes >= 256 && (double)K * nframes > loopFrames;
 }
 
-// host reference of K1o for one z-slot: a stable counting sort of blocks [0, K) by bucket (K1o places the blocks of one
-// bucket in any order: every bijection renders the same bits).  key == nullptr: the identity.  hist holds nbkt ints.
+// host reference of K1o for one z-slot: a stable counting sort of blocks [0, K) by bucket, then each bucket's segment by exact phase as K1o
+// does (above; every bijection renders the same bits).  key == nullptr: the identity.  hist holds nbkt ints.
 inline void zl_order_sort_host(const ZlOrderKey *key, int K, int *hist, int *order)
 {
     if (!key) { for (int k = 0; k < K; ++k) order[k] = k; return; }
@@ -99,4 +118,17 @@ inline void zl_order_sort_host(const ZlOrderKey *key, int K, int *hist, int *ord
     int run = 0;
     for (int b = 0; b < key->nbkt; ++b) { const int c = hist[b]; hist[b] = run; run += c; }
     for (int k = 0; k < K; ++k) order[hist[zl_order_bucket(*key, k)]++] = k;
+    // inside a bucket: by exact phase, ties by block number (hist[b] is now the end of bucket b's segment); an insertion sort of the packed words
+    if (!zl_order_sorts(*key, K)) return;
+    for (int b = 0, s = 0; b < key->nbkt; s = hist[b], ++b) {
+        const int e = hist[b];
+        if (e - s < 2 || e - s > ZL_ORDER_SORT_MAX) continue;
+        for (int i = s + 1; i < e; ++i) {
+            const int k = order[i];
+            const unsigned w = zl_order_pack(*key, k);
+            int j = i;
+            for (; j > s && zl_order_pack(*key, order[j - 1]) > w; --j) order[j] = order[j - 1];
+            order[j] = k;
+        }
+    }
 }

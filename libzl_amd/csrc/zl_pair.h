@@ -32,3 +32,15 @@ inline bool zl_pair_scalar_window(int sw, bool pair, bool phase_order, bool have
 {
     return sw != 0 && pair && phase_order && have_tab && VPB > 0 && (VPB % 8) == 0;
 }
+
+// ---- two slots per workgroup (ZL_K2_PAIR_LAPS; zl_launch.h, zl_k2_pair_body): may the workgroup that holds blocks kA and kB of a bus render them in
+// one walk (zl_k2_pair_fast2)?  One text for the kernel and for the CPU tier's count (tests/cpu_harness/pair_laps_host.cpp).
+#if defined(__HIPCC__)
+#define ZL_PAIR_HD __host__ __device__
+#else
+#define ZL_PAIR_HD
+#endif
+// the blocks: both at or behind run_end (every record an explicit one), neither the call's last block (`last`, in the window's numbering)
+ZL_PAIR_HD inline bool zl_pair_laps_blocks(int kA, int kB, int run_end, int last) { return kA >= run_end && kB >= run_end && kA != last && kB != last; }
+// the kinds zl_k2_pair_fast_kind gives the two (0 = not fast, 1 = stereo, 2 = mono): both fast and of one layout -> the walk's layout, else 0
+ZL_PAIR_HD inline int zl_pair_laps_kind(int kindA, int kindB) { return kindA != 0 && kindA == kindB ? kindA : 0; }
