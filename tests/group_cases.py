@@ -195,6 +195,8 @@ MEMBER_CASES = [SpanCase(f"n{n}-{_MODE_NAMES[mode]}", n, 128, 12, mode, 40 + n, 
 # falls one short (off = 1); one frame into a second tile; a partial second tile; seven tiles with a tail
 BLOCK_SIZE_CASES = [SpanCase(f"N{N}-{_MODE_NAMES[mode]}", 3, N, 5, mode, 60 + N % 17, uneven=True)
                     for N in (33, 64, 65, 100, 441) for mode in (MODE_FAITHFUL, MODE_FIX_DELAY)]
+# ... and the four-tap interpolation with the fixed delay (mode 6): the sum kernel's front-frame handling goes by MODE_FIX_DELAY alone
+BLOCK_SIZE_CASES.append(SpanCase("N100-hermite-fixdelay", 3, 100, 5, MODE_HERMITE | MODE_FIX_DELAY, 66, uneven=True))
 
 ROOT_CASES = [SpanCase("n3-root1", 3, 128, 12, MODE_FAITHFUL, 71, B=3, root=1, voice_calls=True),
               SpanCase("n3-root2", 3, 100, 12, MODE_FIX_DELAY, 72, B=3, root=2, voice_calls=True),

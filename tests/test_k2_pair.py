@@ -16,48 +16,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from level_checks import INT_MAX, check_levels, peak_int      # (tests/test_k2_pair_*.py take check_levels from here)
 from scenario import Scene, compare_runs, play_cmd, rand_source, run_backend, run_oracle, stop_cmd
 from test_k2_ongrid import ADVERSARIAL, loop_scene, same_bits_nan_aware
 
 pytestmark = pytest.mark.gpu
-
-INT_MAX = 2 ** 31 - 1
 
 
 @pytest.fixture(scope="module")
 def Engine(built):
     from libzl_amd import SamplerSynth
     return SamplerSynth
-
-
-def peak_int(rows):
-    """(int)fabsf(131072.f * x) with the oracle's definition of the open cases: NaN -> 0, 2^31 and above -> INT_MAX"""
-    with np.errstate(over="ignore", invalid="ignore"):
-        v = np.abs(np.float32(131072.0) * rows.astype(np.float32))
-    out = np.zeros(v.shape, dtype=np.int64)
-    big, ok = v >= np.float32(2.0 ** 31), np.isfinite(v) & (v < np.float32(2.0 ** 31))
-    out[big] = INT_MAX
-    out[ok] = v[ok].astype(np.int64)
-    return out
-
-
-def check_levels(syn, bus, nframes):
-    """the fused level scan of the LAST call (what block_peaks / levels_tick see) against the bus it belongs to"""
-    from oracle import zl_oracle as zo
-    lib = zo.load()
-    K, N = syn._last
-    assert N == nframes
-    B = bus.shape[0]
-    tail = bus[:, :, bus.shape[2] - K * N:]
-    exp = np.stack([peak_int(tail[:, c].reshape(B, K, N)).max(axis=2) for c in (0, 1)], axis=-1)      # [B][K][2]
-    assert np.array_equal(syn.block_peaks(), exp.transpose(1, 0, 2))
-    for k in sorted({0, K // 3, K - 1}):
-        lv = syn.levels_tick(block_index=k)
-        for b in range(B):
-            for c, got in ((0, lv[b].rms_a), (1, lv[b].rms_b)):
-                row = np.ascontiguousarray(tail[b, c, k * N:(k + 1) * N])
-                want = lib.zlo_block_rms(row.ctypes.data, N, 1)
-                assert got == want or (np.isnan(got) and np.isnan(want)), (k, b, c, got, want)
 
 
 def _all(monkeypatch, sc, factory, V, *, orders=("0", "2"), nan_ok=False, levels=True, **kw):

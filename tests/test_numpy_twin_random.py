@@ -77,7 +77,9 @@ def run_numpy(scene):
 _SHAPES = [{}, dict(nframes=64, nblocks=20), dict(nframes=256, nblocks=8), dict(fs=44100.0), dict(voices_per_bus=2), dict(num_buses=3, nclips=8, nblocks=16)]
 
 
-@pytest.mark.parametrize("seed,mode,kw", [(7001 + i, [0, 0, 4, 3, 2, 0, 4, 1][i % 8], _SHAPES[i % len(_SHAPES)]) for i in range(32)])
+# (Hermite with either or both fixes: every one of the three modes on every shape)
+@pytest.mark.parametrize("seed,mode,kw", [(7001 + i, [0, 0, 4, 3, 2, 0, 4, 1][i % 8], _SHAPES[i % len(_SHAPES)]) for i in range(32)]
+                         + [(7101 + i, [5, 6, 7][i % 3], _SHAPES[i // 3]) for i in range(3 * len(_SHAPES))])
 def test_c_oracle_equals_the_numpy_restatement_on_random_scenes(seed, mode, kw):
     args = dict(num_buses=2, voices_per_bus=3, nframes=128, nblocks=12, nclips=5, min_len=900, max_len=2600, mode=mode)
     args.update(kw)
