@@ -272,6 +272,28 @@ int  libzl_hotpath_clip_trim_silence(ClipAudioSource *c, float threshold_db, flo
  * applied_out[i] (may be NULL) is 1 where clip i was trimmed.  Duplicate clips are ZLHIP_ERR_INVALID.  Returns the number of clips
  * trimmed, or a negative status (nothing has changed then). */
 int  libzl_hotpath_clips_trim(ClipAudioSource **clips, int count, float threshold_db, float pre_roll_ms, float hold_ms, int *applied_out);
+/* extension (build-defined: the reference measures no peak): the sample peak and the true peak of the data the clip plays now between
+ * its start and its start + length, measured on the device (zlhip_sound_peak with ZLHIP_LIMIT_TRUE_PEAK), in dB
+ * (20 log10; -inf for silence).  Returns 1, or a negative zlhip status (nothing is written then; ZLHIP_ERR_INVALID at a rate the true
+ * peak cannot be asked at). */
+int  libzl_hotpath_clip_true_peak(ClipAudioSource *c, float *sample_peak_db, float *true_peak_db);
+/* extension: brings the clip's peaks under ceiling_db (<= 0 dBFS) with a look-ahead limiter baked into its data at its current level,
+ * on the device and under the clip's own id (zlhip_sound_limit with gain 1).  lookahead_ms: the ramp in front of
+ * and behind a peak (0: 5 ms; at most 512 frames); hold_ms: how long the reduction stays behind a peak (at most 512 frames); true_peak:
+ * detect on the inter-sample peaks as well.  A frame out of reach of every peak keeps its bits.  *reduction_db (may be NULL): the largest
+ * reduction, >= 0.  The limit cannot be taken back: reload the clip.  A clip that plays a re-render is refused with ZLHIP_ERR_STATE:
+ * limit first, then tune.  Returns 1, or 0 for a clip already under the ceiling (nothing has changed), or a negative status (nothing
+ * has changed). */
+int  libzl_hotpath_clip_limit(ClipAudioSource *c, float ceiling_db, float lookahead_ms, float hold_ms, int true_peak, float *reduction_db);
+/* Level a bank under a ceiling: ONE zlhip_sound_loudness_batch and ONE zlhip_sound_limit_batch.  Every clip is driven by target_lufs -
+ * lufs -- NOT held by the ceiling, as libzl_hotpath_clips_level is -- the drive is baked as the limiter's gain and the peaks it lifts
+ * over ceiling_db are limited.  The limiter takes some loudness back, so a clip lands at or under the target; the caller may measure
+ * again (libzl_hotpath_clip_loudness) and call again.  The clip's gain (ClipAudioSource_setGain) is not touched: the levelled data is the
+ * clip's original from now on.  A clip that is NULL, not in the engine, playing a re-render or without loudness stays as it is;
+ * drive_db_out[i], reduction_db_out[i] (may be NULL): the drive baked into clip i and its largest reduction (0 where it was left).
+ * Duplicate clips are ZLHIP_ERR_INVALID.  Returns the number of clips changed, or a negative status (nothing has changed then). */
+int  libzl_hotpath_clips_level_limited(ClipAudioSource **clips, int count, float target_lufs, float ceiling_db, float lookahead_ms, float hold_ms, int true_peak,
+                                       float *drive_db_out, float *reduction_db_out);
 /* Crops the clip's data to its selected region -- exactly the frames a voice derives from start .. start + length -- and fades its ends:
  * fade_in_ms, fade_out_ms (each cut to half the region), curve ZLHIP_EDIT_LINEAR, _SQRT or _SMOOTH.  Afterwards the start is 0 and the
  * length and the duration are the data's.  *new_length_frames may be NULL.  No undo; a clip that plays a re-render is ZLHIP_ERR_STATE.

@@ -46,7 +46,9 @@ extern "C" {
  *    key, detected on the device), zlhip_key_resolve, zlhip_key_design, zlhip_debug_live_resources, zlhip_sound_loop_crossfade / _batch (a loop crossfade
  *    baked into a clip's data on the device), zlhip_xfade_resolve, zlhip_xfade_design, zlhip_sound_edit / _batch (a clip's data cropped,
  *    trimmed of silence, reversed and faded on the device), zlhip_edit_resolve, zlhip_edit_design, zlhip_debug_edit_timings,
- *    zlhip_group_sound_edit_batch. */
+ *    zlhip_group_sound_edit_batch, zlhip_sound_peak / _batch (a clip's sample and true peak, measured on the device), zlhip_peak_resolve,
+ *    zlhip_debug_peak_chunks, zlhip_sound_limit / _batch (a clip's peaks brought under a ceiling on the device), zlhip_limit_resolve,
+ *    zlhip_limit_design, zlhip_debug_limit_timings, zlhip_group_sound_peak_batch, zlhip_group_sound_limit_batch. */
 #define ZLHIP_ABI_VERSION 3
 
 /* status codes */
@@ -380,7 +382,8 @@ int zlhip_debug_pitch_timings(zlhip_engine *e, float *diff_ms, float *rest_ms);
  *   written; one bad request fails the call.
  *   A call is one kernel launch whatever its size, behind one copy of the request records; it waits once and 24 bytes per sub-block
  *   come back.  It runs on the engine's stream behind what is queued there and the resident real-time kernel keeps running.
- *   Not provided: true peak (the peak is the sample peak: leave headroom), loudness range, momentary / short-term meters (the
+ *   (The true peak: zlhip_sound_peak, below.)
+ *   Not provided: loudness range, momentary / short-term meters (the
  *   sub-block sums are there through zlhip_debug_loudness_subs), channel weights beyond stereo. */
 typedef struct zlhip_loudness_request { int32_t id, first_frame, num_frames, sub_frames; } zlhip_loudness_request;
 typedef struct zlhip_loudness { double lufs, mean_square, relative_gate; float peak[2]; int32_t sub_blocks, blocks, above_absolute, above_relative; } zlhip_loudness;
@@ -519,8 +522,8 @@ int zlhip_debug_xfade_timings(zlhip_engine *e, float *measure_ms, float *render_
  *   edited data.  Clip parameters are seconds and keep their values: the caller moves start and length (libzl_hotpath_clip_trim_silence,
  *   _crop and _reverse do).  A voice that plays the clip during the call keeps its frame position, which is safe and musically wrong:
  *   edit before playing.
- *   Not provided: undo; extracting a region into a NEW clip, or slices into clips; a baked gain or peak normalise (the clip's gain
- *   re-render stays the reversible route); DC removal; editing under a re-render; fades at a region inside the data. */
+ *   Not provided: undo; extracting a region into a NEW clip, or slices into clips; a baked gain alone (zlhip_sound_limit bakes one under a
+ *   ceiling; the clip's gain re-render stays the reversible route); DC removal; editing under a re-render; fades at a region inside the data. */
 enum { ZLHIP_EDIT_TRIM = 1, ZLHIP_EDIT_REVERSE = 2 };
 enum { ZLHIP_EDIT_LINEAR = 0, ZLHIP_EDIT_SQRT = 1, ZLHIP_EDIT_SMOOTH = 2 };
 typedef struct zlhip_edit_request { int32_t id, first_frame, num_frames, flags, pre_roll_frames, hold_frames, fade_in_frames, fade_out_frames, curve;
@@ -538,6 +541,64 @@ int zlhip_sound_edit_batch(zlhip_engine *e, const zlhip_edit_request *reqs, int3
 /* measurement: device time of the scanning launch (0 for a call without TRIM) and of the render and publishing launches of the last
  * call made with profiling on */
 int zlhip_debug_edit_timings(zlhip_engine *e, float *scan_ms, float *render_ms);
+/* Peaks: a clip's sample peak and true peak measured on the device, and a look-ahead limiter that brings the few peaks of a clip under a
+ * ceiling and leaves everything else as it was, bit for bit, under the clip's own id (a build-defined extension,
+ * the reference has neither).  All arithmetic is fp32, one IEEE operation per operator, nothing fused.
+ *   Detector.  v = x gain (one rounded multiply).  Sample peak of a frame and channel: |v|.  Inter-sample peak ips[f][c], with
+ *   ZLHIP_LIMIT_TRUE_PEAK: the oversampling factor F is 4 for a rate below 70000, 2 below 140000, else 1 (BS.1770-4 Annex 2); the filter
+ *   is zlhip_resample_design(rate, F rate)'s table unchanged (L = F, M = 1, 64 taps), rows p = 1 .. F - 1: y = sum over t of
+ *   h[p][t] v[f - 31 + t] in increasing t, a rounded multiply and a rounded add per tap, v = +0 outside the request's region;
+ *   ips[f][c] = max over p of |y|, ips[-1] = 0, and 0 with F = 1.  A rate the design refuses, with the flag, is ZLHIP_ERR_INVALID.  The frame
+ *   detector is p[f] = max over the channels of max(|v[f]|, ips[f - 1], ips[f]); without the flag max over the channels of |v[f]|.
+ *   Maxima compare bits: every order gives the same answer.
+ *   zlhip_sound_peak: request { id, first_frame, num_frames, flags } over the sound's CURRENT playback data (num_frames >= 1, the region
+ *   inside the data); gain 1, a non-finite sample is +0.  The device writes one record { sample_peak[2], inter_peak[2] } per chunk of 1024
+ *   frames of the region (zlhip_debug_peak_chunks), maxima over the chunk's own frames, a mono sound leaves index 1 zero; the host takes
+ *   the maxima: true_peak = max(sample_peak, inter_peak); oversampling = F (1 without the flag), chunks.  One launch, one wait; the
+ *   resident real-time kernel keeps running.
+ *   zlhip_sound_limit: request { id, flags, lookahead_frames L, hold_frames H, ceiling c, gain } over the slot's ORIGINAL data, the whole
+ *   clip, n frames.  zlhip_limit_resolve fills the defaults: ceiling 0 means (float)0.8912509381337456 (-1 dBFS), else finite in (0, 1];
+ *   gain 0 means 1, else finite and above 0; lookahead_frames 0 means floor(rate 0.005 + 0.5) clipped to [1, 512], else in [1, 512];
+ *   hold_frames in [0, 512]; a flag other than TRUE_PEAK, or anything else, is ZLHIP_ERR_INVALID.
+ *     1. g[f] = p[f] > c ? c / p[f] : 1; r[f] = 1 - g[f].  (The limiter works on the reduction: nothing above the ceiling means r = 0,
+ *        R = 0 and G = 1 exactly.)
+ *     2. mr[i] = max r[j] over j in [max(i - H, 0), min(i + L, n - 1)], i in [-L, n - 1].
+ *     3. R[f] = sum over k = 0 .. L of w[k] mr[f - k], from +0 in increasing k, a rounded multiply and a rounded add per tap;
+ *        w[k] = (double)((k + 1)(L + 1 - k)) / (double)((L + 1)(L + 2)(L + 3) / 6), rounded to fp32 (zlhip_limit_design).
+ *     4. G[f] = max(1 - R[f], 0).
+ *     5. y = v G[f]; out = y > c ? c : (y < -c ? -c : y).  No output sample exceeds c; the clamp moves a sample by at most
+ *        |v| (L + 4) 2^-23.  A frame more than L frames before and more than L + H frames behind every hot frame is v, bit for bit.
+ *   The output is not delayed and keeps length, channels and rate; attack and release are both the L-frame ramp.
+ *   gain == 1 and the detector's maximum <= c: applied = 0, no extent, no render.  gain != 1 and nothing hot: applied = 1, every sample
+ *   is x gain.  The clip must have ZL_SOUND_FINITE (else ZLHIP_ERR_STATE) and keeps it iff every written sample is finite.
+ *   The result: applied, lookahead_frames, hold_frames, oversampling, frames_reduced (frames with G < 1), peak_before (the detector's
+ *   maximum), min_gain (the smallest G), ceiling, gain.
+ *   A clip that plays a re-render is ZLHIP_ERR_STATE; ids not in use or repeated are ZLHIP_ERR_INVALID; an arena that cannot hold the
+ *   applied clips is ZLHIP_ERR_CAPACITY, decided behind the detecting pass, which changes nothing.  All or nothing; on any error out is
+ *   not written.  Synchronisation is zlhip_sound_edit's: a detecting launch, a wait, one render and one publishing launch, a second wait.
+ *   Not provided: a separate release time (a recursive release is serial); a guarantee on the TRUE peak of the output (gain modulation can
+ *   recreate small inter-sample overs: measure with zlhip_sound_peak afterwards); undo; limiting a region; limiting under a re-render. */
+enum { ZLHIP_LIMIT_TRUE_PEAK = 1 };
+typedef struct zlhip_peak_request { int32_t id, first_frame, num_frames, flags; } zlhip_peak_request;
+typedef struct zlhip_peak { float sample_peak[2], true_peak[2]; int32_t oversampling, chunks; } zlhip_peak;
+typedef struct zlhip_peak_chunk { float sample_peak[2], inter_peak[2]; } zlhip_peak_chunk;
+typedef struct zlhip_limit_request { int32_t id, flags, lookahead_frames, hold_frames; float ceiling, gain; } zlhip_limit_request;
+typedef struct zlhip_limit { int32_t applied, lookahead_frames, hold_frames, oversampling, frames_reduced; float peak_before, min_gain, ceiling, gain;
+                             int32_t reserved; } zlhip_limit;
+/* host only: checks the request against a sound of `length` frames at `sample_rate` */
+int zlhip_peak_resolve(double sample_rate, int32_t length, const zlhip_peak_request *r);
+int zlhip_sound_peak(zlhip_engine *e, const zlhip_peak_request *r, zlhip_peak *out);
+int zlhip_sound_peak_batch(zlhip_engine *e, const zlhip_peak_request *reqs, int32_t nreq, zlhip_peak *out);
+/* the chunk records of request `request` of the last call (records: [capacity], may be NULL to ask for *count only) */
+int zlhip_debug_peak_chunks(zlhip_engine *e, int32_t request, zlhip_peak_chunk *records, int32_t capacity, int32_t *count);
+/* host only: fills the fields given as 0 and checks every limit; a refused request is left as it was */
+int zlhip_limit_resolve(double sample_rate, zlhip_limit_request *r);
+/* host only: the L + 1 weights of the window, w: [L + 1]; L outside [1, 512] is ZLHIP_ERR_INVALID.  The engine builds its tables with this code */
+int zlhip_limit_design(int32_t lookahead_frames, float *w);
+int zlhip_sound_limit(zlhip_engine *e, const zlhip_limit_request *r, zlhip_limit *out);
+int zlhip_sound_limit_batch(zlhip_engine *e, const zlhip_limit_request *reqs, int32_t count, zlhip_limit *out);
+/* measurement: device time of the detecting launch and of the render and publishing launches of the last limit call made with profiling on */
+int zlhip_debug_limit_timings(zlhip_engine *e, float *detect_ms, float *render_ms);
 /* Warp: a clip fitted to the session grid on the device, a time stretch cut at the clip's hits (a build-defined
  * extension, the reference has no warp).  A uniform stretch leaves a hit that is early or late early or late; here every region between
  * two anchors gets its own ratio, starts exactly at its anchor with no seek (the attack is copied 1:1) and is searched by its own
@@ -870,6 +931,11 @@ int  zlhip_group_sound_loop_crossfade_batch(zlhip_group *g, const zlhip_xfade_re
 /* zlhip_sound_edit_batch on every member, in member order, with zlhip_group_sound_convert_rate_batch's semantics; out receives member
  * 0's results (the members hold the same data: every member finds the same frames) */
 int  zlhip_group_sound_edit_batch(zlhip_group *g, const zlhip_edit_request *reqs, int32_t count, zlhip_edit *out);
+/* zlhip_sound_peak_batch: member 0 answers */
+int  zlhip_group_sound_peak_batch(zlhip_group *g, const zlhip_peak_request *reqs, int32_t nreq, zlhip_peak *out);
+/* zlhip_sound_limit_batch on every member, in member order, with zlhip_group_sound_convert_rate_batch's semantics; out receives member
+ * 0's results (the members hold the same data: every member computes the same gains) */
+int  zlhip_group_sound_limit_batch(zlhip_group *g, const zlhip_limit_request *reqs, int32_t count, zlhip_limit *out);
 /* zlhip_sound_warp_batch on every member, in member order, with zlhip_group_sound_convert_rate_batch's semantics; out receives member
  * 0's results (the members hold the same data: every member finds the same offsets) */
 int  zlhip_group_sound_warp_batch(zlhip_group *g, const zlhip_warp_request *reqs, int32_t count, zlhip_warp *out);

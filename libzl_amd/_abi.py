@@ -198,6 +198,30 @@ EDIT_LINEAR, EDIT_SQRT, EDIT_SMOOTH = 0, 1, 2
 STRUCT_SIZES = {"zlhip_edit_request": (EditRequest, 40), "zlhip_edit": (Edit, 48)}
 
 
+class PeakRequest(C.Structure):
+    _fields_ = [("id", C.c_int32), ("first_frame", C.c_int32), ("num_frames", C.c_int32), ("flags", C.c_int32)]
+
+
+class Peak(C.Structure):
+    _fields_ = [("sample_peak", C.c_float * 2), ("true_peak", C.c_float * 2), ("oversampling", C.c_int32), ("chunks", C.c_int32)]
+
+
+class PeakChunk(C.Structure):
+    _fields_ = [("sample_peak", C.c_float * 2), ("inter_peak", C.c_float * 2)]
+
+
+class LimitRequest(C.Structure):
+    _fields_ = [("id", C.c_int32), ("flags", C.c_int32), ("lookahead_frames", C.c_int32), ("hold_frames", C.c_int32), ("ceiling", C.c_float), ("gain", C.c_float)]
+
+
+class Limit(C.Structure):
+    _fields_ = [("applied", C.c_int32), ("lookahead_frames", C.c_int32), ("hold_frames", C.c_int32), ("oversampling", C.c_int32), ("frames_reduced", C.c_int32),
+                ("peak_before", C.c_float), ("min_gain", C.c_float), ("ceiling", C.c_float), ("gain", C.c_float), ("reserved", C.c_int32)]
+
+
+LIMIT_TRUE_PEAK = 1
+
+
 class WarpAnchor(C.Structure):
     _fields_ = [("src_frame", C.c_int32), ("dst_frame", C.c_int32)]
 
@@ -325,6 +349,15 @@ SIGNATURES = {
     "zlhip_sound_edit": (C.c_int, [_E, C.POINTER(EditRequest), C.POINTER(Edit)]),
     "zlhip_sound_edit_batch": (C.c_int, [_E, C.POINTER(EditRequest), C.c_int32, C.POINTER(Edit)]),
     "zlhip_debug_edit_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "zlhip_peak_resolve": (C.c_int, [C.c_double, C.c_int32, C.POINTER(PeakRequest)]),
+    "zlhip_sound_peak": (C.c_int, [_E, C.POINTER(PeakRequest), C.POINTER(Peak)]),
+    "zlhip_sound_peak_batch": (C.c_int, [_E, C.POINTER(PeakRequest), C.c_int32, C.POINTER(Peak)]),
+    "zlhip_debug_peak_chunks": (C.c_int, [_E, C.c_int32, C.POINTER(PeakChunk), C.c_int32, C.POINTER(C.c_int32)]),
+    "zlhip_limit_resolve": (C.c_int, [C.c_double, C.POINTER(LimitRequest)]),
+    "zlhip_limit_design": (C.c_int, [C.c_int32, C.c_void_p]),
+    "zlhip_sound_limit": (C.c_int, [_E, C.POINTER(LimitRequest), C.POINTER(Limit)]),
+    "zlhip_sound_limit_batch": (C.c_int, [_E, C.POINTER(LimitRequest), C.c_int32, C.POINTER(Limit)]),
+    "zlhip_debug_limit_timings": (C.c_int, [_E, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "zlhip_warp_resolve": (C.c_int, [C.c_double, C.c_int32, C.POINTER(WarpAnchor), C.c_int32, C.POINTER(Warp)]),
     "zlhip_warp_plan": (C.c_int, [C.c_double, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32,
                                   C.POINTER(WarpAnchor), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -411,6 +444,8 @@ SIGNATURES = {
     "zlhip_group_sound_loop_batch": (C.c_int, [_E, C.POINTER(LoopRequest), C.c_int32, C.POINTER(Loop)]),
     "zlhip_group_sound_loop_crossfade_batch": (C.c_int, [_E, C.POINTER(XfadeRequest), C.c_int32, C.POINTER(Xfade)]),
     "zlhip_group_sound_edit_batch": (C.c_int, [_E, C.POINTER(EditRequest), C.c_int32, C.POINTER(Edit)]),
+    "zlhip_group_sound_peak_batch": (C.c_int, [_E, C.POINTER(PeakRequest), C.c_int32, C.POINTER(Peak)]),
+    "zlhip_group_sound_limit_batch": (C.c_int, [_E, C.POINTER(LimitRequest), C.c_int32, C.POINTER(Limit)]),
     "zlhip_group_sound_warp_batch": (C.c_int, [_E, C.POINTER(WarpRequest), C.c_int32, C.POINTER(Warp)]),
     "zlhip_group_sound_key_batch": (C.c_int, [_E, C.POINTER(KeyRequest), C.c_int32, C.POINTER(Key)]),
     "zlhip_group_sound_loudness_batch": (C.c_int, [_E, C.POINTER(LoudnessRequest), C.c_int32, C.POINTER(Loudness)]),

@@ -19,8 +19,8 @@ CSRC = os.path.join(ROOT, "libzl_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "libzl_amd", "lib")
 LIB = os.path.join(LIBDIR, "libzlhip.so")
 
-HIP_SOURCES = ["zl_kernels.hip", "zl_stretch.hip", "zl_overview.hip", "zl_onset.hip", "zl_tempo.hip", "zl_pitch.hip", "zl_loudness.hip", "zl_loop.hip", "zl_key.hip", "zl_xfade.hip", "zl_edit.hip", "zl_warp.hip", "zl_decode.hip", "zl_resample.hip", "zl_engine.cpp", "zl_clip_calls.cpp", "zl_libzl.cpp", "zl_group.cpp"]
-HEADERS = ["zl_types.h", "zl_arena.h", "zl_plan.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_render.h", "zl_kernels.h", "zl_host.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", "zl_overview.h", "zl_onset.h", "zl_tempo.h", "zl_pitch.h", "zl_loudness.h", "zl_loop.h", "zl_key.h", "zl_xfade.h", "zl_edit.h", "zl_warp.h", "zl_decode.h", "zl_resample.h", "zl_group.h", "zl_member.h", "zl_owned.h", "zl_engine_impl.h",
+HIP_SOURCES = ["zl_kernels.hip", "zl_stretch.hip", "zl_overview.hip", "zl_onset.hip", "zl_tempo.hip", "zl_pitch.hip", "zl_loudness.hip", "zl_loop.hip", "zl_key.hip", "zl_xfade.hip", "zl_edit.hip", "zl_limit.hip", "zl_warp.hip", "zl_decode.hip", "zl_resample.hip", "zl_engine.cpp", "zl_clip_calls.cpp", "zl_libzl.cpp", "zl_group.cpp"]
+HEADERS = ["zl_types.h", "zl_arena.h", "zl_plan.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_render.h", "zl_kernels.h", "zl_host.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", "zl_overview.h", "zl_onset.h", "zl_tempo.h", "zl_pitch.h", "zl_loudness.h", "zl_loop.h", "zl_key.h", "zl_xfade.h", "zl_edit.h", "zl_limit.h", "zl_warp.h", "zl_decode.h", "zl_resample.h", "zl_group.h", "zl_member.h", "zl_owned.h", "zl_engine_impl.h",
            os.path.join("..", "..", "include", "zlhip.h"), os.path.join("..", "..", "include", "libzl_hotpath.h")]
 
 
@@ -77,13 +77,14 @@ SOURCE_DEPS = {
     "zl_key.hip": ["zl_types.h", "zl_stretch.h", "zl_overview.h", "zl_onset.h", "zl_pitch.h", "zl_key.h"],
     "zl_xfade.hip": ["zl_types.h", "zl_stretch.h", "zl_overview.h", "zl_onset.h", "zl_pitch.h", "zl_xfade.h"],
     "zl_edit.hip": ["zl_types.h", "zl_overview.h", "zl_edit.h"],
+    "zl_limit.hip": ["zl_types.h", "zl_overview.h", "zl_resample.h", "zl_limit.h"],
     "zl_warp.hip": ["zl_types.h", "zl_stretch.h", "zl_warp.h"],
     "zl_decode.hip": ["zl_types.h", "zl_decode.h"],
     "zl_resample.hip": ["zl_types.h", "zl_resample.h"],
     # (zl_stretch.h: through zl_arena.h)
     "zl_engine.cpp": ["zl_types.h", "zl_arena.h", "zl_plan.h", "zl_render.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_owned.h", "zl_engine_impl.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h")],
     # the clip services: the engine's state and the services' own headers, none of the render kernels'
-    "zl_clip_calls.cpp": ["zl_types.h", "zl_arena.h", "zl_plan.h", "zl_host.h", "zl_owned.h", "zl_engine_impl.h", "zl_stretch.h", "zl_overview.h", "zl_onset.h", "zl_tempo.h", "zl_pitch.h", "zl_loudness.h", "zl_loop.h", "zl_key.h", "zl_xfade.h", "zl_edit.h", "zl_warp.h", "zl_decode.h", "zl_resample.h", os.path.join(_INC, "zlhip.h")],
+    "zl_clip_calls.cpp": ["zl_types.h", "zl_arena.h", "zl_plan.h", "zl_host.h", "zl_owned.h", "zl_engine_impl.h", "zl_stretch.h", "zl_overview.h", "zl_onset.h", "zl_tempo.h", "zl_pitch.h", "zl_loudness.h", "zl_loop.h", "zl_key.h", "zl_xfade.h", "zl_edit.h", "zl_limit.h", "zl_warp.h", "zl_decode.h", "zl_resample.h", os.path.join(_INC, "zlhip.h")],
     "zl_group.cpp": ["zl_types.h", "zl_plan.h", "zl_order.h", "zl_pair.h", "zl_launch.h", "zl_host.h", "zl_kernels.h", "zl_member.h", "zl_group.h", os.path.join(_INC, "zlhip.h")],
     "zl_libzl.cpp": ["zl_render.h", "zl_types.h", "zl_sched.h", "zl_handoff.h", "zl_stretch.h", os.path.join(_INC, "zlhip.h"), os.path.join(_INC, "libzl_hotpath.h")],
 }
@@ -351,6 +352,11 @@ def build_xfade_harness(force: bool = False) -> str:
 def build_edit_harness(force: bool = False) -> str:
     """The clip edit's resolve, region, fades and weights and a call's walk workgroup by workgroup and group by group (zl_edit.h)."""
     return _build_harness("zl_edit_host", "edit_host.cpp", ["zl_types.h", "zl_overview.h", "zl_edit.h", _ZLHIP_H], _NO_CONTRACT + ["-Wall"], force)
+
+
+def build_limit_harness(force: bool = False) -> str:
+    """The peak measurement's and the limiter's resolve, window and tables and a call's walk chunk by chunk and tile by tile (zl_limit.h)."""
+    return _build_harness("zl_limit_host", "limit_host.cpp", ["zl_types.h", "zl_overview.h", "zl_resample.h", "zl_limit.h", _ZLHIP_H], _NO_CONTRACT + ["-Wall"], force)
 
 
 def build_warp_harness(force: bool = False) -> str:

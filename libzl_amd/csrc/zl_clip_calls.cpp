@@ -17,6 +17,7 @@
 #include "zl_decode.h"
 #include "zl_edit.h"
 #include "zl_key.h"
+#include "zl_limit.h"
 #include "zl_loop.h"
 #include "zl_loudness.h"
 #include "zl_onset.h"
@@ -1530,6 +1531,300 @@ int zlhip_debug_edit_timings(zlhip_engine *e, float *scan_ms, float *render_ms)
     if (!e) return ZLHIP_ERR_INVALID;
     if (scan_ms) *scan_ms = e->ed.scanMs;
     if (render_ms) *render_ms = e->ed.renderMs;
+    return ZLHIP_OK;
+}
+
+// ---- peaks and limiter (zl_limit.h, zl_limit.hip) -----------------------------------------------------------------------------------
+// The analysis is the loudness measurement's shape: one launch that writes a record per chunk into mapped host memory, one wait, the
+// maxima taken here; the resident real-time kernel stays.  The limiter is the clip edit's order: the detecting launch -- the same kernel,
+// over the originals, into a device buffer the render reads -- and the call's first wait come first and write nothing but their own
+// records, so that an arena that cannot hold the call leaves every clip as it was; only then every applied clip gets its new extent,
+// the windows are made here, one launch renders every clip, the sound-table entries switch and the call waits a last time.
+static void lm_tables(zlhip_engine *e)
+{
+    if (e->lm.tables.empty()) { e->lm.tables.resize(ZL_LM_TABLE_FLOATS); zl_lm_tables(e->lm.tables.data()); }
+}
+
+int zlhip_peak_resolve(double sample_rate, int32_t length, const zlhip_peak_request *r)
+{
+    static_assert(sizeof(zlhip_peak_request) == 16 && sizeof(zlhip_peak_request) == sizeof(ZlLmPeakRequest), "zlhip_peak_request's layout");
+    if (!r) return ZLHIP_ERR_INVALID;
+    ZlLmPeakRequest q;
+    std::memcpy(&q, r, sizeof q);
+    return zl_lm_peak_resolve(sample_rate, length, &q) != 0 ? ZLHIP_ERR_INVALID : ZLHIP_OK;
+}
+
+int zlhip_sound_peak_batch(zlhip_engine *e, const zlhip_peak_request *reqs, int32_t nreq, zlhip_peak *out)
+{
+    static_assert(sizeof(zlhip_peak) == 24, "zlhip_peak's layout");
+    static_assert(sizeof(zlhip_peak_chunk) == sizeof(ZlLmRecord) && sizeof(ZlLmRecord) == 16, "the device writes zlhip_peak_chunk's layout");
+    static_assert(ZLHIP_LIMIT_TRUE_PEAK == ZL_LM_TRUE_PEAK, "the flag");
+    if (!e || nreq < 0 || (nreq > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
+    if (nreq == 0) return ZLHIP_OK;
+    // validate everything before anything is written and before the first HIP call
+    std::vector<ZlLmScan> geo((size_t)nreq);
+    int64_t chunks = 0;
+    bool anyTp = false;
+    for (int32_t i = 0; i < nreq; ++i) {
+        zlhip_peak_request q = reqs[i];
+        auto resolve = [&](const ZlSound &s) {
+            return (q.flags & ~ZL_LM_TRUE_PEAK) || ((q.flags & ZL_LM_TRUE_PEAK) && !zl_lm_rate_ok(s.sample_rate)) ? "an unknown flag, or the true peak at a rate that is no integer in [1000, 768000]" : nullptr;
+        };
+        { const int rc = check_request(e, "sound_peak", q, resolve); if (rc != ZLHIP_OK) return rc; }
+        const ZlSound &s = e->hc.sounds[q.id];
+        ZlLmScan &S = geo[(size_t)i];
+        std::memset(&S, 0, sizeof S);
+        S.channels = s.channels; S.a = q.first_frame; S.b = q.first_frame + q.num_frames; S.wg_base = (int32_t)chunks;
+        S.F = (q.flags & ZL_LM_TRUE_PEAK) ? zl_lm_oversampling(s.sample_rate) : 1; S.sanitize = 1; S.gain = 1.0f;
+        anyTp = anyTp || S.F > 1;
+        chunks += zl_lm_chunks(q.num_frames);
+        if (chunks > ZL_LM_MAX_CALL_CHUNKS) return fail(e, ZLHIP_ERR_INVALID, "sound_peak_batch: more than 4194304 chunks in one call");
+    }
+    { const int rc = call_begin(e, false); if (rc != ZLHIP_OK) return rc; }
+    zlhip_engine::Limit &t = e->lm;
+    const size_t n = (size_t)nreq;
+    const char *what = "sound_peak: no memory for the call's buffers";
+    const int rsv = reserve(e, true, { { ZB_LM_SCAN, n, sizeof(ZlLmScan), std::max<size_t>(n * 2, 64), true, what },
+                                       { ZB_LM_TABLES, ZL_LM_TABLE_FLOATS, sizeof(float), ZL_LM_TABLE_FLOATS, true, what } },
+                            { mapped_need(t.out, std::max<size_t>((size_t)chunks, 512)) });
+    if (rsv != ZLHIP_OK) return rsv;
+    ZlLmScan *const hReq = (ZlLmScan *)e->scratch[ZB_LM_SCAN].h, *const dReq = (ZlLmScan *)e->scratch[ZB_LM_SCAN].d;
+    float *const hTab = (float *)e->scratch[ZB_LM_TABLES].h, *const dTab = (float *)e->scratch[ZB_LM_TABLES].d;
+    t.last.clear();
+    for (int32_t i = 0; i < nreq; ++i) {
+        hReq[i] = geo[(size_t)i];
+        hReq[i].src = (uint64_t)(uintptr_t)arena_ptr(e, e->hc.sounds[reqs[i].id].offset);
+        t.last.push_back({ geo[(size_t)i].wg_base, zl_lm_chunks(geo[(size_t)i].b - geo[(size_t)i].a) });
+    }
+    t.peakTimer.on = e->profiling;
+    ZL_HIP(e, hipMemcpyAsync(dReq, hReq, n * sizeof(ZlLmScan), hipMemcpyHostToDevice, e->stream));
+    if (anyTp) {
+        lm_tables(e);
+        std::memcpy(hTab, t.tables.data(), ZL_LM_TABLE_FLOATS * sizeof(float));
+        ZL_HIP(e, hipMemcpyAsync(dTab, hTab, ZL_LM_TABLE_FLOATS * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    }
+    ZL_HIP(e, t.peakTimer.mark(0, e->stream));
+    ZL_KERNEL(e, zl_launch_limit_detect(dReq, nreq, (int32_t)chunks, dTab, t.out.d, e->stream));
+    ZL_HIP(e, t.peakTimer.mark(1, e->stream));
+    { int w_ = engine_wait(e); if (w_ != ZLHIP_OK) return w_; }
+    ZL_HIP(e, t.peakTimer.elapsed(0, 1, &t.peakMs));
+    for (int32_t i = 0; i < nreq; ++i) {
+        const ZlLmScan &S = geo[(size_t)i];
+        uint32_t m[4] = {0u, 0u, 0u, 0u};
+        const int32_t nc = zl_lm_chunks(S.b - S.a);
+        for (int32_t k = 0; k < nc; ++k) {
+            const ZlLmRecord &r = t.out.h[S.wg_base + k];
+            m[0] = zl_lm_max_bits(m[0], zl_lm_bits(r.sample_peak[0])); m[1] = zl_lm_max_bits(m[1], zl_lm_bits(r.sample_peak[1]));
+            m[2] = zl_lm_max_bits(m[2], zl_lm_bits(r.inter_peak[0])); m[3] = zl_lm_max_bits(m[3], zl_lm_bits(r.inter_peak[1]));
+        }
+        zlhip_peak &o = out[i];
+        o.sample_peak[0] = zl_lm_float(m[0]); o.sample_peak[1] = zl_lm_float(m[1]);
+        o.true_peak[0] = zl_lm_float(zl_lm_max_bits(m[0], m[2])); o.true_peak[1] = zl_lm_float(zl_lm_max_bits(m[1], m[3]));
+        o.oversampling = S.F; o.chunks = nc;
+    }
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_peak(zlhip_engine *e, const zlhip_peak_request *r, zlhip_peak *out) { return zlhip_sound_peak_batch(e, r, 1, out); }
+
+int zlhip_debug_peak_chunks(zlhip_engine *e, int32_t request, zlhip_peak_chunk *records, int32_t capacity, int32_t *count)
+{
+    if (!e || request < 0 || (size_t)request >= e->lm.last.size()) return ZLHIP_ERR_INVALID;
+    const zlhip_engine::Limit::Last &l = e->lm.last[(size_t)request];
+    if (count) *count = l.chunks;
+    if (!records) return ZLHIP_OK;
+    if (capacity < l.chunks) return fail(e, ZLHIP_ERR_CAPACITY, "debug_peak_chunks: capacity below the request's chunks");
+    std::memcpy(records, e->lm.out.h + l.rec_base, (size_t)l.chunks * sizeof(ZlLmRecord));      // (the call has waited: the records are in host memory)
+    return ZLHIP_OK;
+}
+
+int zlhip_limit_resolve(double sample_rate, zlhip_limit_request *r)
+{
+    static_assert(sizeof(zlhip_limit_request) == 24 && sizeof(zlhip_limit_request) == sizeof(ZlLmRequest), "zlhip_limit_request's layout");
+    if (!r) return ZLHIP_ERR_INVALID;
+    ZlLmRequest q;
+    std::memcpy(&q, r, sizeof q);
+    if (zl_lm_resolve(sample_rate, &q) != 0) return ZLHIP_ERR_INVALID;
+    std::memcpy(r, &q, sizeof q);
+    return ZLHIP_OK;
+}
+
+int zlhip_limit_design(int32_t lookahead_frames, float *w)
+{
+    if (!w || lookahead_frames < 1 || lookahead_frames > ZL_LM_MAX_L) return ZLHIP_ERR_INVALID;
+    zl_lm_design(lookahead_frames, w);
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_limit_batch(zlhip_engine *e, const zlhip_limit_request *reqs, int32_t count, zlhip_limit *out)
+{
+    static_assert(sizeof(zlhip_limit) == 40, "zlhip_limit's layout");
+    if (!e || count < 0 || (count > 0 && (!reqs || !out))) return ZLHIP_ERR_INVALID;
+    if (count == 0) return ZLHIP_OK;
+    // validate and resolve everything before the first HIP call
+    std::vector<zlhip_limit_request> res((size_t)count);
+    std::vector<ZlLmScan> scans((size_t)count);
+    int32_t scanWgs = 0;
+    bool anyTp = false;
+    {
+        ZlDistinct distinct(e);
+        int64_t swgs = 0, tiles = 0;
+        for (int32_t i = 0; i < count; ++i) {
+            zlhip_limit_request &q = res[(size_t)i];
+            q = reqs[i];
+            { const int rc = distinct.check(e, "sound_limit", q.id); if (rc != ZLHIP_OK) return rc; }
+            const ZlSound &o = e->soundSlots[(size_t)q.id].orig;
+            if (zlhip_limit_resolve(o.sample_rate, &q) != ZLHIP_OK)
+                return fail_in(e, ZLHIP_ERR_INVALID, "sound_limit", "an unknown flag, the true peak at a rate that is no integer in [1000, 768000], a ceiling outside (0, 1], a gain that is not finite and above 0, or lookahead_frames or hold_frames outside [0, 512]");
+            ZlLmScan &S = scans[(size_t)i];
+            std::memset(&S, 0, sizeof S);
+            S.channels = o.channels; S.a = 0; S.b = o.length; S.wg_base = (int32_t)swgs;
+            S.F = (q.flags & ZL_LM_TRUE_PEAK) ? zl_lm_oversampling(o.sample_rate) : 1; S.sanitize = 0; S.gain = q.gain;
+            anyTp = anyTp || S.F > 1;
+            ZlLmJob J; std::memset(&J, 0, sizeof J);
+            J.n = o.length; J.channels = o.channels;
+            swgs += zl_lm_chunks(o.length); tiles += zl_lm_job_tiles(J);
+            if (swgs > ZL_LM_MAX_CALL_CHUNKS || tiles > (int64_t)INT32_MAX) return fail(e, ZLHIP_ERR_INVALID, "sound_limit_batch: more than 4194304 chunks in one call");
+        }
+        scanWgs = (int32_t)swgs;
+        for (int32_t i = 0; i < count; ++i) {
+            const int rc = check_plays_original(e, res[(size_t)i].id, "sound_limit: the clip plays a re-render (limit first, re-render afterwards; re-render it with gain 0, pitch 0, speed 1 first)");
+            if (rc != ZLHIP_OK) return rc;
+        }
+        for (int32_t i = 0; i < count; ++i) {
+            if (!(e->soundSlots[(size_t)res[(size_t)i].id].orig.flags & ZL_SOUND_FINITE))
+                return fail(e, ZLHIP_ERR_STATE, "sound_limit: the clip holds a sample that is not finite (the limiter needs a finite detector)");
+        }
+    }
+    zlhip_engine::Limit &t = e->lm;
+    t.timer.on = e->profiling;
+    if (e->profiling) { t.detectMs = 0.0f; t.renderMs = 0.0f; }
+    const char *what = "sound_limit: no memory for the call's records";
+    { const int rc = call_begin(e, true); if (rc != ZLHIP_OK) return rc; }
+    const size_t nq = (size_t)count;
+    {
+        const int rsv = reserve(e, false, { { ZB_LM_SCAN, nq, sizeof(ZlLmScan), std::max<size_t>(nq * 2, 64), true, what },
+                                            { ZB_LM_TABLES, ZL_LM_TABLE_FLOATS, sizeof(float), ZL_LM_TABLE_FLOATS, true, what },
+                                            { ZB_LM_REC, (size_t)scanWgs, sizeof(ZlLmRecord), std::max<size_t>((size_t)scanWgs * 2, 512), false, what } });
+        if (rsv != ZLHIP_OK) return rsv;
+    }
+    ZlLmScan *const hScan = (ZlLmScan *)e->scratch[ZB_LM_SCAN].h, *const dScan = (ZlLmScan *)e->scratch[ZB_LM_SCAN].d;
+    float *const hTab = (float *)e->scratch[ZB_LM_TABLES].h, *const dTab = (float *)e->scratch[ZB_LM_TABLES].d;
+    ZlLmRecord *const dRec = (ZlLmRecord *)e->scratch[ZB_LM_REC].d;
+    // the detector over every clip: the chunk records
+    std::vector<ZlLmRecord> records((size_t)scanWgs);
+    {
+        for (int32_t i = 0; i < count; ++i) {
+            hScan[i] = scans[(size_t)i];
+            hScan[i].src = (uint64_t)(uintptr_t)arena_ptr(e, e->soundSlots[(size_t)res[(size_t)i].id].orig.offset);
+        }
+        int krc = (int)hipMemcpyAsync(dScan, hScan, nq * sizeof(ZlLmScan), hipMemcpyHostToDevice, e->stream);
+        if (krc == 0 && anyTp) {
+            lm_tables(e);
+            std::memcpy(hTab, t.tables.data(), ZL_LM_TABLE_FLOATS * sizeof(float));
+            krc = (int)hipMemcpyAsync(dTab, hTab, ZL_LM_TABLE_FLOATS * sizeof(float), hipMemcpyHostToDevice, e->stream);
+        }
+        if (krc == 0) krc = (int)t.timer.mark(0, e->stream);
+        if (krc == 0) krc = zl_launch_limit_detect(dScan, count, scanWgs, dTab, dRec, e->stream);
+        if (krc == 0) krc = (int)t.timer.mark(1, e->stream);
+        if (krc == 0) krc = (int)hipMemcpyAsync(records.data(), dRec, records.size() * sizeof(ZlLmRecord), hipMemcpyDeviceToHost, e->stream);
+        if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);  // the call's first wait: the records are in host memory
+        if (krc == 0) krc = (int)t.timer.elapsed(0, 1, &t.detectMs);
+        if (krc != 0) {                                            // (the detector has changed nothing: nothing to undo)
+            e->err = std::string("sound_limit: ") + hipGetErrorString((hipError_t)krc);
+            (void)hipStreamSynchronize(e->stream);
+            return ZLHIP_ERR_HIP;
+        }
+    }
+    // who is applied
+    std::vector<zlhip_limit> results((size_t)count);
+    std::vector<char> applied((size_t)count, 0);
+    int32_t njobs = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        const zlhip_limit_request &q = res[(size_t)i];
+        const ZlLmScan &S = scans[(size_t)i];
+        uint32_t peak = 0u;
+        for (int32_t k = 0; k < zl_lm_chunks(S.b); ++k) peak = zl_lm_max_bits(peak, zl_lm_record_bits(records[(size_t)(S.wg_base + k)]));
+        zlhip_limit &r = results[(size_t)i];
+        std::memset(&r, 0, sizeof r);
+        r.lookahead_frames = q.lookahead_frames; r.hold_frames = q.hold_frames; r.oversampling = S.F; r.peak_before = zl_lm_float(peak);
+        r.min_gain = 1.0f; r.ceiling = q.ceiling; r.gain = q.gain;
+        if (q.gain == 1.0f && !(peak > zl_lm_bits(q.ceiling))) continue;
+        r.applied = 1; applied[(size_t)i] = 1;
+        ++njobs;
+    }
+    if (njobs == 0) {                                              // every clip is under its ceiling already: no extent, no render
+        std::memcpy(out, results.data(), results.size() * sizeof(zlhip_limit));
+        return ZLHIP_OK;
+    }
+    // only now the new extents, and the jobs
+    ZlNewExtents ext(e, count);
+    ZlClipSwap swap{ e, "sound_limit", ext };
+    std::vector<ZlLmJob> jobs;
+    std::vector<float> weights;
+    std::vector<int32_t> weightsAt((size_t)ZL_LM_MAX_L + 1, -1);  // one window per look-ahead of the call
+    int32_t wgs = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        if (!applied[(size_t)i]) continue;
+        const zlhip_limit_request &q = res[(size_t)i];
+        const ZlSound &o = e->soundSlots[(size_t)q.id].orig;
+        { const int rc = ext.take(i, o.length, o.channels); if (rc != ZLHIP_OK) return rc; }
+        ZlLmJob J; std::memset(&J, 0, sizeof J);
+        J.src = (uint64_t)(uintptr_t)arena_ptr(e, o.offset);
+        J.dst = (uint64_t)(uintptr_t)ext.ptr(i);
+        J.channels = o.channels; J.n = o.length; J.L = q.lookahead_frames; J.H = q.hold_frames; J.F = scans[(size_t)i].F;
+        J.ceiling = q.ceiling; J.gain = q.gain; J.wg_base = wgs; J.rec_base = scans[(size_t)i].wg_base;
+        if (weightsAt[(size_t)J.L] < 0) {
+            weightsAt[(size_t)J.L] = (int32_t)weights.size();
+            weights.resize(weights.size() + (size_t)J.L + 1);
+            zl_lm_design(J.L, weights.data() + weightsAt[(size_t)J.L]);
+        }
+        J.weights = weightsAt[(size_t)J.L];
+        J.verdict = swap.add(i, q.id, o);
+        wgs += zl_lm_job_tiles(J);
+        jobs.push_back(J);
+    }
+    const size_t nj = jobs.size(), n = std::max<size_t>(nj * 2, 64), np = weights.size();
+    const int rsv = reserve(e, false, { { ZB_LM_JOBS, nj, sizeof(ZlLmJob), n, false, what }, { ZB_LM_WEIGHTS, np, sizeof(float), std::max<size_t>(np * 2, 4096), false, what },
+                                       { ZB_LM_STATS, nj, sizeof(ZlLmStats), n, false, what }, { ZB_LM_PUB, nj, sizeof(ZlRsPublish), n, false, what },
+                                       { ZB_LM_VERDICTS, nj, sizeof(uint32_t), n, false, what } });
+    if (rsv != ZLHIP_OK) { ext.rollback(); return rsv; }
+    ZlLmJob *const dJobs = (ZlLmJob *)e->scratch[ZB_LM_JOBS].d; float *const dWeights = (float *)e->scratch[ZB_LM_WEIGHTS].d;
+    ZlLmStats *const dStats = (ZlLmStats *)e->scratch[ZB_LM_STATS].d;
+    ZlRsPublish *const dPub = (ZlRsPublish *)e->scratch[ZB_LM_PUB].d; uint32_t *const dVerdicts = (uint32_t *)e->scratch[ZB_LM_VERDICTS].d;
+    // everything is decided: from here on only a HIP error fails the call
+    std::vector<ZlLmStats> stats(nj, ZlLmStats{ 0u, 0x3f800000u });
+    std::vector<uint32_t> verdictsOut(nj, 0u);
+    int krc = (int)hipMemcpyAsync(dJobs, jobs.data(), nj * sizeof(ZlLmJob), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dWeights, weights.data(), np * sizeof(float), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dStats, stats.data(), nj * sizeof(ZlLmStats), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dVerdicts, swap.words.data(), nj * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(dPub, swap.pub.data(), nj * sizeof(ZlRsPublish), hipMemcpyHostToDevice, e->stream);
+    if (krc == 0) krc = (int)t.timer.mark(2, e->stream);
+    if (krc == 0) krc = zl_launch_limit_render(dJobs, (int32_t)nj, wgs, dTab, dRec, dWeights, dStats, dVerdicts, e->stream);
+    if (krc == 0) krc = zl_launch_resample_publish(dPub, (int32_t)nj, dVerdicts, e->dSounds, e->stream);
+    if (krc == 0) krc = (int)t.timer.mark(3, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(verdictsOut.data(), dVerdicts, nj * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream);
+    if (krc == 0) krc = (int)hipMemcpyAsync(stats.data(), dStats, nj * sizeof(ZlLmStats), hipMemcpyDeviceToHost, e->stream);
+    if (krc == 0) krc = (int)hipStreamSynchronize(e->stream);      // the call's last wait
+    if (krc == 0) krc = (int)t.timer.elapsed(2, 3, &t.renderMs);
+    if (krc != 0) return swap.hip_failed(krc);
+    swap.commit(verdictsOut);
+    for (size_t j = 0; j < nj; ++j) {
+        zlhip_limit &r = results[(size_t)swap.jobReq[j]];
+        r.frames_reduced = (int32_t)stats[j].frames_reduced; r.min_gain = zl_lm_float(stats[j].min_gain_bits);
+    }
+    std::memcpy(out, results.data(), results.size() * sizeof(zlhip_limit));
+    return ZLHIP_OK;
+}
+
+int zlhip_sound_limit(zlhip_engine *e, const zlhip_limit_request *r, zlhip_limit *out) { return zlhip_sound_limit_batch(e, r, 1, out); }
+
+int zlhip_debug_limit_timings(zlhip_engine *e, float *detect_ms, float *render_ms)
+{
+    if (!e) return ZLHIP_ERR_INVALID;
+    if (detect_ms) *detect_ms = e->lm.detectMs;
+    if (render_ms) *render_ms = e->lm.renderMs;
     return ZLHIP_OK;
 }
 

@@ -17,7 +17,7 @@
 #include "zl_owned.h"
 #include "zl_types.h"
 
-struct ZlOnOnset; struct ZlTpResult; struct ZlPtResult; struct ZlLdSub; struct ZlLpResult; struct ZlKyResult; struct ZlXfSums;     // (zl_onset.h, zl_tempo.h, zl_pitch.h, zl_loudness.h, zl_loop.h, zl_key.h, zl_xfade.h)
+struct ZlOnOnset; struct ZlTpResult; struct ZlPtResult; struct ZlLdSub; struct ZlLpResult; struct ZlKyResult; struct ZlXfSums; struct ZlLmRecord;     // (zl_onset.h, zl_tempo.h, zl_pitch.h, zl_loudness.h, zl_loop.h, zl_key.h, zl_xfade.h, zl_limit.h)
 
 #pragma GCC visibility push(hidden)
 // scratch[]: a call's records and staging (GrowBuf; grow_buf); an engine that never re-renders, asks for an overview or loads PCM has none
@@ -33,6 +33,7 @@ enum { ZB_ST_JOBS, ZB_ST_LIST, ZB_ST_OFFS,                    // re-render: a ca
        ZB_KY_REQ, ZB_KY_BINS, ZB_KY_TABLE, ZB_KY_STAT, ZB_KY_ACC, ZB_KY_TOTAL,   // key: a call's request records, its bin tables and the paired cosine table (each with a host twin), per frame the gate's verdict, per frame and bin re and im, per bin the totals
        ZB_XF_JOBS, ZB_XF_WEIGHTS, ZB_XF_PUB, ZB_XF_VERDICTS,  // loop crossfade: a call's job records, its (a, b) pairs, its publish records, its verdict words
        ZB_ED_SCAN, ZB_ED_FOUND, ZB_ED_JOBS, ZB_ED_WEIGHTS, ZB_ED_PUB, ZB_ED_VERDICTS,   // clip edit: a call's scan records and their two words each, its job records, its fade weights, its publish records, its verdict words
+       ZB_LM_SCAN, ZB_LM_TABLES, ZB_LM_REC, ZB_LM_JOBS, ZB_LM_WEIGHTS, ZB_LM_STATS, ZB_LM_PUB, ZB_LM_VERDICTS,   // peaks and limiter: a call's detecting records and the two filter tables (each with a host twin), the limiter's chunk records, its job records, its windows, its statistics, its publish records, its verdict words
        ZB_WP_JOBS, ZB_WP_REGIONS, ZB_WP_LIST, ZB_WP_OFFS, ZB_WP_PUB, ZB_WP_VERDICTS,   // warp: a call's job and region records, the regions whose seek runs, the seek offsets, its publish records, its verdict words
        ZB_COUNT };
 
@@ -127,6 +128,15 @@ struct zlhip_engine {
     } xf;
     // clip edit (zlhip_sound_edit; zl_edit.h)
     struct Edit { ZlStageTimer<4> timer; float scanMs = 0.0f, renderMs = 0.0f; } ed;      // marks: around the scanning launch, around the render and publish launches
+    // peaks and limiter (zlhip_sound_peak, zlhip_sound_limit; zl_limit.h)
+    struct Limit {
+        ZlMapped<ZlLmRecord> out;                                   // an analysis call's chunk records
+        struct Last { int32_t rec_base, chunks; };
+        std::vector<Last> last;                                     // per request of the last analysis call (zlhip_debug_peak_chunks)
+        std::vector<float> tables;                                  // the two filter tables, made by the first call that asks for the true peak
+        ZlStageTimer<2> peakTimer; float peakMs = 0.0f;             // marks: around the analysis launch
+        ZlStageTimer<4> timer; float detectMs = 0.0f, renderMs = 0.0f;   // marks: around the detecting launch, around the render and publish launches
+    } lm;
     // warp (zlhip_sound_warp; zl_warp.h)
     struct Warp { ZlStageTimer<3> timer; float seekMs = 0.0f, synthMs = 0.0f; } wp;       // marks: before the seek, between the launches, behind the publish
     // clips from raw PCM (zlhip_sound_upload_pcm; zl_decode.h)

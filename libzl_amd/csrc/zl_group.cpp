@@ -364,6 +364,25 @@ int zlhip_group_sound_edit_batch(zlhip_group *g, const zlhip_edit_request *reqs,
     return ZLHIP_OK;
 }
 
+int zlhip_group_sound_peak_batch(zlhip_group *g, const zlhip_peak_request *reqs, int32_t nreq, zlhip_peak *out)
+{
+    if (!g) return ZLHIP_ERR_INVALID;
+    const int rc = zlhip_sound_peak_batch(g->m[0], reqs, nreq, out);
+    return rc != ZLHIP_OK ? member_fail(g, 0, rc) : ZLHIP_OK;
+}
+
+int zlhip_group_sound_limit_batch(zlhip_group *g, const zlhip_limit_request *reqs, int32_t count, zlhip_limit *out)
+{
+    if (!g) return ZLHIP_ERR_INVALID;
+    // (as zlhip_group_sound_loop_crossfade_batch: a call that is invalid or does not fit fails on member 0 and leaves every member as it was)
+    std::vector<zlhip_limit> rest((size_t)(count > 0 ? count : 0));
+    for (int r = 0; r < g->L.n; ++r) {
+        const int rc = zlhip_sound_limit_batch(g->m[(size_t)r], reqs, count, r == 0 ? out : rest.data());
+        if (rc != ZLHIP_OK) return member_fail(g, r, rc);
+    }
+    return ZLHIP_OK;
+}
+
 int zlhip_group_sound_warp_batch(zlhip_group *g, const zlhip_warp_request *reqs, int32_t count, zlhip_warp *out)
 {
     if (!g) return ZLHIP_ERR_INVALID;

@@ -1507,6 +1507,95 @@ int libzl_hotpath_clip_reverse(ClipAudioSource *c)
     return 1;
 }
 
+// A recorded hit with one sharp transient cannot be levelled with the rest of its bank while the gain is held under the ceiling by the
+// peak (level_gain): here the few peaks come down instead and everything else stays as it was -- the true-peak measurement and the
+// look-ahead limiter on the device (zlhip_sound_peak, zlhip_sound_limit).  Build-defined: the reference has neither.
+static float peak_db_of(float a, float b) { return (float)(20.0 * std::log10((double)std::max(a, b))); }      // (a peak of 0: -inf)
+
+int libzl_hotpath_clip_true_peak(ClipAudioSource *c, float *sample_peak_db, float *true_peak_db)
+{
+    if (!c) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    if (!G.engine || c->engineClip < 0) return ZLHIP_ERR_STATE;
+    zlhip_sound_info info; int64_t start, stop;
+    { const int rc = clip_region(c, &info, &start, &stop); if (rc != ZLHIP_OK) return rc; }
+    const zlhip_peak_request q = { c->engineClip, (int32_t)start, (int32_t)(stop - start), ZLHIP_LIMIT_TRUE_PEAK };
+    zlhip_peak r;
+    { const int rc = zlhip_sound_peak(G.engine, &q, &r); if (rc != ZLHIP_OK) return rc; }
+    if (sample_peak_db) *sample_peak_db = peak_db_of(r.sample_peak[0], r.sample_peak[1]);
+    if (true_peak_db) *true_peak_db = peak_db_of(r.true_peak[0], r.true_peak[1]);
+    return 1;
+}
+
+static int clip_limit_request(ClipAudioSource *c, float ceiling_db, float lookahead_ms, float hold_ms, int true_peak, zlhip_limit_request *q)     // call with G.mu held
+{
+    zlhip_sound_info info;
+    { const int rc = clip_edit_ready(c, &info); if (rc != ZLHIP_OK) return rc; }
+    const float ceiling = (float)std::pow(10.0, (double)ceiling_db / 20.0);
+    if (!(ceiling > 0.0f && ceiling <= 1.0f)) return ZLHIP_ERR_INVALID;                            // (a NaN fails here; above 0 dBFS)
+    const double look = std::rint((double)lookahead_ms * info.sample_rate / 1000.0), hold = std::rint((double)hold_ms * info.sample_rate / 1000.0);
+    if (!(look >= 0.0 && look <= 2147483647.0) || !(hold >= 0.0 && hold <= 2147483647.0) || (lookahead_ms > 0.0f && look < 1.0)) return ZLHIP_ERR_INVALID;
+    *q = zlhip_limit_request{ c->engineClip, true_peak ? ZLHIP_LIMIT_TRUE_PEAK : 0, (int32_t)look, (int32_t)hold, ceiling, 1.0f };
+    return zlhip_limit_resolve(info.sample_rate, q) == ZLHIP_OK ? ZLHIP_OK : ZLHIP_ERR_INVALID;    // (beyond 512 frames, the flag at a rate it cannot be asked at)
+}
+
+static float reduction_db_of(const zlhip_limit &r) { return r.applied && r.min_gain < 1.0f ? (float)(-20.0 * std::log10((double)r.min_gain)) : 0.0f; }   // (a gain of 0: +inf)
+
+int libzl_hotpath_clip_limit(ClipAudioSource *c, float ceiling_db, float lookahead_ms, float hold_ms, int true_peak, float *reduction_db)
+{
+    if (!c) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    zlhip_limit_request q; zlhip_limit r;
+    { const int rc = clip_limit_request(c, ceiling_db, lookahead_ms, hold_ms, true_peak, &q); if (rc != ZLHIP_OK) return rc; }
+    { const int rc = zlhip_sound_limit(G.engine, &q, &r); if (rc != ZLHIP_OK) return rc; }
+    if (reduction_db) *reduction_db = reduction_db_of(r);
+    return r.applied ? 1 : 0;
+}
+
+// A whole bank: ONE zlhip_sound_loudness_batch and ONE zlhip_sound_limit_batch.  Every clip with a loudness is driven by target - lufs,
+// not held by the ceiling, the drive baked as the limiter's gain; the limiter takes some loudness back, so a clip lands at or under the
+// target (the caller may measure again).  gainDb is not touched: the levelled data is the clip's original from now on.
+int libzl_hotpath_clips_level_limited(ClipAudioSource **clips, int count, float target_lufs, float ceiling_db, float lookahead_ms, float hold_ms, int true_peak,
+                                      float *drive_db_out, float *reduction_db_out)
+{
+    if (count < 0 || (count > 0 && !clips) || target_lufs != target_lufs) return ZLHIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(G.mu);
+    if (!G.engine) return ZLHIP_ERR_STATE;
+    for (int i = 0; i < count; ++i)
+        for (int j = 0; clips[i] && j < i; ++j) if (clips[j] == clips[i]) return ZLHIP_ERR_INVALID;
+    std::vector<int> who; std::vector<zlhip_loudness_request> lreqs; std::vector<zlhip_limit_request> reqs;
+    for (int i = 0; i < count; ++i) {
+        zlhip_limit_request q; zlhip_loudness_request l;
+        if (!clips[i]) continue;
+        const int rc = clip_limit_request(clips[i], ceiling_db, lookahead_ms, hold_ms, true_peak, &q);
+        if (rc == ZLHIP_ERR_INVALID) return rc;                    // (the arguments are the call's: wrong for one clip, wrong for all)
+        if (rc != ZLHIP_OK || clip_loudness_request(clips[i], &l) != ZLHIP_OK) continue;      // not in the engine, plays a re-render: stays as it is
+        who.push_back(i); reqs.push_back(q); lreqs.push_back(l);
+    }
+    std::vector<zlhip_loudness> loud(lreqs.size());
+    if (!lreqs.empty()) { const int rc = zlhip_sound_loudness_batch(G.engine, lreqs.data(), (int32_t)lreqs.size(), loud.data()); if (rc != ZLHIP_OK) return rc; }
+    std::vector<int> sent; std::vector<zlhip_limit_request> batch; std::vector<float> drives;
+    for (size_t n = 0; n < who.size(); ++n) {
+        if (loud[n].above_absolute == 0) continue;                 // no loudness: stays as it is
+        const double drive = (double)target_lufs - loud[n].lufs;
+        const float gain = (float)std::pow(10.0, drive / 20.0);
+        if (!(gain > 0.0f && gain <= FLT_MAX)) continue;
+        reqs[n].gain = gain;
+        sent.push_back(who[n]); batch.push_back(reqs[n]); drives.push_back((float)drive);
+    }
+    std::vector<zlhip_limit> res(batch.size());
+    if (!batch.empty()) { const int rc = zlhip_sound_limit_batch(G.engine, batch.data(), (int32_t)batch.size(), res.data()); if (rc != ZLHIP_OK) return rc; }
+    for (int i = 0; i < count; ++i) { if (drive_db_out) drive_db_out[i] = 0.0f; if (reduction_db_out) reduction_db_out[i] = 0.0f; }
+    int applied = 0;
+    for (size_t n = 0; n < sent.size(); ++n) {
+        if (!res[n].applied) continue;
+        if (drive_db_out) drive_db_out[sent[n]] = drives[n];
+        if (reduction_db_out) reduction_db_out[sent[n]] = reduction_db_of(res[n]);
+        ++applied;
+    }
+    return applied;
+}
+
 // Fit a loop to the session grid hit by hit: the clip's transients over its whole original (zlhip_sound_onsets, defaults), its tempo
 // (given, or detected as libzl_hotpath_clip_tempo(c, 0, 0, ...) does), the plan from hits to anchors on the host (zlhip_warp_plan; the
 // grid counts from the clip's start frame by the voice's own cast) and the warp on the device (zlhip_sound_warp).

@@ -242,6 +242,33 @@ def _edit_call(fn, handle, requests):
     return rc, [{k: getattr(out[i], k) for k in EDIT_FIELDS} for i in range(len(requests))]
 
 
+LIMIT_FIELDS = tuple(name for name, _ in _abi.Limit._fields_ if name != "reserved")
+
+
+def _peak_call(fn, handle, requests):
+    """one zlhip_sound_peak_batch-shaped call over dicts with "clip", "first_frame", "num_frames" (0: to the end of `length`, which the
+    caller fills in) and "flags" -> (status, one dict of zlhip_peak's fields per request)"""
+    reqs = (_abi.PeakRequest * max(1, len(requests)))()
+    for i, r in enumerate(requests):
+        reqs[i] = _abi.PeakRequest(int(r["clip"]), int(r.get("first_frame", 0)), int(r.get("num_frames", 0)), int(r.get("flags", 0)))
+    out = (_abi.Peak * max(1, len(requests)))()
+    rc = fn(handle, reqs, len(requests), out)
+    return rc, [dict(sample_peak=tuple(out[i].sample_peak), true_peak=tuple(out[i].true_peak), oversampling=out[i].oversampling, chunks=out[i].chunks)
+                for i in range(len(requests))]
+
+
+def _limit_call(fn, handle, requests):
+    """one zlhip_sound_limit_batch-shaped call over dicts with "clip" and any of zlhip_limit_request's other fields (missing = 0: the
+    default) -> (status, one dict of zlhip_limit's fields per request)"""
+    reqs = (_abi.LimitRequest * max(1, len(requests)))()
+    for i, r in enumerate(requests):
+        reqs[i] = _abi.LimitRequest(int(r["clip"]), int(r.get("flags", 0)), int(r.get("lookahead_frames", 0)), int(r.get("hold_frames", 0)),
+                                    float(r.get("ceiling", 0.0)), float(r.get("gain", 0.0)))
+    out = (_abi.Limit * max(1, len(requests)))()
+    rc = fn(handle, reqs, len(requests), out)
+    return rc, [{k: getattr(out[i], k) for k in LIMIT_FIELDS} for i in range(len(requests))]
+
+
 WARP_FIELDS = tuple(name for name, _ in _abi.Warp._fields_)
 
 
@@ -723,6 +750,54 @@ class SamplerSynth:
         """device ms of the scanning launch (0 for a call that trims nothing) and of the render and publishing launches of the last edit call made with profiling on"""
         a, b = C.c_float(0.0), C.c_float(0.0)
         self._ck(self._lib.zlhip_debug_edit_timings(self._e, C.byref(a), C.byref(b)), "debug_edit_timings")
+        return a.value, b.value
+
+    def clip_peak(self, clip: int, first_frame: int = 0, num_frames: int = 0, flags: int = 0) -> dict:
+        """The sample peak and the true peak of the clip's current playback data, measured on the device (zlhip_sound_peak; DESIGN.md
+        section 21): a dict of zlhip_peak's fields -- sample_peak and true_peak per channel (linear), oversampling, chunks.  num_frames
+        0: to the end.  flags 1 (ZLHIP_LIMIT_TRUE_PEAK) adds the inter-sample peaks (4x below 70 kHz, 2x below 140 kHz)."""
+        return self.clip_peak_batch([dict(clip=clip, first_frame=first_frame, num_frames=num_frames, flags=flags)])[0]
+
+    def clip_peak_batch(self, requests: Sequence):
+        """Several requests in one call (zlhip_sound_peak_batch: one launch whatever the count).  requests: dicts with "clip" and any of
+        clip_peak's other arguments"""
+        reqs = []
+        for r in requests:
+            r = dict(r)
+            if int(r.get("num_frames", 0)) == 0:
+                r["num_frames"] = self.clip_length(int(r["clip"])) - int(r.get("first_frame", 0))
+            reqs.append(r)
+        rc, res = _peak_call(self._lib.zlhip_sound_peak_batch, self._e, reqs)
+        self._ck(rc, "sound_peak_batch")
+        return res
+
+    def peak_chunks(self, request: int = 0):
+        """debug: the chunk records of request `request` of the last peak call, float32 [chunks][4]: sample peak L R, inter-sample peak L R"""
+        n = C.c_int32(0)
+        self._ck(self._lib.zlhip_debug_peak_chunks(self._e, request, None, 0, C.byref(n)), "debug_peak_chunks")
+        recs = np.zeros((max(1, n.value), 4), np.float32)
+        self._ck(self._lib.zlhip_debug_peak_chunks(self._e, request, C.cast(recs.ctypes.data, C.POINTER(_abi.PeakChunk)), n.value, C.byref(n)), "debug_peak_chunks")
+        return recs[:n.value]
+
+    def clip_limit(self, clip: int, ceiling: float = 0.0, lookahead_frames: int = 0, hold_frames: int = 0, gain: float = 0.0, flags: int = 0) -> dict:
+        """Bring the clip's peaks under a ceiling on the device, under its own id (zlhip_sound_limit): a look-ahead
+        limiter over the clip's original data, baked.  ceiling 0: -1 dBFS (linear, in (0, 1]); lookahead_frames 0: 5 ms; gain is
+        multiplied in first (0: 1); flags 1 detects on the true peak.  A frame out of reach of every peak keeps its bits (times gain).  A
+        dict of zlhip_limit's fields -- applied (0: already under the ceiling, the clip is untouched), frames_reduced, peak_before,
+        min_gain and the resolved request.  There is no undo.  A clip that plays a re-render, or holds a non-finite sample, is refused."""
+        return self.clip_limit_batch([dict(clip=clip, ceiling=ceiling, lookahead_frames=lookahead_frames, hold_frames=hold_frames, gain=gain, flags=flags)])[0]
+
+    def clip_limit_batch(self, requests: Sequence):
+        """Several clips in one call (zlhip_sound_limit_batch: a detecting launch, a wait, one render launch whatever the count; all or
+        nothing).  requests: dicts with "clip" and any of clip_limit's other arguments"""
+        rc, res = _limit_call(self._lib.zlhip_sound_limit_batch, self._e, requests)
+        self._ck(rc, "sound_limit_batch")
+        return res
+
+    def limit_timings(self):
+        """device ms of the detecting launch and of the render and publishing launches of the last limit call made with profiling on"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        self._ck(self._lib.zlhip_debug_limit_timings(self._e, C.byref(a), C.byref(b)), "debug_limit_timings")
         return a.value, b.value
 
     def clip_warp(self, clip: int, anchors) -> dict:
@@ -1242,6 +1317,24 @@ class SamplerSynthGroup:
         """SamplerSynth.clip_edit_batch on every member; member 0's results (zlhip_group_sound_edit_batch)"""
         rc, res = _edit_call(self._lib.zlhip_group_sound_edit_batch, self._g, requests)
         self._ck(rc, "group_sound_edit_batch")
+        return res
+
+    def clip_peak_batch(self, requests: Sequence):
+        """SamplerSynth.clip_peak_batch; member 0 answers (zlhip_group_sound_peak_batch)"""
+        reqs = []
+        for r in requests:
+            r = dict(r)
+            if int(r.get("num_frames", 0)) == 0:
+                r["num_frames"] = self.clip_length(int(r["clip"])) - int(r.get("first_frame", 0))
+            reqs.append(r)
+        rc, res = _peak_call(self._lib.zlhip_group_sound_peak_batch, self._g, reqs)
+        self._ck(rc, "group_sound_peak_batch")
+        return res
+
+    def clip_limit_batch(self, requests: Sequence):
+        """SamplerSynth.clip_limit_batch on every member; member 0's results (zlhip_group_sound_limit_batch)"""
+        rc, res = _limit_call(self._lib.zlhip_group_sound_limit_batch, self._g, requests)
+        self._ck(rc, "group_sound_limit_batch")
         return res
 
     def clip_warp(self, clip: int, anchors) -> dict:
